@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mbursts/s of the burst detect+demod hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--workload normal|rach|config4|config5]
+  python bench.py --gpus N --steps K --warmup W [--workload normal|rach|config4|config5] [--dump-outputs DIR]
   N>1 without WORLD_SIZE in the environment: this process never touches the GPU; it starts the N ranks itself
   (a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py`)
   and exits with the child's code.  Under torchrun (WORLD_SIZE set) it is one of the ranks.
@@ -37,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 NSOFT = 148
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
 
 
 def measured_traffic(kernel, units, key="bursts_per_launch"):
@@ -132,6 +133,10 @@ class Normal:
         else:
             self.ctx.detect_demod_normal(self.xf, self.off, self.length, self.tsc, self.flags, self.amp, self.toa, self.soft,
                                          detect_thresh=3.0, energy_thresh=0.0, nsoft=NSOFT, soft_stride=NSOFT)
+
+    def outputs(self):
+        """What a step returns to its caller (--dump-outputs)."""
+        return {"flags": self.flags, "amp": self.amp, "toa": self.toa, "soft": self.soft}
 
     def units_per_step(self):
         return self.B
@@ -701,6 +706,33 @@ class Config4:
         return out
 
 
+def dump_outputs(out_dir, arrays, seed=0xD0):
+    """--dump-outputs: the arrays the timed path returned in its last step, as out_dir/<name>.npy in float32 (float64 where
+    the values are float64 or integers float32 would not hold exactly).  Where they come to more than DUMP_BYTES, each keeps
+    the same seeded sample of rows (the leading dimension they share), so that two runs with the same arguments write the
+    same elements."""
+    import numpy as np
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        wide = a.dtype == np.float64 or (a.dtype.kind in "iu" and a.dtype.itemsize > 2)
+        host[name] = np.ascontiguousarray(a, np.float64 if wide else np.float32)
+    rows = {a.shape[0] for a in host.values()}
+    assert len(rows) == 1, "the outputs do not share a leading dimension"
+    n = rows.pop()
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_BYTES - 4096 * len(host)                   # (room for the .npy headers)
+    sample = None
+    if total > budget:
+        sample = np.sort(np.random.default_rng(seed).choice(n, n * budget // total, replace=False))
+        host = {name: a[sample] for name, a in host.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "shapes": {name: list(a.shape) for name, a in host.items()}, "rows": n,
+            "sampled_rows": None if sample is None else int(sample.size)}
+
+
 # ======================================================================================================================
 def _free_port():
     import socket
@@ -811,10 +843,22 @@ def main():
                          "tensors (RCCL refuses two ranks on one device).  Exercises the whole N-rank flow -- spawn, table broadcast, "
                          "per-rank workloads, barriers, MAX over ranks, the one line -- but its number is N workloads time-sharing ONE "
                          "GPU: the line is marked \"rehearsal\" and is not a scaling measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (normal / rach: flags, amp, toa, soft; config5: "
+                         "flags, amp, toa, soft, w, b) as DIR/<name>.npy, float32 or float64, at most 64 MB in all (a fixed seeded "
+                         "sample of rows beyond that).  The inputs are seeded: the same arguments give the same inputs on every run.  "
+                         "Rank 0's outputs under --gpus N")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="exercise the N-rank launch path on the CPU (gloo): rendezvous, table broadcast, reductions; "
                          "no bursts are processed and no number is reported")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.workload == "config4":
+        ap.error("--dump-outputs: config4's streams carry state from step to step, and the untimed clock ramp runs as many steps "
+                 "as fit in --preheat-ms, so its last step's outputs differ from run to run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args, sys.argv[1:])                     # does not return
@@ -907,6 +951,8 @@ def main():
     elapsed = tdist.max_over_ranks(elapsed_own, cdev)
     seen = tdist.ranks_seen(rank, cdev)
     per_rank = tdist.gather_floats(elapsed_own, cdev)       # every rank's own time for the same K steps (a straggler shows here)
+    # ---- the outputs of the last timed step (outside the timed region, before anything else runs on the buffers)
+    dumped = dump_outputs(args.dump_outputs, wl.outputs()) if (args.dump_outputs and rank == 0) else None
     # ---- more repetitions of the same K steps (outside `value`): the spread of a short run
     n_rep = args.repeats if args.repeats is not None else (4 if args.steps < 100 else 0)
     rep_ms = [elapsed / args.steps * 1e3]
@@ -1006,6 +1052,8 @@ def main():
         out["other_soft_mode"] = other_mode
     if stepping:
         out["stepping_state_machine"] = stepping
+    if dumped:
+        out["dumped_outputs"] = dumped
     if args.rehearse_one_gpu:
         out["rehearsal"] = "all %d ranks shared cuda:0 (gloo collectives): launch-path check, not a scaling number" % world
     if not args.no_cpu_baseline and world == 1:

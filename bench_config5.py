@@ -54,6 +54,10 @@ class Config5:
         self.ctx.equalize_normal(self.half, self.off, self.length, self.tsc, self.flags, self.amp, self.toa, self.soft, w=self.w, b=self.b,
                                  energy_thresh=10.0, variant52m=True, max_toa=4, nsoft=156, soft_stride=157, fp16=True)
 
+    def outputs(self):
+        """What a step returns to its caller (bench.py --dump-outputs): the 156 soft bits it writes of each 157-wide row."""
+        return {"flags": self.flags, "amp": self.amp, "toa": self.toa, "soft": self.soft[:, :156], "w": self.w, "b": self.b}
+
     def units_per_step(self):
         return self.B
 

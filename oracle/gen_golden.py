@@ -9,6 +9,7 @@ functions produced for that input.  The reference cannot travel to the GPU box;
 these vectors can.  TEST INFRASTRUCTURE ONLY.
 """
 import os
+import re
 import sys
 
 import numpy as np
@@ -461,6 +462,16 @@ def gen_gsm_time():
          plus=np.array([g(8, x, y) for x, y in pairs], np.int32))
 
 
+def gen_sigproclib_h():
+    """The free functions Transceiver/sigProcLib.h:101-384 declares (tests/test_host_tables.py holds include/sigProcLib_trx.h
+    to them).  REF: where the reference's sources lie, as in oracle/Makefile."""
+    path = os.path.join(os.environ.get("REF", "/root/reference"), "Transceiver", "sigProcLib.h")
+    text = "".join(open(path).read().splitlines(True)[100:384])
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    names = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\(", text)) - {"complex"})
+    save("sigproclib_h.npz", names=np.array(names))
+
+
 BITVECTORTEST_MC = ("000000000000111100000000000001110000011100001101000011000000000000000111000011110000100100001010"
                     "000010100000101000001010000010100000010000000000000000000000000000000000000000000000001100001111"
                     "000000000000000000000000000000000000000000000000000010010000101000001010000010100000101000001010"
@@ -566,3 +577,4 @@ if __name__ == "__main__":
     gen_config1()
     gen_gsm_time()
     gen_fec()
+    gen_sigproclib_h()

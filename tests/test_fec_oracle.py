@@ -1,12 +1,13 @@
 """L1 FEC soft decode, CPU side: the restatement oracle/fec_oracle.c against (1) the
 golden vectors captured from the real reference BitVector / ViterbiR2O4 / Parity code -- including the
-input string of the reference's own CommonLibs/BitVectorTest.cpp:72 -- everywhere, and (2) that
-reference itself on random inputs where oracle/_ref/libref_fec.so exists (build container)."""
+input string of the reference's own CommonLibs/BitVectorTest.cpp:72 -- and (2) that reference itself on
+random inputs: live where oracle/_ref/libref_fec.so is built, replayed from tests/golden/ref_calls/ elsewhere
+(tests/ref_replay.py)."""
 import numpy as np
 import pytest
 
 import fecbind
-import reffec
+from ref_replay import refs  # noqa: F401  (fixture)
 
 
 @pytest.fixture(scope="module")
@@ -114,9 +115,8 @@ def test_batch_layout_and_wire(o, golden):
     assert np.array_equal(out[:, 1], g["rach_bsic_out"]) and np.array_equal(out[:, 2], g["rach_ra_out"])
 
 
-@pytest.mark.skipif(not reffec.available(), reason="oracle/_ref/libref_fec.so not built (reference absent)")
-def test_random_vs_reference(o):
-    r = reffec.RefFec()
+def test_random_vs_reference(o, refs):
+    r = refs.fec()
     rng = np.random.default_rng(77)
     for it in range(250):
         d = rng.integers(0, 2, 184).astype(np.uint8)

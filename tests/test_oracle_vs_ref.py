@@ -1,14 +1,13 @@
 """Randomised bit-exact comparison of the CPU oracle against the REAL reference library
-(oracle/_ref, built in place from /root/reference by `make -C oracle ref`).  Runs only where
-that library exists (the build container); the golden-vector tests cover the GPU box."""
+(oracle/_ref, built in place from the reference's sources by `make -C oracle ref`).  Where that library
+is absent the reference's answers are replayed from tests/golden/ref_calls/ (tests/ref_replay.py)."""
 import numpy as np
 import pytest
 
 import oraclebind
 import refbind
+from ref_replay import refs  # noqa: F401  (fixture)
 from util import assert_beq
-
-pytestmark = pytest.mark.skipif(not refbind.available(), reason="oracle/_ref not built (reference absent)")
 
 
 def cn(rng, n):
@@ -20,9 +19,9 @@ def awgn(rng, n, s):
 
 
 @pytest.mark.parametrize("sps", [1, 2, 4])
-def test_burst_paths(sps):
+def test_burst_paths(sps, refs):
     rng = np.random.default_rng(1000 + sps)
-    r = refbind.Ref(sps); o = oraclebind.Oracle(sps)
+    o = oraclebind.Oracle(sps); r = refs.sigproc(sps, derive={"modulate": o.modulate, "delay_vector": o.delay_vector})
     tscb, _, rachb = r.gsm_bits()
     for it in range(160):
         tsc = it % 8
@@ -53,9 +52,9 @@ def test_burst_paths(sps):
             assert_beq(r.demodulate(x, rr["amp"], rr["toa"]), o.demodulate(x, ro["amp"], ro["toa"]), "demod")
 
 
-def test_primitives_random():
+def test_primitives_random(refs):
     rng = np.random.default_rng(2000)
-    r = refbind.Ref(4); o = oraclebind.Oracle(4)
+    o = oraclebind.Oracle(4); r = refs.sigproc(4, derive={"delay_vector": o.delay_vector})
     for span in range(5):
         for (ar, br) in [(0, 0), (1, 0), (0, 1), (1, 1)]:
             for (na, nb) in [(50, 7), (50, 8), (7, 50), (30, 30), (1, 1), (5, 1)]:
@@ -77,9 +76,9 @@ def test_primitives_random():
         assert r.sinc(x) == o.sinc(x) and r.sinLookup(x) == o.sinLookup(x) and r.cosLookup(x) == o.cosLookup(x)
 
 
-def test_resample_random():
+def test_resample_random(refs):
     rng = np.random.default_rng(3000)
-    r = refbind.Ref(4); o = oraclebind.Oracle(4)
+    r = refs.sigproc(4); o = oraclebind.Oracle(4)
     rcv, snd = r.lpf_raw()
     snd961 = np.concatenate([snd, [0]]).astype(np.float32)
     assert_beq(r.create_lpf651(260.0), o.create_lpf(rcv, 260.0))
@@ -91,9 +90,11 @@ def test_resample_random():
 
 
 @pytest.mark.parametrize("variant", ["", "52m"])
-def test_dfe_flow(variant):
+def test_dfe_flow(variant, refs):
     rng = np.random.default_rng(4000)
-    r = refbind.Ref(1, variant); o = oraclebind.Oracle(1, variant52m=(variant == "52m"))
+    o = oraclebind.Oracle(1, variant52m=(variant == "52m"))
+    r = refs.sigproc(1, variant, derive={"modulate": o.modulate, "delay_vector": o.delay_vector, "convolve": o.convolve,
+                                         "scale_vector": o.scale_vector})
     for t in range(8):
         sq, toa, g = r.midamble(t)
         assert_beq(sq, o.mid[t]); assert np.float32(toa) == o.mid_toa[t] and np.complex64(g) == o.mid_gain[t]
@@ -126,7 +127,7 @@ def test_dfe_flow(variant):
 
 
 @pytest.mark.parametrize("variant", ["", "52m"])
-def test_equalised_leg_strung_together_inside_the_reference(variant):
+def test_equalised_leg_strung_together_inside_the_reference(variant, refs):
     """oracle/ref_driver.cpp::ref_eq_batch runs energyDetect -> analyzeTrafficBurst(requestChannel) -> SNR, scaleVector, designDFE
     -> scaleVector, equalizeBurst(TOA - chanRespOffset) burst by burst INSIDE the compiled reference, as Transceiver::pullRadioVector
     strings them together (Transceiver.cpp:298, 331-349, 391-396) -- bench.py's config-5 cpu_baseline times it.  The oracle's chain
@@ -141,7 +142,7 @@ def test_equalised_leg_strung_together_inside_the_reference(variant):
         s[1:] = s[1:] + np.complex64(0.4 + 0.2j) * s[:-1].copy()
     for i in range(0, B, 16):                                           # and some below the energy gate
         x[off[i]:off[i] + length[i]] *= np.float32(1e-3)
-    r = refbind.Ref(1, variant); o = oraclebind.Oracle(1, variant52m=(variant == "52m"))
+    r = refs.sigproc(1, variant); o = oraclebind.Oracle(1, variant52m=(variant == "52m"))
     ok, soft = r.eq_batch(x, off, length, tsc, 3.0, thr, 4)
     n_ok = 0
     for i in range(B):
