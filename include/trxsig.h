@@ -353,6 +353,49 @@ int trxsig_fec_tch_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft_s
 int trxsig_fec_viterbi_batch(trxsig_ctx *ctx, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
                              uint8_t *d_bits, int64_t out_stride);
 
+/* ---- downlink L1 encode of traffic and sync channels ------------------------------------------------------
+ * TCH/FS + FACCH/F stream encoder (TCHFACCHL1Encoder::dispatch / encodeTCH / interleave, GSML1FEC.cpp:1252-1393):
+ *   n_chan channels x n_blocks 20-ms blocks per call, the interleaver state carried from call to call.
+ *   d_kind[s][m]: what block m of channel s carries -- TRXSIG_TCH_SPEECH: d_payload[s][m][0..33) = d[260] in GSM 05.03
+ *     order, packed MSB first (exactly what trxsig_fec_tch_decode_batch writes to d_tch; the g610BitOrder permutation
+ *     of the vocoder frame stays with the caller, as on the decode side).  TRXSIG_TCH_FACCH: d_payload[s][m][0..23) =
+ *     the 23-octet L2 frame trxsig_fec_xcch_encode_batch takes (octets 23..32 are ignored); the block is stolen (Hu
+ *     set, and Hl of the next block).  TRXSIG_TCH_FILLER: the context's filler c[] (trxsig_fec_tch_set_filler).
+ *     The kind of every block is the caller's choice: the reference's priority rule (FACCH, then speech, then
+ *     filler) and its speech-queue latency control (mMaxQSize) are queue policy and stay with the host.
+ *   d_tsc[s] (0..7): the channel's training sequence.  d_bits[s][m][4][148]: the block's four normal bursts, one bit
+ *     per byte, ready for trxsig_modulate_batch / trxsig_trx_add_radio_vector: zero tails, e-bits at 3..59 and
+ *     88..144, Hl (bit 60) = the previous block's FACCH flag, the training sequence at 61..86, Hu (bit 87) = this
+ *     block's FACCH flag.  Burst b of block m carries this block's c[k], k = b mod 8, at the even e-bit positions and
+ *     the previous block's c[k], k = b+4 mod 8, at the odd ones (GSM 05.03 3.1.3).
+ *   d_state[s][TRXSIG_TCH_TX_STATE_BYTES] (in / out): what the encoder carries from one block to the next.  Bytes
+ *     0..28 hold the odd half of the previous block's c[] -- the 228 bits c[k] with k mod 8 >= 4 in increasing k,
+ *     bit i in byte i/8 at weight 1 << (i mod 8); byte 29 = the previous block's FACCH flag (mPreviousFACCH);
+ *     bytes 30..31 are written as zero.  All-zero bytes are a freshly constructed encoder (mI[] zero-filled,
+ *     mPreviousFACCH false).  The call reads the old state and writes the new one (after block n_blocks-1) in
+ *     place, race-free: one call of n blocks equals k calls of n/k.  Treat the layout as opaque.
+ *   Bad inputs (device side, deterministic): a channel whose d_tsc is above 7 gets all-zero bursts and its state is
+ *     left untouched; a block whose kind is above 2 encodes as an all-zero c[] that is not stolen, and its bursts (and
+ *     its successor's) are formed normally.  Host side: a NULL pointer, a negative size or n_chan * n_blocks >= 2^31
+ *     returns TRXSIG_EINVAL before any launch; n_chan == 0 or n_blocks == 0 is a no-op.
+ * trxsig_fec_tch_set_filler: the 456 bits (one per byte, low bit used) the encoder sends in a block of kind
+ *   TRXSIG_TCH_FILLER.  The reference's pattern (a capture, GSML1FEC.cpp:1348) is not a GSM constant and is not built
+ *   in: the default is all zero, and an integrator who wants the reference's behaviour passes its pattern at set-up.
+ *   Synchronises the context's stream (blocks already enqueued keep the filler they were enqueued with).
+ * SCH encoder (SCHL1Encoder::generate, GSML1FEC.cpp:879-920): n (d_fn[i], d_bsic[i]) -> d_bits[i][148]: d[25] =
+ *   BSIC (6 bits), T1 (11), T2 (5), T3' (3), MSB first; LSB8MSB (the first three octets: bit 24 stays); 10 inverted
+ *   parity bits (generator 0x575); 4 zero tail bits; rate-1/2 coder; e[0..39) at 3..41, the extended training
+ *   sequence (GSM 05.02 5.2.5) at 42..105, e[39..78) at 106..144, zero tails.  T1 / T2 / T3' follow GSMCommon.h:465-474
+ *   for any FN, including T3' = (T3 - 1) / 10 in unsigned arithmetic (its low 3 bits are 1 at T3 = 0; the reference
+ *   itself only sends SCH at T3 = 1, 11, 21, 31, 41).  An FN outside [0, 2715648) or a BSIC above 63 gives a zero
+ *   burst.  FCCH bursts are 148 zero bits and need no kernel. */
+enum { TRXSIG_TCH_FILLER = 0, TRXSIG_TCH_SPEECH = 1, TRXSIG_TCH_FACCH = 2 };
+#define TRXSIG_TCH_TX_STATE_BYTES 32
+int trxsig_fec_tch_set_filler(trxsig_ctx *ctx, const uint8_t *h_c456);
+int trxsig_fec_tch_encode_batch(trxsig_ctx *ctx, int n_chan, int n_blocks, const uint8_t *d_kind, const uint8_t *d_payload,
+                                const uint8_t *d_tsc, void *d_state, uint8_t *d_bits);
+int trxsig_fec_sch_encode_batch(trxsig_ctx *ctx, const uint32_t *d_fn, const uint8_t *d_bsic, int n, uint8_t *d_bits);
+
 /* ---- the free-standing vector primitives of sigProcLib.h (csrc/trxsig_prim.hip) -------------------------------
  * On the burst path these only run fused into the burst kernels above; the stand-alone forms complete the
  * sigProcLib.h surface (convolve :126, correlate :162, vectorSlicer :168, delayVector :180, interpolatePoint :198,
@@ -465,6 +508,10 @@ enum { TRXSIG_K_TSC_CORR = 0, TRXSIG_K_TSC_PEAK = 1, TRXSIG_K_DEMOD = 2, TRXSIG_
        TRXSIG_K_CONVERT = 8, TRXSIG_K_NORMAL_FUSED = 9, TRXSIG_K_FEC = 10, TRXSIG_K_NORMAL_CHAIN = 11,
        TRXSIG_K_EQ_DELAY = 12, TRXSIG_K_EQ_DFE = 13, TRXSIG_K_GROUP = 14, TRXSIG_K_COUNT = 15 };
 /* TRXSIG_K_EQUALIZE = k_eq_detect / k_design_dfe; TRXSIG_K_GROUP = the Transceiver group's replay (trxsig_trxgroup.h) */
+/* Kernels added after TRXSIG_K_COUNT was fixed for ABI 2 (k_fec_tch_encode, k_fec_sch_encode): trxsig_profile_collect
+ * (arrays of TRXSIG_K_COUNT entries) leaves them out; trxsig_profile_collect_n reports them, and trxsig_kernel_count()
+ * counts them. */
+enum { TRXSIG_K_FEC_TCH_ENC = 15, TRXSIG_K_FEC_SCH_ENC = 16 };
 const char *trxsig_kernel_name(int kernel_id);
 int trxsig_profile_enable(trxsig_ctx *ctx, int on);
 int trxsig_profile_collect(trxsig_ctx *ctx, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]);

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("TRXSIG_LIB", os.path.join(_HERE, "libtrxsig.so"))   #
 F_ENERGY, F_DETECT, F_BADLEN = 1, 2, 128
 SOFT_EXACT, SOFT_TOLERANCE = 0, 1                # trxsig_set_soft_mode
 ABI_VERSION = 2                                  # TRXSIG_ABI_VERSION of include/trxsig.h
+TCH_FILLER, TCH_SPEECH, TCH_FACCH = 0, 1, 2      # block kinds of trxsig_fec_tch_encode_batch
+TCH_TX_STATE_BYTES = 32                          # TRXSIG_TCH_TX_STATE_BYTES
 
 
 class TrxSigError(RuntimeError):
@@ -113,6 +115,9 @@ def _load(path):
         L.trxsig_fec_xcch_encode_batch.argtypes = [vp, vp, i32, i32, vp]
         L.trxsig_fec_tch_decode_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
         L.trxsig_fec_viterbi_batch.argtypes = [vp, vp, i32, C.c_int64, i32, vp, C.c_int64]
+        L.trxsig_fec_tch_set_filler.argtypes = [vp, vp]
+        L.trxsig_fec_tch_encode_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+        L.trxsig_fec_sch_encode_batch.argtypes = [vp, vp, vp, i32, vp]
         # sigProcLib.h's free-standing primitives
         L.trxsig_convolve_out_len.argtypes = [i32, i32, i32, i32]
         L.trxsig_convolve_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]
@@ -476,6 +481,26 @@ class TrxSig:
 
     def fec_xcch_encode(self, frames, n_blocks, tsc, bits):
         self._chk(self.L.trxsig_fec_xcch_encode_batch(self.h, _ptr(frames), n_blocks, tsc, _ptr(bits)), "trxsig_fec_xcch_encode_batch")
+
+    def fec_tch_set_filler(self, c456):
+        """The 456 bits (host array, one per byte) sent in a TCH block of kind TCH_FILLER; all zero until set."""
+        import numpy as np
+        h = np.ascontiguousarray(np.asarray(c456, dtype=np.uint8).ravel())
+        if h.size != 456:
+            raise ValueError("the filler is 456 bits")
+        self._chk(self.L.trxsig_fec_tch_set_filler(self.h, h.ctypes.data), "trxsig_fec_tch_set_filler")
+
+    def fec_tch_encode(self, kind, payload, tsc, state, bits):
+        """TCH/FS + FACCH/F stream encode of kind[S, n] blocks (TCH_FILLER / TCH_SPEECH / TCH_FACCH); payload[S, n, 33],
+        tsc[S] (uint8), state[S, TCH_TX_STATE_BYTES] (in / out, zero = a fresh encoder), bits[S, n, 4, 148] (all device)."""
+        S, n = kind.shape
+        self._chk(self.L.trxsig_fec_tch_encode_batch(self.h, S, n, _ptr(kind), _ptr(payload), _ptr(tsc), _ptr(state), _ptr(bits)),
+                  "trxsig_fec_tch_encode_batch")
+
+    def fec_sch_encode(self, fn, bsic, bits):
+        """SCH bursts for fn[n] (uint32 / int32) and bsic[n] (uint8) -> bits[n, 148] (all device)."""
+        self._chk(self.L.trxsig_fec_sch_encode_batch(self.h, _ptr(fn), _ptr(bsic), fn.numel(), _ptr(bits)),
+                  "trxsig_fec_sch_encode_batch")
 
     def fec_tch_decode(self, soft, n_bursts, tch, tch_good, stolen, facch=None, facch_ok=None, wire=True, soft_stride=None):
         self._chk(self.L.trxsig_fec_tch_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n_bursts, int(wire),

@@ -19,6 +19,9 @@
 #include "trxsig_launch.h"
 #include "trxsig_tablegen.h"
 
+// kernel ids the profiler knows: the TRXSIG_K_COUNT of ABI 2, then the ones appended since (trxsig.h)
+constexpr int kKernels = TRXSIG_K_FEC_SCH_ENC + 1;
+
 struct EventProfiler : TrxProfiler {
   struct Rec { int id; hipEvent_t a, b; };
   std::vector<Rec> recs;
@@ -49,7 +52,7 @@ struct EventProfiler : TrxProfiler {
     recs.clear();
   }
   ~EventProfiler() override {
-    float ms[TRXSIG_K_COUNT] = {0}; int n[TRXSIG_K_COUNT] = {0};
+    float ms[kKernels] = {0}; int n[kKernels] = {0};
     collect(ms, n);
     for (hipEvent_t e : pool) (void)hipEventDestroy(e);
   }
@@ -112,7 +115,8 @@ struct trxsig_ctx {
   int chain_dbg = 0;                  // timing experiments (env TRXSIG_CHAIN_DBG): 1 = no detect role, 2 = no demodulate role
   bool chain_broken = false;          // a wait ran out once: three launches from then on
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint8_t *d_tsc = nullptr;          // 8 x 26 training-sequence bits (XCCH encoder), uploaded on first use
+  uint8_t *d_tsc = nullptr;          // 8 x 26 training-sequence bits (XCCH / TCH encoders), uploaded on first use
+  uint8_t *d_tch_filler = nullptr;   // 456 bits of the TCH encoder's filler c[] (trxsig_fec_tch_set_filler), zero until set
   std::string err;
 };
 
@@ -423,6 +427,7 @@ static void destroy_now(trxsig_ctx *c) {
     if (c->h_chain_status) (void)hipHostFree(c->h_chain_status);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->d_tsc) (void)hipFree(c->d_tsc);
+    if (c->d_tch_filler) (void)hipFree(c->d_tch_filler);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->det) { (void)hipStreamSynchronize(c->det); (void)hipStreamDestroy(c->det); }
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
@@ -1201,10 +1206,11 @@ int trxsig_timer_stop(trxsig_ctx *c, float *ms) {
 }
 
 const char *trxsig_kernel_name(int id) {
-  static const char *names[TRXSIG_K_COUNT] = { "k_tsc_corr", "k_tsc_peak", "k_demod", "k_rach_corr", "k_rach_peak",
+  static const char *names[kKernels] = { "k_tsc_corr", "k_tsc_peak", "k_demod", "k_rach_corr", "k_rach_peak",
                                                "k_modulate", "k_resample", "k_eq_detect", "k_convert", "k_normal_fused", "k_fec_viterbi",
-                                               "k_normal_chain", "k_eq_delay", "k_eq_dfe", "k_group_replay" };
-  return (id >= 0 && id < TRXSIG_K_COUNT) ? names[id] : "?";
+                                               "k_normal_chain", "k_eq_delay", "k_eq_dfe", "k_group_replay",
+                                               "k_fec_tch_encode", "k_fec_sch_encode" };
+  return (id >= 0 && id < kKernels) ? names[id] : "?";
 }
 int trxsig_fec_xcch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n_blocks, int wire,
                                  uint8_t *d_frames, uint8_t *d_ok) {
@@ -1224,19 +1230,39 @@ int trxsig_fec_rach_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_st
   HIPCHK(c, trx_launch_fec(c->stream, 2, d_soft, soft_stride, 36, 18, n_bursts, wire, d_tail_ok, d_bsic, d_ra, 0, c->prof));
   return TRXSIG_OK;
 }
+namespace {
+// the 8 x 26 training-sequence bits of the encoders, uploaded on first use (caller holds the DeviceGuard)
+int upload_tsc_bits(trxsig_ctx *c) {
+  if (c->d_tsc) return TRXSIG_OK;
+  uint8_t h[8 * 26];
+  for (int t = 0; t < 8; t++)
+    for (int k = 0; k < 26; k++) h[26 * t + k] = trx_training_sequence(t)[k] == '1';
+  uint8_t *d = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, sizeof h));
+  const hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(d); return fail(c, TRXSIG_EHIP, "training-sequence upload", e); }
+  c->d_tsc = d;
+  return TRXSIG_OK;
+}
+// the TCH filler c[], all zero until trxsig_fec_tch_set_filler (caller holds the DeviceGuard)
+int alloc_tch_filler(trxsig_ctx *c) {
+  if (c->d_tch_filler) return TRXSIG_OK;
+  uint8_t *d = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, 456));
+  const hipError_t e = hipMemset(d, 0, 456);
+  if (e != hipSuccess) { (void)hipFree(d); return fail(c, TRXSIG_EHIP, "TCH filler allocation", e); }
+  c->d_tch_filler = d;
+  return TRXSIG_OK;
+}
+}  // namespace
 int trxsig_fec_xcch_encode_batch(trxsig_ctx *c, const uint8_t *d_frames, int n_blocks, int tsc, uint8_t *d_bits) {
   if (!c) return TRXSIG_EINVAL;
   if (n_blocks < 0 || tsc < 0 || tsc > 7 || (n_blocks > 0 && (!d_frames || !d_bits)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_xcch_encode_batch: bad argument");
   if (n_blocks == 0) return TRXSIG_OK;
   DeviceGuard g(c->device);
-  if (!c->d_tsc) {
-    uint8_t h[8 * 26];
-    for (int t = 0; t < 8; t++)
-      for (int k = 0; k < 26; k++) h[26 * t + k] = trx_training_sequence(t)[k] == '1';
-    HIPCHK(c, hipMalloc((void **)&c->d_tsc, sizeof h));
-    HIPCHK(c, hipMemcpy(c->d_tsc, h, sizeof h, hipMemcpyHostToDevice));
-  }
+  const int rc = upload_tsc_bits(c);
+  if (rc != TRXSIG_OK) return rc;
   HIPCHK(c, trx_launch_fec_xcch_encode(c->stream, d_frames, n_blocks, c->d_tsc + 26 * tsc, d_bits, c->prof));
   return TRXSIG_OK;
 }
@@ -1254,6 +1280,45 @@ int trxsig_fec_tch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_str
   if (d_facch)
     HIPCHK(c, trx_launch_fec(c->stream, 1, d_soft, soft_stride, 456, 228, nblk, wire, d_facch, d_facch_ok, nullptr, 0,
                              c->prof, 1));
+  return TRXSIG_OK;
+}
+int trxsig_fec_tch_set_filler(trxsig_ctx *c, const uint8_t *h_c456) {
+  if (!c) return TRXSIG_EINVAL;
+  if (!h_c456) return fail(c, TRXSIG_EINVAL, "trxsig_fec_tch_set_filler: bad argument");
+  DeviceGuard g(c->device);
+  const int rc = alloc_tch_filler(c);
+  if (rc != TRXSIG_OK) return rc;
+  uint8_t h[456];
+  for (int i = 0; i < 456; i++) h[i] = h_c456[i] & 1u;
+  HIPCHK(c, hipStreamSynchronize(c->stream));              // blocks already enqueued read the old pattern
+  HIPCHK(c, hipMemcpy(c->d_tch_filler, h, sizeof h, hipMemcpyHostToDevice));
+  return TRXSIG_OK;
+}
+int trxsig_fec_tch_encode_batch(trxsig_ctx *c, int n_chan, int n_blocks, const uint8_t *d_kind, const uint8_t *d_payload,
+                                const uint8_t *d_tsc, void *d_state, uint8_t *d_bits) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n_chan < 0 || n_blocks < 0 || (long long)n_chan * n_blocks > 0x7fffffffLL ||
+      (n_chan > 0 && n_blocks > 0 && (!d_kind || !d_payload || !d_tsc || !d_state || !d_bits)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_tch_encode_batch: bad argument");
+  if (n_chan == 0 || n_blocks == 0) return TRXSIG_OK;
+  DeviceGuard g(c->device);
+  int rc = upload_tsc_bits(c);
+  if (rc == TRXSIG_OK) rc = alloc_tch_filler(c);
+  if (rc != TRXSIG_OK) return rc;
+  HIPCHK(c, trx_launch_fec_tch_encode(c->stream, n_chan, n_blocks, d_kind, d_payload, d_tsc, c->d_tsc, c->d_tch_filler,
+                                      static_cast<uint8_t *>(d_state), d_bits, c->prof));
+  return TRXSIG_OK;
+}
+int trxsig_fec_sch_encode_batch(trxsig_ctx *c, const uint32_t *d_fn, const uint8_t *d_bsic, int n, uint8_t *d_bits) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n < 0 || (n > 0 && (!d_fn || !d_bsic || !d_bits)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_sch_encode_batch: bad argument");
+  if (n == 0) return TRXSIG_OK;
+  DeviceGuard g(c->device);
+  unsigned long long xts = 0;
+  const char *x = trx_sch_extended_training_sequence();
+  for (int t = 0; t < 64; t++) xts |= (unsigned long long)(x[t] == '1') << t;
+  HIPCHK(c, trx_launch_fec_sch_encode(c->stream, d_fn, d_bsic, n, xts, d_bits, c->prof));
   return TRXSIG_OK;
 }
 int trxsig_fec_viterbi_batch(trxsig_ctx *c, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
@@ -1344,22 +1409,29 @@ int trxsig_profile_enable(trxsig_ctx *c, int on) {
   if (!on && c->prof) { delete c->prof; c->prof = nullptr; }
   return TRXSIG_OK;
 }
-int trxsig_profile_collect(trxsig_ctx *c, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]) {
-  if (!c || !total_ms || !launches) return TRXSIG_EINVAL;
-  for (int i = 0; i < TRXSIG_K_COUNT; i++) { total_ms[i] = 0; launches[i] = 0; }
+namespace {
+int profile_collect_all(trxsig_ctx *c, float ms[kKernels], int n[kKernels]) {
+  for (int i = 0; i < kKernels; i++) { ms[i] = 0; n[i] = 0; }
   if (!c->prof) return TRXSIG_OK;
   DeviceGuard g(c->device);
-  c->prof->collect(total_ms, launches);
+  c->prof->collect(ms, n);
   return TRXSIG_OK;
 }
-int trxsig_kernel_count(void) { return TRXSIG_K_COUNT; }
+}  // namespace
+int trxsig_profile_collect(trxsig_ctx *c, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]) {
+  if (!c || !total_ms || !launches) return TRXSIG_EINVAL;
+  float ms[kKernels]; int n[kKernels];
+  profile_collect_all(c, ms, n);
+  for (int i = 0; i < TRXSIG_K_COUNT; i++) { total_ms[i] = ms[i]; launches[i] = n[i]; }
+  return TRXSIG_OK;
+}
+int trxsig_kernel_count(void) { return kKernels; }
 int trxsig_profile_collect_n(trxsig_ctx *c, int cap, float *total_ms, int *launches) {
   if (!c || cap < 0 || (cap > 0 && (!total_ms || !launches))) return TRXSIG_EINVAL;
-  float ms[TRXSIG_K_COUNT]; int n[TRXSIG_K_COUNT];
-  const int rc = trxsig_profile_collect(c, ms, n);
-  if (rc != TRXSIG_OK) return rc;
-  for (int i = 0; i < cap && i < TRXSIG_K_COUNT; i++) { total_ms[i] = ms[i]; launches[i] = n[i]; }
-  return TRXSIG_K_COUNT;
+  float ms[kKernels]; int n[kKernels];
+  profile_collect_all(c, ms, n);
+  for (int i = 0; i < cap && i < kKernels; i++) { total_ms[i] = ms[i]; launches[i] = n[i]; }
+  return kKernels;
 }
 int trxsig_tables_validate_host(const void *h_blob, size_t bytes) {
   if (!h_blob || bytes != sizeof(TrxTables)) return TRXSIG_EINVAL;

@@ -14,6 +14,7 @@
 // input bit (24 steps back) is the output.  Numerical contract as in trxsig_dev.h: float costs are added
 // exactly as the reference adds them (cost + (second-bit cost + first-bit cost), -ffp-contract=off),
 // so survivor selection, ties included, is bit-identical.
+// The downlink encoders live here too: k_fec_xcch_encode, k_fec_tch_encode (TCH/FS + FACCH/F streams), k_fec_sch_encode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -350,6 +351,225 @@ __global__ __launch_bounds__(64) void k_fec_xcch_encode(const uint8_t *__restric
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_fec_tch_encode: TCHFACCHL1Encoder::dispatch / encodeTCH / interleave (fec:1252-1284, 1297-1393) for S channels x
+// n blocks, a wave per (channel, block).  The encoder's eight interleaver rows mI[] and its alternating mOffset carry
+// no information of their own: burst b (0..3) of block m carries, at e-bit position j = 2*((49k) mod 57) + (k mod 8)/4,
+// c_m[k] (k = b mod 8) where j is even and c_{m-1}[k] (k = b+4 mod 8) where j is odd -- whatever the offset.  So a
+// block's bursts depend on its own input and its predecessor's only: the wave re-forms c_{m-1} (or, for m = 0, takes
+// its odd half from the channel's state) and every (channel, block) runs in the same launch.  The wave of block 0
+// is the only one that touches a channel's state: it reads the old state and writes the new one (from block n-1).
+// c[] is formed as the reference forms it: FACCH = the XCCH coder on the LSB8MSB'd L2 frame (fec:1320-1327),
+// speech = encodeTCH (3 inverted parity bits over class 1a, u[] reordering, coder on u[189], class 2 copied),
+// filler = the caller's c[] (fec:1346-1350), any other kind = zeros.  The output is gathered: each lane forms 16
+// consecutive bytes of the block's 592 through an inverse interleaver table and stores them at once.
+// ---------------------------------------------------------------------------------------------
+struct TchInv {                                            // (burst b, e-bit j) -> k; j even: c_m[k], j odd: c_{m-1}[k]
+  uint16_t k[4][114];
+  constexpr TchInv() : k() {
+    for (int c = 0; c < 456; c++) k[(c % 8) & 3][2 * ((49 * c) % 57) + ((c % 8) / 4)] = (uint16_t)c;
+  }
+};
+__device__ __constant__ const TchInv kTchInv;
+
+enum { TCH_FILLER = 0, TCH_SPEECH = 1, TCH_FACCH = 2 };
+constexpr int kTchState = 32;                              // TRXSIG_TCH_TX_STATE_BYTES
+constexpr int kTchOddBytes = 29;                           // 228 bits of c[k], k mod 8 >= 4, bit i = (byte i/8 >> i%8) & 1
+
+// c[456] of one block into LDS (one byte per bit); the whole wave calls it with the same kind.  pl: the block's 33
+// payload octets (global), u: 232 bytes of LDS scratch.
+__device__ void tch_form_c(int kind, const uint8_t *__restrict__ pl, const uint8_t *__restrict__ filler, uint8_t *u,
+                           uint8_t *c, uint8_t *pls, int lane) {
+  if (kind == TCH_SPEECH || kind == TCH_FACCH) {
+    if (lane < 33) pls[lane] = pl[lane];
+    wave_fence();
+  }
+  if (kind == TCH_SPEECH) {
+    auto dq = [&](int q) { return (unsigned)(pls[q >> 3] >> (7 - (q & 7))) & 1u; };   // d[q], octets MSB first
+    unsigned par = (lane < 50 && dq(lane)) ? kTchPar.v[lane] : 0u;                     // encoderShift over d[0..50)
+    for (int m = 1; m < 64; m <<= 1) par ^= (unsigned)__shfl_xor((int)par, m, 64);
+    par = ~par & 7u;                                                                   // writeParityWord inverts (bv:413)
+    for (int i = lane; i < 189; i += 64) {
+      unsigned v = 0;
+      if (i <= 90) v = dq(2 * i);                                                      // u[k] = d[2k]
+      else if (i <= 93) v = (par >> (93 - i)) & 1u;                                    // u[91..93] = parity, MSB first
+      else if (i <= 184) v = dq(2 * (184 - i) + 1);                                    // u[184-k] = d[2k+1]
+      u[i] = (uint8_t)v;                                                               // u[185..188] = 0
+    }
+    for (int i = lane; i < 78; i += 64) c[378 + i] = (uint8_t)dq(182 + i);             // class 2 copied
+    wave_fence();
+    for (int k = lane; k < 189; k += 64) {
+      unsigned idx = 0;
+      for (int h = 0; h < 5; h++) idx |= (k - h >= 0 ? (unsigned)u[k - h] : 0u) << h;
+      const unsigned g = (unsigned)(kGen >> (2 * idx)) & 3u;
+      c[2 * k] = (uint8_t)(g >> 1); c[2 * k + 1] = (uint8_t)(g & 1u);
+    }
+  } else if (kind == TCH_FACCH) {
+    // d[] = the L2 frame after LSB8MSB: u[8o + b] = bit b of octet o; 40 inverted Fire parity bits; 4 zero tail bits
+    unsigned long long par = 0;
+    for (int i = lane; i < 184; i += 64)
+      if ((pls[i >> 3] >> (i & 7)) & 1u) par ^= kXcchPar.v[i];
+    unsigned lo = (unsigned)par, hi = (unsigned)(par >> 32);
+    for (int m = 1; m < 64; m <<= 1) { lo ^= (unsigned)__shfl_xor((int)lo, m, 64); hi ^= (unsigned)__shfl_xor((int)hi, m, 64); }
+    const unsigned long long pw = ~(((unsigned long long)hi << 32) | lo) & ((1ULL << 40) - 1);
+    for (int i = lane; i < 228; i += 64) {
+      unsigned v = 0;
+      if (i < 184) v = (pls[i >> 3] >> (i & 7)) & 1u;
+      else if (i < 224) v = (unsigned)(pw >> (39 - (i - 184))) & 1u;
+      u[i] = (uint8_t)v;
+    }
+    wave_fence();
+    for (int k = lane; k < 228; k += 64) {
+      unsigned idx = 0;
+      for (int h = 0; h < 5; h++) idx |= (k - h >= 0 ? (unsigned)u[k - h] : 0u) << h;
+      const unsigned g = (unsigned)(kGen >> (2 * idx)) & 3u;
+      c[2 * k] = (uint8_t)(g >> 1); c[2 * k + 1] = (uint8_t)(g & 1u);
+    }
+  } else {
+    for (int i = lane; i < 456; i += 64) c[i] = kind == TCH_FILLER ? (uint8_t)(filler[i] & 1u) : (uint8_t)0;
+  }
+  wave_fence();
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_fec_tch_encode(int n_blocks, const uint8_t *__restrict__ kinds,
+                                                       const uint8_t *__restrict__ payload, const uint8_t *__restrict__ tscs,
+                                                       const uint8_t *__restrict__ tsc_bits /* 8 x 26 */,
+                                                       const uint8_t *__restrict__ filler /* 456 */, uint8_t *state,
+                                                       uint8_t *__restrict__ bits) {
+  __shared__ uint8_t ca[456], cb[456], u[232], pls[36];
+  const int lane = threadIdx.x;
+  const int ch = blockIdx.x / n_blocks, m = blockIdx.x - ch * n_blocks;
+  const size_t blk = (size_t)ch * n_blocks + m;
+  uint8_t *out = bits + blk * 592;
+  const unsigned tsc = tscs[ch];
+  if (tsc > 7) {                                           // bad training sequence: zero bursts, state untouched
+    if (VEC) { if (lane < 37) reinterpret_cast<uint4 *>(out)[lane] = make_uint4(0, 0, 0, 0); }
+    else for (int i = lane; i < 592; i += 64) out[i] = 0;
+    return;
+  }
+  const int kind = kinds[blk];
+  tch_form_c(kind, payload + blk * 33, filler, u, ca, pls, lane);
+  const unsigned curF = kind == TCH_FACCH;
+  unsigned prevF;
+  uint8_t *st = state + (size_t)ch * kTchState;
+  if (m > 0) {
+    const int pk = kinds[blk - 1];
+    tch_form_c(pk, payload + (blk - 1) * 33, filler, u, cb, pls, lane);
+    prevF = pk == TCH_FACCH;
+  } else {
+    for (int k = lane; k < 456; k += 64) {
+      const int i = 4 * (k >> 3) + (k & 3);
+      cb[k] = (k & 4) ? (uint8_t)((st[i >> 3] >> (i & 7)) & 1u) : (uint8_t)0;
+    }
+    prevF = st[kTchOddBytes] & 1u;
+    wave_fence();
+  }
+  const uint8_t *tb = tsc_bits + 26 * tsc;
+  auto obyte = [&](int p) -> unsigned {
+    const int b = p / 148, pos = p - 148 * b;
+    if (pos < 3 || pos >= 145) return 0u;
+    if (pos == 60) return prevF;                           // Hl: the previous block was stolen (fec:1367)
+    if (pos == 87) return curF;                            // Hu: this block is stolen (fec:1366)
+    if (pos > 60 && pos < 87) return tb[pos - 61] & 1u;
+    const int j = pos < 60 ? pos - 3 : pos - 31;
+    const int k = kTchInv.k[b][j];
+    return (j & 1) ? cb[k] : ca[k];
+  };
+  if (VEC) {
+    if (lane < 37) {
+      unsigned w[4];
+      for (int q = 0; q < 4; q++) {
+        unsigned v = 0;
+        for (int r = 0; r < 4; r++) v |= obyte(16 * lane + 4 * q + r) << (8 * r);
+        w[q] = v;
+      }
+      reinterpret_cast<uint4 *>(out)[lane] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  } else {
+    for (int i = lane; i < 592; i += 64) out[i] = (uint8_t)obyte(i);
+  }
+  if (m != 0) return;
+  // the channel's new state: the odd half of block n-1's c[] and its FACCH flag (the old state is in cb already)
+  const int lk = kinds[blk + n_blocks - 1];
+  if (n_blocks > 1) {
+    wave_fence();
+    tch_form_c(lk, payload + (blk + n_blocks - 1) * 33, filler, u, ca, pls, lane);
+  }
+  if (lane < kTchState) {
+    unsigned v = 0;
+    if (lane < kTchOddBytes) {
+      for (int t = 0; t < 8; t++) {
+        const int i = 8 * lane + t;
+        if (i < 228) v |= (unsigned)ca[8 * (i >> 2) + 4 + (i & 3)] << t;
+      }
+    } else if (lane == kTchOddBytes) {
+      v = lk == TCH_FACCH;
+    }
+    st[lane] = (uint8_t)v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_fec_sch_encode: SCHL1Encoder::generate (fec:897-920): d[25] = BSIC, T1, T2, T3' (writeField, MSB first), LSB8MSB
+// (the first three octets only: bit 24 stays), 10 inverted parity bits (Parity(0x0575, 10, 25)), 4 zero tail bits,
+// rate-1/2 coder, e[0..39) at 3..41, the extended training sequence at 42..105, e[39..78) at 106..144.  16 lanes per
+// burst, each storing a dword of its 148 bytes; an FN outside the hyperframe or a BSIC above 63 gives a zero burst.
+// ---------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_fec_sch_encode(const uint32_t *__restrict__ fns, const uint8_t *__restrict__ bsics,
+                                                       int n, unsigned long long xts /* bit t = XTS[t] */,
+                                                       uint8_t *__restrict__ bits) {
+  const int lane = threadIdx.x & 15, i = blockIdx.x * 4 + (threadIdx.x >> 4);
+  if (i >= n) return;
+  const unsigned fn = fns[i], bsic = bsics[i];
+  const bool valid = fn < 2715648u && bsic < 64u;
+  unsigned long long e0 = 0, e1 = 0;                       // e[0..64), e[64..78)
+  if (valid) {
+    const unsigned t1 = (fn / (26u * 51u)) % 2048u, t2 = fn % 26u, t3 = fn % 51u;
+    const unsigned t3p = (t3 - 1u) / 10u;                  // unsigned, as GSMCommon.h:474: wraps at T3 = 0
+    const unsigned D = (bsic << 19) | (t1 << 8) | ((t2 & 31u) << 3) | (t3p & 7u);   // d[i] = bit 24-i
+    unsigned d = 0;                                        // after LSB8MSB: bit 24-i = d'[i]
+    for (int q = 0; q < 25; q++) {
+      const int src = q < 24 ? 8 * (q >> 3) + 7 - (q & 7) : 24;
+      d |= ((D >> (24 - src)) & 1u) << (24 - q);
+    }
+    unsigned par = 0;                                      // encoderShift (bh:80-85), generator 0x575
+    for (int q = 0; q < 25; q++) {
+      const unsigned fb = ((par >> 9) ^ (d >> (24 - q))) & 1u;
+      par <<= 1;
+      if (fb) par ^= 0x575u;
+    }
+    const unsigned pw = ~par & 0x3ffu;
+    unsigned long long uu = ((unsigned long long)d << 14) | ((unsigned long long)pw << 4);   // u[i] = bit 38-i
+    unsigned acc = 0;
+    for (int q = 0; q < 39; q++) {
+      acc = (acc << 1) | (unsigned)((uu >> (38 - q)) & 1ULL);
+      const unsigned long long g = (kGen >> (2 * (acc & 31u))) & 3ULL;
+      const int p = 2 * q;
+      if (p < 64) e0 |= (g >> 1) << p; else e1 |= (g >> 1) << (p - 64);
+      if (p + 1 < 64) e0 |= (g & 1ULL) << (p + 1); else e1 |= (g & 1ULL) << (p + 1 - 64);
+    }
+  }
+  auto ebit = [&](int k) { return (unsigned)((k < 64 ? e0 >> k : e1 >> (k - 64)) & 1ULL); };
+  auto obyte = [&](int pos) -> unsigned {
+    if (!valid || pos < 3 || pos >= 145) return 0u;
+    if (pos < 42) return ebit(pos - 3);
+    if (pos < 106) return (unsigned)(xts >> (pos - 42)) & 1u;
+    return ebit(39 + pos - 106);
+  };
+  uint8_t *out = bits + (size_t)i * 148;
+  for (int w = lane; w < 37; w += 16) {
+    if (VEC) {
+      unsigned v = 0;
+      for (int r = 0; r < 4; r++) v |= obyte(4 * w + r) << (8 * r);
+      reinterpret_cast<unsigned *>(out)[w] = v;
+    } else {
+      for (int r = 0; r < 4; r++) out[4 * w + r] = (uint8_t)obyte(4 * w + r);
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t trx_launch_fec_xcch_encode(hipStream_t st, const uint8_t *frames, int nblk, const uint8_t *tsc_bits, uint8_t *bits,
@@ -376,5 +596,32 @@ hipError_t trx_launch_fec(hipStream_t st, int mode, const float *soft, long long
     default: return hipErrorInvalidValue;
   }
   if (prof) prof->end(TRXSIG_K_FEC, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_tch_encode(hipStream_t st, int n_chan, int n_blocks, const uint8_t *kinds, const uint8_t *payload,
+                                     const uint8_t *tscs, const uint8_t *tsc_bits, const uint8_t *filler, uint8_t *state,
+                                     uint8_t *bits, TrxProfiler *prof) {
+  if (n_chan <= 0 || n_blocks <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((long long)n_chan * n_blocks)), block(64);
+  if (prof) prof->begin(TRXSIG_K_FEC_TCH_ENC, st);
+  if (((uintptr_t)bits & 15) == 0)
+    k_fec_tch_encode<true><<<grid, block, 0, st>>>(n_blocks, kinds, payload, tscs, tsc_bits, filler, state, bits);
+  else
+    k_fec_tch_encode<false><<<grid, block, 0, st>>>(n_blocks, kinds, payload, tscs, tsc_bits, filler, state, bits);
+  if (prof) prof->end(TRXSIG_K_FEC_TCH_ENC, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_sch_encode(hipStream_t st, const uint32_t *fns, const uint8_t *bsics, int n, unsigned long long xts,
+                                     uint8_t *bits, TrxProfiler *prof) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((n + 3) / 4)), block(64);
+  if (prof) prof->begin(TRXSIG_K_FEC_SCH_ENC, st);
+  if (((uintptr_t)bits & 3) == 0)
+    k_fec_sch_encode<true><<<grid, block, 0, st>>>(fns, bsics, n, xts, bits);
+  else
+    k_fec_sch_encode<false><<<grid, block, 0, st>>>(fns, bsics, n, xts, bits);
+  if (prof) prof->end(TRXSIG_K_FEC_SCH_ENC, st);
   return hipGetLastError();
 }

@@ -227,3 +227,11 @@ hipError_t trx_launch_equalize_taps(hipStream_t st, const TrxTables *dT, const v
 // training-sequence bits (device)
 hipError_t trx_launch_fec_xcch_encode(hipStream_t st, const uint8_t *frames, int nblk, const uint8_t *tsc_bits, uint8_t *bits,
                                       TrxProfiler *prof);
+// TCH/FS + FACCH/F stream encode (trxsig_fec_tch_encode_batch): n_chan x n_blocks blocks -> 4 bursts of 148 bits each;
+// tsc_bits: the 8 x 26 training-sequence bits, filler: 456 bits, state: 32 bytes per channel, in / out (all device)
+hipError_t trx_launch_fec_tch_encode(hipStream_t st, int n_chan, int n_blocks, const uint8_t *kinds, const uint8_t *payload,
+                                     const uint8_t *tscs, const uint8_t *tsc_bits, const uint8_t *filler, uint8_t *state,
+                                     uint8_t *bits, TrxProfiler *prof);
+// SCH encode (trxsig_fec_sch_encode_batch): n (FN, BSIC) -> n bursts of 148 bits; xts: bit t = extended training sequence bit t
+hipError_t trx_launch_fec_sch_encode(hipStream_t st, const uint32_t *fns, const uint8_t *bsics, int n, unsigned long long xts,
+                                     uint8_t *bits, TrxProfiler *prof);

@@ -118,6 +118,7 @@ const char *kTSC[8] = {                                                  // GSM/
   "01000111101101000100011110", "00011010111001000001101011", "01001110101100000100111010",
   "10100111110110001010011111", "11101111000100101110111100" };
 const char *kRACH = "01001011011111111001100110101010001111000";       // GSM/GSMCommon.cpp:57
+const char *kXTS = "1011100101100010000001000000111100101101010001010111011000011011";   // SCH extended training sequence, GSM 05.02 5.2.5
 
 uint32_t fnv1a(const unsigned char *p, size_t n) {
   uint32_t h = 2166136261u;
@@ -199,3 +200,4 @@ int trx_build_tables(TrxTables *T, int sps) {
 
 // the 26 training-sequence bits of TSC 0..7 as '0'/'1' characters (GSM 05.02 5.2.3; GSM/GSMCommon.cpp:44-53)
 const char *trx_training_sequence(int tsc) { return (tsc >= 0 && tsc < 8) ? kTSC[tsc] : nullptr; }
+const char *trx_sch_extended_training_sequence() { return kXTS; }
