@@ -94,8 +94,10 @@ int trxsig_rxfe_push_wideband(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks
  * over the raw samples: sixteen partial sums of real taps on raw samples per output instant, shared by all carriers, then sixteen
  * complex multiply-adds per carrier from registers (csrc/trxsig_chan.hip).  The same sum in another order, with exact cos / sin
  * instead of the reference's table trig and fused multiply-adds: equal to the per-carrier form to ~1e-6 of the signal's scale
- * (tests/test_gpu_channeliser.py grades it at 1e-4, identical hard bits), 5-10x faster.  Needs 1, 2, 4, 8 or 16 carriers on that
- * grid and at most 32 taps per output (L <= 32 P); TRXSIG_EINVAL otherwise.  on = 0 returns to the per-carrier form. */
+ * (tests/test_gpu_channeliser.py grades it at 1e-4, identical hard bits; tests/test_gpu_channeliser_graded.py per output against a
+ * float64 reference), 5-10x faster.  Needs 1, 2, 4, 8 or 16 carriers on that grid, at most 32 taps per output (L <= 32 P) and a tile's
+ * window span 255 Q / P + 36 <= 1024 raw samples, Q = 96 rate_factor (so rate_factor <= 2 at sps 1, <= 5 at sps 2, <= 10 at sps 4);
+ * TRXSIG_EINVAL otherwise.  on = 0 returns to the per-carrier form. */
 int trxsig_rxfe_set_shared_filter(trxsig_rxfe *fe, int on);
 
 /* h_lpf: the L (normally 651, createLPF(cutoff, 651, 96): radioInterface.cpp:134-138) normalised taps.  max_bursts: the

@@ -11,7 +11,10 @@
 //     y_c[o] = m_c[n mod 16] * sum_j conj(m_c[j]) * T_j             (sixteen complex multiply-adds per carrier, from registers)
 // -- the window is staged once, unmixed; a sample and a tap are read once per output instead of C times; the mixer is two
 // small constant tables.  Same sum up to the order of its terms: NOT bit-equal to the per-carrier form (which stays the pinned
-// one and the default); checked against it at 1e-4 of the signal's scale with identical hard bits (tests/test_gpu_channeliser.py).
+// one and the default).  Graded per output against a float64 reference of the same sum (tests/chan_ref.py, exact grid theta):
+// |y - y_ref| <= c u A(o), u = 2^-24, A(o) = sum_k |h_k| (|Re x| + |Im x|), c = 26 for the FFT path and 53 for the direct one, derived
+// in tests/test_gpu_channeliser_graded.py (every C, odd and even bins, DC and +-pi, several (sps, rate factor) pairs and filters); and
+// against the per-carrier form at 1e-4 of the signal's scale with identical hard bits (tests/test_gpu_channeliser.py).
 // Because the form is approximate by construction its multiply-adds may fuse (explicit v_fma_f32 with the marker comment
 // "approx-form", counted apart by tools/asm_stats.py); the twiddles are exact cos / sin (double, rounded once).
 // With four carriers or more the sixteen sums sum_j conj(m_c[j]) T_j are taken from ONE 16-point FFT of T (they are bins k_c of its
@@ -210,27 +213,43 @@ __global__ __launch_bounds__(256) void k_channelise16(TrxResampleArgs a, const f
 
 }  // namespace
 
-// tw: device table [C][16] of exp(-j theta_c j).  Requirements (checked by the caller, trxsig_frontend.cpp): int16 input, window
-// start and length multiples of 16 raw samples, at most 32 taps per output, C in {1, 2, 4, 8, 16}.
+namespace {
+struct Chan16Shape { int g, kt, xcap; size_t lds; };
+Chan16Shape chan16_shape(int P, int Q, int L, int C) {
+  Chan16Shape sh;
+  int g = P, r = Q % P;
+  while (r) { const int t = g % r; g = r; r = t; }          // gcd(P, Q): only branches that are multiples of it occur
+  sh.g = g;
+  sh.kt = (L + P - 1) / P;
+  sh.xcap = (int)(((long long)(kTile - 1) * Q) / P + 32 + 4);
+  sh.lds = ((sizeof(short2) * (size_t)sh.xcap + 15) & ~(size_t)15) + sizeof(float) * ((((size_t)(P / g) * kTapPitch) + 1) & ~(size_t)1) +
+           sizeof(float2) * 16 * (size_t)C;
+  return sh;
+}
+}  // namespace
+
+bool trx_channelise16_fits(int P, int Q, int L, int C) {
+  if (P <= 0 || Q <= 0 || L <= 0 || !(C == 1 || C == 2 || C == 4 || C == 8 || C == 16)) return false;
+  const Chan16Shape sh = chan16_shape(P, Q, L, C);
+  return sh.kt <= 32 && sh.xcap <= 4 * 256 && sh.lds <= 64 * 1024;   // (4 * 256: NQ staged samples per thread)
+}
+
+// tw: device table [C][16] of exp(-j theta_c j).  Requirements (checked by the caller, trxsig_frontend.cpp, with trx_channelise16_fits and
+// the grid): int16 input, window start and length multiples of 16 raw samples, at most 32 taps per output, C in {1, 2, 4, 8, 16}.
 hipError_t trx_launch_channelise16(hipStream_t st, TrxResampleArgs a, int S_wide, int C, int n_windows, const float2 *tw, TrxProfiler *prof,
                                    unsigned long long binmap) {
   if (S_wide <= 0 || n_windows <= 0 || a.n_out <= a.o_skip) return hipSuccess;
-  const int kt = (a.L + a.P - 1) / a.P;
-  if (kt > 32 || S_wide > 65535 || n_windows > 65535) return hipErrorInvalidValue;
-  int g = a.P, r = a.Q % a.P;
-  while (r) { const int t = g % r; g = r; r = t; }          // gcd(P, Q): only branches that are multiples of it occur
+  if (!trx_channelise16_fits(a.P, a.Q, a.L, C) || S_wide > 65535 || n_windows > 65535) return hipErrorInvalidValue;
+  const Chan16Shape sh = chan16_shape(a.P, a.Q, a.L, C);
+  const int g = sh.g, kt = sh.kt, xcap = sh.xcap;
+  const size_t lds = sh.lds;
   a.tap_g = g;
-  const int xcap = (int)(((long long)(kTile - 1) * a.Q) / a.P + 32 + 4);
-  const size_t lds = ((sizeof(short2) * (size_t)xcap + 15) & ~(size_t)15) + sizeof(float) * ((((size_t)(a.P / g) * kTapPitch) + 1) & ~(size_t)1) +
-                     sizeof(float2) * 16 * (size_t)C;
   a.row_inv = 0;                                            // ((Q mod P) / g)^-1 mod P / g: the rows of the tap table in visiting order
   {
     const int nbr = a.P / g, st1 = (a.Q % a.P) / g;
     for (int v = 1; v < nbr; v++)
       if (((long long)v * st1) % nbr == 1) { a.row_inv = v; break; }
   }
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  if (xcap > 4 * 256) return hipErrorInvalidValue;
   const int n_tiles = (a.n_out - a.o_skip + kTile - 1) / kTile;
   int tpw = 1;                                              // tiles per workgroup: up to four (measured: 1: 174, 2: 130, 4: 117, 8: 145 us), as long as
   for (int cand = 4; cand > 1; cand >>= 1)                  // the machine keeps eight workgroups per CU
@@ -244,7 +263,7 @@ hipError_t trx_launch_channelise16(hipStream_t st, TrxResampleArgs a, int S_wide
     case 4: k_channelise16<4><<<grid, block, lds, st>>>(a, tw, xcap, kt, binmap, tpw); break;
     case 8: k_channelise16<8><<<grid, block, lds, st>>>(a, tw, xcap, kt, binmap, tpw); break;
     case 16: k_channelise16<16><<<grid, block, lds, st>>>(a, tw, xcap, kt, binmap, tpw); break;
-    default: if (prof) prof->end(TRXSIG_K_RESAMPLE, st); return hipErrorInvalidValue;
+    default: if (prof) prof->end(TRXSIG_K_RESAMPLE, st); return hipErrorInvalidValue;   // (not reached: trx_channelise16_fits)
   }
   if (prof) prof->end(TRXSIG_K_RESAMPLE, st);
   return hipGetLastError();

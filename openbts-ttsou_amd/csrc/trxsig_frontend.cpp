@@ -160,6 +160,12 @@ int trxsig_rxfe_create_wideband(trxsig_rxfe **out, trxsig_ctx *c, int n_wide_str
     *out = nullptr;
     return rc;
   }
+  if (!trx_resample_mix_fits(fe->P, TRXSIG_OUTRATE * rate_factor, L, fe->n_out, fe->skip)) {   // (e.g. sps 1 with rate factor >= 44)
+    const int rc = trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_create_wideband: the rate factor is too high for this sps and filter (a tile's window span exceeds the resampler's staging)", hipSuccess);
+    trxsig_rxfe_destroy(fe);
+    *out = nullptr;
+    return rc;
+  }
   fe->n_total = (long long)TRXSIG_OUTHISTORY * rate_factor;   // (the zero history in front of the stream holds raw samples 0 .. hist - 1)
   Guard g(trxsig_device(c));
   // the history is per wideband stream and rate_factor times longer; the fused (narrowband) tables are not used
@@ -225,6 +231,9 @@ int trxsig_rxfe_set_shared_filter(trxsig_rxfe *fe, int on) {
     return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_set_shared_filter: 1, 2, 4, 8 or 16 carriers", hipSuccess);
   if ((fe->L + fe->P - 1) / fe->P > 32 || (TRXSIG_OUTCHUNK * fe->Cw) % 16 || (TRXSIG_OUTHISTORY * fe->Cw) % 16)
     return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_set_shared_filter: needs at most 32 taps per output and chunks of a multiple of 16 samples", hipSuccess);
+  // what the kernel stages per tile: 255 Q / P + 36 raw samples, at most 1024 (e.g. sps 1 with rate factor >= 3, sps 2 with >= 6, sps 4 with >= 11 do not fit)
+  if (!trx_channelise16_fits(fe->P, TRXSIG_OUTRATE * fe->Cw, fe->L, C))
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_set_shared_filter: the rate factor is too high for this sps (a tile's window span exceeds the kernel's staging)", hipSuccess);
   // every carrier on the grid of sixteenths of the wideband rate: theta_c = 2 pi k_c / 16 (to float accuracy)
   std::vector<float2> tw((size_t)C * 16);
   unsigned long long binmap = 0;

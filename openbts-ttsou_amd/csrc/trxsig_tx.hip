@@ -463,13 +463,25 @@ static int resample_tile(const TrxResampleArgs &a, int xcap_limit) {
   return (int)(ob < want ? ob : want);
 }
 
+// staged samples a tile of OB outputs can need
+static long long resample_span(const TrxResampleArgs &a) { return ((long long)(a.OB - 1) * a.Q) / a.P + (a.L + a.P - 1) / a.P + 4; }
+
+bool trx_resample_mix_fits(int P, int Q, int L, int n_out, int o_skip) {
+  TrxResampleArgs a = {};
+  a.P = P; a.Q = Q; a.L = L; a.n_out = n_out; a.o_skip = o_skip; a.mix_carriers = 1;
+  if (P <= 0 || Q <= 0 || L <= 0) return false;
+  if (n_out <= o_skip) return true;                         // (nothing is launched)
+  a.OB = resample_tile(a, 2048);
+  return resample_span(a) <= TRX_RES_XCAP;
+}
+
 hipError_t trx_launch_resample_ex(hipStream_t st, TrxResampleArgs a, int S, int n_windows, bool in_i16, bool out_i16,
                                   TrxProfiler *prof, bool in_bits) {
   if (S <= 0 || n_windows <= 0 || a.n_out <= a.o_skip) return hipSuccess;
   // the channeliser's tiles are smaller: its staging is arithmetic (the mixer), not copying, and wants more waves in flight
   a.OB = resample_tile(a, a.mix_carriers > 0 ? 2048 : TRX_RES_XCAP);
-  long long span = ((long long)(a.OB - 1) * a.Q) / a.P + (a.L + a.P - 1) / a.P + 4;      // staged samples a tile can need
-  if (span > TRX_RES_XCAP) return hipErrorInvalidValue;
+  long long span = resample_span(a);
+  if (span > TRX_RES_XCAP) return hipErrorInvalidValue;     // (the channeliser's front end refuses such a configuration at create: trx_resample_mix_fits)
   if (span > a.n) span = a.n;
   if (S > 65535 || n_windows > 65535) return hipErrorInvalidValue;
   a.xcap = (int)((span + 1) & ~1LL);
@@ -488,9 +500,10 @@ hipError_t trx_launch_resample_ex(hipStream_t st, TrxResampleArgs a, int S, int 
   const size_t lds = sizeof(trx_c32) * (size_t)a.xcap + tap_bytes;
   const dim3 grid((a.n_out - a.o_skip + a.OB - 1) / a.OB, n_windows, S), block(256);
   if (prof) prof->begin(TRXSIG_K_RESAMPLE, st);
-  // the receive front end's shape (whole window per workgroup, <= 4 taps per output, indices inside 32 bits): k_rx_resample
+  // the receive front end's shape (whole window per workgroup, <= 4 taps per output, indices inside 32 bits): k_rx_resample.  It has
+  // no mixer: the channeliser (mix_carriers > 0) stays on k_resample whatever its window size (at rate factor 1 it would fit)
   const int kq = a.L <= 4 * a.P ? 1 : (a.L <= 8 * a.P ? 2 : 4);
-  const bool rx_fast = in_i16 && !out_i16 && a.OB == a.n_out - a.o_skip && a.L <= 16 * a.P && a.n <= 5 * 256 && a.P <= 1024 &&
+  const bool rx_fast = in_i16 && !out_i16 && a.mix_carriers == 0 && a.OB == a.n_out - a.o_skip && a.L <= 16 * a.P && a.n <= 5 * 256 && a.P <= 1024 &&
                        (long long)(a.n_out + (a.L - 1) / 2 / a.Q + 256) * a.Q < 0x7fffffffLL && (long long)n_windows * a.win_step < 0x7fffffffLL &&
                        ((long long)(a.n_out - 1 + (a.L - 1) / 2 / a.Q) * a.Q) / a.P <= a.n + 4 * kq - 1;
   if (rx_fast) {
