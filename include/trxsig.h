@@ -174,9 +174,10 @@ int trxsig_demodulate_batch(trxsig_ctx *ctx,
  *   TRXSIG_SOFT_TOLERANCE: the accuracy the reference's users are promised elsewhere ("within 1e-4 on soft symbols") spent on
  *     speed -- 1/amp is applied to the 148 outputs instead of the 625 samples and the delay filter accumulates with fused
  *     multiply-adds (csrc/trxsig_demod.h, fused_demod_tol: ~200 instead of ~530 VALU instructions per burst).  Guaranteed
- *     |soft - reference soft| <= 7.4e-5 on the [0, 1] scale of a soft bit (derivation there; measured <= 1.5e-6); a burst for
+ *     |soft - reference soft| <= 3.7e-5 on the [0, 1] scale of a soft bit (derivation there); the parity contract (<= 1e-6, or
+ *     1e-4 relative) is held on tested input families, a hostile one included; a burst for
  *     which the guarantee cannot be given (a soft symbol too close to the slicer's 0.5 for the hard bit to be certain, a NaN or
- *     infinity anywhere, max|sample| * |1/amp| > 8, a TOA off peakDetect's 1/512 grid, an odd burst geometry) is computed by
+ *     infinity anywhere, max|sample| * |1/amp| > 4, a TOA off peakDetect's 1/512 grid, an odd burst geometry) is computed by
  *     the exact code inside the same launch and comes out IEEE-equal.  nsoft > 148 always takes the exact code.
  *   Takes effect from the next call on (host-side switch, no synchronisation). */
 enum { TRXSIG_SOFT_EXACT = 0, TRXSIG_SOFT_TOLERANCE = 1 };

@@ -551,7 +551,8 @@ class TrxSig:
 
     def set_soft_mode(self, mode):
         """SOFT_EXACT (default: soft bits IEEE-equal to the reference's) or SOFT_TOLERANCE (hard bits, flags, amp, TOA exact;
-        soft bits within 7.4e-5 of the reference's -- trxsig_set_soft_mode)."""
+        soft bits within 3.7e-5 of the reference's, and within 1e-6 or 1e-4 relative on the tested input families --
+        trxsig_set_soft_mode)."""
         self._chk(self.L.trxsig_set_soft_mode(self.h, int(mode)), "trxsig_set_soft_mode")
 
     def soft_mode(self):

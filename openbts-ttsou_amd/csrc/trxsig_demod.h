@@ -326,8 +326,11 @@ __device__ __forceinline__ void fused_demod(const TrxTables *__restrict__ T, cx 
 //   this form:        |re' - R| <= 25.0 u (|c|+|d|) S Z        the sinc grid: tests/test_soft_tolerance.py), Z = max|x|_inf * (|inv.r|+|inv.i|)
 // (scaleVector 2u per component, 22 u for the 21 rounded products and 21 rounded sums, 2u + propagation for the rotation; fma chain 21 u,
 // the folded factor 2u, the last product-difference 2u), so |re - re'| <= 51.2 * 1.5 * 4 u Z < 308 u Z, and a soft bit (re + 1) / 2
-// moves by at most 154 u Z + u = 9.2e-6 Z.  The fast form is only taken when Z <= 8 (and everything is far from the float
-// range's ends), i.e. GUARANTEED |soft' - soft| <= 7.4e-5 on the [0, 1] scale; measured: <= 1.5e-6 (profiles/r05_parity_campaign.txt).
+// moves by at most 154 u Z + u = 9.2e-6 Z.  The fast form is only taken when Z <= 4 (and everything is far from the float
+// range's ends), i.e. GUARANTEED |soft' - soft| <= 3.7e-5 on the [0, 1] scale.  The parity contract (|soft' - soft| <= 1e-6 or
+// <= 1e-4 |soft|) cannot be guaranteed by any rearranged float32 form; it is checked on stated input families
+// (tests/test_tol_contract.py).  ZMAX 4 is what keeps its worst case inside: a family built to cancel large partial sums of the
+// fma chain into the low band (soft < 0.01, where only the 1e-6 floor applies) errs by up to 1.3e-6 at Z = 8, 6.6e-7 at Z = 4.
 // HARD BITS ARE EXACT: a burst with a valid output whose |re'| is not above 512 u Z + 2^-22 (where the two forms could fall on
 // different sides of the slicer's 0.5), or with a NaN anywhere (the test is written so that NaN fails it), or off the 1/512
 // TOA grid, or with an odd geometry, is redone by the value-exact code in the same wave (the samples are still in registers):
@@ -366,7 +369,7 @@ __device__ __forceinline__ float umax_f(float a, float b) {
   const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
   return __uint_as_float(ua > ub ? ua : ub);
 }
-#define TRX_TOL_ZMAX 8.0f                     /* fast form only when max|x| * |1/amp|_1 <= this: |soft' - soft| <= 7.4e-5 guaranteed */
+#define TRX_TOL_ZMAX 4.0f                     /* fast form only when max|x| * |1/amp|_1 <= this: |soft' - soft| <= 3.7e-5 guaranteed */
 #define TRX_TOL_GUARD 3.0517578125e-05f       /* 512 u = 2^-15: |re'| must exceed this times Z (+ 2^-22) for the hard bit to be safe */
 
 // fused_demod_tol_ex: the staging step handed in, as fused_demod_ex -- stage_raw(P, lo) writes sample n, AS IT IS, to position

@@ -111,7 +111,7 @@ hipError_t trx_launch_demod(hipStream_t st, int sps, const TrxTables *dT, const 
                             const int32_t *off, const int32_t *len, int B, const trx_c32 *amp,
                             const float *toa, const uint8_t *flags, int need_mask, float *soft,
                             uint8_t *hard, int nsoft, int stride, TrxProfiler *prof, int soft_tolerance = 0);
-// (soft_tolerance: TRXSIG_SOFT_TOLERANCE -- the rearranged demodulator of trxsig_demod.h; hard bits exact, soft bits within 7.4e-5)
+// (soft_tolerance: TRXSIG_SOFT_TOLERANCE -- the rearranged demodulator of trxsig_demod.h; hard bits exact, soft bits within 3.7e-5)
 
 hipError_t trx_launch_modulate(hipStream_t st, int sps, const TrxTables *dT, const uint8_t *bits, const int32_t *guard,
                                const float *gain, int B, trx_c32 *out, const int32_t *out_off, TrxProfiler *prof);

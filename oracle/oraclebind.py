@@ -84,8 +84,33 @@ def lib():
                                       C.c_int, C.c_int]
         L.so_rach_batch.argtypes = [vp, f32p, i32p, i32p, C.c_int, C.c_float, u8p, f32p, f32p, f32p,
                                     C.c_int, C.c_int]
+        L.so_demod_tol.argtypes = [f32p, C.c_int, C.c_int, c32, C.c_float, f32p, C.c_int, f32p, C.c_float, C.c_int, f32p]
+        L.so_demod_tol_batch.argtypes = [f32p, i32p, i32p, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, f32p, C.c_float, i8p,
+                                         f32p, C.c_int, C.c_int]
+        L.so_demod_batch.argtypes = [vp, f32p, i32p, i32p, C.c_int, f32p, f32p, f32p, C.c_int, C.c_int]
         _lib = L
     return _lib
+
+
+TOL_TAKEN, TOL_HANDED_OVER, TOL_NOT_DEMODULATED = 1, 0, -1     # so_demod_tol's verdicts (oracle/tol_oracle.h)
+
+
+def demod_tol(tables, x, off, length, amp, toa, zmax, nsoft=148, nthreads=8):
+    """The tolerance-mode fast form restated (oracle/tol_oracle.c) over packed bursts with the caller's amp / TOA.
+    tables: the library's host tables (pkg.build_tables_host(sps) viewed as pkg.tables_dtype(), one record), whose
+    sinc_grid and rev the kernel reads.  Returns (verdict int8 [B]: TOL_*, soft float32 [B, nsoft]; rows whose verdict is
+    not TOL_TAKEN are zero)."""
+    sps = int(tables["sps"])
+    grid = np.ascontiguousarray(tables["sinc_grid"], np.float32)
+    assert grid.shape[0] == 512 and grid.shape[1] >= 21
+    rev = c64(tables["rev"])
+    x = c64(x); B = len(off)
+    taken = np.zeros(B, np.int8); soft = np.zeros(B * nsoft, np.float32)
+    lib().so_demod_tol_batch(x, np.ascontiguousarray(off, np.int32), np.ascontiguousarray(length, np.int32), B, sps,
+                             c64(np.broadcast_to(np.asarray(amp, np.complex64), (B,))),
+                             np.ascontiguousarray(np.broadcast_to(np.asarray(toa, np.float32), (B,))), grid, grid.shape[1], rev,
+                             np.float32(zmax), taken, soft, nsoft, nthreads)
+    return taken, soft.reshape(B, nsoft)
 
 
 # so_ctx field layout (sigproc_oracle.h); offsets computed below from the same constants
@@ -297,6 +322,15 @@ class Oracle:
                                np.ascontiguousarray(length, np.int32), B, tsc, np.float32(thresh),
                                ok, amp, toa, soft, nsoft, nthreads)
         return ok, amp.view(np.complex64), toa, soft.reshape(B, nsoft)
+
+    def demod_batch(self, x, off, length, amp, toa, nsoft=148, nthreads=1):
+        """demodulateBurst over packed bursts with the caller's amp / TOA (so_demod_batch): soft [B, nsoft]."""
+        x = c64(x); B = len(off)
+        soft = np.zeros(B * nsoft, np.float32)
+        self.L.so_demod_batch(self.ctx, x, np.ascontiguousarray(off, np.int32), np.ascontiguousarray(length, np.int32), B,
+                              c64(np.broadcast_to(np.asarray(amp, np.complex64), (B,))),
+                              np.ascontiguousarray(np.broadcast_to(np.asarray(toa, np.float32), (B,))), soft, nsoft, nthreads)
+        return soft.reshape(B, nsoft)
 
     def rach_batch(self, x, off, length, thresh=5.0, nsoft=148, nthreads=1):
         x = c64(x); B = len(off)

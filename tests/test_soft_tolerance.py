@@ -9,6 +9,7 @@ import pytest
 import _pkg
 import oraclebind
 import synth
+import tol_family
 
 U = 2.0 ** -24
 
@@ -51,6 +52,9 @@ def test_bound_on_seeded_bursts(pkg, sps, sigmas):
     ok, amp, toa, soft = o.normal_batch(x, off, length, tsc, nsoft=148, nthreads=4)
     worst_ref = worst_tol = worst_pair = 0.0
     n_used = 0
+    # the correctly rounded restatement of the kernel (oracle/tol_oracle.c) on the same bursts
+    verdict, soft_c = oraclebind.demod_tol(T, x, off, length, amp, toa, tol_family.ZMAX)
+    n_ulp = n_cmp = 0
     for b in np.flatnonzero(ok.astype(bool)):
         xs = x[off[b]:off[b] + length[b]]
         N = len(xs)
@@ -81,7 +85,8 @@ def test_bound_on_seeded_bursts(pkg, sps, sigmas):
         inv64 = complex(float(inv_r), float(inv_i))
         R = ((rv.astype(np.complex128) * inv64) * (xw.astype(np.complex128) * tp.astype(np.float64)[None, :]).sum(axis=1)).real
         Z = max(np.abs(xs.real).max(), np.abs(xs.imag).max()) * (abs(float(inv_r)) + abs(float(inv_i)))
-        if Z > 8.0:
+        if Z > tol_family.ZMAX:
+            assert verdict[b] != oraclebind.TOL_TAKEN
             continue                                         # the kernel hands such a burst to the exact code
         n_used += 1
         # (1) the reference order, from the oracle's soft bits: re = 2 soft - 1 where the slicer did not clip
@@ -108,10 +113,23 @@ def test_bound_on_seeded_bursts(pkg, sps, sigmas):
         err_tol = np.abs(re_tol - R)[valid]
         assert np.all(err_tol <= (25.0 * U * cd * S * Z)[valid] + 1e-30), (b, err_tol.max())
         worst_tol = max(worst_tol, (err_tol / (U * Z)).max())
+        # the emulation against the restatement: the same soft bits, and the same verdict from the guard; the only
+        # difference allowed is fma32's double rounding (one unit in the last place, rarely)
+        guard = np.float32(np.float64(Z) * 2.0 ** -15 + 2.0 ** -22)
+        s_emul = np.clip(fma32(re_tol.astype(np.float32), np.full(148, 0.5, np.float32), np.full(148, 0.5, np.float32)), 0, 1)
+        s_emul = np.where(valid, s_emul, np.float32(0.5))
+        if verdict[b] == oraclebind.TOL_TAKEN:
+            assert np.all(np.abs(re_tol[valid]) > guard)
+            d = np.abs(s_emul.view(np.int32).astype(np.int64) - soft_c[b].view(np.int32).astype(np.int64))
+            assert d.max() <= 1, d.max()
+            n_ulp += int((d > 0).sum()); n_cmp += d.size
+        else:
+            assert verdict[b] == oraclebind.TOL_HANDED_OVER and not np.all(np.abs(re_tol[valid]) > guard * 1.000001)
         pair = np.abs(re_tol - re_ref)[unclipped]
         assert np.all(pair <= 308.0 * U * Z + 2 * U)
         worst_pair = max(worst_pair, (pair / (U * Z)).max() if pair.size else 0.0)
     assert n_used >= B // 8, n_used
+    assert n_cmp > 0 and n_ulp <= 1e-4 * n_cmp, (n_ulp, n_cmp)
     # the typical error is far inside the bound: a few u * Z
     assert worst_pair < 40.0, (worst_ref, worst_tol, worst_pair)
 

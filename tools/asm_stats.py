@@ -34,7 +34,7 @@ for m in re.finditer(r"\n(_Z\w+):.*?\n(.*?)\n\.Lfunc_end", text, flags=re.S):
     # trxsig_chan.hip: the per-carrier sums in another order)
     approx = sum(1 for i in ins if "; approx-form" in i)
     # ... and those of the tolerance-mode demodulator (fused_demod_tol, trxsig_demod.h: TRXSIG_SOFT_TOLERANCE -- soft bits within
-    # 7.4e-5 of the reference's, hard bits exact; only in kernels instantiated with TOL = true)
+    # 3.7e-5 of the reference's, hard bits exact; only in kernels instantiated with TOL = true)
     tol = sum(1 for i in ins if "; soft-tolerance" in i)
     fma = [i for i, o in enumerate(ops) if re.match(r"v_(fma_f|mac_f|fmac_f|mad_f|pk_fma)", o)
            and "exact-product" not in ins[i] and "; steering" not in ins[i] and "; approx-form" not in ins[i]
