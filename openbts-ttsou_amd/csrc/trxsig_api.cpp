@@ -136,22 +136,6 @@ int trx_ctx_fail(trxsig_ctx *c, int code, const char *what, hipError_t e) { retu
 TrxProfiler *trx_ctx_profiler(trxsig_ctx *c) { return c ? c->prof : nullptr; }
 namespace {
 
-#define HIPCHK(c, call)                                          \
-  do {                                                           \
-    hipError_t e_ = (call);                                      \
-    if (e_ != hipSuccess) return fail((c), TRXSIG_EHIP, #call, e_); \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 int check_device(int device, std::string &why) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -178,19 +162,19 @@ int finish_create(trxsig_ctx *c) {
 #endif
   }
   c->rach_amp_err = trx_rach_amp_err(c->h_tables);
-  HIPCHK(c, hipEventCreate(&c->ev0));
-  HIPCHK(c, hipEventCreate(&c->ev1));
+  TRX_HIPCHK(c, hipEventCreate(&c->ev0));
+  TRX_HIPCHK(c, hipEventCreate(&c->ev1));
   return TRXSIG_OK;
 }
 
 int ensure_ws(trxsig_ctx *c, int B) {
   if (B <= c->cap_bursts) return TRXSIG_OK;
   int cap = (B + 255) & ~255;
-  if (c->d_rec) { HIPCHK(c, hipFree(c->d_rec)); c->d_rec = nullptr; c->cap_bursts = 0; }
+  if (c->d_rec) { TRX_HIPCHK(c, hipFree(c->d_rec)); c->d_rec = nullptr; c->cap_bursts = 0; }
   size_t per_burst = sizeof(trx_c32) * (size_t)trx_rec_slots(c->sps);
   const size_t rach = sizeof(float) * (size_t)trx_rach_rec_floats(c->sps);
   if (rach > per_burst) per_burst = rach;
-  HIPCHK(c, hipMalloc((void **)&c->d_rec, per_burst * cap));
+  TRX_HIPCHK(c, hipMalloc((void **)&c->d_rec, per_burst * cap));
   c->cap_bursts = cap;
   return TRXSIG_OK;
 }
@@ -198,11 +182,11 @@ int ensure_ws(trxsig_ctx *c, int B) {
 int ensure_ws2(trxsig_ctx *c, int B) {
   if (B <= c->cap2_bursts) return TRXSIG_OK;
   const int cap = (B + 255) & ~255;
-  if (c->d_rec2) { HIPCHK(c, hipDeviceSynchronize()); HIPCHK(c, hipFree(c->d_rec2)); c->d_rec2 = nullptr; c->cap2_bursts = 0; }
+  if (c->d_rec2) { TRX_HIPCHK(c, hipDeviceSynchronize()); TRX_HIPCHK(c, hipFree(c->d_rec2)); c->d_rec2 = nullptr; c->cap2_bursts = 0; }
   size_t per_burst = sizeof(trx_c32) * (size_t)trx_rec_slots(c->sps);
   const size_t rach = sizeof(float) * (size_t)trx_rach_rec_floats(c->sps);
   if (rach > per_burst) per_burst = rach;
-  HIPCHK(c, hipMalloc((void **)&c->d_rec2, per_burst * cap));
+  TRX_HIPCHK(c, hipMalloc((void **)&c->d_rec2, per_burst * cap));
   c->cap2_bursts = cap;
   return TRXSIG_OK;
 }
@@ -210,12 +194,12 @@ int ensure_ws2(trxsig_ctx *c, int B) {
 // the context's stream waits for every demodulator still running on the side stream (TRXSIG_TUNE_DEMOD_BESIDE)
 int join_demod(trxsig_ctx *c) {
   if (c->det_in_flight) {                                   // (flags / amp / TOA of the last call are written on the detect stream)
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pk[c->pb_k], 0));
+    TRX_HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pk[c->pb_k], 0));
     c->det_in_flight = false;
   }
   for (int k = 0; k < 2; k++) {
     if (!c->dm_in_flight[k]) continue;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_dm[k], 0));
+    TRX_HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_dm[k], 0));
     c->dm_in_flight[k] = false;
   }
   return TRXSIG_OK;
@@ -234,8 +218,8 @@ void cu_mask(int n_cu, int det, int layout, bool detect_set, uint32_t *mask, int
   }
 }
 int drop_beside_streams(trxsig_ctx *c) {
-  if (c->side) { HIPCHK(c, hipStreamSynchronize(c->side)); HIPCHK(c, hipStreamDestroy(c->side)); c->side = nullptr; }
-  if (c->det) { HIPCHK(c, hipStreamSynchronize(c->det)); HIPCHK(c, hipStreamDestroy(c->det)); c->det = nullptr; }
+  if (c->side) { TRX_HIPCHK(c, hipStreamSynchronize(c->side)); TRX_HIPCHK(c, hipStreamDestroy(c->side)); c->side = nullptr; }
+  if (c->det) { TRX_HIPCHK(c, hipStreamSynchronize(c->det)); TRX_HIPCHK(c, hipStreamDestroy(c->det)); c->det = nullptr; }
   c->dm_in_flight[0] = c->dm_in_flight[1] = false;
   c->det_in_flight = false;
   return TRXSIG_OK;
@@ -244,46 +228,46 @@ int ensure_beside(trxsig_ctx *c, int B) {
   if (!c->side) {
     if (c->det_cus > 0) {
       hipDeviceProp_t p;
-      HIPCHK(c, hipGetDeviceProperties(&p, c->device));
+      TRX_HIPCHK(c, hipGetDeviceProperties(&p, c->device));
       const int n_cu = p.multiProcessorCount;
       if (c->det_cus >= n_cu || n_cu > 512) return fail(c, TRXSIG_EINVAL, "TRXSIG_TUNE_BESIDE_DET_CUS: more CUs than the device has");
       uint32_t m[16];
       const int words = (n_cu + 31) / 32;
       cu_mask(n_cu, c->det_cus, c->cu_layout, true, m, words);
-      HIPCHK(c, hipExtStreamCreateWithCUMask(&c->det, (uint32_t)words, m));
+      TRX_HIPCHK(c, hipExtStreamCreateWithCUMask(&c->det, (uint32_t)words, m));
       cu_mask(n_cu, c->det_cus, c->cu_layout, false, m, words);
-      HIPCHK(c, hipExtStreamCreateWithCUMask(&c->side, (uint32_t)words, m));
+      TRX_HIPCHK(c, hipExtStreamCreateWithCUMask(&c->side, (uint32_t)words, m));
     } else if (c->side_prio) {
       int lo = 0, hi = 0;                                   // (numerically: `hi` is the greatest priority, the smaller number)
-      HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-      HIPCHK(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, c->side_prio == 1 ? hi : lo));
+      TRX_HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
+      TRX_HIPCHK(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, c->side_prio == 1 ? hi : lo));
     } else {
-      HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+      TRX_HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     }
     if (!c->ev_in) {
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+      TRX_HIPCHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
       for (int k = 0; k < 2; k++) {
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_pk[k], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_dm[k], hipEventDisableTiming));
+        TRX_HIPCHK(c, hipEventCreateWithFlags(&c->ev_pk[k], hipEventDisableTiming));
+        TRX_HIPCHK(c, hipEventCreateWithFlags(&c->ev_dm[k], hipEventDisableTiming));
       }
     }
   }
   if (B <= c->pb_cap) return TRXSIG_OK;
-  HIPCHK(c, hipStreamSynchronize(c->side));
-  if (c->det) HIPCHK(c, hipStreamSynchronize(c->det));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRX_HIPCHK(c, hipStreamSynchronize(c->side));
+  if (c->det) TRX_HIPCHK(c, hipStreamSynchronize(c->det));
+  TRX_HIPCHK(c, hipStreamSynchronize(c->stream));
   const int cap = (B + 255) & ~255;
   for (int k = 0; k < 2; k++) {
-    if (c->pb_flags[k]) { HIPCHK(c, hipFree(c->pb_flags[k])); c->pb_flags[k] = nullptr; }
-    if (c->pb_amp[k]) { HIPCHK(c, hipFree(c->pb_amp[k])); c->pb_amp[k] = nullptr; }
-    if (c->pb_toa[k]) { HIPCHK(c, hipFree(c->pb_toa[k])); c->pb_toa[k] = nullptr; }
+    if (c->pb_flags[k]) { TRX_HIPCHK(c, hipFree(c->pb_flags[k])); c->pb_flags[k] = nullptr; }
+    if (c->pb_amp[k]) { TRX_HIPCHK(c, hipFree(c->pb_amp[k])); c->pb_amp[k] = nullptr; }
+    if (c->pb_toa[k]) { TRX_HIPCHK(c, hipFree(c->pb_toa[k])); c->pb_toa[k] = nullptr; }
     c->dm_in_flight[k] = false;
   }
   c->pb_cap = 0;
   for (int k = 0; k < 2; k++) {
-    HIPCHK(c, hipMalloc((void **)&c->pb_flags[k], (size_t)cap));
-    HIPCHK(c, hipMalloc((void **)&c->pb_amp[k], sizeof(trx_c32) * (size_t)cap));
-    HIPCHK(c, hipMalloc((void **)&c->pb_toa[k], sizeof(float) * (size_t)cap));
+    TRX_HIPCHK(c, hipMalloc((void **)&c->pb_flags[k], (size_t)cap));
+    TRX_HIPCHK(c, hipMalloc((void **)&c->pb_amp[k], sizeof(trx_c32) * (size_t)cap));
+    TRX_HIPCHK(c, hipMalloc((void **)&c->pb_toa[k], sizeof(float) * (size_t)cap));
   }
   c->pb_cap = cap;
   return TRXSIG_OK;
@@ -292,15 +276,15 @@ int ensure_beside(trxsig_ctx *c, int B) {
 #ifdef TRX_TUNING_BUILD
 int ensure_chain(trxsig_ctx *c, int B) {
   if (!c->h_chain_status) {
-    HIPCHK(c, hipHostMalloc((void **)&c->h_chain_status, 64, hipHostMallocMapped));
+    TRX_HIPCHK(c, hipHostMalloc((void **)&c->h_chain_status, 64, hipHostMallocMapped));
     *c->h_chain_status = 0;
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->d_chain_status, c->h_chain_status, 0));
+    TRX_HIPCHK(c, hipHostGetDevicePointer((void **)&c->d_chain_status, c->h_chain_status, 0));
   }
   if (B <= c->det_cap) return TRXSIG_OK;
   const int cap = (B + 255) & ~255;
-  if (c->d_det) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->d_det)); c->d_det = nullptr; c->det_cap = 0; }
-  HIPCHK(c, hipMalloc(&c->d_det, trx_chain_ws_bytes(cap)));
-  HIPCHK(c, hipMemsetAsync(c->d_det, 0, trx_chain_ws_bytes(cap), c->stream));
+  if (c->d_det) { TRX_HIPCHK(c, hipStreamSynchronize(c->stream)); TRX_HIPCHK(c, hipFree(c->d_det)); c->d_det = nullptr; c->det_cap = 0; }
+  TRX_HIPCHK(c, hipMalloc(&c->d_det, trx_chain_ws_bytes(cap)));
+  TRX_HIPCHK(c, hipMemsetAsync(c->d_det, 0, trx_chain_ws_bytes(cap), c->stream));
   c->det_cap = cap;
   return TRXSIG_OK;
 }
@@ -326,18 +310,18 @@ int chain_check(trxsig_ctx *c) {
 
 int ensure_stage(trxsig_ctx *c, size_t bytes) {
   if (bytes <= c->stage_bytes) return TRXSIG_OK;
-  if (c->d_stage) { HIPCHK(c, hipFree(c->d_stage)); c->d_stage = nullptr; c->stage_bytes = 0; }
+  if (c->d_stage) { TRX_HIPCHK(c, hipFree(c->d_stage)); c->d_stage = nullptr; c->stage_bytes = 0; }
   bytes = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
-  HIPCHK(c, hipMalloc(&c->d_stage, bytes));
+  TRX_HIPCHK(c, hipMalloc(&c->d_stage, bytes));
   c->stage_bytes = bytes;
   return TRXSIG_OK;
 }
 
 int ensure_pin(trxsig_ctx *c, size_t bytes) {
   if (bytes <= c->pin_bytes) return TRXSIG_OK;
-  if (c->h_pin) { HIPCHK(c, hipHostFree(c->h_pin)); c->h_pin = nullptr; c->pin_bytes = 0; }
+  if (c->h_pin) { TRX_HIPCHK(c, hipHostFree(c->h_pin)); c->h_pin = nullptr; c->pin_bytes = 0; }
   bytes = (bytes + 0xFFFF) & ~(size_t)0xFFFF;
-  HIPCHK(c, hipHostMalloc(&c->h_pin, bytes, hipHostMallocDefault));
+  TRX_HIPCHK(c, hipHostMalloc(&c->h_pin, bytes, hipHostMallocDefault));
   c->pin_bytes = bytes;
   return TRXSIG_OK;
 }
@@ -345,6 +329,70 @@ int ensure_pin(trxsig_ctx *c, size_t bytes) {
 bool bad_batch(const void *s, const void *o, const void *l, int B) { return B < 0 || (B > 0 && (!s || !o || !l)); }
 
 }  // namespace
+
+// ---- the *_host forms' round trip (trxsig_ctx.h) -------------------------------------------------------
+TrxHostCall::TrxHostCall(trxsig_ctx *c) : c_(c), guard_(c->device) {}
+
+TrxHostCall::~TrxHostCall() {
+  if (queued_) (void)hipStreamSynchronize(c_->stream);
+}
+
+int TrxHostCall::stage() {
+  trxsig_ctx *c = c_;
+  size_t end = 0, in_end = 0, up_end = 0;
+  for (Kind kind : {kIn, kInOut, kOut}) {
+    for (Region &r : regs_)
+      if (r.kind == kind) { r.off = end; end += ((r.dev_bytes ? r.dev_bytes : 1) + 255) & ~(size_t)255; }
+    if (kind == kIn) in_end = end;
+    if (kind == kInOut) up_end = end;
+  }
+  dl_lo_ = dl_hi_ = in_end;
+  for (const Region &r : regs_)
+    if (r.dst && r.bytes && r.off + r.bytes > dl_hi_) dl_hi_ = r.off + r.bytes;
+  int rc = ensure_stage(c, end);
+  if (rc != TRXSIG_OK) return rc;
+  d_ = (char *)c->d_stage;
+  if (end <= kPinnedMax) {
+    if ((rc = ensure_pin(c, end)) != TRXSIG_OK) return rc;
+    m_ = (char *)c->h_pin;
+  }
+  for (const Region &r : regs_) {
+    const void *src = r.inline_val ? r.v : r.src;
+    if (r.kind == kOut || !src || !r.bytes) continue;
+    if (m_) { std::memcpy(m_ + r.off, src, r.bytes); continue; }
+    queued_ = true;
+    TRX_HIPCHK(c, hipMemcpyAsync(d_ + r.off, src, r.bytes, hipMemcpyHostToDevice, c->stream));
+  }
+  if (m_ && up_end) {
+    queued_ = true;
+    TRX_HIPCHK(c, hipMemcpyAsync(d_, m_, up_end, hipMemcpyHostToDevice, c->stream));
+  }
+  for (const Region &r : regs_)
+    if (r.zero && r.dev_bytes) TRX_HIPCHK(c, hipMemsetAsync(d_ + r.off, 0, r.dev_bytes, c->stream));
+  return TRXSIG_OK;
+}
+
+int TrxHostCall::finish(int rc) {
+  trxsig_ctx *c = c_;
+  if (rc == TRXSIG_OK && dl_hi_ > dl_lo_) {
+    queued_ = true;
+    if (m_) {
+      TRX_HIPCHK(c, hipMemcpyAsync(m_ + dl_lo_, d_ + dl_lo_, dl_hi_ - dl_lo_, hipMemcpyDeviceToHost, c->stream));
+    } else {
+      for (const Region &r : regs_)
+        if (r.dst && r.bytes) TRX_HIPCHK(c, hipMemcpyAsync(r.dst, d_ + r.off, r.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  if (queued_) {
+    queued_ = false;
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == TRXSIG_OK && e != hipSuccess) return fail(c, TRXSIG_EHIP, "hipStreamSynchronize(c->stream)", e);
+  }
+  if (rc == TRXSIG_OK && m_)
+    for (const Region &r : regs_)
+      if (r.dst && r.bytes) std::memcpy(r.dst, m_ + r.off, r.bytes);
+  return rc;
+}
 
 extern "C" {
 
@@ -360,7 +408,7 @@ int trxsig_create(trxsig_ctx **out, int device, int sps) {
   trxsig_ctx *c = new (std::nothrow) trxsig_ctx;
   if (!c) return TRXSIG_ENOMEM;
   c->device = device; c->sps = sps;
-  DeviceGuard g(device);
+  TrxDeviceGuard g(device);
   c->h_tables = (TrxTables *)std::malloc(sizeof(TrxTables));
   if (!c->h_tables || trx_build_tables(c->h_tables, sps) != 0) { trxsig_destroy(c); return TRXSIG_ENOMEM; }
   if (hipMalloc((void **)&c->d_tables, sizeof(TrxTables)) != hipSuccess ||
@@ -383,7 +431,7 @@ int trxsig_create_from_tables(trxsig_ctx **out, int device, const void *d_blob, 
   trxsig_ctx *c = new (std::nothrow) trxsig_ctx;
   if (!c) return TRXSIG_ENOMEM;
   c->device = device;
-  DeviceGuard g(device);
+  TrxDeviceGuard g(device);
   c->h_tables = (TrxTables *)std::malloc(sizeof(TrxTables));
   if (!c->h_tables) { trxsig_destroy(c); return TRXSIG_ENOMEM; }
   if (hipMalloc((void **)&c->d_tables, sizeof(TrxTables)) != hipSuccess ||
@@ -417,7 +465,7 @@ void trxsig_destroy(trxsig_ctx *c) {
 }
 static void destroy_now(trxsig_ctx *c) {
   {
-    DeviceGuard g(c->device);
+    TrxDeviceGuard g(c->device);
     if (c->d_tables) (void)hipFree(c->d_tables);
     if (c->d_rec) (void)hipFree(c->d_rec);
     if (c->d_rec2) (void)hipFree(c->d_rec2);
@@ -455,18 +503,18 @@ int trxsig_get_device(trxsig_ctx *c) { return c ? c->device : -1; }
 int trxsig_synchronize(trxsig_ctx *c) {
   if (!c) return TRXSIG_EINVAL;
   {
-    DeviceGuard g(c->device);
+    TrxDeviceGuard g(c->device);
     int rc = join_demod(c);
     if (rc != TRXSIG_OK) return rc;
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRX_HIPCHK(c, hipStreamSynchronize(c->stream));
   return chain_check(c);
 }
 const char *trxsig_last_error(const trxsig_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
 int trxsig_reserve(trxsig_ctx *c, int max_bursts) {
   if (!c || max_bursts < 0) return TRXSIG_EINVAL;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   return ensure_ws(c, max_bursts);
 }
 
@@ -478,8 +526,8 @@ int trxsig_tables_build_host(int sps, void *h_buf, size_t cap) {
 void *trxsig_tables_device(trxsig_ctx *c) { return c ? (void *)c->d_tables : nullptr; }
 int trxsig_tables_export(trxsig_ctx *c, void *h_buf, size_t cap) {
   if (!c || !h_buf || cap < sizeof(TrxTables)) return TRXSIG_EINVAL;
-  DeviceGuard g(c->device);
-  HIPCHK(c, hipMemcpy(h_buf, c->d_tables, sizeof(TrxTables), hipMemcpyDeviceToHost));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, hipMemcpy(h_buf, c->d_tables, sizeof(TrxTables), hipMemcpyDeviceToHost));
   return TRXSIG_OK;
 }
 
@@ -512,7 +560,7 @@ int trxsig_detect_demod_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples,
       soft_stride < nsoft || (B > 0 && (!d_flags || !d_amp || !d_toa || (nsoft > 0 && !d_soft))))
     return fail(c, TRXSIG_EINVAL, "trxsig_detect_demod_normal_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = chain_check(c);
   if (rc != TRXSIG_OK) return rc;
 #ifdef TRX_TUNING_BUILD
@@ -520,7 +568,7 @@ int trxsig_detect_demod_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples,
     // one launch: detect workgroups hand over to demodulate workgroups inside it (trxsig_chain.hip)
     rc = ensure_chain(c, B);
     if (rc != TRXSIG_OK) return rc;
-    HIPCHK(c, trx_launch_normal_chain(c->stream, c->sps, c->d_tables, c->h_tables, (const trx_c32 *)d_samples, d_offset,
+    TRX_HIPCHK(c, trx_launch_normal_chain(c->stream, c->sps, c->d_tables, c->h_tables, (const trx_c32 *)d_samples, d_offset,
                                       d_length, B, tsc, detect_thresh, energy_thresh, d_flags, (trx_c32 *)d_amp, d_toa,
                                       d_avgpwr, d_soft, d_hard, nsoft, soft_stride, c->d_det, c->d_chain_status,
                                       c->chain_lag, c->chain_spin, c->generic_taps, c->prof, c->chain_dbg, c->soft_mode));
@@ -532,18 +580,18 @@ int trxsig_detect_demod_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples,
 #ifdef TRX_TUNING_BUILD
   if (c->variant == 4) {
     // detection (correlation + speculative bisection, four bursts per wave) in one kernel, then k_demod
-    HIPCHK(c, trx_launch_normal_fused(c->stream, c->sps, 16, c->d_tables, c->h_tables, (const trx_c32 *)d_samples,
+    TRX_HIPCHK(c, trx_launch_normal_fused(c->stream, c->sps, 16, c->d_tables, c->h_tables, (const trx_c32 *)d_samples,
                                       d_offset, d_length, B, tsc, detect_thresh, energy_thresh, d_flags,
                                       (trx_c32 *)d_amp, d_toa, d_avgpwr, nullptr, nullptr, 0, 0, c->generic_taps, c->prof));
     if (nsoft > 0)
-      HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
+      TRX_HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                                  (const trx_c32 *)d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_soft, d_hard, nsoft,
                                  soft_stride, c->prof, c->soft_mode));
     return TRXSIG_OK;
   }
   if (c->variant >= 1 && c->variant <= 3 && nsoft <= 148) {
     // one kernel for the whole leg: every burst crosses HBM once (k_normal_fused)
-    HIPCHK(c, trx_launch_normal_fused(c->stream, c->sps, c->variant == 1 ? 64 : (c->variant == 2 ? 32 : 16), c->d_tables, c->h_tables,
+    TRX_HIPCHK(c, trx_launch_normal_fused(c->stream, c->sps, c->variant == 1 ? 64 : (c->variant == 2 ? 32 : 16), c->d_tables, c->h_tables,
                                       (const trx_c32 *)d_samples, d_offset, d_length, B, tsc, detect_thresh,
                                       energy_thresh, d_flags, (trx_c32 *)d_amp, d_toa, d_avgpwr, d_soft, d_hard, nsoft,
                                       soft_stride, c->generic_taps, c->prof, c->soft_mode));
@@ -560,35 +608,35 @@ int trxsig_detect_demod_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples,
     if (c->det) {                                           // masked detect stream: it starts when the caller's inputs are ready
       sdet = c->det;
       if (c->beside_nodeps < 1) {
-        HIPCHK(c, hipEventRecord(c->ev_in, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(sdet, c->ev_in, 0));
+        TRX_HIPCHK(c, hipEventRecord(c->ev_in, c->stream));
+        TRX_HIPCHK(c, hipStreamWaitEvent(sdet, c->ev_in, 0));
       }
     }
     if (c->dm_in_flight[k]) {                               // the demodulator that read this copy two calls ago
-      if (c->beside_nodeps < 2) HIPCHK(c, hipStreamWaitEvent(sdet, c->ev_dm[k], 0));
+      if (c->beside_nodeps < 2) TRX_HIPCHK(c, hipStreamWaitEvent(sdet, c->ev_dm[k], 0));
       c->dm_in_flight[k] = false;
     }
   } else {
     rc = join_demod(c);                                     // (outputs of this call must not be overtaken by an older demodulator)
     if (rc != TRXSIG_OK) return rc;
   }
-  HIPCHK(c, trx_launch_tsc_detect(sdet, c->sps, c->d_tables, c->h_tables, (const trx_c32 *)d_samples, d_offset, d_length,
+  TRX_HIPCHK(c, trx_launch_tsc_detect(sdet, c->sps, c->d_tables, c->h_tables, (const trx_c32 *)d_samples, d_offset, d_length,
                                   B, tsc, detect_thresh, energy_thresh, c->d_rec, c->cap_bursts, d_flags,
                                   (trx_c32 *)d_amp, d_toa, d_avgpwr, c->generic_taps | (c->spec_peak == 1 ? 2 : 0) | (c->spec_peak == 2 ? 4 : 0), c->prof));
   if (beside) {
     // the demodulator reads its own copy of the verdict: the next call's k_tsc_peak2 overwrites d_flags / d_amp / d_toa beside it
-    HIPCHK(c, trx_launch_copy_verdict(sdet, d_flags, (const trx_c32 *)d_amp, d_toa, B, c->pb_flags[k], c->pb_amp[k], c->pb_toa[k]));
-    HIPCHK(c, hipEventRecord(c->ev_pk[k], sdet));
+    TRX_HIPCHK(c, trx_launch_copy_verdict(sdet, d_flags, (const trx_c32 *)d_amp, d_toa, B, c->pb_flags[k], c->pb_amp[k], c->pb_toa[k]));
+    TRX_HIPCHK(c, hipEventRecord(c->ev_pk[k], sdet));
     if (c->det) c->det_in_flight = true;
-    if (c->beside_nodeps < 2) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_pk[k], 0));
-    HIPCHK(c, trx_launch_demod(c->side, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, c->pb_amp[k], c->pb_toa[k],
+    if (c->beside_nodeps < 2) TRX_HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_pk[k], 0));
+    TRX_HIPCHK(c, trx_launch_demod(c->side, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, c->pb_amp[k], c->pb_toa[k],
                                c->pb_flags[k], TRXSIG_F_DETECT, d_soft, d_hard, nsoft, soft_stride, c->prof, c->soft_mode));
-    HIPCHK(c, hipEventRecord(c->ev_dm[k], c->side));
+    TRX_HIPCHK(c, hipEventRecord(c->ev_dm[k], c->side));
     c->dm_in_flight[k] = true;
     return TRXSIG_OK;
   }
   if (nsoft > 0)
-    HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
+    TRX_HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                                (const trx_c32 *)d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_soft, d_hard, nsoft,
                                soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
@@ -606,10 +654,10 @@ int trx_ctx_rx_normal(trxsig_ctx *c, const TrxRxGen &gen, int B, int tsc, float 
       (B > 0 && (!d_flags || !d_amp || !d_toa || (nsoft > 0 && !d_soft))))
     return fail(c, TRXSIG_EINVAL, "trxsig_rxfe_push_detect_demod_normal: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_ws(c, B);
   if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, trx_launch_rx_normal(on ? on : c->stream, c->d_tables, c->h_tables, gen, B, tsc, detect_thresh, energy_thresh, c->d_rec, c->cap_bursts,
+  TRX_HIPCHK(c, trx_launch_rx_normal(on ? on : c->stream, c->d_tables, c->h_tables, gen, B, tsc, detect_thresh, energy_thresh, c->d_rec, c->cap_bursts,
                                  d_flags, (trx_c32 *)d_amp, d_toa, d_avgpwr, d_soft, d_hard, nsoft, soft_stride, c->generic_taps, c->prof,
                                  c->soft_mode));
   return TRXSIG_OK;
@@ -620,10 +668,10 @@ int trx_ctx_rx_rach(trxsig_ctx *c, const TrxRxGen &gen, const int32_t *d_len, in
   if (c->sps != 4) return fail(c, TRXSIG_EINVAL, "the fused receive front end needs sps == 4");
   if (B < 0 || (B > 0 && (!d_len || !d_flags || !d_amp || !d_toa))) return fail(c, TRXSIG_EINVAL, "trx_ctx_rx_rach: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = own_records ? ensure_ws2(c, B) : ensure_ws(c, B);
   if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, trx_launch_rx_rach(c->stream, c->d_tables, gen, d_len, B, detect_thresh, energy_thresh, c->rach_amp_err,
+  TRX_HIPCHK(c, trx_launch_rx_rach(c->stream, c->d_tables, gen, d_len, B, detect_thresh, energy_thresh, c->rach_amp_err,
                                (float *)(own_records ? c->d_rec2 : c->d_rec), own_records ? c->cap2_bursts : c->cap_bursts, d_flags,
                                (trx_c32 *)d_amp, d_toa, d_avgpwr, c->prof));
   return TRXSIG_OK;
@@ -635,8 +683,8 @@ int trx_ctx_rx_demod(trxsig_ctx *c, const TrxRxGen &gen, int B, const trxsig_c32
   if (B < 0 || nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || (nsoft > 0 && !d_soft))))
     return fail(c, TRXSIG_EINVAL, "trx_ctx_rx_demod: bad argument");
   if (B == 0 || nsoft == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_rx_demod(c->stream, c->d_tables, gen, B, (const trx_c32 *)d_amp, d_toa, d_enable, need_mask, d_soft, nullptr, nsoft,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_rx_demod(c->stream, c->d_tables, gen, B, (const trx_c32 *)d_amp, d_toa, d_enable, need_mask, d_soft, nullptr, nsoft,
                                 soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
 }
@@ -649,8 +697,8 @@ int trx_ctx_demod_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32
       (B > 0 && (!d_amp || !d_toa || !d_soft || !d_enable)))
     return fail(c, TRXSIG_EINVAL, "trx_ctx_demod_masked: bad argument");
   if (B == 0 || nsoft == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                              (const trx_c32 *)d_amp, d_toa, d_enable, need_mask, d_soft, nullptr, nsoft, soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
 }
@@ -665,19 +713,19 @@ int trxsig_detect_demod_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, c
       (B > 0 && (!d_flags || !d_amp || !d_toa || (nsoft > 0 && !d_soft))))
     return fail(c, TRXSIG_EINVAL, "trxsig_detect_demod_rach_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_ws(c, B);
   if (rc != TRXSIG_OK) return rc;
   if (c->rach_variant >= 1)
-    HIPCHK(c, trx_launch_rach_fast(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
+    TRX_HIPCHK(c, trx_launch_rach_fast(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                                    detect_thresh, energy_thresh, c->rach_amp_err, (float *)c->d_rec, c->cap_bursts, c->rach_variant == 2,
                                    d_flags, (trx_c32 *)d_amp, d_toa, d_avgpwr, c->prof));
   else
-    HIPCHK(c, trx_launch_rach_detect(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length,
+    TRX_HIPCHK(c, trx_launch_rach_detect(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length,
                                      B, detect_thresh, energy_thresh, (float *)c->d_rec, c->cap_bursts, d_flags,
                                      (trx_c32 *)d_amp, d_toa, d_avgpwr, c->prof));
   if (nsoft > 0)
-    HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
+    TRX_HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                                (const trx_c32 *)d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_soft, d_hard, nsoft,
                                soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
@@ -692,8 +740,8 @@ int trxsig_demodulate_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const in
       (B > 0 && (!d_amp || !d_toa || !d_soft)))
     return fail(c, TRXSIG_EINVAL, "trxsig_demodulate_batch: bad argument");
   if (B == 0 || nsoft == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                              (const trx_c32 *)d_amp, d_toa, d_enable, 0, d_soft, d_hard, nsoft, soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
 }
@@ -704,8 +752,8 @@ static constexpr int EQ_XS = 160;
 static int ensure_eq(trxsig_ctx *c, int B) {
   if (B > c->eq_cap) {
     const int cap = (B + 255) & ~255;
-    if (c->d_eq) { HIPCHK(c, hipFree(c->d_eq)); c->d_eq = nullptr; c->eq_cap = 0; }
-    HIPCHK(c, hipMalloc((void **)&c->d_eq, (size_t)cap * (4 + 8 * 7 + 8 * 5 + 8 * EQ_XS)));
+    if (c->d_eq) { TRX_HIPCHK(c, hipFree(c->d_eq)); c->d_eq = nullptr; c->eq_cap = 0; }
+    TRX_HIPCHK(c, hipMalloc((void **)&c->d_eq, (size_t)cap * (4 + 8 * 7 + 8 * 5 + 8 * EQ_XS)));
     c->eq_cap = cap;
   }
   return TRXSIG_OK;
@@ -721,10 +769,10 @@ int trxsig_estimate_dfe_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const 
       (B > 0 && (!d_flags || !d_amp || !d_toa || !d_chan_off || !d_w || !d_b)))
     return fail(c, TRXSIG_EINVAL, "trxsig_estimate_dfe_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_eq(c, B);
   if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, trx_launch_estimate_dfe(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, tsc,
+  TRX_HIPCHK(c, trx_launch_estimate_dfe(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, tsc,
                                     detect_thresh, snr_thresh, snr_value, variant52m, max_toa, d_flags, (trx_c32 *)d_amp, d_toa,
                                     (float *)c->d_eq, d_chan_off, (trx_c32 *)d_w, (trx_c32 *)d_b, nullptr, c->prof, nullptr, nullptr,
                                     trx_eq52_geometry(c->h_tables, tsc)));
@@ -740,14 +788,14 @@ int trxsig_channel_estimate_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, co
       (B > 0 && (!d_flags || !d_amp || !d_toa || !d_chan_off || !d_chan)))
     return fail(c, TRXSIG_EINVAL, "trxsig_channel_estimate_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_eq(c, B);
   if (rc != TRXSIG_OK) return rc;
   // (the kernel also designs a DFE for a nominal SNR into scratch: toa_eq [B], w [7 B], b [5 B] of the equaliser workspace)
   float *toa_eq = (float *)c->d_eq;
   trx_c32 *w = (trx_c32 *)(c->d_eq + sizeof(float) * (size_t)c->eq_cap);
   trx_c32 *bq = w + (size_t)7 * c->eq_cap;
-  HIPCHK(c, trx_launch_estimate_dfe(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, tsc,
+  TRX_HIPCHK(c, trx_launch_estimate_dfe(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, tsc,
                                     detect_thresh, -1.0f, 1.0f, variant52m, max_toa, d_flags, (trx_c32 *)d_amp, d_toa, toa_eq,
                                     d_chan_off, w, bq, (trx_c32 *)d_chan, c->prof, nullptr, nullptr, trx_eq52_geometry(c->h_tables, tsc)));
   return TRXSIG_OK;
@@ -758,8 +806,8 @@ int trxsig_design_dfe_batch(trxsig_ctx *c, const trxsig_c32 *d_chan, const trxsi
   if (!c) return TRXSIG_EINVAL;
   if (B < 0 || (B > 0 && (!d_chan || !d_snr || !d_w || !d_b))) return fail(c, TRXSIG_EINVAL, "trxsig_design_dfe_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_design_dfe(c->stream, (const trx_c32 *)d_chan, (const trx_c32 *)d_amp, d_snr, B, (trx_c32 *)d_w,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_design_dfe(c->stream, (const trx_c32 *)d_chan, (const trx_c32 *)d_amp, d_snr, B, (trx_c32 *)d_w,
                                   (trx_c32 *)d_b, c->prof));
   return TRXSIG_OK;
 }
@@ -775,11 +823,11 @@ int trxsig_equalize_taps_batch_fmt(trxsig_ctx *c, const void *d_samples, int sam
       (B > 0 && (!d_amp || !d_toa_eq || !d_enable || !d_w || !d_b || (nsoft > 0 && !d_soft))))
     return fail(c, TRXSIG_EINVAL, "trxsig_equalize_taps_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_eq(c, B);
   if (rc != TRXSIG_OK) return rc;
   trx_c32 *xd = (trx_c32 *)(c->d_eq + (size_t)c->eq_cap * (4 + 56 + 40));
-  HIPCHK(c, trx_launch_equalize_taps(c->stream, c->d_tables, d_samples, sample_format, d_offset, d_length, B,
+  TRX_HIPCHK(c, trx_launch_equalize_taps(c->stream, c->d_tables, d_samples, sample_format, d_offset, d_length, B,
                                      (const trx_c32 *)d_amp, d_toa_eq, d_enable, (const trx_c32 *)d_w, (const trx_c32 *)d_b,
                                      xd, EQ_XS, d_soft, d_hard, nsoft, soft_stride, c->prof));
   return TRXSIG_OK;
@@ -815,7 +863,7 @@ int trxsig_equalize_normal_batch_fmt(trxsig_ctx *c, const void *d_samples, int s
       (B > 0 && (!d_flags || !d_amp || !d_toa || (nsoft > 0 && !d_soft))))
     return fail(c, TRXSIG_EINVAL, "trxsig_equalize_normal_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   constexpr int XS = EQ_XS;
   int rc = ensure_eq(c, B);
   if (rc != TRXSIG_OK) return rc;
@@ -826,7 +874,7 @@ int trxsig_equalize_normal_batch_fmt(trxsig_ctx *c, const void *d_samples, int s
   trx_c32 *xd = (trx_c32 *)(c->d_eq + cap * (4 + 56 + 40));
   if (d_w) w = (trx_c32 *)d_w;
   if (d_b) bq = (trx_c32 *)d_b;
-  HIPCHK(c, trx_launch_equalize(c->stream, c->d_tables, d_samples, sample_format, d_offset, d_length, B, tsc,
+  TRX_HIPCHK(c, trx_launch_equalize(c->stream, c->d_tables, d_samples, sample_format, d_offset, d_length, B, tsc,
                                 detect_thresh, energy_thresh, variant52m, max_toa, d_flags, (trx_c32 *)d_amp, d_toa,
                                 toa_eq, w, bq, xd, XS, d_soft, d_hard, nsoft, soft_stride, c->prof, trx_eq52_geometry(c->h_tables, tsc)));
   return TRXSIG_OK;
@@ -840,12 +888,12 @@ int trx_ctx_group_estimate(trxsig_ctx *c, const trxsig_c32 *d_samples, const int
   if (!c) return TRXSIG_EINVAL;
   if (c->sps != 1) return fail(c, TRXSIG_EINVAL, "the channel estimate / DFE path needs sps == 1");
   if (B <= 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_eq(c, B);
   if (rc != TRXSIG_OK) return rc;
   // (the list of the marked bursts goes where trx_ctx_group_equalize will afterwards put the delayed bursts)
   int32_t *work = (int32_t *)(c->d_eq + (size_t)c->eq_cap * (4 + 56 + 40));
-  HIPCHK(c, trx_launch_estimate_dfe(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, tsc, 3.0f, -1.0f, 1.0f,
+  TRX_HIPCHK(c, trx_launch_estimate_dfe(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, tsc, 3.0f, -1.0f, 1.0f,
                                     0, 0, d_flags, (trx_c32 *)d_amp, d_toa, d_toa_eq, d_chan_off, (trx_c32 *)d_w, (trx_c32 *)d_b,
                                     nullptr, c->prof, d_enable, d_snr, trx_eq52_geometry(c->h_tables, tsc), d_enable ? (d_listed ? d_listed : work) : nullptr,
                                     d_enable && d_listed));
@@ -857,11 +905,11 @@ int trx_ctx_group_equalize(trxsig_ctx *c, const trxsig_c32 *d_samples, const int
   if (!c) return TRXSIG_EINVAL;
   if (c->sps != 1) return fail(c, TRXSIG_EINVAL, "equalizeBurst needs sps == 1");
   if (B <= 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = ensure_eq(c, B);
   if (rc != TRXSIG_OK) return rc;
   trx_c32 *xd = (trx_c32 *)(c->d_eq + (size_t)c->eq_cap * (4 + 56 + 40));
-  HIPCHK(c, trx_launch_equalize_taps(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, (const trx_c32 *)d_amp,
+  TRX_HIPCHK(c, trx_launch_equalize_taps(c->stream, c->d_tables, d_samples, TRXSIG_SAMPLES_C32, d_offset, d_length, B, (const trx_c32 *)d_amp,
                                      d_toa_eq, d_gate, (const trx_c32 *)d_w_tab, (const trx_c32 *)d_b_tab, xd, EQ_XS, d_soft, nullptr,
                                      nsoft, soft_stride, c->prof, d_tap_ix));
   return TRXSIG_OK;
@@ -875,8 +923,8 @@ int trxsig_modulate_batch(trxsig_ctx *c, const uint8_t *d_bits, const int32_t *d
   if (B < 0 || (B > 0 && (!d_bits || !d_guard || !d_out || !d_out_offset)))
     return fail(c, TRXSIG_EINVAL, "trxsig_modulate_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_modulate(c->stream, c->sps, c->d_tables, d_bits, d_guard, d_gain, B, (trx_c32 *)d_out,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_modulate(c->stream, c->sps, c->d_tables, d_bits, d_guard, d_gain, B, (trx_c32 *)d_out,
                                 d_out_offset, c->prof));
   return TRXSIG_OK;
 }
@@ -895,8 +943,8 @@ int trxsig_resample_batch(trxsig_ctx *c, const trxsig_c32 *d_in, int n_in, int64
   const int nout = trxsig_resample_out_len(n_in, P, Q);
   if (S == 0 || nout == 0) return TRXSIG_OK;
   if (S > 65535) return fail(c, TRXSIG_EINVAL, "trxsig_resample_batch: more than 65535 streams");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_resample(c->stream, (const trx_c32 *)d_in, n_in, in_stride, S, P, Q, d_lpf, L,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_resample(c->stream, (const trx_c32 *)d_in, n_in, in_stride, S, P, Q, d_lpf, L,
                                 (trx_c32 *)d_out, out_stride, nout, c->prof));
   return TRXSIG_OK;
 }
@@ -908,48 +956,42 @@ int trxsig_resample_host(trxsig_ctx *c, const trxsig_c32 *h_in, int n_in, int P,
     return fail(c, TRXSIG_EINVAL, "trxsig_resample_host: bad argument");
   const int nout = trxsig_resample_out_len(n_in, P, Q);
   if (nout > out_cap) return fail(c, TRXSIG_EINVAL, "trxsig_resample_host: output buffer too small");
-  DeviceGuard g(c->device);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_in = 0, o_lpf = up(8 * (size_t)n_in), o_out = o_lpf + up(4 * (size_t)L), end = o_out + up(8 * (size_t)nout);
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  HIPCHK(c, hipMemcpyAsync(d + o_in, h_in, 8 * (size_t)n_in, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_lpf, h_lpf, 4 * (size_t)L, hipMemcpyHostToDevice, c->stream));
-  rc = trxsig_resample_batch(c, (const trxsig_c32 *)(d + o_in), n_in, n_in, 1, P, Q, (const float *)(d + o_lpf), L,
-                             (trxsig_c32 *)(d + o_out), nout);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_out, 8 * (size_t)nout, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return nout;
+  TrxHostCall hc(c);
+  const auto in = hc.in(h_in, n_in);
+  const auto lpf = hc.in(h_lpf, L);
+  const auto out = hc.out(h_out, nout);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK) rc = trxsig_resample_batch(c, hc.dev(in), n_in, n_in, 1, P, Q, hc.dev(lpf), L, hc.dev(out), nout);
+  rc = hc.finish(rc);
+  return rc == TRXSIG_OK ? nout : rc;
 }
 
 int trxsig_unpack_int16(trxsig_ctx *c, const int16_t *d_iq, int64_t n, int swap_iq, trxsig_c32 *d_out) {
   if (!c) return TRXSIG_EINVAL;
   if (n < 0 || (n > 0 && (!d_iq || !d_out))) return fail(c, TRXSIG_EINVAL, "trxsig_unpack_int16: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_convert(c->stream, 0, d_iq, n, swap_iq, d_out, c->prof));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_convert(c->stream, 0, d_iq, n, swap_iq, d_out, c->prof));
   return TRXSIG_OK;
 }
 int trxsig_pack_int16_scaled(trxsig_ctx *c, const trxsig_c32 *d_in, int64_t n, float gain, int16_t *d_iq) {
   if (!c) return TRXSIG_EINVAL;
   if (n < 0 || (n > 0 && (!d_iq || !d_in))) return fail(c, TRXSIG_EINVAL, "trxsig_pack_int16_scaled: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_convert(c->stream, 1, d_in, n, 0, d_iq, c->prof, gain));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_convert(c->stream, 1, d_in, n, 0, d_iq, c->prof, gain));
   return TRXSIG_OK;
 }
 int trxsig_unpack_half(trxsig_ctx *c, const uint16_t *d_iq, int64_t n, trxsig_c32 *d_out) {
   if (!c) return TRXSIG_EINVAL;
   if (n < 0 || (n > 0 && (!d_iq || !d_out))) return fail(c, TRXSIG_EINVAL, "trxsig_unpack_half: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_convert(c->stream, 2, d_iq, n, 0, d_out, c->prof));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_convert(c->stream, 2, d_iq, n, 0, d_out, c->prof));
   return TRXSIG_OK;
 }
 int trxsig_pack_int16(trxsig_ctx *c, const trxsig_c32 *d_in, int64_t n, int16_t *d_iq) {
   if (!c) return TRXSIG_EINVAL;
   if (n < 0 || (n > 0 && (!d_iq || !d_in))) return fail(c, TRXSIG_EINVAL, "trxsig_pack_int16: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_convert(c->stream, 1, d_in, n, 0, d_iq, c->prof));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_convert(c->stream, 1, d_in, n, 0, d_iq, c->prof));
   return TRXSIG_OK;
 }
 
@@ -963,25 +1005,16 @@ int trxsig_modulate_host(trxsig_ctx *c, const uint8_t *h_bits, const int32_t *h_
     if (h_guard[b] < 0 || h_guard[b] > 9 || h_out_offset[b] < 0 ||
         (int64_t)h_out_offset[b] + (int64_t)c->sps * (148 + h_guard[b]) > out_samples)
       return fail(c, TRXSIG_EINVAL, "trxsig_modulate_host: guard/offset out of range");
-  DeviceGuard g(c->device);
-  auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-  const size_t o_bits = 0, o_g = up((size_t)B * 148), o_off = o_g + up(4 * (size_t)B), o_gain = o_off + up(4 * (size_t)B),
-               o_out = o_gain + up(4 * (size_t)B), end = o_out + up(8 * (size_t)out_samples);
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  HIPCHK(c, hipMemcpyAsync(d + o_bits, h_bits, (size_t)B * 148, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_g, h_guard, 4 * (size_t)B, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_off, h_out_offset, 4 * (size_t)B, hipMemcpyHostToDevice, c->stream));
-  if (h_gain) HIPCHK(c, hipMemcpyAsync(d + o_gain, h_gain, 4 * (size_t)B, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(d + o_out, 0, 8 * (size_t)out_samples, c->stream));
-  rc = trxsig_modulate_batch(c, (const uint8_t *)(d + o_bits), (const int32_t *)(d + o_g),
-                             h_gain ? (const float *)(d + o_gain) : nullptr, B, (trxsig_c32 *)(d + o_out),
-                             (const int32_t *)(d + o_off));
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_out, 8 * (size_t)out_samples, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto bits = hc.in(h_bits, (size_t)B * 148);
+  const auto guard = hc.in(h_guard, B);
+  const auto off = hc.in(h_out_offset, B);
+  const auto gain = hc.in(h_gain, B);
+  const auto out = hc.zeroed_out(h_out, out_samples);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_modulate_batch(c, hc.dev(bits), hc.dev(guard), h_gain ? hc.dev(gain) : nullptr, B, hc.dev(out), hc.dev(off));
+  return hc.finish(rc);
 }
 
 // ---- host-buffer wrappers (PCIe-inclusive convenience; never the timed path) ------------------------
@@ -1000,62 +1033,23 @@ static int detect_demod_host(trxsig_ctx *c, bool rach, const trxsig_c32 *h_sampl
     int64_t e = (int64_t)h_offset[b] + h_length[b];
     if (e > total) total = e;
   }
-  DeviceGuard g(c->device);
-  auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-  const size_t o_s = 0, o_off = o_s + up(sizeof(trx_c32) * (size_t)total), o_len = o_off + up(4 * (size_t)B),
-               o_fl = o_len + up(4 * (size_t)B), o_amp = o_fl + up((size_t)B), o_toa = o_amp + up(8 * (size_t)B),
-               o_pwr = o_toa + up(4 * (size_t)B), o_soft = o_pwr + up(4 * (size_t)B),
-               end = o_soft + up(4 * (size_t)B * soft_stride);
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  // A handful of bursts (the drop-in form: one per call): inputs and outputs go through a pinned mirror of the staging
-  // area, one DMA each way instead of eight pageable copies (115 -> 38 us per call, tools/host_path_bench.py)
-  const bool small = end <= (size_t)256 * 1024;
-  char *m = nullptr;
-  if (small) {
-    rc = ensure_pin(c, end);
-    if (rc != TRXSIG_OK) return rc;
-    m = (char *)c->h_pin;
-    std::memcpy(m + o_s, h_samples, sizeof(trx_c32) * (size_t)total);
-    std::memcpy(m + o_off, h_offset, 4 * (size_t)B);
-    std::memcpy(m + o_len, h_length, 4 * (size_t)B);
-    HIPCHK(c, hipMemcpyAsync(d, m, o_fl, hipMemcpyHostToDevice, c->stream));
-  } else {
-    HIPCHK(c, hipMemcpyAsync(d + o_s, h_samples, sizeof(trx_c32) * (size_t)total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_off, h_offset, 4 * (size_t)B, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_len, h_length, 4 * (size_t)B, hipMemcpyHostToDevice, c->stream));
-  }
-  if (rach)
-    rc = trxsig_detect_demod_rach_batch(c, (trxsig_c32 *)(d + o_s), (int32_t *)(d + o_off), (int32_t *)(d + o_len), B,
-                                        detect_thresh, energy_thresh, (uint8_t *)(d + o_fl),
-                                        (trxsig_c32 *)(d + o_amp), (float *)(d + o_toa), (float *)(d + o_pwr),
-                                        (float *)(d + o_soft), nullptr, nsoft, soft_stride);
-  else
-    rc = trxsig_detect_demod_normal_batch(c, (trxsig_c32 *)(d + o_s), (int32_t *)(d + o_off), (int32_t *)(d + o_len),
-                                          B, tsc, detect_thresh, energy_thresh, (uint8_t *)(d + o_fl),
-                                          (trxsig_c32 *)(d + o_amp), (float *)(d + o_toa), (float *)(d + o_pwr),
-                                          (float *)(d + o_soft), nullptr, nsoft, soft_stride);
-  if (rc != TRXSIG_OK) return rc;
-  if (small) {
-    const size_t out_end = nsoft > 0 ? end : o_soft;
-    HIPCHK(c, hipMemcpyAsync(m + o_fl, d + o_fl, out_end - o_fl, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(h_flags, m + o_fl, (size_t)B);
-    std::memcpy(h_amp, m + o_amp, 8 * (size_t)B);
-    std::memcpy(h_toa, m + o_toa, 4 * (size_t)B);
-    if (h_avgpwr) std::memcpy(h_avgpwr, m + o_pwr, 4 * (size_t)B);
-    if (nsoft > 0) std::memcpy(h_soft, m + o_soft, 4 * (size_t)B * soft_stride);
-    return TRXSIG_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(h_flags, d + o_fl, (size_t)B, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_amp, d + o_amp, 8 * (size_t)B, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_toa, d + o_toa, 4 * (size_t)B, hipMemcpyDeviceToHost, c->stream));
-  if (h_avgpwr) HIPCHK(c, hipMemcpyAsync(h_avgpwr, d + o_pwr, 4 * (size_t)B, hipMemcpyDeviceToHost, c->stream));
-  if (nsoft > 0)
-    HIPCHK(c, hipMemcpyAsync(h_soft, d + o_soft, 4 * (size_t)B * soft_stride, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_samples, total);
+  const auto off = hc.in(h_offset, B);
+  const auto len = hc.in(h_length, B);
+  const auto fl = hc.out(h_flags, B);
+  const auto amp = hc.out(h_amp, B);
+  const auto toa = hc.out(h_toa, B);
+  const auto pwr = hc.out(h_avgpwr, B);
+  const auto soft = hc.out(nsoft > 0 ? h_soft : nullptr, (size_t)B * soft_stride);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK && rach)
+    rc = trxsig_detect_demod_rach_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), B, detect_thresh, energy_thresh, hc.dev(fl), hc.dev(amp),
+                                        hc.dev(toa), hc.dev(pwr), hc.dev(soft), nullptr, nsoft, soft_stride);
+  else if (rc == TRXSIG_OK)
+    rc = trxsig_detect_demod_normal_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), B, tsc, detect_thresh, energy_thresh, hc.dev(fl),
+                                          hc.dev(amp), hc.dev(toa), hc.dev(pwr), hc.dev(soft), nullptr, nsoft, soft_stride);
+  return hc.finish(rc);
 }
 
 int trxsig_detect_demod_normal_host(trxsig_ctx *c, const trxsig_c32 *h_samples, const int32_t *h_offset,
@@ -1083,27 +1077,16 @@ int trxsig_demodulate_host(trxsig_ctx *c, const trxsig_c32 *h_samples, int n, tr
   // the one-burst form: the reference's demodulateBurst has no such limits, so a drop-in caller must hear about it
   if (n < 92 * c->sps || n > 157 * c->sps || n % c->sps != 0 || !(std::fabs(toa) <= 4096.0f))
     return fail(c, TRXSIG_EINVAL, "trxsig_demodulate_host: burst must be 92..157 symbols (a multiple of sps samples) and |TOA| <= 4096");
-  DeviceGuard g(c->device);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_s = 0, o_off = up(8 * (size_t)n), o_len = o_off + 256, o_amp = o_len + 256, o_toa = o_amp + 256,
-               o_soft = o_toa + 256, end = o_soft + up(4 * 160);
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  const int32_t zero = 0, len = n;
-  HIPCHK(c, hipMemcpyAsync(d + o_s, h_samples, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_off, &zero, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_len, &len, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_amp, &amp, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_toa, &toa, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));              // the scalars above live on this stack frame
-  rc = trxsig_demodulate_batch(c, (trxsig_c32 *)(d + o_s), (int32_t *)(d + o_off), (int32_t *)(d + o_len), 1,
-                               (trxsig_c32 *)(d + o_amp), (float *)(d + o_toa), nullptr, (float *)(d + o_soft),
-                               nullptr, nsoft, 160);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_soft, d + o_soft, 4 * (size_t)nsoft, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_samples, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto a = hc.val(amp);
+  const auto t = hc.val(toa);
+  const auto soft = hc.out(h_soft, nsoft, 160);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_demodulate_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(a), hc.dev(t), nullptr, hc.dev(soft), nullptr, nsoft, 160);
+  return hc.finish(rc);
 }
 
 // ---- single-burst host forms of the equaliser steps (the source-compatible facade; one PCIe round trip each) ----
@@ -1113,48 +1096,32 @@ int trxsig_channel_estimate_host(trxsig_ctx *c, const trxsig_c32 *h_samples, int
   if (!c) return TRXSIG_EINVAL;
   if (!h_samples || n <= 0 || !h_flags || !h_amp || !h_toa || !h_chan_off || !h_chan)
     return fail(c, TRXSIG_EINVAL, "trxsig_channel_estimate_host: bad argument");
-  DeviceGuard g(c->device);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_s = 0, o_off = up(8 * (size_t)n), o_len = o_off + 256, o_fl = o_len + 256, o_amp = o_fl + 256, o_toa = o_amp + 256,
-               o_co = o_toa + 256, o_ch = o_co + 256, end = o_ch + 256;
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  const int32_t zero = 0, len = n;
-  HIPCHK(c, hipMemcpyAsync(d + o_s, h_samples, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_off, &zero, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_len, &len, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));              // the scalars above live on this stack frame
-  rc = trxsig_channel_estimate_batch(c, (trxsig_c32 *)(d + o_s), (int32_t *)(d + o_off), (int32_t *)(d + o_len), 1, tsc, detect_thresh,
-                                     variant52m, max_toa, (uint8_t *)(d + o_fl), (trxsig_c32 *)(d + o_amp), (float *)(d + o_toa),
-                                     (float *)(d + o_co), (trxsig_c32 *)(d + o_ch));
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_flags, d + o_fl, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_amp, d + o_amp, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_toa, d + o_toa, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_chan_off, d + o_co, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_chan, d + o_ch, 48, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_samples, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto fl = hc.out(h_flags, 1);
+  const auto amp = hc.out(h_amp, 1);
+  const auto toa = hc.out(h_toa, 1);
+  const auto co = hc.out(h_chan_off, 1);
+  const auto ch = hc.out(h_chan, 6);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_channel_estimate_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, tsc, detect_thresh, variant52m, max_toa, hc.dev(fl),
+                                       hc.dev(amp), hc.dev(toa), hc.dev(co), hc.dev(ch));
+  return hc.finish(rc);
 }
 
 int trxsig_design_dfe_host(trxsig_ctx *c, const trxsig_c32 h_chan[6], float snr, trxsig_c32 h_w[7], trxsig_c32 h_b[5]) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_chan || !h_w || !h_b) return fail(c, TRXSIG_EINVAL, "trxsig_design_dfe_host: bad argument");
-  DeviceGuard g(c->device);
-  const size_t o_ch = 0, o_snr = 256, o_w = 512, o_b = 768, end = 1024;
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  HIPCHK(c, hipMemcpyAsync(d + o_ch, h_chan, 48, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_snr, &snr, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_design_dfe_batch(c, (trxsig_c32 *)(d + o_ch), nullptr, (float *)(d + o_snr), 1, (trxsig_c32 *)(d + o_w), (trxsig_c32 *)(d + o_b));
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_w, d + o_w, 56, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_b, d + o_b, 40, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto ch = hc.in(h_chan, 6);
+  const auto s = hc.val(snr);
+  const auto w = hc.out(h_w, 7);
+  const auto b = hc.out(h_b, 5);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK) rc = trxsig_design_dfe_batch(c, hc.dev(ch), nullptr, hc.dev(s), 1, hc.dev(w), hc.dev(b));
+  return hc.finish(rc);
 }
 
 int trxsig_equalize_taps_host(trxsig_ctx *c, const trxsig_c32 *h_samples, int n, trxsig_c32 amp, float toa_eq,
@@ -1162,46 +1129,35 @@ int trxsig_equalize_taps_host(trxsig_ctx *c, const trxsig_c32 *h_samples, int n,
   if (!c) return TRXSIG_EINVAL;
   if (!h_samples || n <= 0 || !h_w || !h_b || !h_soft || nsoft < 0 || nsoft > 157)
     return fail(c, TRXSIG_EINVAL, "trxsig_equalize_taps_host: bad argument");
-  DeviceGuard g(c->device);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_s = 0, o_off = up(8 * (size_t)n), o_len = o_off + 256, o_fl = o_len + 256, o_amp = o_fl + 256, o_toa = o_amp + 256,
-               o_w = o_toa + 256, o_b = o_w + 256, o_soft = o_b + 256, end = o_soft + up(4 * 160);
-  int rc = ensure_stage(c, end);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = (char *)c->d_stage;
-  const int32_t zero = 0, len = n;
-  const uint8_t fl = TRXSIG_F_ENERGY | TRXSIG_F_DETECT;
-  HIPCHK(c, hipMemcpyAsync(d + o_s, h_samples, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_off, &zero, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_len, &len, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_fl, &fl, 1, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_amp, &amp, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_toa, &toa_eq, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_w, h_w, 56, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_b, h_b, 40, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_equalize_taps_batch(c, (trxsig_c32 *)(d + o_s), (int32_t *)(d + o_off), (int32_t *)(d + o_len), 1, (trxsig_c32 *)(d + o_amp),
-                                  (float *)(d + o_toa), (uint8_t *)(d + o_fl), (trxsig_c32 *)(d + o_w), (trxsig_c32 *)(d + o_b),
-                                  (float *)(d + o_soft), nullptr, nsoft, 160);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_soft, d + o_soft, 4 * (size_t)nsoft, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_samples, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto fl = hc.val<uint8_t>(TRXSIG_F_ENERGY | TRXSIG_F_DETECT);
+  const auto a = hc.val(amp);
+  const auto t = hc.val(toa_eq);
+  const auto w = hc.in(h_w, 7);
+  const auto b = hc.in(h_b, 5);
+  const auto soft = hc.out(h_soft, nsoft, 160);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_equalize_taps_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(a), hc.dev(t), hc.dev(fl), hc.dev(w), hc.dev(b),
+                                    hc.dev(soft), nullptr, nsoft, 160);
+  return hc.finish(rc);
 }
 
 // ---- measurement helpers ------------------------------------------------------------------------------
 int trxsig_timer_start(trxsig_ctx *c) {
   if (!c) return TRXSIG_EINVAL;
-  DeviceGuard g(c->device);
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, hipEventRecord(c->ev0, c->stream));
   return TRXSIG_OK;
 }
 int trxsig_timer_stop(trxsig_ctx *c, float *ms) {
   if (!c || !ms) return TRXSIG_EINVAL;
-  DeviceGuard g(c->device);
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  HIPCHK(c, hipEventSynchronize(c->ev1));
-  HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  TRX_HIPCHK(c, hipEventSynchronize(c->ev1));
+  TRX_HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
   return TRXSIG_OK;
 }
 
@@ -1217,8 +1173,8 @@ int trxsig_fec_xcch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_st
   if (!c) return TRXSIG_EINVAL;
   if (n_blocks < 0 || soft_stride < 148 || (n_blocks > 0 && (!d_soft || !d_frames || !d_ok)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_xcch_decode_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_fec(c->stream, 1, d_soft, soft_stride, 456, 228, n_blocks, wire, d_frames, d_ok, nullptr, 0, c->prof));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec(c->stream, 1, d_soft, soft_stride, 456, 228, n_blocks, wire, d_frames, d_ok, nullptr, 0, c->prof));
   return TRXSIG_OK;
 }
 int trxsig_fec_rach_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n_bursts, int wire,
@@ -1226,29 +1182,29 @@ int trxsig_fec_rach_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_st
   if (!c) return TRXSIG_EINVAL;
   if (n_bursts < 0 || soft_stride < 85 || (n_bursts > 0 && (!d_soft || !d_tail_ok || !d_bsic || !d_ra)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_rach_decode_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_fec(c->stream, 2, d_soft, soft_stride, 36, 18, n_bursts, wire, d_tail_ok, d_bsic, d_ra, 0, c->prof));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec(c->stream, 2, d_soft, soft_stride, 36, 18, n_bursts, wire, d_tail_ok, d_bsic, d_ra, 0, c->prof));
   return TRXSIG_OK;
 }
 namespace {
-// the 8 x 26 training-sequence bits of the encoders, uploaded on first use (caller holds the DeviceGuard)
+// the 8 x 26 training-sequence bits of the encoders, uploaded on first use (caller holds the TrxDeviceGuard)
 int upload_tsc_bits(trxsig_ctx *c) {
   if (c->d_tsc) return TRXSIG_OK;
   uint8_t h[8 * 26];
   for (int t = 0; t < 8; t++)
     for (int k = 0; k < 26; k++) h[26 * t + k] = trx_training_sequence(t)[k] == '1';
   uint8_t *d = nullptr;
-  HIPCHK(c, hipMalloc((void **)&d, sizeof h));
+  TRX_HIPCHK(c, hipMalloc((void **)&d, sizeof h));
   const hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(d); return fail(c, TRXSIG_EHIP, "training-sequence upload", e); }
   c->d_tsc = d;
   return TRXSIG_OK;
 }
-// the TCH filler c[], all zero until trxsig_fec_tch_set_filler (caller holds the DeviceGuard)
+// the TCH filler c[], all zero until trxsig_fec_tch_set_filler (caller holds the TrxDeviceGuard)
 int alloc_tch_filler(trxsig_ctx *c) {
   if (c->d_tch_filler) return TRXSIG_OK;
   uint8_t *d = nullptr;
-  HIPCHK(c, hipMalloc((void **)&d, 456));
+  TRX_HIPCHK(c, hipMalloc((void **)&d, 456));
   const hipError_t e = hipMemset(d, 0, 456);
   if (e != hipSuccess) { (void)hipFree(d); return fail(c, TRXSIG_EHIP, "TCH filler allocation", e); }
   c->d_tch_filler = d;
@@ -1260,10 +1216,10 @@ int trxsig_fec_xcch_encode_batch(trxsig_ctx *c, const uint8_t *d_frames, int n_b
   if (n_blocks < 0 || tsc < 0 || tsc > 7 || (n_blocks > 0 && (!d_frames || !d_bits)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_xcch_encode_batch: bad argument");
   if (n_blocks == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   const int rc = upload_tsc_bits(c);
   if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, trx_launch_fec_xcch_encode(c->stream, d_frames, n_blocks, c->d_tsc + 26 * tsc, d_bits, c->prof));
+  TRX_HIPCHK(c, trx_launch_fec_xcch_encode(c->stream, d_frames, n_blocks, c->d_tsc + 26 * tsc, d_bits, c->prof));
   return TRXSIG_OK;
 }
 int trxsig_fec_tch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n_bursts, int wire,
@@ -1275,23 +1231,23 @@ int trxsig_fec_tch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_str
       ((d_facch == nullptr) != (d_facch_ok == nullptr)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_tch_decode_batch: bad argument");
   if (nblk <= 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_fec(c->stream, 3, d_soft, soft_stride, 378, 189, nblk, wire, d_tch, d_tch_good, d_stolen, 0, c->prof));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec(c->stream, 3, d_soft, soft_stride, 378, 189, nblk, wire, d_tch, d_tch_good, d_stolen, 0, c->prof));
   if (d_facch)
-    HIPCHK(c, trx_launch_fec(c->stream, 1, d_soft, soft_stride, 456, 228, nblk, wire, d_facch, d_facch_ok, nullptr, 0,
+    TRX_HIPCHK(c, trx_launch_fec(c->stream, 1, d_soft, soft_stride, 456, 228, nblk, wire, d_facch, d_facch_ok, nullptr, 0,
                              c->prof, 1));
   return TRXSIG_OK;
 }
 int trxsig_fec_tch_set_filler(trxsig_ctx *c, const uint8_t *h_c456) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_c456) return fail(c, TRXSIG_EINVAL, "trxsig_fec_tch_set_filler: bad argument");
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   const int rc = alloc_tch_filler(c);
   if (rc != TRXSIG_OK) return rc;
   uint8_t h[456];
   for (int i = 0; i < 456; i++) h[i] = h_c456[i] & 1u;
-  HIPCHK(c, hipStreamSynchronize(c->stream));              // blocks already enqueued read the old pattern
-  HIPCHK(c, hipMemcpy(c->d_tch_filler, h, sizeof h, hipMemcpyHostToDevice));
+  TRX_HIPCHK(c, hipStreamSynchronize(c->stream));              // blocks already enqueued read the old pattern
+  TRX_HIPCHK(c, hipMemcpy(c->d_tch_filler, h, sizeof h, hipMemcpyHostToDevice));
   return TRXSIG_OK;
 }
 int trxsig_fec_tch_encode_batch(trxsig_ctx *c, int n_chan, int n_blocks, const uint8_t *d_kind, const uint8_t *d_payload,
@@ -1301,11 +1257,11 @@ int trxsig_fec_tch_encode_batch(trxsig_ctx *c, int n_chan, int n_blocks, const u
       (n_chan > 0 && n_blocks > 0 && (!d_kind || !d_payload || !d_tsc || !d_state || !d_bits)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_tch_encode_batch: bad argument");
   if (n_chan == 0 || n_blocks == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   int rc = upload_tsc_bits(c);
   if (rc == TRXSIG_OK) rc = alloc_tch_filler(c);
   if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, trx_launch_fec_tch_encode(c->stream, n_chan, n_blocks, d_kind, d_payload, d_tsc, c->d_tsc, c->d_tch_filler,
+  TRX_HIPCHK(c, trx_launch_fec_tch_encode(c->stream, n_chan, n_blocks, d_kind, d_payload, d_tsc, c->d_tsc, c->d_tch_filler,
                                       static_cast<uint8_t *>(d_state), d_bits, c->prof));
   return TRXSIG_OK;
 }
@@ -1314,11 +1270,11 @@ int trxsig_fec_sch_encode_batch(trxsig_ctx *c, const uint32_t *d_fn, const uint8
   if (n < 0 || (n > 0 && (!d_fn || !d_bsic || !d_bits)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_sch_encode_batch: bad argument");
   if (n == 0) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   unsigned long long xts = 0;
   const char *x = trx_sch_extended_training_sequence();
   for (int t = 0; t < 64; t++) xts |= (unsigned long long)(x[t] == '1') << t;
-  HIPCHK(c, trx_launch_fec_sch_encode(c->stream, d_fn, d_bsic, n, xts, d_bits, c->prof));
+  TRX_HIPCHK(c, trx_launch_fec_sch_encode(c->stream, d_fn, d_bsic, n, xts, d_bits, c->prof));
   return TRXSIG_OK;
 }
 int trxsig_fec_viterbi_batch(trxsig_ctx *c, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
@@ -1327,8 +1283,8 @@ int trxsig_fec_viterbi_batch(trxsig_ctx *c, const float *d_soft, int n_soft, int
   if (n_blocks < 0 || n_soft < 2 || n_soft > 1024 || (n_soft & 1) || in_stride < n_soft || out_stride < n_soft / 2 ||
       (n_blocks > 0 && (!d_soft || !d_bits)))
     return fail(c, TRXSIG_EINVAL, "trxsig_fec_viterbi_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_fec(c->stream, 0, d_soft, in_stride, n_soft, n_soft / 2, n_blocks, 0, d_bits, nullptr, nullptr,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec(c->stream, 0, d_soft, in_stride, n_soft, n_soft / 2, n_blocks, 0, d_bits, nullptr, nullptr,
                            out_stride, c->prof));
   return TRXSIG_OK;
 }
@@ -1373,7 +1329,7 @@ int trxsig_set_tuning(trxsig_ctx *c, int key, int value) {
   if (key == TRXSIG_TUNE_RACH_PATH && value >= 0 && value <= 2) { c->rach_variant = value; return TRXSIG_OK; }
   if (key == TRXSIG_TUNE_GENERIC_TAPS && value >= 0 && value <= 1) { c->generic_taps = value; return TRXSIG_OK; }
   if (key == TRXSIG_TUNE_DEMOD_BESIDE && value >= 0 && value <= 1) {
-    DeviceGuard g(c->device);
+    TrxDeviceGuard g(c->device);
     int rc = join_demod(c);
     if (rc != TRXSIG_OK) return rc;
     c->demod_beside = value;
@@ -1389,10 +1345,10 @@ int trxsig_set_tuning(trxsig_ctx *c, int key, int value) {
   if (key == TRXSIG_TUNE_GROUP_REPLAY && value >= 0 && value <= 1) { trx_knob_set(TRX_KNOB_GROUP_REPLAY, value); return TRXSIG_OK; }
   if ((key == TRXSIG_TUNE_BESIDE_DET_CUS && value >= 0 && value <= 504) || (key == TRXSIG_TUNE_CU_LAYOUT && value >= 0 && value <= 1) ||
       (key == TRXSIG_TUNE_BESIDE_PRIORITY && value >= 0 && value <= 2)) {
-    DeviceGuard g(c->device);
+    TrxDeviceGuard g(c->device);
     int rc = join_demod(c);
     if (rc != TRXSIG_OK) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRX_HIPCHK(c, hipStreamSynchronize(c->stream));
     rc = drop_beside_streams(c);                            // re-created with the new masks at the next call
     if (rc != TRXSIG_OK) return rc;
     if (key == TRXSIG_TUNE_BESIDE_DET_CUS) c->det_cus = value;
@@ -1404,7 +1360,7 @@ int trxsig_set_tuning(trxsig_ctx *c, int key, int value) {
 }
 int trxsig_profile_enable(trxsig_ctx *c, int on) {
   if (!c) return TRXSIG_EINVAL;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   if (on && !c->prof) c->prof = new (std::nothrow) EventProfiler;
   if (!on && c->prof) { delete c->prof; c->prof = nullptr; }
   return TRXSIG_OK;
@@ -1413,7 +1369,7 @@ namespace {
 int profile_collect_all(trxsig_ctx *c, float ms[kKernels], int n[kKernels]) {
   for (int i = 0; i < kKernels; i++) { ms[i] = 0; n[i] = 0; }
   if (!c->prof) return TRXSIG_OK;
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   c->prof->collect(ms, n);
   return TRXSIG_OK;
 }
@@ -1482,49 +1438,31 @@ int trxsig_convolve_batch(trxsig_ctx *c, const trxsig_c32 *d_a, const int32_t *d
   if (bad_batch(d_a, d_a_off, d_a_len, B) || max_len <= 0 || !d_b || Lb <= 0 || span < 0 || span > TRXSIG_CUSTOM ||
       (flags & ~7) || ((flags & 4) && correlate) || (B > 0 && (!d_out || !d_out_off)) || (span == TRXSIG_CUSTOM && (cust_start < 0 || cust_len <= 0)))
     return fail(c, TRXSIG_EINVAL, "trxsig_convolve_batch: bad argument");
-  DeviceGuard g(c->device);
+  TrxDeviceGuard g(c->device);
   const int max_out = trx_convolve_out_len(max_len, Lb, span, cust_len);
   // (OVERLAP_ONLY's length is |La - Lb| + 1: the longest output may belong to the shortest vector)
   const int grid_out = span == TRXSIG_OVERLAP_ONLY ? (max_len > Lb ? max_len : Lb) + 1 : max_out;
-  HIPCHK(c, trx_launch_convolve(c->stream, (const trx_c32 *)d_a, d_a_off, d_a_len, B, grid_out, (const trx_c32 *)d_b, Lb, span,
+  TRX_HIPCHK(c, trx_launch_convolve(c->stream, (const trx_c32 *)d_a, d_a_off, d_a_len, B, grid_out, (const trx_c32 *)d_b, Lb, span,
                                 flags, correlate != 0, cust_start, cust_len, (trx_c32 *)d_out, d_out_off));
   return TRXSIG_OK;
 }
-
-namespace {
-// staging-area layout helper for the single-vector host forms: 256-byte aligned regions handed out in order
-struct Stager {
-  trxsig_ctx *c;
-  size_t used = 0;
-  explicit Stager(trxsig_ctx *ctx) : c(ctx) {}
-  size_t take(size_t bytes) { const size_t o = used; used += (bytes + 255) & ~(size_t)255; return o; }
-  char *base() const { return (char *)c->d_stage; }
-};
-}  // namespace
 
 int trxsig_convolve_host(trxsig_ctx *c, const trxsig_c32 *h_a, int La, const trxsig_c32 *h_b, int Lb, int span, int flags,
                          int correlate, int cust_start, int cust_len, trxsig_c32 *h_out, int out_cap) {
   if (!c) return TRXSIG_EINVAL;
   const int nout = (La > 0 && Lb > 0) ? trx_convolve_out_len(La, Lb, span, cust_len) : -1;
   if (!h_a || !h_b || !h_out || nout <= 0 || out_cap < nout) return fail(c, TRXSIG_EINVAL, "trxsig_convolve_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_a = s.take(8 * (size_t)La), o_b = s.take(8 * (size_t)Lb), o_m = s.take(16), o_out = s.take(8 * (size_t)nout);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  const int32_t meta[3] = {0, La, 0};                      // a_off, a_len, out_off
-  HIPCHK(c, hipMemcpyAsync(d + o_a, h_a, 8 * (size_t)La, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_b, h_b, 8 * (size_t)Lb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));              // meta lives on this stack frame
-  rc = trxsig_convolve_batch(c, (trxsig_c32 *)(d + o_a), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1, La,
-                             (trxsig_c32 *)(d + o_b), Lb, span, flags, correlate, cust_start, cust_len, (trxsig_c32 *)(d + o_out),
-                             (int32_t *)(d + o_m) + 2);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_out, 8 * (size_t)nout, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return nout;
+  TrxHostCall hc(c);
+  const auto a = hc.in(h_a, La);
+  const auto b = hc.in(h_b, Lb);
+  const auto zero = hc.val(0), len = hc.val(La);           // a's offset and length; the output's offset is zero too
+  const auto out = hc.out(h_out, nout);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_convolve_batch(c, hc.dev(a), hc.dev(zero), hc.dev(len), 1, La, hc.dev(b), Lb, span, flags, correlate, cust_start, cust_len,
+                               hc.dev(out), hc.dev(zero));
+  rc = hc.finish(rc);
+  return rc == TRXSIG_OK ? nout : rc;
 }
 
 int trxsig_delay_vector_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *d_off, const int32_t *d_len, int B,
@@ -1532,8 +1470,8 @@ int trxsig_delay_vector_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || (B > 0 && (!d_delay || !d_out || d_out == d_in)))
     return fail(c, TRXSIG_EINVAL, "trxsig_delay_vector_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_delay_vector(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, d_delay, real_only != 0,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_delay_vector(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, d_delay, real_only != 0,
                                     (trx_c32 *)d_out));
   return TRXSIG_OK;
 }
@@ -1543,23 +1481,14 @@ int trxsig_delay_vector_host(trxsig_ctx *c, trxsig_c32 *h_x, int n, float delay,
   if (!h_x || n <= 0) return fail(c, TRXSIG_EINVAL, "trxsig_delay_vector_host: bad argument");
   if (!(std::fabs(delay) <= TRXSIG_MAX_INDEX))
     return fail(c, TRXSIG_EINVAL, "trxsig_delay_vector_host: delay beyond +-2^24 (or not finite): the reference's sinc range reduction would not end");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_y = s.take(8 * (size_t)n), o_m = s.take(16);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  int32_t meta[3] = {0, n, 0};
-  std::memcpy(&meta[2], &delay, 4);
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_delay_vector_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1,
-                                 (float *)(d + o_m) + 2, real_only, (trxsig_c32 *)(d + o_y));
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_x, d + o_y, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto d = hc.val(delay);
+  const auto y = hc.out(h_x, n);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK) rc = trxsig_delay_vector_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(d), real_only, hc.dev(y));
+  return hc.finish(rc);
 }
 
 int trxsig_interpolate_point_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *d_off, const int32_t *d_len, int B,
@@ -1567,8 +1496,8 @@ int trxsig_interpolate_point_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const 
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || (B > 0 && (!d_ix || !d_out)))
     return fail(c, TRXSIG_EINVAL, "trxsig_interpolate_point_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_interpolate_point(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, d_ix, real_only != 0,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_interpolate_point(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, d_ix, real_only != 0,
                                          (trx_c32 *)d_out));
   return TRXSIG_OK;
 }
@@ -1578,31 +1507,22 @@ int trxsig_interpolate_point_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, f
   if (!h_x || n <= 0 || !h_out) return fail(c, TRXSIG_EINVAL, "trxsig_interpolate_point_host: bad argument");
   if (!(std::fabs(ix) <= TRXSIG_MAX_INDEX))
     return fail(c, TRXSIG_EINVAL, "trxsig_interpolate_point_host: index beyond +-2^24 (or not finite): the reference's sinc range reduction would not end");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(16), o_out = s.take(8);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  int32_t meta[3] = {0, n, 0};
-  std::memcpy(&meta[2], &ix, 4);
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_interpolate_point_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1,
-                                      (float *)(d + o_m) + 2, real_only, (trxsig_c32 *)(d + o_out));
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_out, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto i = hc.val(ix);
+  const auto out = hc.out(h_out, 1);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK) rc = trxsig_interpolate_point_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(i), real_only, hc.dev(out));
+  return hc.finish(rc);
 }
 
 int trxsig_peak_detect_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *d_off, const int32_t *d_len, int B,
                              trxsig_c32 *d_peak, float *d_index, float *d_avgpwr) {
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || (B > 0 && !d_peak)) return fail(c, TRXSIG_EINVAL, "trxsig_peak_detect_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_peak_detect(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, (trx_c32 *)d_peak, d_index,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_peak_detect(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, (trx_c32 *)d_peak, d_index,
                                    d_avgpwr));
   return TRXSIG_OK;
 }
@@ -1610,26 +1530,16 @@ int trxsig_peak_detect_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_
 int trxsig_peak_detect_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, trxsig_c32 *h_peak, float *h_index, float *h_avgpwr) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_x || n <= 0 || !h_peak) return fail(c, TRXSIG_EINVAL, "trxsig_peak_detect_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(16), o_out = s.take(16);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  const int32_t meta[2] = {0, n};
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_peak_detect_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1,
-                                (trxsig_c32 *)(d + o_out), (float *)(d + o_out) + 2, (float *)(d + o_out) + 3);
-  if (rc != TRXSIG_OK) return rc;
-  float res[4];
-  HIPCHK(c, hipMemcpyAsync(res, d + o_out, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  h_peak->re = res[0]; h_peak->im = res[1];
-  if (h_index) *h_index = res[2];
-  if (h_avgpwr) *h_avgpwr = res[3];
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto peak = hc.out(h_peak, 1);
+  const auto index = hc.out(h_index, 1);
+  const auto pwr = hc.out(h_avgpwr, 1);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_peak_detect_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(peak), hc.dev(index), hc.dev(pwr));
+  return hc.finish(rc);
 }
 
 int trxsig_energy_detect_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *d_off, const int32_t *d_len, int B,
@@ -1637,8 +1547,8 @@ int trxsig_energy_detect_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int3
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || (sample_step != 1 && sample_step != 4))
     return fail(c, TRXSIG_EINVAL, "trxsig_energy_detect_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_energy_detect(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, window, sample_step, thresh, d_avgpwr, d_ok));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_energy_detect(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, window, sample_step, thresh, d_avgpwr, d_ok));
   return TRXSIG_OK;
 }
 
@@ -1646,24 +1556,17 @@ int trxsig_energy_detect_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, unsig
                               float *h_avgpwr) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_x || n <= 0) return fail(c, TRXSIG_EINVAL, "trxsig_energy_detect_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(16), o_out = s.take(16);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  const int32_t meta[2] = {0, n};
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_energy_detect_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1, window, sample_step,
-                                  thresh, (float *)(d + o_out), (uint8_t *)(d + o_out) + 8);
-  if (rc != TRXSIG_OK) return rc;
-  unsigned char res[16];
-  HIPCHK(c, hipMemcpyAsync(res, d + o_out, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h_avgpwr) std::memcpy(h_avgpwr, res, 4);
-  return res[8] ? 1 : 0;
+  uint8_t detected = 0;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto pwr = hc.out(h_avgpwr, 1);
+  const auto ok = hc.out(&detected, 1);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_energy_detect_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, window, sample_step, thresh, hc.dev(pwr), hc.dev(ok));
+  rc = hc.finish(rc);
+  return rc != TRXSIG_OK ? rc : detected ? 1 : 0;
 }
 
 namespace {
@@ -1671,8 +1574,8 @@ int elementwise_batch(trxsig_ctx *c, const char *who, int op, trxsig_c32 *d_x, c
                       int max_len, const trxsig_c32 *d_scale, int real_only) {
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_x, d_off, d_len, B) || max_len <= 0 || (op == 0 && B > 0 && !d_scale)) return fail(c, TRXSIG_EINVAL, who);
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_elementwise(c->stream, op, c->d_tables, (trx_c32 *)d_x, d_off, d_len, B, max_len, (const trx_c32 *)d_scale,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_elementwise(c->stream, op, c->d_tables, (trx_c32 *)d_x, d_off, d_len, B, max_len, (const trx_c32 *)d_scale,
                                    real_only != 0));
   return TRXSIG_OK;
 }
@@ -1766,32 +1669,21 @@ int trxsig_vector_norm2_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32
                               float *d_power) {
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B)) return fail(c, TRXSIG_EINVAL, "trxsig_vector_norm2_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_vector_norm2(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, d_norm2, d_power));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_vector_norm2(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, d_norm2, d_power));
   return TRXSIG_OK;
 }
 int trxsig_vector_norm2_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, float *norm2, float *power) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_x || n <= 0) return fail(c, TRXSIG_EINVAL, "trxsig_vector_norm2_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(16), o_out = s.take(16);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  const int32_t meta[2] = {0, n};
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_vector_norm2_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1, (float *)(d + o_out),
-                                 (float *)(d + o_out) + 1);
-  if (rc != TRXSIG_OK) return rc;
-  float res[2];
-  HIPCHK(c, hipMemcpyAsync(res, d + o_out, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (norm2) *norm2 = res[0];
-  if (power) *power = res[1];
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto e = hc.out(norm2, 1);
+  const auto p = hc.out(power, 1);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK) rc = trxsig_vector_norm2_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(e), hc.dev(p));
+  return hc.finish(rc);
 }
 
 int trxsig_frequency_shift_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *d_off, const int32_t *d_len, int B,
@@ -1799,8 +1691,8 @@ int trxsig_frequency_shift_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const in
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || (B > 0 && (!d_freq || !d_start_phase || !d_out)))
     return fail(c, TRXSIG_EINVAL, "trxsig_frequency_shift_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_frequency_shift(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, d_freq, d_start_phase, real_only != 0,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_frequency_shift(c->stream, c->d_tables, (const trx_c32 *)d_in, d_off, d_len, B, d_freq, d_start_phase, real_only != 0,
                                        (trx_c32 *)d_out, d_final_phase));
   return TRXSIG_OK;
 }
@@ -1810,26 +1702,15 @@ int trxsig_frequency_shift_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, flo
   if (!h_x || n <= 0 || !h_out) return fail(c, TRXSIG_EINVAL, "trxsig_frequency_shift_host: bad argument");
   if (!(std::fabs((double)start_phase) + (double)n * std::fabs((double)freq) <= (double)trx_frequency_shift_max_phase()))
     return fail(c, TRXSIG_EINVAL, "trxsig_frequency_shift_host: phase beyond +-25000 rad (the reference's range reduction would not return)");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(32);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  int32_t meta[5] = {0, n, 0, 0, 0};
-  std::memcpy(&meta[2], &freq, 4); std::memcpy(&meta[3], &start_phase, 4);
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 20, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_frequency_shift_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1, (float *)(d + o_m) + 2,
-                                    (float *)(d + o_m) + 3, real_only, (trxsig_c32 *)(d + o_x), (float *)(d + o_m) + 4);
-  if (rc != TRXSIG_OK) return rc;
-  float fin = 0.0f;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_x, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&fin, (float *)(d + o_m) + 4, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (final_phase) *final_phase = fin;
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.inout(h_x, h_out, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto f = hc.val(freq), p = hc.val(start_phase);
+  const auto fin = hc.out(final_phase, 1);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_frequency_shift_batch(c, hc.dev(x), hc.dev(off), hc.dev(len), 1, hc.dev(f), hc.dev(p), real_only, hc.dev(x), hc.dev(fin));
+  return hc.finish(rc);
 }
 
 int trxsig_add_vector_batch(trxsig_ctx *c, trxsig_c32 *d_x, const int32_t *d_xoff, const int32_t *d_xlen, const trxsig_c32 *d_y,
@@ -1837,30 +1718,21 @@ int trxsig_add_vector_batch(trxsig_ctx *c, trxsig_c32 *d_x, const int32_t *d_xof
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_x, d_xoff, d_xlen, B) || bad_batch(d_y, d_yoff, d_ylen, B) || max_len <= 0)
     return fail(c, TRXSIG_EINVAL, "trxsig_add_vector_batch: bad argument");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_add_vector(c->stream, (trx_c32 *)d_x, d_xoff, d_xlen, (const trx_c32 *)d_y, d_yoff, d_ylen, B, max_len));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_add_vector(c->stream, (trx_c32 *)d_x, d_xoff, d_xlen, (const trx_c32 *)d_y, d_yoff, d_ylen, B, max_len));
   return TRXSIG_OK;
 }
 int trxsig_add_vector_host(trxsig_ctx *c, trxsig_c32 *h_x, int nx, const trxsig_c32 *h_y, int ny) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_x || !h_y || nx <= 0 || ny <= 0) return fail(c, TRXSIG_EINVAL, "trxsig_add_vector_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)nx), o_y = s.take(8 * (size_t)ny), o_m = s.take(16);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  const int32_t meta[3] = {0, nx, ny};
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)nx, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_y, h_y, 8 * (size_t)ny, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_add_vector_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, (trxsig_c32 *)(d + o_y),
-                               (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 2, 1, nx < ny ? nx : ny);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_x, d + o_x, 8 * (size_t)nx, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.inout(h_x, h_x, nx);
+  const auto y = hc.in(h_y, ny);
+  const auto zero = hc.val(0), xlen = hc.val(nx), ylen = hc.val(ny);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_add_vector_batch(c, hc.dev(x), hc.dev(zero), hc.dev(xlen), hc.dev(y), hc.dev(zero), hc.dev(ylen), 1, nx < ny ? nx : ny);
+  return hc.finish(rc);
 }
 
 int trxsig_resample_linear_out_len(int n, float exp_factor) {
@@ -1872,8 +1744,8 @@ int trxsig_resample_linear_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const in
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || !(exp_factor >= 1.0f) || !(exp_factor <= 65536.0f) || (B > 0 && (!d_end_point || !d_out || !d_out_off)))
     return fail(c, TRXSIG_EINVAL, "trxsig_resample_linear_batch: bad argument (resampleVector returns NULL for expFactor < 1)");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_resample_linear(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, exp_factor, (const trx_c32 *)d_end_point,
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_resample_linear(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, exp_factor, (const trx_c32 *)d_end_point,
                                        (trx_c32 *)d_out, d_out_off));
   return TRXSIG_OK;
 }
@@ -1882,23 +1754,16 @@ int trxsig_resample_linear_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, flo
   if (!c) return TRXSIG_EINVAL;
   const int nout = trxsig_resample_linear_out_len(n, exp_factor);
   if (!h_x || n <= 0 || !h_out || nout < 0 || nout > out_cap) return fail(c, TRXSIG_EINVAL, "trxsig_resample_linear_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(32), o_out = s.take(8 * (size_t)(nout > 0 ? nout : 1));
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  int32_t meta[6] = {0, n, 0, 0, 0, 0};
-  std::memcpy(&meta[4], &end_point, 8);
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 24, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_resample_linear_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1, exp_factor,
-                                    (trxsig_c32 *)((int32_t *)(d + o_m) + 4), (trxsig_c32 *)(d + o_out), (int32_t *)(d + o_m) + 2);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_out, 8 * (size_t)nout, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return nout;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto zero = hc.val(0), len = hc.val(n);            // x's offset and length; the output's offset is zero too
+  const auto end = hc.val(end_point);
+  const auto out = hc.out(h_out, nout);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_resample_linear_batch(c, hc.dev(x), hc.dev(zero), hc.dev(len), 1, exp_factor, hc.dev(end), hc.dev(out), hc.dev(zero));
+  rc = hc.finish(rc);
+  return rc == TRXSIG_OK ? nout : rc;
 }
 
 int trxsig_decimate_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *d_off, const int32_t *d_len, int B, int max_len,
@@ -1906,53 +1771,36 @@ int trxsig_decimate_batch(trxsig_ctx *c, const trxsig_c32 *d_in, const int32_t *
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_in, d_off, d_len, B) || max_len <= 0 || factor <= 1 || (B > 0 && (!d_out || !d_out_off)))
     return fail(c, TRXSIG_EINVAL, "trxsig_decimate_batch: bad argument (decimateVector returns NULL for a factor <= 1)");
-  DeviceGuard g(c->device);
-  HIPCHK(c, trx_launch_decimate(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, max_len, factor, (trx_c32 *)d_out, d_out_off));
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_decimate(c->stream, (const trx_c32 *)d_in, d_off, d_len, B, max_len, factor, (trx_c32 *)d_out, d_out_off));
   return TRXSIG_OK;
 }
 
 int trxsig_elementwise_host(trxsig_ctx *c, int op, trxsig_c32 *h_x, int n, trxsig_c32 scale, int real_only) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_x || n <= 0 || op < 0 || op > 4) return fail(c, TRXSIG_EINVAL, "trxsig_elementwise_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(16);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  int32_t meta[4] = {0, n, 0, 0};
-  std::memcpy(&meta[2], &scale, 8);
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 16, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = elementwise_batch(c, "trxsig_elementwise_host: bad argument", op, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m),
-                         (int32_t *)(d + o_m) + 1, 1, n, (trxsig_c32 *)((int32_t *)(d + o_m) + 2), real_only);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_x, d + o_x, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TRXSIG_OK;
+  TrxHostCall hc(c);
+  const auto x = hc.inout(h_x, h_x, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto s = hc.val(scale);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = elementwise_batch(c, "trxsig_elementwise_host: bad argument", op, hc.dev(x), hc.dev(off), hc.dev(len), 1, n, hc.dev(s), real_only);
+  return hc.finish(rc);
 }
 
 int trxsig_decimate_host(trxsig_ctx *c, const trxsig_c32 *h_x, int n, int factor, trxsig_c32 *h_out) {
   if (!c) return TRXSIG_EINVAL;
   if (!h_x || n <= 0 || factor <= 1 || !h_out || n / factor <= 0) return fail(c, TRXSIG_EINVAL, "trxsig_decimate_host: bad argument");
-  DeviceGuard g(c->device);
-  Stager s(c);
   const int nout = n / factor;
-  const size_t o_x = s.take(8 * (size_t)n), o_m = s.take(16), o_out = s.take(8 * (size_t)nout);
-  int rc = ensure_stage(c, s.used);
-  if (rc != TRXSIG_OK) return rc;
-  char *d = s.base();
-  const int32_t meta[3] = {0, n, 0};
-  HIPCHK(c, hipMemcpyAsync(d + o_x, h_x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d + o_m, meta, 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = trxsig_decimate_batch(c, (trxsig_c32 *)(d + o_x), (int32_t *)(d + o_m), (int32_t *)(d + o_m) + 1, 1, n, factor,
-                             (trxsig_c32 *)(d + o_out), (int32_t *)(d + o_m) + 2);
-  if (rc != TRXSIG_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(h_out, d + o_out, 8 * (size_t)nout, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return nout;
+  TrxHostCall hc(c);
+  const auto x = hc.in(h_x, n);
+  const auto zero = hc.val(0), len = hc.val(n);            // x's offset and length; the output's offset is zero too
+  const auto out = hc.out(h_out, nout);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK) rc = trxsig_decimate_batch(c, hc.dev(x), hc.dev(zero), hc.dev(len), 1, n, factor, hc.dev(out), hc.dev(zero));
+  rc = hc.finish(rc);
+  return rc == TRXSIG_OK ? nout : rc;
 }
 
 }  // extern "C"

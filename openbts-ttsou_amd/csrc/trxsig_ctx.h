@@ -1,10 +1,96 @@
-// trxsig_ctx.h -- internal: what the other host translation units of the library (trxsig_frontend.cpp, trxsig_trxgroup.cpp)
-// may ask of a context (trxsig_api.cpp owns struct trxsig_ctx).
+// trxsig_ctx.h -- internal: what the other host translation units of the library (trxsig_frontend.cpp, trxsig_trxgroup.cpp,
+// trxsig_transceiver.cpp) may ask of a context (trxsig_api.cpp owns struct trxsig_ctx).
 #pragma once
+#include <cstring>
+#include <vector>
+
 #include "trxsig.h"
 #include "trxsig_launch.h"
 
 int trx_ctx_fail(trxsig_ctx *c, int code, const char *what, hipError_t e);
+
+// (TRX_INTERNAL: a class of the library's own that adds no exported symbol)
+#define TRX_INTERNAL __attribute__((visibility("hidden")))
+
+// the context's device is current for the call; the caller's comes back after it
+struct TRX_INTERNAL TrxDeviceGuard {
+  int prev = -1;
+  explicit TrxDeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
+  ~TrxDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// a failing HIP call returns TRXSIG_EHIP from the enclosing function, with the call's text as the context's last error
+#define TRX_HIPCHK(c, call)                                                   \
+  do {                                                                        \
+    hipError_t e_ = (call);                                                   \
+    if (e_ != hipSuccess) return trx_ctx_fail((c), TRXSIG_EHIP, #call, e_);   \
+  } while (0)
+
+// One *_host call's round trip through the context's device staging area:
+//   TrxHostCall hc(c);
+//   const auto x = hc.in(h_x, n);      n elements uploaded from h_x (h_x == nullptr: the region is only reserved)
+//   const auto k = hc.val(delay);      one scalar, copied here at once: nothing on the caller's stack is read later
+//   const auto z = hc.inout(h_src, h_dst, n);   uploaded from h_src, downloaded to h_dst (the in-place forms: the same pointer)
+//   const auto y = hc.out(h_y, n);     downloaded to h_y (h_y == nullptr: a device region only); out(h_y, n, m) reserves m >= n
+//   const auto o = hc.zeroed_out(h_o, n);       an out() that is cleared on the device first
+//   int rc = hc.stage();               sizes the scratch, uploads
+//   if (rc == TRXSIG_OK) rc = trxsig_..._batch(c, hc.dev(x), ...);
+//   return hc.finish(rc);              downloads if rc is TRXSIG_OK, waits for the stream, returns rc (or the copy's error)
+// The regions are laid out inputs, in/outs, outputs (256-byte aligned), so the upload and the download are one range each.  A
+// call that fits in kPinnedMax goes through the context's pinned mirror of the staging area, one DMA each way (115 -> 38 us for
+// the one-burst detect + demodulate, tools/host_path_bench.py); a larger one copies each region straight from and to the caller's
+// buffers.  Once a copy is queued, every way out waits for the stream -- the destructor does it for the early returns -- so no
+// copy outlives the call.
+class TRX_INTERNAL TrxHostCall {
+ public:
+  static constexpr size_t kPinnedMax = 256 * 1024;
+  template <class T> struct Reg { int i; };
+  explicit TrxHostCall(trxsig_ctx *c);
+  ~TrxHostCall();
+  TrxHostCall(const TrxHostCall &) = delete;
+  TrxHostCall &operator=(const TrxHostCall &) = delete;
+
+  template <class T> Reg<T> in(const T *h, size_t n) { return add<T>(kIn, h, nullptr, n, n); }
+  template <class T> Reg<T> val(const T &v) {
+    static_assert(sizeof(T) <= sizeof(Region::v), "val() takes a scalar");
+    const Reg<T> r = add<T>(kIn, nullptr, nullptr, 1, 1);
+    std::memcpy(regs_[r.i].v, &v, sizeof(T));
+    regs_[r.i].inline_val = true;
+    return r;
+  }
+  template <class T> Reg<T> inout(const T *src, T *dst, size_t n) { return add<T>(kInOut, src, dst, n, n); }
+  template <class T> Reg<T> out(T *h, size_t n, size_t reserve = 0) { return add<T>(kOut, nullptr, h, n, reserve > n ? reserve : n); }
+  template <class T> Reg<T> zeroed_out(T *h, size_t n) {
+    const Reg<T> r = out(h, n);
+    regs_[r.i].zero = true;
+    return r;
+  }
+  int stage();
+  template <class T> T *dev(Reg<T> r) const { return (T *)(d_ + regs_[r.i].off); }
+  int finish(int rc);
+
+ private:
+  enum Kind { kIn, kInOut, kOut };
+  struct Region {
+    Kind kind;
+    const void *src;
+    void *dst;
+    size_t bytes, dev_bytes, off;
+    bool inline_val, zero;
+    alignas(8) unsigned char v[8];
+  };
+  template <class T> Reg<T> add(Kind kind, const void *src, void *dst, size_t n, size_t dev_n) {
+    regs_.push_back(Region{kind, src, dst, sizeof(T) * n, sizeof(T) * dev_n, 0, false, false, {}});
+    return Reg<T>{(int)regs_.size() - 1};
+  }
+  trxsig_ctx *c_;
+  TrxDeviceGuard guard_;
+  std::vector<Region> regs_;
+  char *d_ = nullptr;                  // the staging area
+  char *m_ = nullptr;                  // its pinned mirror (a call that fits in kPinnedMax), else nullptr
+  size_t dl_lo_ = 0, dl_hi_ = 0;       // the download range
+  bool queued_ = false;                // a copy is queued that nobody has waited for yet
+};
 
 // Small tables a call makes on the host and a kernel of the same call reads: pinned staging blocks taken in turn, each free again
 // when the upload that read it has run.  (A PAGEABLE source makes hipMemcpyAsync wait until the stream has drained -- the host then

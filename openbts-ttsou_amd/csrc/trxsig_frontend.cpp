@@ -14,17 +14,6 @@
 #include "trxsig_launch.h"
 
 namespace {
-#define FE_HIP(c, call)                                                        \
-  do {                                                                         \
-    hipError_t e_ = (call);                                                    \
-    if (e_ != hipSuccess) return trx_ctx_fail((c), TRXSIG_EHIP, #call, e_);    \
-  } while (0)
-
-struct Guard {
-  int prev = -1;
-  explicit Guard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
-  ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 inline int burst_len(int tn, int sps) { return (156 + ((tn & 3) == 0)) * sps; }   // radioInterface.cpp:370-378
 }  // namespace
 
@@ -107,7 +96,7 @@ int trxsig_rxfe_create(trxsig_rxfe **out, trxsig_ctx *c, int n_streams, int max_
     delete fe;
     return rc;
   }
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   const size_t rcv_b = sizeof(trx_c32) * (size_t)fe->stride * fe->S, tmp_b = sizeof(trx_c32) * (size_t)157 * fe->sps * fe->S;
   if (hipMalloc((void **)&fe->d_rcv, rcv_b) != hipSuccess || hipMalloc((void **)&fe->d_tmp, tmp_b) != hipSuccess ||
       hipMalloc((void **)&fe->d_hist, sizeof(short2) * TRXSIG_OUTHISTORY * (size_t)fe->S) != hipSuccess ||
@@ -167,7 +156,7 @@ int trxsig_rxfe_create_wideband(trxsig_rxfe **out, trxsig_ctx *c, int n_wide_str
     return rc;
   }
   fe->n_total = (long long)TRXSIG_OUTHISTORY * rate_factor;   // (the zero history in front of the stream holds raw samples 0 .. hist - 1)
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   // the history is per wideband stream and rate_factor times longer; the fused (narrowband) tables are not used
   (void)hipFree(fe->d_hist); fe->d_hist = nullptr;
   (void)hipFree(fe->d_keep); fe->d_keep = nullptr; (void)hipFree(fe->d_tpb); fe->d_tpb = nullptr;
@@ -189,14 +178,14 @@ int trxsig_rxfe_push_wideband(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks
   if (!fe->Cw) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_push_wideband: not a wideband front end", hipSuccess);
   if (!d_iq || n_chunks <= 0 || n_chunks > fe->max_chunks) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_push_wideband: bad argument", hipSuccess);
   fe->mode = 1;
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   const int left = fe->wr - fe->rd;
   if (fe->rd > 0 && left <= 157 * fe->sps) {                // the uncut tail moves to the front of every row (as trxsig_rxfe_push)
     if (left > 0) {
-      FE_HIP(c, hipMemcpy2DAsync(fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps, fe->d_rcv + fe->rd, sizeof(trx_c32) * (size_t)fe->stride,
+      TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps, fe->d_rcv + fe->rd, sizeof(trx_c32) * (size_t)fe->stride,
                                  sizeof(trx_c32) * (size_t)left, fe->S, hipMemcpyDeviceToDevice, st));
-      FE_HIP(c, hipMemcpy2DAsync(fe->d_rcv, sizeof(trx_c32) * (size_t)fe->stride, fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps,
+      TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_rcv, sizeof(trx_c32) * (size_t)fe->stride, fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps,
                                  sizeof(trx_c32) * (size_t)left, fe->S, hipMemcpyDeviceToDevice, st));
     }
     fe->rd = 0; fe->wr = left;
@@ -211,10 +200,10 @@ int trxsig_rxfe_push_wideband(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks
   a.o_skip = fe->skip; a.n_out = fe->n_out;
   a.out = fe->d_rcv + fe->wr; a.out_stride = fe->stride; a.out_win_step = fe->per_chunk;
   a.mix_freq = fe->d_freq; a.mix_carriers = fe->C; a.mix_n0 = fe->n_total; a.mix_tables = (const TrxTables *)trxsig_tables_device(c);
-  if (fe->shared) FE_HIP(c, trx_launch_channelise16(st, a, fe->Sw, fe->C, n_chunks, fe->d_tw, trx_ctx_profiler(c), fe->binmap));
-  else FE_HIP(c, trx_launch_resample_ex(st, a, fe->S, n_chunks, true, false, trx_ctx_profiler(c)));
+  if (fe->shared) TRX_HIPCHK(c, trx_launch_channelise16(st, a, fe->Sw, fe->C, n_chunks, fe->d_tw, trx_ctx_profiler(c), fe->binmap));
+  else TRX_HIPCHK(c, trx_launch_resample_ex(st, a, fe->S, n_chunks, true, false, trx_ctx_profiler(c)));
   const short2 *tail = reinterpret_cast<const short2 *>(d_iq) + ((size_t)n_chunks * chunk - hist);
-  FE_HIP(c, hipMemcpy2DAsync(fe->d_hist, sizeof(short2) * (size_t)hist, tail, sizeof(short2) * (size_t)n_chunks * chunk,
+  TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_hist, sizeof(short2) * (size_t)hist, tail, sizeof(short2) * (size_t)n_chunks * chunk,
                              sizeof(short2) * (size_t)hist, fe->Sw, hipMemcpyDeviceToDevice, st));
   fe->wr += n_chunks * fe->per_chunk;
   fe->n_total += (long long)n_chunks * chunk;
@@ -252,10 +241,10 @@ int trxsig_rxfe_set_shared_filter(trxsig_rxfe *fe, int on) {
       tw[(size_t)k * 16 + j] = make_float2((float)std::cos(ph), (float)-std::sin(ph));   // exp(-j theta_c j)
     }
   }
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   if (!fe->d_tw && hipMalloc((void **)&fe->d_tw, sizeof(float2) * tw.size()) != hipSuccess)
     return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_rxfe_set_shared_filter: device allocation failed", hipSuccess);
-  FE_HIP(c, hipMemcpy(fe->d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+  TRX_HIPCHK(c, hipMemcpy(fe->d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
   fe->binmap = binmap;
   fe->shared = 1;
   return TRXSIG_OK;
@@ -264,7 +253,7 @@ int trxsig_rxfe_set_shared_filter(trxsig_rxfe *fe, int on) {
 void trxsig_rxfe_destroy(trxsig_rxfe *fe) {
   if (!fe) return;
   {
-    Guard g(trxsig_device(fe->c));
+    TrxDeviceGuard g(trxsig_device(fe->c));
     (void)hipFree(fe->d_freq); (void)hipFree(fe->d_tw);
     (void)hipFree(fe->d_rcv); (void)hipFree(fe->d_tmp); (void)hipFree(fe->d_hist); (void)hipFree(fe->d_lpf); (void)hipFree(fe->d_idx);
     (void)hipFree(fe->d_keep); (void)hipFree(fe->d_tpb);
@@ -282,15 +271,15 @@ int trxsig_rxfe_push(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks) {
   if (fe->mode == 2) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_push: this front end is used through the fused call", hipSuccess);
   if (fe->Cw) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_rxfe_push: a wideband front end takes trxsig_rxfe_push_wideband", hipSuccess);
   fe->mode = 1;
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   const int left = fe->wr - fe->rd;
   if (fe->rd > 0 && left <= 157 * fe->sps) {
     // the uncut tail (less than a burst after a pop) moves to the front of every row: two small strided copies
     if (left > 0) {
-      FE_HIP(c, hipMemcpy2DAsync(fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps, fe->d_rcv + fe->rd, sizeof(trx_c32) * (size_t)fe->stride,
+      TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps, fe->d_rcv + fe->rd, sizeof(trx_c32) * (size_t)fe->stride,
                                  sizeof(trx_c32) * (size_t)left, fe->S, hipMemcpyDeviceToDevice, st));
-      FE_HIP(c, hipMemcpy2DAsync(fe->d_rcv, sizeof(trx_c32) * (size_t)fe->stride, fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps,
+      TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_rcv, sizeof(trx_c32) * (size_t)fe->stride, fe->d_tmp, sizeof(trx_c32) * (size_t)157 * fe->sps,
                                  sizeof(trx_c32) * (size_t)left, fe->S, hipMemcpyDeviceToDevice, st));
     }
     fe->rd = 0; fe->wr = left;
@@ -303,10 +292,10 @@ int trxsig_rxfe_push(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks) {
   a.lpf = fe->d_lpf; a.L = fe->L; a.P = fe->P; a.Q = TRXSIG_OUTRATE;
   a.o_skip = fe->skip; a.n_out = fe->n_out;
   a.out = fe->d_rcv + fe->wr; a.out_stride = fe->stride; a.out_win_step = fe->per_chunk;
-  FE_HIP(c, trx_launch_resample_ex(st, a, fe->S, n_chunks, true, false, trx_ctx_profiler(c)));
+  TRX_HIPCHK(c, trx_launch_resample_ex(st, a, fe->S, n_chunks, true, false, trx_ctx_profiler(c)));
   // rcvHistory = the last OUTHISTORY samples received (:259)
   const short2 *tail = reinterpret_cast<const short2 *>(d_iq) + ((size_t)n_chunks * TRXSIG_OUTCHUNK - TRXSIG_OUTHISTORY);
-  FE_HIP(c, hipMemcpy2DAsync(fe->d_hist, sizeof(short2) * TRXSIG_OUTHISTORY, tail, sizeof(short2) * (size_t)n_chunks * TRXSIG_OUTCHUNK,
+  TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_hist, sizeof(short2) * TRXSIG_OUTHISTORY, tail, sizeof(short2) * (size_t)n_chunks * TRXSIG_OUTCHUNK,
                              sizeof(short2) * TRXSIG_OUTHISTORY, fe->S, hipMemcpyDeviceToDevice, st));
   fe->wr += n_chunks * fe->per_chunk;
   return TRXSIG_OK;
@@ -328,17 +317,17 @@ int trxsig_rxfe_pop(trxsig_rxfe *fe, const trxsig_c32 **d_samples, const int32_t
   *n_bursts = nb;
   *d_samples = (const trxsig_c32 *)fe->d_rcv;
   if (nb == 0) { *d_offset = *d_length = nullptr; return TRXSIG_OK; }
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   if (fe->S * nb > fe->idx_cap) {
-    FE_HIP(c, hipStreamSynchronize(st));
+    TRX_HIPCHK(c, hipStreamSynchronize(st));
     (void)hipFree(fe->d_idx); fe->d_idx = nullptr; fe->idx_cap = 0;
     const int cap = fe->S * nb + 1024;
-    FE_HIP(c, hipMalloc((void **)&fe->d_idx, sizeof(int32_t) * 2 * (size_t)cap));
+    TRX_HIPCHK(c, hipMalloc((void **)&fe->d_idx, sizeof(int32_t) * 2 * (size_t)cap));
     fe->idx_cap = cap;
   }
   int32_t *off = fe->d_idx, *len = fe->d_idx + fe->idx_cap;
-  FE_HIP(c, trx_launch_burst_index(st, fe->S, nb, fe->stride, fe->rd, fe->tn, fe->sps, off, len));
+  TRX_HIPCHK(c, trx_launch_burst_index(st, fe->S, nb, fe->stride, fe->rd, fe->tn, fe->sps, off, len));
   *d_offset = off; *d_length = len;
   fe->rd += pos; fe->tn = tn;
   return TRXSIG_OK;
@@ -380,16 +369,16 @@ int trx_rxfe_fused_begin(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks, Trx
 int trx_rxfe_fused_end(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks, const TrxRxfePush &p) {
   trxsig_ctx *c = fe->c;
   fe->mode = 2;
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   // [its 192-sample history | the chunk] (stream-ordered behind the kernels that read d_keep)
   const size_t kb = sizeof(short2) * (size_t)fe->n_in, rowb = sizeof(short2) * (size_t)n_chunks * TRXSIG_OUTCHUNK;
   const short2 *raw = reinterpret_cast<const short2 *>(d_iq);
   if (n_chunks >= 2) {
-    FE_HIP(c, hipMemcpy2DAsync(fe->d_keep, kb, raw + ((size_t)n_chunks * TRXSIG_OUTCHUNK - fe->n_in), rowb, kb, fe->S, hipMemcpyDeviceToDevice, st));
+    TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_keep, kb, raw + ((size_t)n_chunks * TRXSIG_OUTCHUNK - fe->n_in), rowb, kb, fe->S, hipMemcpyDeviceToDevice, st));
   } else {
-    FE_HIP(c, hipMemcpy2DAsync(fe->d_keep, kb, fe->d_keep + TRXSIG_OUTCHUNK, kb, sizeof(short2) * TRXSIG_OUTHISTORY, fe->S, hipMemcpyDeviceToDevice, st));
-    FE_HIP(c, hipMemcpy2DAsync(fe->d_keep + TRXSIG_OUTHISTORY, kb, raw, rowb, sizeof(short2) * TRXSIG_OUTCHUNK, fe->S, hipMemcpyDeviceToDevice, st));
+    TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_keep, kb, fe->d_keep + TRXSIG_OUTCHUNK, kb, sizeof(short2) * TRXSIG_OUTHISTORY, fe->S, hipMemcpyDeviceToDevice, st));
+    TRX_HIPCHK(c, hipMemcpy2DAsync(fe->d_keep + TRXSIG_OUTHISTORY, kb, raw, rowb, sizeof(short2) * TRXSIG_OUTCHUNK, fe->S, hipMemcpyDeviceToDevice, st));
   }
   int pos = 0, tn = p.tn0;
   for (int j = 0; j < p.nb; j++) { pos += burst_len(tn, fe->sps); tn = (tn + 1) & 7; }
@@ -437,7 +426,7 @@ int trxsig_txbe_create(trxsig_txbe **out, trxsig_ctx *c, int n_streams, int max_
   const long long cap = (long long)be->inchunk + (long long)max_bursts * 157 * be->sps;
   be->stride = (be->inhist + cap + 63) & ~63LL;
   be->iq_stride = ((long long)trxsig_resample_out_len((int)be->stride, TRXSIG_OUTRATE, be->Q) + 63) & ~63LL;
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   bool ok = true;
   for (int k = 0; k < 2 && ok; k++) {
     ok = hipMalloc((void **)&be->d_send[k], sizeof(trx_c32) * (size_t)be->stride * be->S) == hipSuccess &&
@@ -465,7 +454,7 @@ int trxsig_txbe_create(trxsig_txbe **out, trxsig_ctx *c, int n_streams, int max_
 void trxsig_txbe_destroy(trxsig_txbe *be) {
   if (!be) return;
   {
-    Guard g(trxsig_device(be->c));
+    TrxDeviceGuard g(trxsig_device(be->c));
     (void)hipFree(be->d_send[0]); (void)hipFree(be->d_send[1]); (void)hipFree(be->d_lpf); (void)hipFree(be->d_iq); (void)hipFree(be->d_meta);
     (void)hipFree(be->d_ring); (void)hipFree(be->d_rgain); (void)hipFree(be->d_tab);
     be->tab_up.release();
@@ -513,12 +502,12 @@ int trxsig_txbe_push_bursts(trxsig_txbe *be, const uint8_t *d_bits, const int32_
   if (ok != TRXSIG_OK) return ok;
   long long tot = 0;
   for (int j = 0; j < n_bursts; j++) tot += (long long)be->sps * (148 + h_guard[j]);
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   be->started = 1;
   if (be->fused) {
     // only the bits travel: burst j of this push takes ring slot head + j and starts where the pending samples end
-    FE_HIP(c, trx_launch_tx_ring_store(st, d_bits, d_gain, be->S, n_bursts, be->ring_head, be->ring_cap, be->d_ring, be->d_rgain));
+    TRX_HIPCHK(c, trx_launch_tx_ring_store(st, d_bits, d_gain, be->S, n_bursts, be->ring_head, be->ring_cap, be->d_ring, be->d_rgain));
     long long pos = (long long)be->inhist + be->fill;
     for (int j = 0; j < n_bursts; j++) {
       TxBurst b;
@@ -541,8 +530,8 @@ int trxsig_txbe_push_bursts(trxsig_txbe *be, const uint8_t *d_bits, const int32_
       pos += (long long)be->sps * (148 + h_guard[j]);
     }
   }
-  FE_HIP(c, hipMemcpyAsync(be->d_meta, meta.data(), sizeof(int32_t) * meta.size(), hipMemcpyHostToDevice, st));
-  FE_HIP(c, hipStreamSynchronize(st));                      // meta is a local
+  TRX_HIPCHK(c, hipMemcpyAsync(be->d_meta, meta.data(), sizeof(int32_t) * meta.size(), hipMemcpyHostToDevice, st));
+  TRX_HIPCHK(c, hipStreamSynchronize(st));                      // meta is a local
   int rc = trxsig_modulate_batch(c, d_bits, be->d_meta, d_gain, B, (trxsig_c32 *)be->d_send[be->cur], be->d_meta + B);
   if (rc != TRXSIG_OK) return rc;
   be->fill += (int)tot;
@@ -559,7 +548,7 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
   const int ntr = nch * be->inchunk;                        // truncatedBuffer (:131-132)
   const int n_in = be->inhist + ntr;                        // signalVector(*sendHistory, *truncatedBuffer) (:141)
   const int n_out = trxsig_resample_out_len(n_in, TRXSIG_OUTRATE, be->Q);
-  Guard g(trxsig_device(c));
+  TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   TrxResampleArgs a = {};
   a.in = be->d_send[be->cur]; a.in_stride = be->stride; a.n = n_in;
@@ -571,7 +560,7 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
     const int M = (int)be->live.size();
     void *tab_p = nullptr;
     int tab_slot = 0;
-    FE_HIP(c, be->tab_up.take(sizeof(int32_t) * 2 * (size_t)be->tab_cap, &tab_p, &tab_slot));
+    TRX_HIPCHK(c, be->tab_up.take(sizeof(int32_t) * 2 * (size_t)be->tab_cap, &tab_p, &tab_slot));
     int32_t *tab = (int32_t *)tab_p;
     std::memset(tab, 0, sizeof(int32_t) * 2 * (size_t)be->tab_cap);
     int m_used = 0;
@@ -582,11 +571,11 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
       tab[(size_t)be->tab_cap + m_used] = b.slot | (b.guard << 16) | (b.has_gain << 20);
       m_used++;
     }
-    FE_HIP(c, be->tab_up.upload(tab_slot, be->d_tab, sizeof(int32_t) * 2 * (size_t)be->tab_cap, st));
+    TRX_HIPCHK(c, be->tab_up.upload(tab_slot, be->d_tab, sizeof(int32_t) * 2 * (size_t)be->tab_cap, st));
     a.in = be->d_ring; a.in_stride = be->ring_cap;
     a.tx_tables = (const TrxTables *)trxsig_tables_device(c); a.tx_gain = be->d_rgain; a.tx_start = be->d_tab; a.tx_meta = be->d_tab + be->tab_cap;
     a.tx_n = m_used; a.tx_sps = be->sps;
-    FE_HIP(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c), true));
+    TRX_HIPCHK(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c), true));
     // sendHistory = the last INHISTORY samples sent, the rest of sendBuffer follows it (:183-191): the window's origin moves on
     // by ntr samples; bursts that end before it are done
     size_t keep_from = 0;
@@ -599,10 +588,10 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
     *n_samples = n_out - TRXSIG_OUTHISTORY;
     return TRXSIG_OK;
   }
-  FE_HIP(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c)));
+  TRX_HIPCHK(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c)));
   // sendHistory = the last INHISTORY samples sent (:183-184), the rest of sendBuffer follows it (:187-191): into the other buffer
   const int keep = be->inhist + be->fill - ntr;             // history + left-over, contiguous at [ntr, ntr + keep)
-  FE_HIP(c, hipMemcpy2DAsync(be->d_send[be->cur ^ 1], sizeof(trx_c32) * (size_t)be->stride, be->d_send[be->cur] + ntr,
+  TRX_HIPCHK(c, hipMemcpy2DAsync(be->d_send[be->cur ^ 1], sizeof(trx_c32) * (size_t)be->stride, be->d_send[be->cur] + ntr,
                              sizeof(trx_c32) * (size_t)be->stride, sizeof(trx_c32) * (size_t)keep, be->S, hipMemcpyDeviceToDevice, st));
   be->cur ^= 1;
   be->fill -= ntr;

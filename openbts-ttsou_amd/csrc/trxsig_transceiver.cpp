@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "trxsig_ctx.h"
 #include "trxsig_transceiver.h"
 #include "trxsig_trxstate.h"
 
@@ -88,10 +89,6 @@ struct trxsig_trx {
   // transmit state (fillerModulus lives in ctl)
   std::vector<trxsig_c32> fillerTable[102][8];
   TxQueue queue;                                            // earliest time on top (VectorQueue)
-  // device scratch for the single-burst calls
-  char *d = nullptr;
-  char *hpin = nullptr;              // pinned host mirror of the first part of d (samples + scalars + taps): one DMA per step
-  size_t d_bytes = 0;
 };
 
 namespace {
@@ -100,11 +97,6 @@ int fail(trxsig_trx *t, int code, const std::string &what) {
   if (t) t->err = what;
   return code;
 }
-#define TRX_HIP(t, call)                                                                  \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess) return fail(t, TRXSIG_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 #define TRX_LIB(t, call)                                                                  \
   do {                                                                                    \
     int rc_ = (call);                                                                     \
@@ -117,6 +109,25 @@ int modulate(trxsig_trx *t, const uint8_t *bits, int tn, const float *gain, std:
   out.assign((size_t)t->sps * (148 + guard), trxsig_c32{0.0f, 0.0f});
   TRX_LIB(t, trxsig_modulate_host(t->ctx, bits, &guard, gain, 1, out.data(), &off, (int64_t)out.size()));
   return TRXSIG_OK;
+}
+
+// analyzeTrafficBurst(requestChannel) + designDFE(chan, SNRestimate[tn]) on the GPU, into timeslot tn's channel / DFE cache
+// (*flags: the estimate's detection flags)
+int estimate_dfe(trxsig_trx *t, const trxsig_c32 *h_burst, int n, int tn, uint8_t *flags) {
+  TrxHostCall hc(t->ctx);
+  const auto x = hc.in(h_burst, n);
+  const auto off = hc.val(0), len = hc.val(n);
+  const auto fl = hc.out(flags, 1);
+  const auto amp = hc.out<trxsig_c32>(nullptr, 1);
+  const auto toa = hc.out<float>(nullptr, 1);
+  const auto co = hc.out(&t->chanRespOffset[tn], 1);
+  const auto w = hc.out(t->dfeW[tn], 7);
+  const auto b = hc.out(t->dfeB[tn], 5);
+  int rc = hc.stage();
+  if (rc == TRXSIG_OK)
+    rc = trxsig_estimate_dfe_batch(t->ctx, hc.dev(x), hc.dev(off), hc.dev(len), 1, (int)t->ctl.tsc, 3.0f, -1.0f, t->SNRestimate[tn], 0, 0,
+                                   hc.dev(fl), hc.dev(amp), hc.dev(toa), hc.dev(co), hc.dev(w), hc.dev(b));
+  return hc.finish(rc);
 }
 
 }  // namespace
@@ -261,12 +272,6 @@ int trxsig_trx_create(trxsig_trx **out, int device, int sps, int start_fn, int s
     t->SNRestimate[i] = 0.0f;
     t->channelEstimateTime[i] = start;
   }
-  // device scratch: one burst (<= 157*sps samples) + offsets + results + taps
-  t->d_bytes = 8 * (size_t)157 * sps + 4096;
-  if (hipMalloc((void **)&t->d, t->d_bytes) != hipSuccess) { trxsig_destroy(t->ctx); delete t; return TRXSIG_EHIP; }
-  if (hipHostMalloc((void **)&t->hpin, t->d_bytes, hipHostMallocDefault) != hipSuccess) {
-    (void)hipFree(t->d); trxsig_destroy(t->ctx); delete t; return TRXSIG_EHIP;
-  }
   *out = t;
   return TRXSIG_OK;
 }
@@ -274,8 +279,6 @@ int trxsig_trx_create(trxsig_trx **out, int device, int sps, int start_fn, int s
 void trxsig_trx_destroy(trxsig_trx *t) {
   if (!t) return;
   while (!t->queue.empty()) { delete t->queue.top(); t->queue.pop(); }
-  if (t->d) (void)hipFree(t->d);
-  if (t->hpin) (void)hipHostFree(t->hpin);
   if (t->ctx) trxsig_destroy(t->ctx);
   delete t;
 }
@@ -359,28 +362,11 @@ int trxsig_trx_pull_radio_vector(trxsig_trx *t, const trxsig_c32 *h_burst, int n
       const float n2 = amplitude.im * amplitude.im + amplitude.re * amplitude.re;          // Complex::norm2 (Complex.h:119)
       t->SNRestimate[tn] = (float)(n2 / (t->energyThreshold * t->energyThreshold + 1.0));  // :340
       if (estimateChannel) {                               // :341-349, on the GPU with this SNR
-        char *d = t->d;
-        hipStream_t st = (hipStream_t)trxsig_get_stream(t->ctx);
-        trxsig_c32 *d_x = (trxsig_c32 *)d;
-        char *p = d + 8 * (size_t)157 * t->sps;
-        int32_t *d_off = (int32_t *)p, *d_len = (int32_t *)(p + 16);
-        uint8_t *d_fl = (uint8_t *)(p + 32);
-        trxsig_c32 *d_amp = (trxsig_c32 *)(p + 64), *d_w = (trxsig_c32 *)(p + 128), *d_b = (trxsig_c32 *)(p + 256);
-        float *d_toa = (float *)(p + 96), *d_co = (float *)(p + 112);
-        TRX_HIP(t, hipMemcpyAsync(d_x, h_burst, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        TRX_HIP(t, hipMemcpyAsync(d_off, &off, 4, hipMemcpyHostToDevice, st));
-        TRX_HIP(t, hipMemcpyAsync(d_len, &len, 4, hipMemcpyHostToDevice, st));
         // the SNR estimate goes in as formed above (the reference squares its DOUBLE threshold; the batch
         // kernel's own formula squares a float one)
         if (!(t->SNRestimate[tn] > 0.0f)) return fail(t, TRXSIG_EINVAL, "SNR estimate is not positive");
-        TRX_LIB(t, trxsig_estimate_dfe_batch(t->ctx, d_x, d_off, d_len, 1, (int)t->ctl.tsc, 3.0f, -1.0f, t->SNRestimate[tn], 0, 0,
-                                             d_fl, d_amp, d_toa, d_co, d_w, d_b));
         uint8_t efl = 0;
-        TRX_HIP(t, hipMemcpyAsync(&efl, d_fl, 1, hipMemcpyDeviceToHost, st));
-        TRX_HIP(t, hipMemcpyAsync(&t->chanRespOffset[tn], d_co, 4, hipMemcpyDeviceToHost, st));
-        TRX_HIP(t, hipMemcpyAsync(t->dfeW[tn], d_w, 8 * 7, hipMemcpyDeviceToHost, st));
-        TRX_HIP(t, hipMemcpyAsync(t->dfeB[tn], d_b, 8 * 5, hipMemcpyDeviceToHost, st));
-        TRX_HIP(t, hipStreamSynchronize(st));
+        TRX_LIB(t, estimate_dfe(t, h_burst, n, tn, &efl));
         if (!(efl & TRXSIG_F_DETECT)) return fail(t, TRXSIG_EHIP, "channel estimate disagrees with the detector");
         t->haveChan[tn] = true;
         t->channelEstimateTime[tn] = now;
@@ -406,30 +392,8 @@ int trxsig_trx_pull_radio_vector(trxsig_trx *t, const trxsig_c32 *h_burst, int n
 
   if (corrType == TRXSIG_CORR_TSC && needDFE) {
     // scaleVector(burst, 1/amp); equalizeBurst(burst, TOA - chanRespOffset[ts], sps, w[ts], b[ts]) (:391-396)
-    char *d = t->d;
-    hipStream_t st = (hipStream_t)trxsig_get_stream(t->ctx);
-    trxsig_c32 *d_x = (trxsig_c32 *)d;
-    char *p = d + 8 * (size_t)157 * t->sps;
-    int32_t *d_off = (int32_t *)p, *d_len = (int32_t *)(p + 16);
-    uint8_t *d_fl = (uint8_t *)(p + 32);
-    trxsig_c32 *d_amp = (trxsig_c32 *)(p + 64), *d_w = (trxsig_c32 *)(p + 128), *d_b = (trxsig_c32 *)(p + 256);
-    float *d_toa = (float *)(p + 96), *d_soft = (float *)(p + 512);
     const float toa_eq = TOA - t->chanRespOffset[tn];
-    const uint8_t en = TRXSIG_F_DETECT;
-    // everything the step needs in ONE host-to-device copy from the pinned mirror (same layout as d), the soft bits back
-    // in one (134 -> 94 us per call)
-    {
-      char *m = t->hpin, *mp = m + (p - d);
-      std::memcpy(m, h_burst, 8 * (size_t)n);
-      std::memcpy(mp, &off, 4); std::memcpy(mp + 16, &len, 4); std::memcpy(mp + 32, &en, 1);
-      std::memcpy(mp + 64, &amplitude, 8); std::memcpy(mp + 96, &toa_eq, 4);
-      std::memcpy(mp + 128, t->dfeW[tn], 56); std::memcpy(mp + 256, t->dfeB[tn], 40);
-      TRX_HIP(t, hipMemcpyAsync(d, m, (size_t)(p - d) + 512, hipMemcpyHostToDevice, st));
-    }
-    TRX_LIB(t, trxsig_equalize_taps_batch(t->ctx, d_x, d_off, d_len, 1, d_amp, d_toa, d_fl, d_w, d_b, d_soft, nullptr, nsoft, 160));
-    TRX_HIP(t, hipMemcpyAsync(t->hpin + (p - d) + 512, d_soft, 4 * (size_t)nsoft, hipMemcpyDeviceToHost, st));
-    TRX_HIP(t, hipStreamSynchronize(st));
-    std::memcpy(h_soft, t->hpin + (p - d) + 512, 4 * (size_t)nsoft);
+    TRX_LIB(t, trxsig_equalize_taps_host(t->ctx, h_burst, n, amplitude, toa_eq, t->dfeW[tn], t->dfeB[tn], h_soft, nsoft));
   }
   *n_soft = nsoft;
   // :400-402 -- Complex::abs() is (float)sqrt((double)norm2) (Complex.h:131)

@@ -21,12 +21,6 @@ namespace {
 constexpr int kHyperframe = 2048 * 26 * 51;                 // GSM/GSMCommon.h:306
 constexpr int kSoft = 148;                                  // soft values kept per burst (gSlotLen: what the datagram carries, :658-672)
 
-struct Guard {
-  int prev = -1;
-  explicit Guard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
-  ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 // one column of a timeslot's segment table: the ARFCNs that share (channel combination, TSC) on that timeslot take the
 // same path at every frame number
 struct Column { int chanType, tsc, count; };
@@ -152,11 +146,6 @@ namespace {
 // workgroups wait for that kernel to drain (80 us): everything on ONE stream is faster (309 against 279 Mbursts/s on bench.py
 // --workload config4).  The side-stream arrangement stays selectable (trxsig_trxgroup_set_beside_rows) and tested.
 constexpr int kBesideRows = 0x7fffffff;
-#define G_HIP(g, call)                                                          \
-  do {                                                                          \
-    hipError_t e_ = (call);                                                     \
-    if (e_ != hipSuccess) return trx_ctx_fail((g)->c, TRXSIG_EHIP, #call, e_);  \
-  } while (0)
 #define G_LIB(call)                       \
   do {                                    \
     int rc_ = (call);                     \
@@ -183,8 +172,8 @@ int derive_tables(trxsig_trxgroup *g) {
     if ((int)cs.size() > G) G = (int)cs.size();
   }
   g->G = G;
-  G_HIP(g, hipMemcpy(g->d_gid, gid.data(), sizeof(uint16_t) * gid.size(), hipMemcpyHostToDevice));
-  G_HIP(g, hipMemcpy(g->d_pos, pos.data(), sizeof(int32_t) * pos.size(), hipMemcpyHostToDevice));
+  TRX_HIPCHK(g->c, hipMemcpy(g->d_gid, gid.data(), sizeof(uint16_t) * gid.size(), hipMemcpyHostToDevice));
+  TRX_HIPCHK(g->c, hipMemcpy(g->d_pos, pos.data(), sizeof(int32_t) * pos.size(), hipMemcpyHostToDevice));
   g->dirty = false;
   return TRXSIG_OK;
 }
@@ -210,7 +199,7 @@ int trxsig_trxgroup_create(trxsig_trxgroup **out, trxsig_ctx *c, int n_arfcn, in
   if (!g) return TRXSIG_ENOMEM;
   g->c = c; trx_ctx_retain(c); g->S = n_arfcn; g->sps = trxsig_sps(c); g->leg = tsc_leg;
   g->ctl.resize((size_t)n_arfcn);
-  Guard gd(trxsig_device(c));
+  TrxDeviceGuard gd(trxsig_device(c));
   const int S = n_arfcn;
   std::vector<TrxGroupArfcn> st((size_t)S);
   for (TrxGroupArfcn &a : st) {                             // Transceiver::Transceiver (:58-92)
@@ -243,7 +232,7 @@ int trxsig_trxgroup_create(trxsig_trxgroup **out, trxsig_ctx *c, int n_arfcn, in
 void trxsig_trxgroup_destroy(trxsig_trxgroup *g) {
   if (!g) return;
   {
-    Guard gd(trxsig_device(g->c));
+    TrxDeviceGuard gd(trxsig_device(g->c));
     (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(g->c));
     if (g->side) { (void)hipStreamSynchronize(g->side); (void)hipStreamDestroy(g->side); }
     if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
@@ -312,7 +301,7 @@ struct PullSource {
 int join_side(trxsig_trxgroup *g, hipStream_t st) {
   for (int k = 0; k < 2; k++) {
     if (!g->wk[k].in_flight) continue;
-    G_HIP(g, hipStreamWaitEvent(st, g->wk[k].done, 0));
+    TRX_HIPCHK(g->c, hipStreamWaitEvent(st, g->wk[k].done, 0));
     g->wk[k].in_flight = false;
   }
   return TRXSIG_OK;
@@ -326,7 +315,7 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   const long long cells = (long long)n_slots * S;
   if (cells > std::numeric_limits<int32_t>::max() / 2)
     return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull: too many bursts in one call (split it)", hipSuccess);
-  Guard gd(trxsig_device(c));
+  TrxDeviceGuard gd(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   g->have = false;
   if (g->dirty) G_LIB(derive_tables(g));
@@ -335,7 +324,7 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   if (g->wk[g->cur].in_flight) g->cur ^= 1;
   trxsig_trxgroup::Work &W = g->wk[g->cur];
   if (W.in_flight) {
-    G_HIP(g, hipStreamWaitEvent(st, W.done, 0));
+    TRX_HIPCHK(g->c, hipStreamWaitEvent(st, W.done, 0));
     W.in_flight = false;
   }
 
@@ -370,35 +359,35 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   const size_t R = (size_t)(n_rows > 0 ? n_rows : 1), S8 = (size_t)S * 8;
 
   // ---- workspace (grow-only; an array that grows waits for the stream first) ----
-  G_HIP(g, W.rowmap.need((size_t)cells, st)); G_HIP(g, W.packed.need((size_t)cells, st)); G_HIP(g, W.seg.need((size_t)n_slots * G, st));
-  G_HIP(g, W.off.need(R, st)); G_HIP(g, W.len.need(R, st)); G_HIP(g, W.tap_ix.need(R, st));
-  G_HIP(g, W.flags.need(R, st)); G_HIP(g, W.gate.need(R, st)); G_HIP(g, W.ev.need(R, st)); G_HIP(g, W.ev_flags.need(R, st));
-  G_HIP(g, W.amp.need(R, st)); G_HIP(g, W.ev_amp.need(R, st));
-  G_HIP(g, W.toa.need(R, st)); G_HIP(g, W.avgpwr.need(R, st)); G_HIP(g, W.toa_eq.need(R, st)); G_HIP(g, W.snr.need(R, st));
-  G_HIP(g, W.ev_toa.need(R, st)); G_HIP(g, W.ev_toaeq.need(R, st)); G_HIP(g, W.thr_after.need(R, st));
-  G_HIP(g, W.soft.need(R * kSoft, st));
+  TRX_HIPCHK(g->c, W.rowmap.need((size_t)cells, st)); TRX_HIPCHK(g->c, W.packed.need((size_t)cells, st)); TRX_HIPCHK(g->c, W.seg.need((size_t)n_slots * G, st));
+  TRX_HIPCHK(g->c, W.off.need(R, st)); TRX_HIPCHK(g->c, W.len.need(R, st)); TRX_HIPCHK(g->c, W.tap_ix.need(R, st));
+  TRX_HIPCHK(g->c, W.flags.need(R, st)); TRX_HIPCHK(g->c, W.gate.need(R, st)); TRX_HIPCHK(g->c, W.ev.need(R, st)); TRX_HIPCHK(g->c, W.ev_flags.need(R, st));
+  TRX_HIPCHK(g->c, W.amp.need(R, st)); TRX_HIPCHK(g->c, W.ev_amp.need(R, st));
+  TRX_HIPCHK(g->c, W.toa.need(R, st)); TRX_HIPCHK(g->c, W.avgpwr.need(R, st)); TRX_HIPCHK(g->c, W.toa_eq.need(R, st)); TRX_HIPCHK(g->c, W.snr.need(R, st));
+  TRX_HIPCHK(g->c, W.ev_toa.need(R, st)); TRX_HIPCHK(g->c, W.ev_toaeq.need(R, st)); TRX_HIPCHK(g->c, W.thr_after.need(R, st));
+  TRX_HIPCHK(g->c, W.soft.need(R * kSoft, st));
   {
     const size_t ns = trx_group_replay_scratch(S, n_slots);
-    G_HIP(g, W.thr_g.need(ns, st)); G_HIP(g, W.succ_g.need(ns, st));
-    if (g->leg == TRXSIG_TSCLEG_EQUALIZE) G_HIP(g, W.tix_g.need(ns > R + 16 ? ns : R + 16, st));
+    TRX_HIPCHK(g->c, W.thr_g.need(ns, st)); TRX_HIPCHK(g->c, W.succ_g.need(ns, st));
+    if (g->leg == TRXSIG_TSCLEG_EQUALIZE) TRX_HIPCHK(g->c, W.tix_g.need(ns > R + 16 ? ns : R + 16, st));
   }
-  G_HIP(g, g->w_tab.need((S8 + R) * 7, st, S8 * 7)); G_HIP(g, g->b_tab.need((S8 + R) * 5, st, S8 * 5));
-  G_HIP(g, g->chan_off.need(S8 + R, st, S8));
+  TRX_HIPCHK(g->c, g->w_tab.need((S8 + R) * 7, st, S8 * 7)); TRX_HIPCHK(g->c, g->b_tab.need((S8 + R) * 5, st, S8 * 5));
+  TRX_HIPCHK(g->c, g->chan_off.need(S8 + R, st, S8));
 
   {
     void *up = nullptr;
     int slot = 0;
     const size_t bytes = sizeof(int32_t) * g->h_seg.size();
-    G_HIP(g, g->seg_up.take(bytes, &up, &slot));
+    TRX_HIPCHK(g->c, g->seg_up.take(bytes, &up, &slot));
     std::memcpy(up, g->h_seg.data(), bytes);
-    G_HIP(g, g->seg_up.upload(slot, W.seg.p, bytes, st));
+    TRX_HIPCHK(g->c, g->seg_up.upload(slot, W.seg.p, bytes, st));
   }
   TrxGroupExpand ex = {};
   ex.S = S; ex.n_slots = n_slots; ex.tn0 = tn; ex.sps = sps; ex.fixed_len = burst_len; ex.G = G;
   ex.slot_stride = src.slot_stride; ex.arfcn_stride = src.arfcn_stride; ex.base = 0; ex.rx_nb = src.gen ? src.gen->nb : 0;
   ex.src_off = src.d_off; ex.src_len = src.d_len; ex.src_nb = n_slots;
   ex.gid = g->d_gid; ex.pos = g->d_pos; ex.seg_base = W.seg.p; ex.rowmap = W.rowmap.p; ex.off = W.off.p; ex.len = W.len.p;
-  G_HIP(g, trx_launch_group_expand(st, ex));
+  TRX_HIPCHK(g->c, trx_launch_group_expand(st, ex));
 
   // ---- the stateless detectors, a launch per class in use; thresholds 3.0 / 5.0 (:331, 363), energy gate off ----
   struct SideGuard {                                        // (an error return between a fork and its join must not leave the side stream working on this call's arrays)
@@ -414,8 +403,8 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   // become the critical path, profiles/r05_config4_ab_rach_beside.txt.)
   const bool split = src.gen && g->split_rows > 0 && n_rows >= g->split_rows && count[TRXG_CLASS_RACH] > 0 && n_tsc > 0;
   if (split) {
-    G_HIP(g, hipEventRecord(g->ev_fork, st));
-    G_HIP(g, hipStreamWaitEvent(g->side, g->ev_fork, 0));
+    TRX_HIPCHK(g->c, hipEventRecord(g->ev_fork, st));
+    TRX_HIPCHK(g->c, hipStreamWaitEvent(g->side, g->ev_fork, 0));
     side_guard.s = g->side;
     {
       const int k = TRXG_CLASS_RACH, b0 = base[k];
@@ -432,8 +421,8 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
       G_LIB(trx_ctx_rx_normal(c, gen, count[k], k, 3.0f, -1.0f, W.flags.p + b0, (trxsig_c32 *)W.amp.p + b0, W.toa.p + b0, W.avgpwr.p + b0,
                               nullptr, nullptr, 0, 0, g->side));
     }
-    G_HIP(g, hipEventRecord(g->ev_join, g->side));
-    G_HIP(g, hipStreamWaitEvent(st, g->ev_join, 0));
+    TRX_HIPCHK(g->c, hipEventRecord(g->ev_join, g->side));
+    TRX_HIPCHK(g->c, hipStreamWaitEvent(st, g->ev_join, 0));
     side_guard.s = nullptr;
   }
   for (int k = 0; k < TRXG_NCLASS && !split; k++) {
@@ -476,15 +465,15 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   const bool beside = lean && n_rows >= g->beside_rows;   // (trxsig_trxgroup_set_beside_rows: A/B and the tests of the side-stream arrangement)
   const bool piped = beside && g->pipelined;                // the join is left to the next call but one / trxsig_trxgroup_sync
   if (!piped) G_LIB(join_side(g, st));                      // (state order: nothing replays on this stream before the side stream is done)
-  G_HIP(g, trx_launch_group_pack(st, rp, W.packed.p));
+  TRX_HIPCHK(g->c, trx_launch_group_pack(st, rp, W.packed.p));
   if (beside) {
-    G_HIP(g, hipEventRecord(g->ev_fork, st));
-    G_HIP(g, hipStreamWaitEvent(g->side, g->ev_fork, 0));
+    TRX_HIPCHK(g->c, hipEventRecord(g->ev_fork, st));
+    TRX_HIPCHK(g->c, hipStreamWaitEvent(g->side, g->ev_fork, 0));
     side_guard.s = g->side;
   }
-  G_HIP(g, trx_launch_group_replay(beside ? g->side : st, rp, W.packed.p, W.thr_g.p, W.succ_g.p, equalize ? W.tix_g.p : nullptr,
+  TRX_HIPCHK(g->c, trx_launch_group_replay(beside ? g->side : st, rp, W.packed.p, W.thr_g.p, W.succ_g.p, equalize ? W.tix_g.p : nullptr,
                                    trx_ctx_profiler(c)));
-  if (beside) G_HIP(g, hipEventRecord(piped ? W.done : g->ev_join, g->side));
+  if (beside) TRX_HIPCHK(g->c, hipEventRecord(piped ? W.done : g->ev_join, g->side));
   const uint8_t *demod_gate = beside ? W.flags.p : W.gate.p;   // (gate holds TRXSIG_F_DETECT or 0: the same mask serves both)
 
   // ---- what comes back as a SoftVector ----
@@ -498,7 +487,7 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
                                      (trxsig_c32 *)g->w_tab.p + (S8 + b0) * 7, (trxsig_c32 *)g->b_tab.p + (S8 + b0) * 5,
                                      rp.ev_list ? rp.ev_list + b0 + k : nullptr));
       }
-      G_HIP(g, trx_launch_group_toa_eq(st, n_tsc, W.gate.p, W.toa.p, W.tap_ix.p, g->chan_off.p, W.toa_eq.p));
+      TRX_HIPCHK(g->c, trx_launch_group_toa_eq(st, n_tsc, W.gate.p, W.toa.p, W.tap_ix.p, g->chan_off.p, W.toa_eq.p));
       G_LIB(trx_ctx_group_equalize(c, d_samples, W.off.p, W.len.p, n_tsc, (const trxsig_c32 *)W.amp.p, W.toa_eq.p, W.gate.p,
                                    (const trxsig_c32 *)g->w_tab.p, (const trxsig_c32 *)g->b_tab.p, W.tap_ix.p, W.soft.p, kSoft, kSoft));
     } else if (!src.gen) {
@@ -517,10 +506,10 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
     W.in_flight = true;                                     // d_valid / d_threshold / the state: complete behind W.done
     side_guard.s = nullptr;
   } else if (beside) {
-    G_HIP(g, hipStreamWaitEvent(st, g->ev_join, 0));
+    TRX_HIPCHK(g->c, hipStreamWaitEvent(st, g->ev_join, 0));
     side_guard.s = nullptr;                                 // joined: ordered on the context's stream from here on
   }
-  if (equalize) G_HIP(g, trx_launch_group_commit(st, S, g->d_state, g->w_tab.p, g->b_tab.p, g->chan_off.p));
+  if (equalize) TRX_HIPCHK(g->c, trx_launch_group_commit(st, S, g->d_state, g->w_tab.p, g->b_tab.p, g->chan_off.p));
 
   g->n_slots = n_slots; g->n_rows = n_rows; g->n_tsc_rows = n_tsc; g->have = true;
   if (res) {
@@ -606,7 +595,7 @@ int trxsig_trxgroup_collect(trxsig_trxgroup *g, uint8_t *h_valid, float *h_soft,
   trxsig_ctx *c = g->c;
   if (!g->have) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_collect: no pull to collect", hipSuccess);
   if (!h_valid || !h_rssi || !h_timing) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_collect: bad argument", hipSuccess);
-  Guard gd(trxsig_device(c));
+  TrxDeviceGuard gd(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   G_LIB(join_side(g, st));
   trxsig_trxgroup::Work &W = g->wk[g->cur];
@@ -617,16 +606,16 @@ int trxsig_trxgroup_collect(trxsig_trxgroup *g, uint8_t *h_valid, float *h_soft,
   std::vector<float> toa(R), soft(h_soft ? R * kSoft : 0);
   std::vector<double> thr(h_threshold ? R : 0);
   int replay_err = 0;
-  G_HIP(g, hipMemcpyAsync(&replay_err, g->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  G_HIP(g, hipMemcpyAsync(row.data(), W.rowmap.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(&replay_err, g->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(row.data(), W.rowmap.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, st));
   if (R) {
-    G_HIP(g, hipMemcpyAsync(gate.data(), W.gate.p, R, hipMemcpyDeviceToHost, st));
-    G_HIP(g, hipMemcpyAsync(amp.data(), W.amp.p, sizeof(trx_c32) * R, hipMemcpyDeviceToHost, st));
-    G_HIP(g, hipMemcpyAsync(toa.data(), W.toa.p, sizeof(float) * R, hipMemcpyDeviceToHost, st));
-    if (h_soft) G_HIP(g, hipMemcpyAsync(soft.data(), W.soft.p, sizeof(float) * R * kSoft, hipMemcpyDeviceToHost, st));
-    if (h_threshold) G_HIP(g, hipMemcpyAsync(thr.data(), W.thr_after.p, sizeof(double) * R, hipMemcpyDeviceToHost, st));
+    TRX_HIPCHK(g->c, hipMemcpyAsync(gate.data(), W.gate.p, R, hipMemcpyDeviceToHost, st));
+    TRX_HIPCHK(g->c, hipMemcpyAsync(amp.data(), W.amp.p, sizeof(trx_c32) * R, hipMemcpyDeviceToHost, st));
+    TRX_HIPCHK(g->c, hipMemcpyAsync(toa.data(), W.toa.p, sizeof(float) * R, hipMemcpyDeviceToHost, st));
+    if (h_soft) TRX_HIPCHK(g->c, hipMemcpyAsync(soft.data(), W.soft.p, sizeof(float) * R * kSoft, hipMemcpyDeviceToHost, st));
+    if (h_threshold) TRX_HIPCHK(g->c, hipMemcpyAsync(thr.data(), W.thr_after.p, sizeof(double) * R, hipMemcpyDeviceToHost, st));
   }
-  G_HIP(g, hipStreamSynchronize(st));
+  TRX_HIPCHK(g->c, hipStreamSynchronize(st));
   if (replay_err) {                                         // (k_group_replay_seg's round bound: the thresholds of that pull are not validated)
     (void)hipMemsetAsync(g->d_err, 0, sizeof(int), st);
     return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_trxgroup: the time-parallel replay of the state machine did not converge within its round bound", hipSuccess);
@@ -659,10 +648,10 @@ int trxsig_trxgroup_pull_host(trxsig_trxgroup *g, const trxsig_c32 *h_samples, i
                          (burst_len > 0 ? burst_len : 157LL * g->sps);
   if (span > std::numeric_limits<int32_t>::max())
     return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_host: the batch's sample offsets must stay below 2^31", hipSuccess);
-  Guard gd(trxsig_device(c));
+  TrxDeviceGuard gd(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
-  G_HIP(g, g->in.need((size_t)span, st));
-  G_HIP(g, hipMemcpyAsync(g->in.p, h_samples, sizeof(trx_c32) * (size_t)span, hipMemcpyHostToDevice, st));
+  TRX_HIPCHK(g->c, g->in.need((size_t)span, st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(g->in.p, h_samples, sizeof(trx_c32) * (size_t)span, hipMemcpyHostToDevice, st));
   return trxsig_trxgroup_pull(g, (const trxsig_c32 *)g->in.p, slot_stride, arfcn_stride, burst_len, fn, tn, n_slots, nullptr);
 }
 
@@ -670,7 +659,7 @@ int trxsig_trxgroup_set_pipelined(trxsig_trxgroup *g, int on) {
   if (!g) return TRXSIG_EINVAL;
   if (g->leg != TRXSIG_TSCLEG_DEMOD && on)
     return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_set_pipelined: the demodulating TSC leg only (the equalising leg needs the machine's events inside the call)", hipSuccess);
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   G_LIB(join_side(g, (hipStream_t)trxsig_get_stream(g->c)));
   g->pipelined = on != 0;
   return TRXSIG_OK;
@@ -686,7 +675,7 @@ int trxsig_trxgroup_set_split_rows(trxsig_trxgroup *g, int rows) {
 int trxsig_trxgroup_set_beside_rows(trxsig_trxgroup *g, int rows) {
   if (!g) return TRXSIG_EINVAL;
   if (rows < 0) return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_set_beside_rows: negative threshold", hipSuccess);
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   G_LIB(join_side(g, (hipStream_t)trxsig_get_stream(g->c)));
   g->beside_rows = rows == 0 ? kBesideRows : rows;
   return TRXSIG_OK;
@@ -694,19 +683,19 @@ int trxsig_trxgroup_set_beside_rows(trxsig_trxgroup *g, int rows) {
 
 int trxsig_trxgroup_sync(trxsig_trxgroup *g) {
   if (!g) return TRXSIG_EINVAL;
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   return join_side(g, (hipStream_t)trxsig_get_stream(g->c));
 }
 
 int trxsig_trxgroup_energy_threshold(trxsig_trxgroup *g, int arfcn, double *thr) {
   if (!g) return TRXSIG_EINVAL;
   if (arfcn < 0 || arfcn >= g->S || !thr) return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_energy_threshold: bad argument", hipSuccess);
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(g->c);
   TrxGroupArfcn a;
   G_LIB(join_side(g, st));
-  G_HIP(g, hipMemcpyAsync(&a, g->d_state + arfcn, sizeof a, hipMemcpyDeviceToHost, st));
-  G_HIP(g, hipStreamSynchronize(st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(&a, g->d_state + arfcn, sizeof a, hipMemcpyDeviceToHost, st));
+  TRX_HIPCHK(g->c, hipStreamSynchronize(st));
   *thr = a.thr;
   return TRXSIG_OK;
 }
@@ -728,16 +717,16 @@ int tx_setup(trxsig_trxgroup *g) {
   TrxGroupTx &x = g->tx;
   x.S = S; x.qcap = kTxQueueCap; x.npool = kTxQueueCap + 102 * 8;
   const size_t nq = (size_t)x.qcap * S, np = (size_t)x.npool * S;
-  G_HIP(g, hipMalloc((void **)&x.q_fn, 4 * nq));
-  G_HIP(g, hipMalloc((void **)&x.q_key, 4 * nq));
-  G_HIP(g, hipMalloc((void **)&x.q_n, 4 * (size_t)S));
-  G_HIP(g, hipMalloc((void **)&x.free_stack, 2 * np));
-  G_HIP(g, hipMalloc((void **)&x.free_n, 4 * (size_t)S));
-  G_HIP(g, hipMalloc((void **)&x.filler, 2 * (size_t)102 * 8 * S));
-  G_HIP(g, hipMalloc((void **)&x.fmod, (size_t)8 * S));
-  G_HIP(g, hipMalloc((void **)&x.pool, 4 * np * TRXG_PAYLOAD_WORDS));
-  G_HIP(g, hipMalloc((void **)&x.status, 4 * (size_t)S));
-  G_HIP(g, hipMalloc((void **)&g->d_dummy, 4 * TRXG_PAYLOAD_WORDS));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.q_fn, 4 * nq));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.q_key, 4 * nq));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.q_n, 4 * (size_t)S));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.free_stack, 2 * np));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.free_n, 4 * (size_t)S));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.filler, 2 * (size_t)102 * 8 * S));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.fmod, (size_t)8 * S));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.pool, 4 * np * TRXG_PAYLOAD_WORDS));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&x.status, 4 * (size_t)S));
+  TRX_HIPCHK(g->c, hipMalloc((void **)&g->d_dummy, 4 * TRXG_PAYLOAD_WORDS));
   // Transceiver::Transceiver (:66-75): every filler entry is the dummy burst, unscaled (a gain of 1 is the same samples)
   std::vector<int16_t> fs(np), fill((size_t)102 * 8 * S, (int16_t)-1);
   for (int k = 0; k < x.npool; k++)
@@ -748,17 +737,17 @@ int tx_setup(trxsig_trxgroup *g) {
   for (int i = 0; i < 148; i++) db[i] = kDummyBits[i] == '1';
   const float one = 1.0f;
   std::memcpy(db + 148, &one, 4);
-  G_HIP(g, hipMemcpy(x.free_stack, fs.data(), 2 * np, hipMemcpyHostToDevice));
-  G_HIP(g, hipMemcpy(x.filler, fill.data(), 2 * fill.size(), hipMemcpyHostToDevice));
-  G_HIP(g, hipMemcpy(x.free_n, cnt.data(), 4 * (size_t)S, hipMemcpyHostToDevice));
-  G_HIP(g, hipMemset(x.q_n, 0, 4 * (size_t)S));
-  G_HIP(g, hipMemset(x.status, 0, 4 * (size_t)S));
-  G_HIP(g, hipMemcpy(g->d_dummy, dummy, sizeof dummy, hipMemcpyHostToDevice));
+  TRX_HIPCHK(g->c, hipMemcpy(x.free_stack, fs.data(), 2 * np, hipMemcpyHostToDevice));
+  TRX_HIPCHK(g->c, hipMemcpy(x.filler, fill.data(), 2 * fill.size(), hipMemcpyHostToDevice));
+  TRX_HIPCHK(g->c, hipMemcpy(x.free_n, cnt.data(), 4 * (size_t)S, hipMemcpyHostToDevice));
+  TRX_HIPCHK(g->c, hipMemset(x.q_n, 0, 4 * (size_t)S));
+  TRX_HIPCHK(g->c, hipMemset(x.status, 0, 4 * (size_t)S));
+  TRX_HIPCHK(g->c, hipMemcpy(g->d_dummy, dummy, sizeof dummy, hipMemcpyHostToDevice));
   x.dummy = g->d_dummy;
   // scaleVector(*modBurst, pow(10, -RSSI/10)) (:108): integer division, pow in double, the scale a Complex<float>
   for (int q = -12; q <= 13; q++) g->gain_tab[q + 12] = (float)std::pow(10, q);
-  for (int k = 0; k < trxsig_trxgroup::kTxSets; k++) G_HIP(g, hipEventCreateWithFlags(&g->tx_ev[k], hipEventDisableTiming));
-  G_HIP(g, hipEventCreateWithFlags(&g->tx_fm_ev, hipEventDisableTiming));
+  for (int k = 0; k < trxsig_trxgroup::kTxSets; k++) TRX_HIPCHK(g->c, hipEventCreateWithFlags(&g->tx_ev[k], hipEventDisableTiming));
+  TRX_HIPCHK(g->c, hipEventCreateWithFlags(&g->tx_fm_ev, hipEventDisableTiming));
 
   g->tx_ready = true;
   g->fmod_dirty = true;
@@ -768,44 +757,44 @@ int tx_setup(trxsig_trxgroup *g) {
 // the next host staging set, free to be refilled (its previous uploads have run)
 int tx_take_set(trxsig_trxgroup *g, int *k) {
   *k = g->tx_set = (g->tx_set + 1) % trxsig_trxgroup::kTxSets;
-  if (g->tx_ev_armed[*k]) { G_HIP(g, hipEventSynchronize(g->tx_ev[*k])); g->tx_ev_armed[*k] = false; }
+  if (g->tx_ev_armed[*k]) { TRX_HIPCHK(g->c, hipEventSynchronize(g->tx_ev[*k])); g->tx_ev_armed[*k] = false; }
   // ... and its device arrays: free when the ingest that read them two calls ago has run (here the host is held back when the
   // device is more than a batch behind)
-  if (g->tx_read_armed[*k]) { G_HIP(g, hipEventSynchronize(g->tx_read_ev[*k])); g->tx_read_armed[*k] = false; }
+  if (g->tx_read_armed[*k]) { TRX_HIPCHK(g->c, hipEventSynchronize(g->tx_read_ev[*k])); g->tx_read_armed[*k] = false; }
   return TRXSIG_OK;
 }
 int tx_seal_set(trxsig_trxgroup *g, int k, hipStream_t st) {
-  G_HIP(g, hipEventRecord(g->tx_ev[k], st));
+  TRX_HIPCHK(g->c, hipEventRecord(g->tx_ev[k], st));
   g->tx_ev_armed[k] = true;
   return TRXSIG_OK;
 }
 // the queues' stream (created on first use, with the events), and the context's stream behind everything it has been given
 int tx_streams(trxsig_trxgroup *g) {
   if (g->tx_q) return TRXSIG_OK;
-  G_HIP(g, hipStreamCreateWithFlags(&g->tx_up, hipStreamNonBlocking));
-  G_HIP(g, hipStreamCreateWithFlags(&g->tx_q, hipStreamNonBlocking));
-  G_HIP(g, hipEventCreateWithFlags(&g->tx_q_ev, hipEventDisableTiming));
-  for (int j = 0; j < trxsig_trxgroup::kTxSets; j++) G_HIP(g, hipEventCreateWithFlags(&g->tx_read_ev[j], hipEventDisableTiming));
-  for (int j = 0; j < 2; j++) G_HIP(g, hipEventCreateWithFlags(&g->tx_out_ev[j], hipEventDisableTiming));
+  TRX_HIPCHK(g->c, hipStreamCreateWithFlags(&g->tx_up, hipStreamNonBlocking));
+  TRX_HIPCHK(g->c, hipStreamCreateWithFlags(&g->tx_q, hipStreamNonBlocking));
+  TRX_HIPCHK(g->c, hipEventCreateWithFlags(&g->tx_q_ev, hipEventDisableTiming));
+  for (int j = 0; j < trxsig_trxgroup::kTxSets; j++) TRX_HIPCHK(g->c, hipEventCreateWithFlags(&g->tx_read_ev[j], hipEventDisableTiming));
+  for (int j = 0; j < 2; j++) TRX_HIPCHK(g->c, hipEventCreateWithFlags(&g->tx_out_ev[j], hipEventDisableTiming));
   return TRXSIG_OK;
 }
 // "the queues' stream has run up to here": ONE event record behind every kernel of that stream (each record, each wait is a packet
 // the stream's dependent launches queue up behind: ~3 us apiece on the serial chain)
 int tx_q_mark(trxsig_trxgroup *g, hipEvent_t ev) {
-  G_HIP(g, hipEventRecord(ev, g->tx_q));
+  TRX_HIPCHK(g->c, hipEventRecord(ev, g->tx_q));
   g->tx_q_last = ev;
   g->tx_q_armed = true;
   return TRXSIG_OK;
 }
 int tx_join(trxsig_trxgroup *g, hipStream_t st) {
-  if (g->tx_q_armed) { G_HIP(g, hipStreamWaitEvent(st, g->tx_q_last, 0)); g->tx_q_armed = false; }
+  if (g->tx_q_armed) { TRX_HIPCHK(g->c, hipStreamWaitEvent(st, g->tx_q_last, 0)); g->tx_q_armed = false; }
   return TRXSIG_OK;
 }
 // the queues' stream behind set k's upload and arrival kernel (spared when they have run)
 int tx_wait_arrival(trxsig_trxgroup *g, int k) {
   const bool ran = hipEventQuery(g->tx_ev[k]) == hipSuccess;
   (void)hipGetLastError();                                  // (hipErrorNotReady is an answer, not an error to be found by the next launch check)
-  if (!ran) G_HIP(g, hipStreamWaitEvent(g->tx_q, g->tx_ev[k], 0));
+  if (!ran) TRX_HIPCHK(g->c, hipStreamWaitEvent(g->tx_q, g->tx_ev[k], 0));
   return TRXSIG_OK;
 }
 // the pending ingest as a launch of its own
@@ -814,7 +803,7 @@ int tx_flush_pending(trxsig_trxgroup *g) {
   const int k = g->tx_pend_k;
   g->tx_pend = false;
   G_LIB(tx_wait_arrival(g, k));
-  G_HIP(g, trx_launch_group_tx_ingest(g->tx_q, g->tx, g->tx_pend_n, g->tx_dgram[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->gain_tab,
+  TRX_HIPCHK(g->c, trx_launch_group_tx_ingest(g->tx_q, g->tx, g->tx_pend_n, g->tx_dgram[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->gain_tab,
                                       g->tx_pend_ref, g->tx_pend_far));
   G_LIB(tx_q_mark(g, g->tx_read_ev[k]));                   // (the set's device arrays are free behind it; the context's stream joins on it)
   g->tx_read_armed[k] = true;
@@ -823,13 +812,13 @@ int tx_flush_pending(trxsig_trxgroup *g) {
 // fillerModulus[TN] of every ARFCN (setModulus, :183-204) after a SETSLOT (rare: its own host staging vector, waited for before it is refilled)
 int tx_sync_modulus(trxsig_trxgroup *g, hipStream_t st) {
   if (!g->fmod_dirty) return TRXSIG_OK;
-  if (g->tx_fm_armed) { G_HIP(g, hipEventSynchronize(g->tx_fm_ev)); g->tx_fm_armed = false; }
+  if (g->tx_fm_armed) { TRX_HIPCHK(g->c, hipEventSynchronize(g->tx_fm_ev)); g->tx_fm_armed = false; }
   std::vector<uint8_t> &fm = g->h_fmod;
   fm.assign((size_t)8 * g->S, 0);
   for (int tn = 0; tn < 8; tn++)
     for (int a = 0; a < g->S; a++) fm[(size_t)tn * g->S + a] = (uint8_t)g->ctl[(size_t)a].fillerModulus[tn];
-  G_HIP(g, hipMemcpyAsync(g->tx.fmod, fm.data(), fm.size(), hipMemcpyHostToDevice, st));
-  G_HIP(g, hipEventRecord(g->tx_fm_ev, st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(g->tx.fmod, fm.data(), fm.size(), hipMemcpyHostToDevice, st));
+  TRX_HIPCHK(g->c, hipEventRecord(g->tx_fm_ev, st));
   g->tx_fm_armed = true;
   g->fmod_dirty = false;
   return TRXSIG_OK;
@@ -841,10 +830,10 @@ extern "C" {
 // the pinned staging block of set k, grown to hold n_max datagrams + their ARFCN ids ([ids: 4 n_max bytes][datagrams: 154 n_max])
 static int tx_stage_need(trxsig_trxgroup *g, int k, int n_max) {
   if (n_max <= g->tx_pin_cap[k]) return TRXSIG_OK;
-  if (g->tx_ev_armed[k]) { G_HIP(g, hipEventSynchronize(g->tx_ev[k])); g->tx_ev_armed[k] = false; }
+  if (g->tx_ev_armed[k]) { TRX_HIPCHK(g->c, hipEventSynchronize(g->tx_ev[k])); g->tx_ev_armed[k] = false; }
   const int cap = n_max + n_max / 4 + 256;
   void *q = nullptr;
-  G_HIP(g, hipHostMalloc(&q, (size_t)cap * (TRXSIG_TX_DATAGRAM_BYTES + 4), hipHostMallocDefault));
+  TRX_HIPCHK(g->c, hipHostMalloc(&q, (size_t)cap * (TRXSIG_TX_DATAGRAM_BYTES + 4), hipHostMallocDefault));
   if (g->tx_pin[k]) (void)hipHostFree(g->tx_pin[k]);
   g->tx_pin[k] = (uint8_t *)q;
   g->tx_pin_cap[k] = cap;
@@ -854,7 +843,7 @@ static int tx_stage_need(trxsig_trxgroup *g, int k, int n_max) {
 int trxsig_trxgroup_tx_staging(trxsig_trxgroup *g, int n_max, uint8_t **h_datagrams, int32_t **h_arfcn) {
   if (!g) return TRXSIG_EINVAL;
   if (n_max <= 0 || !h_datagrams || !h_arfcn) return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_tx_staging: bad argument", hipSuccess);
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   G_LIB(tx_setup(g));
   if (!g->tx_stage_held) {                                  // the next set, free to be refilled (its previous upload has run)
     int set = 0;
@@ -888,15 +877,15 @@ static int tx_add_staged(trxsig_trxgroup *g, int n) {
   G_LIB(tx_streams(g));                                     // (the filler moduli are the walk's business: trxsig_trxgroup_push uploads them)
   hipStream_t up = g->tx_up, q = g->tx_q;
   // (set k's device arrays are free: tx_take_set has waited for the ingest that read them two calls ago)
-  G_HIP(g, g->tx_dgram[k].need((size_t)n * TRXSIG_TX_DATAGRAM_BYTES + 8, up));   // (+ 8: the ingest kernel reads whole aligned words round the last payload)
-  G_HIP(g, g->tx_arfcn[k].need((size_t)n, up));
+  TRX_HIPCHK(g->c, g->tx_dgram[k].need((size_t)n * TRXSIG_TX_DATAGRAM_BYTES + 8, up));   // (+ 8: the ingest kernel reads whole aligned words round the last payload)
+  TRX_HIPCHK(g->c, g->tx_arfcn[k].need((size_t)n, up));
   size_t tot_ints = 0;
   const size_t list_ints = trx_group_tx_arrive_ints(S, n, &tot_ints);
-  G_HIP(g, g->tx_alf[k].need(list_ints, up)); G_HIP(g, g->tx_alk[k].need(list_ints, up)); G_HIP(g, g->tx_atot[k].need(tot_ints, up));
-  G_HIP(g, hipMemcpyAsync(g->tx_arfcn[k].p, h_arfcn, 4 * (size_t)n, hipMemcpyHostToDevice, up));
-  G_HIP(g, hipMemcpyAsync(g->tx_dgram[k].p, h_d, (size_t)n * TRXSIG_TX_DATAGRAM_BYTES, hipMemcpyHostToDevice, up));
+  TRX_HIPCHK(g->c, g->tx_alf[k].need(list_ints, up)); TRX_HIPCHK(g->c, g->tx_alk[k].need(list_ints, up)); TRX_HIPCHK(g->c, g->tx_atot[k].need(tot_ints, up));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(g->tx_arfcn[k].p, h_arfcn, 4 * (size_t)n, hipMemcpyHostToDevice, up));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(g->tx_dgram[k].p, h_d, (size_t)n * TRXSIG_TX_DATAGRAM_BYTES, hipMemcpyHostToDevice, up));
   // the arrival half -- parse, sort by ARFCN -- needs nothing of the queues: it runs here, behind its upload, beside the previous batch's walk
-  G_HIP(g, trx_launch_group_tx_arrive(up, S, n, g->tx_dgram[k].p, g->tx_arfcn[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p));
+  TRX_HIPCHK(g->c, trx_launch_group_tx_arrive(up, S, n, g->tx_dgram[k].p, g->tx_arfcn[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p));
   G_LIB(tx_seal_set(g, k, up));                             // (the pinned set is the DMA's until this event has passed: the next staging call takes the other)
   g->tx_stage_held = false;
   (void)q;
@@ -910,7 +899,7 @@ int trxsig_trxgroup_add_staged(trxsig_trxgroup *g, int n) {
   if (!g->tx_stage_held || n < 0 || n > g->tx_pin_cap[g->tx_set])
     return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_add_staged: no staging block is held (trxsig_trxgroup_tx_staging first) or n exceeds it", hipSuccess);
   if (n == 0) return TRXSIG_OK;
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   return tx_add_staged(g, n);
 }
 
@@ -925,7 +914,7 @@ int trxsig_trxgroup_add_bursts(trxsig_trxgroup *g, const uint8_t *h_datagrams, c
   G_LIB(trxsig_trxgroup_tx_staging(g, n, &pd, &pa));
   std::memcpy(pa, h_arfcn, 4 * (size_t)n);
   std::memcpy(pd, h_datagrams, (size_t)n * TRXSIG_TX_DATAGRAM_BYTES);
-  Guard gd(trxsig_device(c));
+  TrxDeviceGuard gd(trxsig_device(c));
   return tx_add_staged(g, n);
 }
 
@@ -937,7 +926,7 @@ int trxsig_trxgroup_push(trxsig_trxgroup *g, int fn, int tn, int n_slots, const 
   if (fn < 0 || fn >= kHyperframe || tn < 0 || tn > 7 || n_slots <= 0 || (long long)n_slots * g->S > (1LL << 28) ||
       (long long)n_slots >= 8LL * kHyperframe)
     return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_push: bad argument", hipSuccess);
-  Guard gd(trxsig_device(c));
+  TrxDeviceGuard gd(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   G_LIB(tx_setup(g));
   G_LIB(tx_streams(g));
@@ -945,19 +934,19 @@ int trxsig_trxgroup_push(trxsig_trxgroup *g, int fn, int tn, int n_slots, const 
   // what the context's stream has been given so far is what may still read the output of the push before this one: the push after
   // this one (same output set) waits for it
   const int o = (int)(g->tx_pushes & 1u);
-  G_HIP(g, hipEventRecord(g->tx_out_ev[o ^ 1], st));
+  TRX_HIPCHK(g->c, hipEventRecord(g->tx_out_ev[o ^ 1], st));
   g->tx_out_armed[o ^ 1] = true;
   if (g->tx_out_armed[o]) {                                 // (a step later that work has normally run: then the queues' stream is spared the wait)
     const bool ran = hipEventQuery(g->tx_out_ev[o]) == hipSuccess;
     (void)hipGetLastError();                                // (hipErrorNotReady is an answer, not an error to be found by the next launch check)
-    if (!ran) G_HIP(g, hipStreamWaitEvent(q, g->tx_out_ev[o], 0));
+    if (!ran) TRX_HIPCHK(g->c, hipStreamWaitEvent(q, g->tx_out_ev[o], 0));
     g->tx_out_armed[o] = false;
   }
   g->tx_pushes++;
   G_LIB(tx_sync_modulus(g, q));
   const size_t cells = (size_t)n_slots * g->S;
-  G_HIP(g, g->tx_bits[o].need(cells * 148, q));
-  G_HIP(g, g->tx_gain[o].need(cells, q)); G_HIP(g, g->tx_fq[o].need(cells, q));
+  TRX_HIPCHK(g->c, g->tx_bits[o].need(cells * 148, q));
+  TRX_HIPCHK(g->c, g->tx_gain[o].need(cells, q)); TRX_HIPCHK(g->c, g->tx_fq[o].need(cells, q));
   // an add call's ingest still pending, and its datagrams near this push's start (all of them then lie inside the packed entries'
   // window round fn): ingest and walk are ONE launch; else the ingest goes first on its own
   const int32_t dref = g->tx_pend ? trxq_fn_delta(g->tx_pend_ref, fn) : 0;
@@ -965,13 +954,13 @@ int trxsig_trxgroup_push(trxsig_trxgroup *g, int fn, int tn, int n_slots, const 
     const int k = g->tx_pend_k;
     g->tx_pend = false;
     G_LIB(tx_wait_arrival(g, k));
-    G_HIP(g, trx_launch_group_tx_both(q, g->tx, g->tx_pend_n, g->tx_dgram[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->gain_tab,
+    TRX_HIPCHK(g->c, trx_launch_group_tx_both(q, g->tx, g->tx_pend_n, g->tx_dgram[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->gain_tab,
                                       g->tx_pend_far, fn, tn, n_slots, g->tx_bits[o].p, g->tx_gain[o].p, g->tx_fq[o].p));
     G_LIB(tx_q_mark(g, g->tx_read_ev[k]));
     g->tx_read_armed[k] = true;
   } else {
     G_LIB(tx_flush_pending(g));
-    G_HIP(g, trx_launch_group_tx_push(q, g->tx, fn, tn, n_slots, g->tx_bits[o].p, g->tx_gain[o].p, g->tx_fq[o].p));
+    TRX_HIPCHK(g->c, trx_launch_group_tx_push(q, g->tx, fn, tn, n_slots, g->tx_bits[o].p, g->tx_gain[o].p, g->tx_fq[o].p));
     G_LIB(tx_q_mark(g, g->tx_q_ev));
   }
   G_LIB(tx_join(g, st));                                    // the caller reads the output on the context's stream
@@ -1004,14 +993,14 @@ int trxsig_trxgroup_tx_queue_size(trxsig_trxgroup *g, int arfcn, int *dropped) {
   if (!g) return TRXSIG_EINVAL;
   if (arfcn < 0 || arfcn >= g->S) return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_tx_queue_size: bad argument", hipSuccess);
   if (!g->tx_ready) { if (dropped) *dropped = 0; return 0; }
-  Guard gd(trxsig_device(g->c));
+  TrxDeviceGuard gd(trxsig_device(g->c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(g->c);
   int32_t n = 0; uint32_t stt = 0;
   G_LIB(tx_flush_pending(g));
   G_LIB(tx_join(g, st));
-  G_HIP(g, hipMemcpyAsync(&n, g->tx.q_n + arfcn, 4, hipMemcpyDeviceToHost, st));
-  G_HIP(g, hipMemcpyAsync(&stt, g->tx.status + arfcn, 4, hipMemcpyDeviceToHost, st));
-  G_HIP(g, hipStreamSynchronize(st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(&n, g->tx.q_n + arfcn, 4, hipMemcpyDeviceToHost, st));
+  TRX_HIPCHK(g->c, hipMemcpyAsync(&stt, g->tx.status + arfcn, 4, hipMemcpyDeviceToHost, st));
+  TRX_HIPCHK(g->c, hipStreamSynchronize(st));
   if (dropped) *dropped = (int)(stt & 1u);
   return n;
 }

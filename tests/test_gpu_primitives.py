@@ -116,6 +116,42 @@ def test_random_primitives_vs_oracle(ctx, sps):
         assert_beq(t.decimate_host(x[:n] if n <= x.size else np.resize(x, n), f), (x[:n] if n <= x.size else np.resize(x, n))[::f], "decimateVector")
 
 
+
+def test_host_forms_across_the_pinned_limit(ctx):
+    """The single-vector host forms on both sides of the host staging's 256 KiB limit: a call that fits goes through the
+    context's pinned mirror, one DMA each way; a larger one (n = 40,000 samples: 320 KB a vector) copies straight from and to
+    the caller's buffers.  Large and small calls alternate on one context, so the grow-only scratch and mirror are reused across
+    the limit.  Bit-exact against the oracle (and the closed forms of vectorSlicer / decimateVector)."""
+    t = ctx[4]; o = oraclebind.Oracle(4)
+    rng = np.random.default_rng(256)
+    m = 157 * 4                                                            # GMSKRotate's tables hold 157*sps entries
+    for n in (40000, 300, 16000, 40001, 157):
+        x = cn(rng, n, 30.0)
+        d = np.float32(rng.uniform(-20, 20))
+        assert_beq(t.delay_vector_host(x, d), o.delay_vector(x, d), "delayVector n %d" % n)
+        s = np.complex64(complex(rng.normal(), rng.normal()))
+        assert_beq(t.elementwise_host(0, x, s), o.scale_vector(x, s), "scaleVector n %d" % n)
+        for op, rev in ((1, False), (2, True)):
+            want = x.copy(); want[:m] = o.gmsk_rotate(x[:m], reverse=rev)
+            assert_beq(t.elementwise_host(op, x), want, "GMSKRotate reverse=%d n %d" % (rev, n))
+        want = np.clip((0.5 * (x.real.astype(np.float64) + np.float64(np.float32(1.0)))).astype(np.float32), 0, 1)
+        got = t.elementwise_host(3, x)
+        assert_beq(got.real.copy(), want, "vectorSlicer n %d" % n); assert not got.imag.any()
+        assert_beq(t.elementwise_host(4, x, s), o.offset_vector(x, s), "offsetVector n %d" % n)
+        y = cn(rng, n - 7, 30.0)
+        assert_beq(t.add_vector_host(x, y), o.add_vector(x, y), "addVector n %d" % n)
+        assert_beq(t.add_vector_host(y, x), o.add_vector(y, x), "addVector (longer y) n %d" % n)
+        assert t.vector_norm2_host(x) == (o.vector_norm2(x), o.vector_power(x)), n
+        f, s0 = np.float32(rng.uniform(-0.5, 0.5)), np.float32(rng.uniform(-50, 50))
+        got, fin = t.frequency_shift_host(x, f, s0); want, wfin = o.frequency_shift(x, f, s0)
+        assert_beq(got, want, "frequencyShift n %d" % n); assert fin == wfin, n
+        for k in (2, 3):
+            assert_beq(t.decimate_host(x, k), x[::k][:n // k], "decimateVector %d n %d" % (k, n))
+        b = cn(rng, 16)
+        for span in range(5):
+            assert_beq(t.convolve_host(x, b, span), o.convolve(x, b, span), "convolve span %d n %d" % (span, n))
+        assert_beq(t.convolve_host(x, b, 0, correlate=True), o.correlate(x, b, 0), "correlate n %d" % n)
+
 def test_batch_forms_ragged(pkg, ctx):
     """The device-pointer batch entry points on ragged batches: same values as vector by vector through the oracle."""
     import torch
