@@ -354,6 +354,49 @@ int trxsig_fec_tch_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft_s
 int trxsig_fec_viterbi_batch(trxsig_ctx *ctx, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
                              uint8_t *d_bits, int64_t out_stride);
 
+/* ---- uplink TCH/FACCH and XCCH decoders as multi-channel streams ---------------------------------------------------
+ * The reference's per-channel decoders -- TCHFACCHL1Decoder::processBurst / deinterleave / decodeTCH up to the parity and
+ * tail check (GSML1FEC.cpp:1030-1163) and XCCHL1Decoder::writeLowSide / processBurst / deinterleave / decode (:556-653) --
+ * for n_chan channels x n_slots burst slots per call, their deinterleaving buffer mI[][] and FER carried on the device.
+ *   Slots: slot t of channel s is the burst at d_soft + d_index[s][t] * soft_stride (148 soft values).  An index of -1 --
+ *     or any index outside [0, n_rows) -- means no burst arrived in that slot (detection failed, the pull returned
+ *     nothing, the channel was idle).  d_soft / n_rows may be a trxsig_trxgroup_result's d_soft / n_rows: d_index[s][t] =
+ *     the row of the channel's timeslot where d_valid is set, -1 elsewhere.
+ *   B index: TCH: B = (d_b0[s] + t) mod 8, d_b0[s] in {0, 4} (NULL: all 0); XCCH: B = t mod 4.  Mapping a frame number to B
+ *     (reverseMapping) is the caller's.  n_slots is a multiple of 4: n_blocks = n_slots / 4 blocks, block m closing at slot
+ *     4m+3 (B = 3 or 7).  A channel whose d_b0 is neither 0 nor 4 is treated as one where no burst arrived in any slot:
+ *     nothing is decoded, its FER and its state stay as they are.
+ *   Per block, exactly as the reference: a present burst's 114 e-bits (after the UDP hop when wire_quantise != 0, as in
+ *     the batch forms) enter row B of mI; a block is decoded only if its closing burst is present, reading c[] through
+ *     the deinterleaver and marking what it read as 0.5 (a block whose closing burst is missing is never deinterleaved,
+ *     and its rows stay for a later block to read).  TCH: stolen = Hl (bit 60 after the UDP hop) of the closing burst
+ *     > 0.5; a stolen block runs the FACCH (XCCH) decode, any other decoded block the class-1 decode -- one Viterbi pass.
+ *   Outputs, [n_chan][n_blocks] (any alignment): d_status = TRXSIG_FEC_* bits: DECODED; STOLEN; FACCH_OK (the FACCH
+ *     frame's parity); TCH_GOOD (decodeTCH's `good`; for XCCH the parity of the L2 frame).  d_tch [..][33] = d[260] as
+ *     trxsig_fec_tch_decode_batch writes it, for every decoded block that is not stolen, good or bad.  d_facch / d_frames
+ *     [..][23] = the L2 frame, for every decoded stolen (TCH) or decoded (XCCH) block.  Every other output block is zero.
+ *     d_fer [..] (float, may be NULL) = mFER after the block (L1Decoder::countGoodFrame / countBadFrame, :390-405, float
+ *     arithmetic as written).  Count order as the reference: a stolen block counts its FACCH frame, then one bad traffic
+ *     frame (decodeTCH(true) returns false); a block that is not decoded does not count.
+ *   d_state[s] (in / out, TRXSIG_TCH_RX_STATE_BYTES / TRXSIG_XCCH_RX_STATE_BYTES per channel, 4-byte aligned): mI as the
+ *     reference holds it after the call's last slot, and mFER.  Bytes 0..3 are mFER as a float: zeroing them is
+ *     L1Decoder::open() (FER reset, mI kept).  The rest is opaque.  All-zero bytes are a freshly constructed decoder (mI
+ *     filled with 0.0, mFER 0).  The call reads the old state and writes the new one in place, race-free: one call of n
+ *     blocks equals k calls of n/k, in every output and in the state byte for byte.
+ *   Host side: a NULL d_soft / d_index / d_state / d_status / d_tch / d_facch / d_frames, a negative size, n_slots not a
+ *     multiple of 4, soft_stride < 148, n_chan * n_slots >= 2^31 or a d_state not 4-byte aligned return TRXSIG_EINVAL
+ *     before any launch; n_chan == 0 or n_slots == 0 is a no-op.  The blocks of a call decode in parallel (a closed form of
+ *     mI): two launches on the context's stream. */
+enum { TRXSIG_FEC_DECODED = 1, TRXSIG_FEC_STOLEN = 2, TRXSIG_FEC_FACCH_OK = 4, TRXSIG_FEC_TCH_GOOD = 8 };
+#define TRXSIG_TCH_RX_STATE_BYTES 3664      /* 16 + 8 x 114 floats */
+#define TRXSIG_XCCH_RX_STATE_BYTES 1840     /* 16 + 4 x 114 floats */
+int trxsig_fec_tch_decode_stream(trxsig_ctx *ctx, int n_chan, int n_slots, const float *d_soft, int soft_stride, int64_t n_rows,
+                                 const int32_t *d_index, const uint8_t *d_b0, int wire_quantise, void *d_state,
+                                 uint8_t *d_status, uint8_t *d_tch, uint8_t *d_facch, float *d_fer);
+int trxsig_fec_xcch_decode_stream(trxsig_ctx *ctx, int n_chan, int n_slots, const float *d_soft, int soft_stride, int64_t n_rows,
+                                  const int32_t *d_index, int wire_quantise, void *d_state, uint8_t *d_status,
+                                  uint8_t *d_frames, float *d_fer);
+
 /* ---- downlink L1 encode of traffic and sync channels ------------------------------------------------------
  * TCH/FS + FACCH/F stream encoder (TCHFACCHL1Encoder::dispatch / encodeTCH / interleave, GSML1FEC.cpp:1252-1393):
  *   n_chan channels x n_blocks 20-ms blocks per call, the interleaver state carried from call to call.
@@ -509,10 +552,11 @@ enum { TRXSIG_K_TSC_CORR = 0, TRXSIG_K_TSC_PEAK = 1, TRXSIG_K_DEMOD = 2, TRXSIG_
        TRXSIG_K_CONVERT = 8, TRXSIG_K_NORMAL_FUSED = 9, TRXSIG_K_FEC = 10, TRXSIG_K_NORMAL_CHAIN = 11,
        TRXSIG_K_EQ_DELAY = 12, TRXSIG_K_EQ_DFE = 13, TRXSIG_K_GROUP = 14, TRXSIG_K_COUNT = 15 };
 /* TRXSIG_K_EQUALIZE = k_eq_detect / k_design_dfe; TRXSIG_K_GROUP = the Transceiver group's replay (trxsig_trxgroup.h) */
-/* Kernels added after TRXSIG_K_COUNT was fixed for ABI 2 (k_fec_tch_encode, k_fec_sch_encode): trxsig_profile_collect
- * (arrays of TRXSIG_K_COUNT entries) leaves them out; trxsig_profile_collect_n reports them, and trxsig_kernel_count()
- * counts them. */
-enum { TRXSIG_K_FEC_TCH_ENC = 15, TRXSIG_K_FEC_SCH_ENC = 16 };
+/* Kernels added after TRXSIG_K_COUNT was fixed for ABI 2 (k_fec_tch_encode, k_fec_sch_encode, the stream decoders'
+ * k_fec_rx_stream for TCH and for XCCH and their k_fec_rx_fold): trxsig_profile_collect (arrays of TRXSIG_K_COUNT entries)
+ * leaves them out; trxsig_profile_collect_n reports them, and trxsig_kernel_count() counts them. */
+enum { TRXSIG_K_FEC_TCH_ENC = 15, TRXSIG_K_FEC_SCH_ENC = 16, TRXSIG_K_FEC_TCH_RX = 17, TRXSIG_K_FEC_XCCH_RX = 18,
+       TRXSIG_K_FEC_RX_FOLD = 19 };
 const char *trxsig_kernel_name(int kernel_id);
 int trxsig_profile_enable(trxsig_ctx *ctx, int on);
 int trxsig_profile_collect(trxsig_ctx *ctx, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]);

@@ -17,6 +17,8 @@ SOFT_EXACT, SOFT_TOLERANCE = 0, 1                # trxsig_set_soft_mode
 ABI_VERSION = 2                                  # TRXSIG_ABI_VERSION of include/trxsig.h
 TCH_FILLER, TCH_SPEECH, TCH_FACCH = 0, 1, 2      # block kinds of trxsig_fec_tch_encode_batch
 TCH_TX_STATE_BYTES = 32                          # TRXSIG_TCH_TX_STATE_BYTES
+FEC_DECODED, FEC_STOLEN, FEC_FACCH_OK, FEC_TCH_GOOD = 1, 2, 4, 8   # status bits of the stream decoders (TRXSIG_FEC_*)
+TCH_RX_STATE_BYTES, XCCH_RX_STATE_BYTES = 3664, 1840              # TRXSIG_TCH_RX_STATE_BYTES, TRXSIG_XCCH_RX_STATE_BYTES
 
 
 class TrxSigError(RuntimeError):
@@ -118,6 +120,8 @@ def _load(path):
         L.trxsig_fec_tch_set_filler.argtypes = [vp, vp]
         L.trxsig_fec_tch_encode_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
         L.trxsig_fec_sch_encode_batch.argtypes = [vp, vp, vp, i32, vp]
+        L.trxsig_fec_tch_decode_stream.argtypes = [vp, i32, i32, vp, i32, C.c_int64, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.trxsig_fec_xcch_decode_stream.argtypes = [vp, i32, i32, vp, i32, C.c_int64, vp, i32, vp, vp, vp, vp]
         # sigProcLib.h's free-standing primitives
         L.trxsig_convolve_out_len.argtypes = [i32, i32, i32, i32]
         L.trxsig_convolve_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]
@@ -506,6 +510,28 @@ class TrxSig:
         self._chk(self.L.trxsig_fec_tch_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n_bursts, int(wire),
                                                      _ptr(tch), _ptr(tch_good), _ptr(facch), _ptr(facch_ok), _ptr(stolen)),
                   "trxsig_fec_tch_decode_batch")
+
+    def fec_tch_decode_stream(self, soft, index, state, status, tch, facch, b0=None, fer=None, wire=True, n_rows=None,
+                              soft_stride=None):
+        """TCH/FACCH uplink stream decode: index[S, T] (int32, -1 = no burst) into soft[n_rows, soft_stride] (a tensor, or a
+        device address with n_rows / soft_stride given); b0[S] (uint8, 0 or 4; None = all 0); state[S, TCH_RX_STATE_BYTES]
+        (in / out); status[S, T/4], tch[S, T/4, 33], facch[S, T/4, 23], fer[S, T/4] float32 or None."""
+        S, T = index.shape
+        if n_rows is None:
+            n_rows = soft.shape[0]
+        self._chk(self.L.trxsig_fec_tch_decode_stream(self.h, S, T, _ptr(soft), soft_stride or soft.shape[-1], n_rows, _ptr(index),
+                                                      _ptr(b0), int(wire), _ptr(state), _ptr(status), _ptr(tch), _ptr(facch),
+                                                      _ptr(fer)), "trxsig_fec_tch_decode_stream")
+
+    def fec_xcch_decode_stream(self, soft, index, state, status, frames, fer=None, wire=True, n_rows=None, soft_stride=None):
+        """XCCH uplink stream decode: as fec_tch_decode_stream with B = t mod 4; state[S, XCCH_RX_STATE_BYTES],
+        frames[S, T/4, 23]."""
+        S, T = index.shape
+        if n_rows is None:
+            n_rows = soft.shape[0]
+        self._chk(self.L.trxsig_fec_xcch_decode_stream(self.h, S, T, _ptr(soft), soft_stride or soft.shape[-1], n_rows, _ptr(index),
+                                                       int(wire), _ptr(state), _ptr(status), _ptr(frames), _ptr(fer)),
+                  "trxsig_fec_xcch_decode_stream")
 
     def fec_viterbi(self, soft, n_soft, n_blocks, bits, in_stride=None, out_stride=None):
         self._chk(self.L.trxsig_fec_viterbi_batch(self.h, _ptr(soft), n_soft, in_stride or soft.shape[-1], n_blocks,

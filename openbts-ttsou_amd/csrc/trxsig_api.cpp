@@ -20,7 +20,7 @@
 #include "trxsig_tablegen.h"
 
 // kernel ids the profiler knows: the TRXSIG_K_COUNT of ABI 2, then the ones appended since (trxsig.h)
-constexpr int kKernels = TRXSIG_K_FEC_SCH_ENC + 1;
+constexpr int kKernels = TRXSIG_K_FEC_RX_FOLD + 1;
 
 struct EventProfiler : TrxProfiler {
   struct Rec { int id; hipEvent_t a, b; };
@@ -1165,7 +1165,8 @@ const char *trxsig_kernel_name(int id) {
   static const char *names[kKernels] = { "k_tsc_corr", "k_tsc_peak", "k_demod", "k_rach_corr", "k_rach_peak",
                                                "k_modulate", "k_resample", "k_eq_detect", "k_convert", "k_normal_fused", "k_fec_viterbi",
                                                "k_normal_chain", "k_eq_delay", "k_eq_dfe", "k_group_replay",
-                                               "k_fec_tch_encode", "k_fec_sch_encode" };
+                                               "k_fec_tch_encode", "k_fec_sch_encode", "k_fec_rx_stream_tch",
+                                               "k_fec_rx_stream_xcch", "k_fec_rx_fold" };
   return (id >= 0 && id < kKernels) ? names[id] : "?";
 }
 int trxsig_fec_xcch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n_blocks, int wire,
@@ -1276,6 +1277,35 @@ int trxsig_fec_sch_encode_batch(trxsig_ctx *c, const uint32_t *d_fn, const uint8
   for (int t = 0; t < 64; t++) xts |= (unsigned long long)(x[t] == '1') << t;
   TRX_HIPCHK(c, trx_launch_fec_sch_encode(c->stream, d_fn, d_bsic, n, xts, d_bits, c->prof));
   return TRXSIG_OK;
+}
+namespace {
+int fec_rx_stream(trxsig_ctx *c, const char *what, int tch, int n_chan, int n_slots, const float *d_soft, int soft_stride,
+                  int64_t n_rows, const int32_t *d_index, const uint8_t *d_b0, int wire, void *d_state, uint8_t *d_status,
+                  uint8_t *d_tch, uint8_t *d_l2, float *d_fer) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n_chan < 0 || n_slots < 0 || n_rows < 0 || (n_slots & 3) || soft_stride < 148 ||
+      (long long)n_chan * n_slots >= 0x80000000LL ||
+      (n_chan > 0 && n_slots > 0 && (!d_soft || !d_index || !d_state || !d_status || (tch && !d_tch) || !d_l2 ||
+                                     ((uintptr_t)d_state & 3))))
+    return fail(c, TRXSIG_EINVAL, what);
+  if (n_chan == 0 || n_slots == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec_rx_stream(c->stream, tch, n_chan, n_slots, d_soft, soft_stride, n_rows, d_index, d_b0, wire,
+                                     static_cast<uint8_t *>(d_state), d_status, d_tch, d_l2, d_fer, c->prof));
+  return TRXSIG_OK;
+}
+}  // namespace
+int trxsig_fec_tch_decode_stream(trxsig_ctx *c, int n_chan, int n_slots, const float *d_soft, int soft_stride, int64_t n_rows,
+                                 const int32_t *d_index, const uint8_t *d_b0, int wire, void *d_state, uint8_t *d_status,
+                                 uint8_t *d_tch, uint8_t *d_facch, float *d_fer) {
+  return fec_rx_stream(c, "trxsig_fec_tch_decode_stream: bad argument", 1, n_chan, n_slots, d_soft, soft_stride, n_rows, d_index,
+                       d_b0, wire, d_state, d_status, d_tch, d_facch, d_fer);
+}
+int trxsig_fec_xcch_decode_stream(trxsig_ctx *c, int n_chan, int n_slots, const float *d_soft, int soft_stride, int64_t n_rows,
+                                  const int32_t *d_index, int wire, void *d_state, uint8_t *d_status, uint8_t *d_frames,
+                                  float *d_fer) {
+  return fec_rx_stream(c, "trxsig_fec_xcch_decode_stream: bad argument", 0, n_chan, n_slots, d_soft, soft_stride, n_rows, d_index,
+                       nullptr, wire, d_state, d_status, nullptr, d_frames, d_fer);
 }
 int trxsig_fec_viterbi_batch(trxsig_ctx *c, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
                              uint8_t *d_bits, int64_t out_stride) {

@@ -14,7 +14,8 @@
 // input bit (24 steps back) is the output.  Numerical contract as in trxsig_dev.h: float costs are added
 // exactly as the reference adds them (cost + (second-bit cost + first-bit cost), -ffp-contract=off),
 // so survivor selection, ties included, is bit-identical.
-// The downlink encoders live here too: k_fec_xcch_encode, k_fec_tch_encode (TCH/FS + FACCH/F streams), k_fec_sch_encode.
+// The downlink encoders live here too: k_fec_xcch_encode, k_fec_tch_encode (TCH/FS + FACCH/F streams), k_fec_sch_encode; and
+// the multi-channel uplink stream decoders k_fec_rx_stream + k_fec_rx_fold (TCH/FACCH and XCCH, mI[][] carried on the device).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -107,29 +108,17 @@ __device__ __forceinline__ float wire_value(float v) {
 
 enum { FEC_GENERIC = 0, FEC_XCCH = 1, FEC_RACH = 2, FEC_TCH = 3 };
 
-// MODE FEC_GENERIC: block b reads soft[b*in_stride + p], p < n, and writes nout bits as bytes to out0 + b*out_stride.
-// MODE FEC_XCCH   : block b = bursts 4b..4b+3 of soft[burst*in_stride + 0..147]; c[k] = i[k%4][j(k)] with the
-//                   e-bits at 3..59 and 88..144 (fec:607-608, 618-629); out0 = 23 octets per block, out1 = ok.
-// MODE FEC_RACH   : block b = burst b, e = burst[49..85) (fec:479); out0 = tail ok, out1 = BSIC, out2 = RA.
-// MODE FEC_TCH    : block b = bursts 4b..4b+7 (diagonal deinterleaver, fec:1108-1116), class 1 = c[0..378) decoded,
-//                   class 2 = c[378..456) sliced (fec:1133-1163); out0 = d[260] packed MSB first (33 octets),
-//                   out1 = good (parity of class 1a and tail), out2 = stolen (Hl of the block's last burst, fec:1077).
-// ilv8 (FEC_XCCH only): read c[] through the TCH deinterleaver instead -- the FACCH decode of a stolen block.
-template <int MODE>
-__global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ soft, long long in_stride, int n, int nout,
-                                                    int nblk, int wire, int ilv8, uint8_t *__restrict__ out0,
-                                                    uint8_t *__restrict__ out1, uint8_t *__restrict__ out2,
-                                                    long long out_stride) {
-  // costs of coder bit 0/1 for both bits of a step, kChunk steps at a time: a small table keeps 8 waves
-  // per SIMD resident (the whole 252-step table of an XCCH block would be 4 KB per block: 2.5 waves)
-  __shared__ float4 ktab[4][kChunk];
-  const int lane = threadIdx.x & 63, row = lane >> 4, s = lane & 15;
-  const int blk = blockIdx.x * 4 + row;
-  const bool live = blk < nblk;
-  const int steps = nout + kDeferral;
-  float2 *K2 = reinterpret_cast<float2 *>(ktab[row]);
-  const float4 *K = ktab[row];
-
+// The trellis of SoftVector::decode (bv:334-399, metric tables bv:462-485) for the code word of this lane's 16-lane row:
+// lane s IS survivor s.  fetch(p) loads soft value p of the row's code word (called for p < n of a live row, eight loads
+// issued together per table refill) and finish(v, p) turns the loaded value into the one the decoder sees.  `steps`
+// (wave-uniform) is at least nout + kDeferral of every row; a row that runs past its own end sees unknowns (0.5) there,
+// which changes none of its first nout output bits.  tab: the row's kChunk-entry LDS table.  Returns lane s's output
+// bits 32s .. 32s+31.
+template <class Fetch, class Finish>
+__device__ __forceinline__ unsigned fec_trellis(float4 *tab, int n, int steps, bool live, int lane, Fetch fetch, Finish finish) {
+  const int s = lane & 15;
+  float2 *K2 = reinterpret_cast<float2 *>(tab);
+  const float4 *K = tab;
   float cost = 0.0f;                                       // lane s is survivor s (bv:334-399)
   unsigned ist = 0, outw = 0;
   const int srcA = (lane & 48) + (s >> 1), srcB = srcA + 8;
@@ -141,17 +130,7 @@ __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ so
     for (int q = 0; q < 8; q++) {
       const int p = 2 * c0 + s + 16 * q;
       float v = 0.0f;
-      if (p < n && live) {
-        if (MODE == FEC_XCCH || MODE == FEC_TCH) {
-          const int B = (MODE == FEC_TCH || ilv8) ? (p & 7) : (p & 3);      // burst within the block
-          const int j = 2 * ((49 * p) % 57) + ((p % 8) / 4);                // GSM 05.03 4.1.4 / 3.1.3 (fec:622-625, 1111)
-          v = soft[(size_t)(4 * blk + B) * in_stride + (j < 57 ? 3 + j : 88 + (j - 57))];
-        } else if (MODE == FEC_RACH) {
-          v = soft[(size_t)blk * in_stride + 49 + p];
-        } else {
-          v = soft[(size_t)blk * in_stride + p];
-        }
-      }
+      if (p < n && live) v = fetch(p);
       vv[q] = v;
     }
 #pragma unroll
@@ -159,8 +138,7 @@ __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ so
       const int p = 2 * c0 + s + 16 * q;
       float k0 = 0.5F, k1 = 0.5F;                          // past the data: unknowns (bv:481-484)
       if (p < n && live) {
-        float v = vv[q];
-        if (wire) v = wire_value(v);
+        const float v = finish(vv[q], p);
         const bool hard = v > 0.5F;                        // sliced() (bv:424-433)
         float pVal = v;
         if (pVal > 0.5F) pVal = 1.0F - pVal;
@@ -207,6 +185,95 @@ __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ so
     }
     wave_fence();                                          // table reads done before the next chunk overwrites it
   }
+  return outw;
+}
+
+// XCCHL1Decoder::decode after the trellis (fec:598, 644-651) for the row of lane s, whose output word is outw: the 23 L2
+// octets to out23 and the parity verdict (every lane of the row returns it).  The whole row must be active.
+__device__ __forceinline__ bool xcch_finish(unsigned outw, int s, uint8_t *__restrict__ out23) {
+  // d[] = u[0..184) with every octet bit-reversed (LSB8MSB, fec:598) and packed MSB first: octet o is
+  // u[8o .. 8o+7] with u[8o] as its LSB, i.e. the bytes of the output words as they stand
+  for (int q = 0; q < 4; q++)
+    if (4 * s + q < 23) out23[4 * s + q] = (uint8_t)(outw >> (8 * q));
+  // syndrome of d[]:~p[] (fec:644-651): XOR of the unit responses of the set bits
+  unsigned w = outw;
+  if (s == 5) w ^= 0xFF000000u;                            // parity bits 184..223 are inverted
+  if (s == 6) w ^= 0xFFFFFFFFu;
+  unsigned long long syn = 0;
+  if (s < 7) {
+    for (int k = 0; k < 32; k++) {
+      const unsigned long long r = kXcchSyn.v[32 * s + k];
+      if ((w >> k) & 1u) syn ^= r;
+    }
+  }
+  unsigned lo = (unsigned)syn, hi = (unsigned)(syn >> 32);
+  lo ^= (unsigned)dpp_i<0xB1>((int)lo); hi ^= (unsigned)dpp_i<0xB1>((int)hi);
+  lo ^= (unsigned)dpp_i<0x4E>((int)lo); hi ^= (unsigned)dpp_i<0x4E>((int)hi);
+  lo ^= (unsigned)dpp_i<0x141>((int)lo); hi ^= (unsigned)dpp_i<0x141>((int)hi);
+  lo ^= (unsigned)dpp_i<0x140>((int)lo); hi ^= (unsigned)dpp_i<0x140>((int)hi);
+  return (lo | hi) == 0;
+}
+
+// decodeTCH(false) after the trellis (fec:1133-1163): uw = u[189] in LDS (word w = bits 32w..32w+31, visible to the row),
+// cbit(k) = c[k] sliced for class 2 (k >= 378).  Writes d[260] packed MSB first (33 octets) to out33; lane s == 0 returns
+// `good` (parity of class 1a and the tail bits), the other lanes false.
+template <class CBit>
+__device__ __forceinline__ bool tch_finish(const unsigned *uw, int s, CBit cbit, uint8_t *__restrict__ out33) {
+  auto ubit = [&](int i) { return (uw[i >> 5] >> (i & 31)) & 1u; };
+  auto dbit = [&](int q) -> unsigned {
+    if (q >= 260) return 0u;
+    if (q >= 182) return cbit(378 + q - 182);
+    const int k = q >> 1;
+    return (q & 1) ? ubit(184 - k) : ubit(k);
+  };
+  for (int o = s; o < 33; o += 16) {
+    unsigned byte = 0;
+    for (int q = 0; q < 8; q++) byte = (byte << 1) | dbit(8 * o + q);
+    out33[o] = (uint8_t)byte;
+  }
+  bool good = false;
+  if (s == 0) {
+    unsigned calc = 0;
+    for (int i = 0; i < 50; i++) if (dbit(i)) calc ^= kTchPar.v[i];
+    const unsigned sent = (~((ubit(91) << 2) | (ubit(92) << 1) | ubit(93))) & 7u;      // peekField(91,3)
+    const unsigned tail = ubit(185) | ubit(186) | ubit(187) | ubit(188);
+    good = (sent == calc) && (tail == 0);
+  }
+  return good;
+}
+
+// MODE FEC_GENERIC: block b reads soft[b*in_stride + p], p < n, and writes nout bits as bytes to out0 + b*out_stride.
+// MODE FEC_XCCH   : block b = bursts 4b..4b+3 of soft[burst*in_stride + 0..147]; c[k] = i[k%4][j(k)] with the
+//                   e-bits at 3..59 and 88..144 (fec:607-608, 618-629); out0 = 23 octets per block, out1 = ok.
+// MODE FEC_RACH   : block b = burst b, e = burst[49..85) (fec:479); out0 = tail ok, out1 = BSIC, out2 = RA.
+// MODE FEC_TCH    : block b = bursts 4b..4b+7 (diagonal deinterleaver, fec:1108-1116), class 1 = c[0..378) decoded,
+//                   class 2 = c[378..456) sliced (fec:1133-1163); out0 = d[260] packed MSB first (33 octets),
+//                   out1 = good (parity of class 1a and tail), out2 = stolen (Hl of the block's last burst, fec:1077).
+// ilv8 (FEC_XCCH only): read c[] through the TCH deinterleaver instead -- the FACCH decode of a stolen block.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ soft, long long in_stride, int n, int nout,
+                                                    int nblk, int wire, int ilv8, uint8_t *__restrict__ out0,
+                                                    uint8_t *__restrict__ out1, uint8_t *__restrict__ out2,
+                                                    long long out_stride) {
+  // costs of coder bit 0/1 for both bits of a step, kChunk steps at a time: a small table keeps 8 waves
+  // per SIMD resident (the whole 252-step table of an XCCH block would be 4 KB per block: 2.5 waves)
+  __shared__ float4 ktab[4][kChunk];
+  const int lane = threadIdx.x & 63, row = lane >> 4, s = lane & 15;
+  const int blk = blockIdx.x * 4 + row;
+  const bool live = blk < nblk;
+  auto fetch = [&](int p) -> float {
+    if (MODE == FEC_XCCH || MODE == FEC_TCH) {
+      const int B = (MODE == FEC_TCH || ilv8) ? (p & 7) : (p & 3);      // burst within the block
+      const int j = 2 * ((49 * p) % 57) + ((p % 8) / 4);                // GSM 05.03 4.1.4 / 3.1.3 (fec:622-625, 1111)
+      return soft[(size_t)(4 * blk + B) * in_stride + (j < 57 ? 3 + j : 88 + (j - 57))];
+    } else if (MODE == FEC_RACH) {
+      return soft[(size_t)blk * in_stride + 49 + p];
+    } else {
+      return soft[(size_t)blk * in_stride + p];
+    }
+  };
+  auto finish = [&](float v, int) -> float { return wire ? wire_value(v) : v; };
+  const unsigned outw = fec_trellis(ktab[row], n, nout + kDeferral, live, lane, fetch, finish);
   if (!live) return;
 
   if (MODE == FEC_GENERIC) {
@@ -215,56 +282,22 @@ __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ so
       if (i < nout) out0[(size_t)blk * out_stride + i] = (uint8_t)((outw >> k) & 1u);
     }
   } else if (MODE == FEC_XCCH) {
-    // d[] = u[0..184) with every octet bit-reversed (LSB8MSB, fec:598) and packed MSB first: octet o is
-    // u[8o .. 8o+7] with u[8o] as its LSB, i.e. the bytes of the output words as they stand
-    for (int q = 0; q < 4; q++)
-      if (4 * s + q < 23) out0[(size_t)blk * 23 + 4 * s + q] = (uint8_t)(outw >> (8 * q));
-    // syndrome of d[]:~p[] (fec:644-651): XOR of the unit responses of the set bits
-    unsigned w = outw;
-    if (s == 5) w ^= 0xFF000000u;                          // parity bits 184..223 are inverted
-    if (s == 6) w ^= 0xFFFFFFFFu;
-    unsigned long long syn = 0;
-    if (s < 7) {
-      for (int k = 0; k < 32; k++) {
-        const unsigned long long r = kXcchSyn.v[32 * s + k];
-        if ((w >> k) & 1u) syn ^= r;
-      }
-    }
-    unsigned lo = (unsigned)syn, hi = (unsigned)(syn >> 32);
-    lo ^= (unsigned)dpp_i<0xB1>((int)lo); hi ^= (unsigned)dpp_i<0xB1>((int)hi);
-    lo ^= (unsigned)dpp_i<0x4E>((int)lo); hi ^= (unsigned)dpp_i<0x4E>((int)hi);
-    lo ^= (unsigned)dpp_i<0x141>((int)lo); hi ^= (unsigned)dpp_i<0x141>((int)hi);
-    lo ^= (unsigned)dpp_i<0x140>((int)lo); hi ^= (unsigned)dpp_i<0x140>((int)hi);
-    if (s == 0) out1[blk] = (lo | hi) == 0;
+    const bool ok = xcch_finish(outw, s, out0 + (size_t)blk * 23);
+    if (s == 0) out1[blk] = ok;
   } else if (MODE == FEC_TCH) {
     // u[189] -> LDS (word w = bits 32w..32w+31), then d[] (fec:1141-1146) octet by octet
     unsigned *uw = reinterpret_cast<unsigned *>(ktab[row]);
     if (s < 6) uw[s] = outw;
     wave_fence();
-    auto ubit = [&](int i) { return (uw[i >> 5] >> (i & 31)) & 1u; };
     auto cbit = [&](int k) {                               // class 2: c[k] sliced, k >= 378
       const int j = 2 * ((49 * k) % 57) + ((k % 8) / 4);
       float v = soft[(size_t)(4 * blk + (k & 7)) * in_stride + (j < 57 ? 3 + j : 88 + (j - 57))];
       if (wire) v = wire_value(v);
       return v > 0.5F ? 1u : 0u;
     };
-    auto dbit = [&](int q) -> unsigned {
-      if (q >= 260) return 0u;
-      if (q >= 182) return cbit(378 + q - 182);
-      const int k = q >> 1;
-      return (q & 1) ? ubit(184 - k) : ubit(k);
-    };
-    for (int o = s; o < 33; o += 16) {
-      unsigned byte = 0;
-      for (int q = 0; q < 8; q++) byte = (byte << 1) | dbit(8 * o + q);
-      out0[(size_t)blk * 33 + o] = (uint8_t)byte;
-    }
+    const bool good = tch_finish(uw, s, cbit, out0 + (size_t)blk * 33);
     if (s == 0) {
-      unsigned calc = 0;
-      for (int i = 0; i < 50; i++) if (dbit(i)) calc ^= kTchPar.v[i];
-      const unsigned sent = (~((ubit(91) << 2) | (ubit(92) << 1) | ubit(93))) & 7u;      // peekField(91,3)
-      const unsigned tail = ubit(185) | ubit(186) | ubit(187) | ubit(188);
-      out1[blk] = (sent == calc) && (tail == 0);
+      out1[blk] = good;
       float hl = soft[(size_t)(4 * blk + 7) * in_stride + 60];
       if (wire) hl = wire_value(hl);
       out2[blk] = hl > 0.5F;
@@ -570,6 +603,208 @@ __global__ __launch_bounds__(64) void k_fec_sch_encode(const uint32_t *__restric
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_fec_rx_stream / k_fec_rx_fold: the uplink decoders of many channels as streams -- TCHFACCHL1Decoder::processBurst /
+// deinterleave / decodeTCH (fec:1030-1163) and XCCHL1Decoder::writeLowSide / processBurst / deinterleave / decode
+// (fec:556-653) with the deinterleaving buffer mI[][] carried from call to call in a per-channel state record.
+//
+// Closed form of mI.  Slot t of a channel writes row B(t) of mI in full when its burst is present; the block that closes
+// at slot 4m+3 (B % 4 == 3) is decoded when that burst is present, and then reads half of every row (TCH: the odd half of
+// rows 0..3 and the even half of rows 4..7 at B = 3, the other way round at B = 7; XCCH: all of every row) and leaves 0.5
+// behind.  Each (row, half) therefore sees one possible write and one possible read per period (P = 8 slots for TCH, 4 for
+// XCCH), and its value at any point of the stream is decided by its most recent event: a present burst (its value), a
+// decoded read (0.5), or -- when the scan back through the periods of the call finds neither -- the incoming state.  A write
+// and a read in the same slot happen in that order.  So every (channel, block) gathers its c[] independently: a 16-lane row
+// of k_fec_rx_stream per code word, one Viterbi pass (the FACCH/XCCH decode of 456 -> 228 or the class-1 decode of
+// 378 -> 189, whichever the block needs), and k_fec_rx_fold, launched after it, writes the new state and folds the FER.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRxHdr = 16;                                 // state: bytes 0..3 mFER (float), 4..15 zero, then the rows of mI
+constexpr int kSrcHalf = -1, kSrcState = -2;               // source of a (row, half): a burst's row (>= 0), 0.5, or the state
+
+struct RxStream {
+  const float *soft;
+  long long stride, n_rows;
+  const int32_t *index;                                    // [n_chan][n_slots]
+  const uint8_t *b0;                                       // [n_chan] or null
+  int n_chan, n_slots, wire;
+};
+
+// the row of slot t's burst, or -1 (no burst: -1, or any index outside [0, n_rows))
+__device__ __forceinline__ int rx_row(const RxStream &a, const int32_t *idx, int t) {
+  const int i = idx[t];
+  return (i >= 0 && (long long)i < a.n_rows) ? i : -1;
+}
+
+// the source of a (row, half) at a point of the stream: tw = the last slot up to the point that writes the row, tr = the
+// last decodable read of the half before the point (both step back by P; negative = before the call)
+__device__ __forceinline__ int rx_source(const RxStream &a, const int32_t *idx, bool chan_ok, int tw, int tr, int P) {
+  if (!chan_ok) return kSrcState;
+  while (tw >= 0 || tr >= 0) {
+    if (tr >= tw) {                                        // the read is the later event (same slot: write, then read)
+      if (rx_row(a, idx, tr) >= 0) return kSrcHalf;
+      tr -= P;
+    } else {
+      const int r = rx_row(a, idx, tw);
+      if (r >= 0) return r;
+      tw -= P;
+    }
+  }
+  return kSrcState;
+}
+
+// e-bit j (0..113) of a burst: data1 = burst[3..60), data2 = burst[88..145) (fec:607-608, 1051-1052)
+__device__ __forceinline__ int rx_pos(int j) { return j < 57 ? 3 + j : 88 + (j - 57); }
+
+// a channel's d_b0 (TCH): 0 or 4; any other value makes the channel one where no burst arrives
+__device__ __forceinline__ int rx_b0(const RxStream &a, int ch) { return a.b0 ? (int)a.b0[ch] : 0; }
+
+template <bool TCH>
+__global__ __launch_bounds__(64) void k_fec_rx_stream(RxStream a, const uint8_t *__restrict__ state, uint8_t *__restrict__ status,
+                                                      uint8_t *__restrict__ out_tch, uint8_t *__restrict__ out_l2) {
+  constexpr int R = TCH ? 8 : 4, P = TCH ? 8 : 4;
+  constexpr int kStateBytes = kRxHdr + R * 114 * 4;
+  __shared__ float4 ktab[4][kChunk];
+  __shared__ int srcd[4][8];
+  const int lane = threadIdx.x & 63, row = lane >> 4, s = lane & 15;
+  const int n_blocks = a.n_slots >> 2;
+  const int blk = blockIdx.x * 4 + row;                    // (channel, block) = blk; n_chan * n_blocks < 2^29
+  const bool live = blk < a.n_chan * n_blocks;
+  const int ch = live ? blk / n_blocks : 0, m = live ? blk - ch * n_blocks : 0;
+  const int32_t *idx = a.index + (size_t)ch * a.n_slots;
+  const int b0 = TCH ? rx_b0(a, ch) : 0;
+  const bool chan_ok = !TCH || b0 == 0 || b0 == 4;
+  const int tc = 4 * m + 3;                                // the closing slot
+  const int cl = (live && chan_ok) ? rx_row(a, idx, tc) : -1;
+  const bool decoded = cl >= 0;
+  const int Bc = TCH ? ((b0 + tc) & 7) : 3;                // B of the closing burst: 3 or 7 (TCH), 3 (XCCH)
+  const int off = Bc == 3 ? 4 : 0;                         // deinterleave(4) at B = 3, deinterleave(0) at B = 7 (fec:1072-1073)
+  bool stolen = false;
+  if (TCH && decoded) {                                    // Hl of the closing burst (fec:1076-1077)
+    float hl = a.soft[(size_t)cl * a.stride + 60];
+    if (a.wire) hl = wire_value(hl);
+    stolen = hl > 0.5F;
+  }
+  // the sources of the row's c[]: (row r, the half this block reads) for r = s < R
+  if (s < R) {
+    const int tw = tc - ((Bc - s) & (P - 1));              // the last slot up to tc with B = r
+    srcd[row][s] = decoded ? rx_source(a, idx, chan_ok, tw, tc - P, P) : kSrcState;
+  }
+  wave_fence();
+  const float *st_rows = reinterpret_cast<const float *>(state + (size_t)ch * kStateBytes + kRxHdr);
+  const int *sd = srcd[row];
+  auto rowB = [&](int k) { return TCH ? ((k + off) & 7) : (k & 3); };
+  auto fetch = [&](int k) -> float {
+    const int B = rowB(k);
+    const int j = 2 * ((49 * k) % 57) + ((k % 8) / 4);     // GSM 05.03 3.1.3 / 4.1.4 (fec:622-625, 1111)
+    const int src = sd[B];
+    if (src >= 0) return a.soft[(size_t)src * a.stride + rx_pos(j)];
+    return src == kSrcHalf ? 0.5F : st_rows[B * 114 + j];
+  };
+  auto finish = [&](float v, int k) -> float {             // the UDP hop applies to a burst's values as they enter mI
+    return (a.wire && sd[rowB(k)] >= 0) ? wire_value(v) : v;
+  };
+  const bool l2 = !TCH || stolen;                          // the FACCH / XCCH decode (456 -> 228), else class 1 (378 -> 189)
+  const unsigned long long any = __builtin_amdgcn_ballot_w64(decoded);
+  const unsigned long long anyl2 = __builtin_amdgcn_ballot_w64(decoded && l2);
+  const int steps = any == 0 ? 0 : (anyl2 ? 228 : 189) + kDeferral;
+  const unsigned outw = fec_trellis(ktab[row], l2 ? 456 : 378, steps, decoded, lane, fetch, finish);
+  if (!live) return;
+
+  const size_t ob = (size_t)blk;
+  bool okl2 = false, good = false;
+  if (TCH) {
+    unsigned *uw = reinterpret_cast<unsigned *>(ktab[row]);
+    if (s < 6) uw[s] = outw;
+    wave_fence();
+    if (decoded && !stolen) {
+      auto cbit = [&](int k) { return finish(fetch(k), k) > 0.5F ? 1u : 0u; };    // class 2 sliced (fec:1141)
+      good = tch_finish(uw, s, cbit, out_tch + ob * 33);
+    } else {
+      for (int o = s; o < 33; o += 16) out_tch[ob * 33 + o] = 0;
+    }
+  }
+  if (decoded && l2) {
+    okl2 = xcch_finish(outw, s, out_l2 + ob * 23);
+  } else {
+    for (int o = s; o < 23; o += 16) out_l2[ob * 23 + o] = 0;
+  }
+  if (s == 0) {
+    unsigned f = 0;
+    if (decoded) {
+      f = TRXSIG_FEC_DECODED;
+      if (TCH && stolen) f |= TRXSIG_FEC_STOLEN | (okl2 ? TRXSIG_FEC_FACCH_OK : 0u);
+      if (TCH ? good : okl2) f |= TRXSIG_FEC_TCH_GOOD;
+    }
+    status[ob] = (uint8_t)f;
+  }
+}
+
+// A workgroup per channel, after k_fec_rx_stream: the FER after every block (L1Decoder::countGoodFrame / countBadFrame,
+// fec:390-405, in the reference's count order) and the new state -- mFER and the rows of mI after the call's last slot.
+// Every position of the state is read and rewritten by the same lane, so the update in place is race-free.
+template <bool TCH>
+__global__ __launch_bounds__(64) void k_fec_rx_fold(RxStream a, uint8_t *state, const uint8_t *__restrict__ status,
+                                                    uint8_t *__restrict__ fer_out) {
+  constexpr int R = TCH ? 8 : 4, P = TCH ? 8 : 4;
+  constexpr int kStateBytes = kRxHdr + R * 114 * 4;
+  __shared__ int srcd[16];
+  const int lane = threadIdx.x, ch = blockIdx.x;
+  const int n_blocks = a.n_slots >> 2, T = a.n_slots;
+  const int32_t *idx = a.index + (size_t)ch * a.n_slots;
+  const int b0 = TCH ? rx_b0(a, ch) : 0;
+  const bool chan_ok = !TCH || b0 == 0 || b0 == 4;
+  uint8_t *st = state + (size_t)ch * kStateBytes;
+  float *rows = reinterpret_cast<float *>(st + kRxHdr);
+  // sources after the last slot: TCH (row r, half h) = srcd[2r + h], XCCH row r = srcd[r]
+  if (lane < (TCH ? 16 : 4)) {
+    const int r = TCH ? lane >> 1 : lane, h = lane & 1;
+    const int Bl = TCH ? ((b0 + T - 1) & 7) : 3;           // B of the last slot
+    const int Br = TCH ? ((((r < 4) == (h == 1)) ? 3 : 7)) : 3;   // the closing B that reads (r, h)
+    srcd[lane] = rx_source(a, idx, chan_ok, T - 1 - ((Bl - r) & (P - 1)), T - 1 - ((Bl - Br) & (P - 1)), P);
+  }
+  wave_fence();
+  for (int i = lane; i < R * 114; i += 64) {
+    const int r = i / 114, j = i - 114 * r;
+    const int src = srcd[TCH ? 2 * r + (j & 1) : r];       // half = the parity of j (fec:1111)
+    if (src >= 0) {
+      float v = a.soft[(size_t)src * a.stride + rx_pos(j)];
+      if (a.wire) v = wire_value(v);
+      rows[i] = v;
+    } else if (src == kSrcHalf) {
+      rows[i] = 0.5F;
+    }                                                      // kSrcState: the old value stays
+  }
+  // the FER, 64 blocks at a time: every lane runs the recurrence on the broadcast status bytes
+  const float fa = 1.0F / 20.0F, fb = 1.0F - fa;          // mFERMemory = 20 (GSML1FEC.h:226)
+  float fer = *reinterpret_cast<const float *>(st);
+  for (int m0 = 0; m0 < n_blocks; m0 += 64) {
+    const int mine = m0 + lane < n_blocks ? (int)status[(size_t)ch * n_blocks + m0 + lane] : 0;
+    const int cnt = n_blocks - m0 < 64 ? n_blocks - m0 : 64;
+    float keep = 0.0F;
+    for (int q = 0; q < cnt; q++) {
+      const int f = __shfl(mine, q, 64);
+      if (f & TRXSIG_FEC_DECODED) {
+        if (TCH && (f & TRXSIG_FEC_STOLEN)) {
+          if (f & TRXSIG_FEC_FACCH_OK) fer *= fb; else fer = fb * fer + fa;   // the FACCH frame (fec:1079-1089)
+          fer = fb * fer + fa;                             // decodeTCH(true) returns false (fec:1094-1098)
+        } else if (f & TRXSIG_FEC_TCH_GOOD) {
+          fer *= fb;
+        } else {
+          fer = fb * fer + fa;
+        }
+      }
+      if (q == lane) keep = fer;
+    }
+    if (fer_out && lane < cnt) {                           // bytewise: d_fer may be unaligned
+      const unsigned u = __float_as_uint(keep);
+      uint8_t *o = fer_out + 4 * ((size_t)ch * n_blocks + m0 + lane);
+      o[0] = (uint8_t)u; o[1] = (uint8_t)(u >> 8); o[2] = (uint8_t)(u >> 16); o[3] = (uint8_t)(u >> 24);
+    }
+  }
+  if (lane == 0) *reinterpret_cast<float *>(st) = fer;
+  if (lane >= 1 && lane < 4) reinterpret_cast<unsigned *>(st)[lane] = 0u;
+}
+
 }  // namespace
 
 hipError_t trx_launch_fec_xcch_encode(hipStream_t st, const uint8_t *frames, int nblk, const uint8_t *tsc_bits, uint8_t *bits,
@@ -623,5 +858,27 @@ hipError_t trx_launch_fec_sch_encode(hipStream_t st, const uint32_t *fns, const 
   else
     k_fec_sch_encode<false><<<grid, block, 0, st>>>(fns, bsics, n, xts, bits);
   if (prof) prof->end(TRXSIG_K_FEC_SCH_ENC, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_slots, const float *soft, long long stride,
+                                    long long n_rows, const int32_t *index, const uint8_t *b0, int wire, uint8_t *state,
+                                    uint8_t *status, uint8_t *out_tch, uint8_t *out_l2, float *fer, TrxProfiler *prof) {
+  if (n_chan <= 0 || n_slots <= 0) return hipSuccess;
+  if (n_slots & 3) return hipErrorInvalidValue;
+  const RxStream a = { soft, stride, n_rows, index, tch ? b0 : nullptr, n_chan, n_slots, wire };
+  const long long nblk = (long long)n_chan * (n_slots / 4);
+  const dim3 grid((unsigned)((nblk + 3) / 4)), block(64);
+  const int id = tch ? TRXSIG_K_FEC_TCH_RX : TRXSIG_K_FEC_XCCH_RX;
+  if (prof) prof->begin(id, st);
+  if (tch) k_fec_rx_stream<true><<<grid, block, 0, st>>>(a, state, status, out_tch, out_l2);
+  else k_fec_rx_stream<false><<<grid, block, 0, st>>>(a, state, status, out_tch, out_l2);
+  if (prof) prof->end(id, st);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (prof) prof->begin(TRXSIG_K_FEC_RX_FOLD, st);
+  if (tch) k_fec_rx_fold<true><<<dim3((unsigned)n_chan), block, 0, st>>>(a, state, status, reinterpret_cast<uint8_t *>(fer));
+  else k_fec_rx_fold<false><<<dim3((unsigned)n_chan), block, 0, st>>>(a, state, status, reinterpret_cast<uint8_t *>(fer));
+  if (prof) prof->end(TRXSIG_K_FEC_RX_FOLD, st);
   return hipGetLastError();
 }

@@ -241,3 +241,8 @@ hipError_t trx_launch_fec_tch_encode(hipStream_t st, int n_chan, int n_blocks, c
 // SCH encode (trxsig_fec_sch_encode_batch): n (FN, BSIC) -> n bursts of 148 bits; xts: bit t = extended training sequence bit t
 hipError_t trx_launch_fec_sch_encode(hipStream_t st, const uint32_t *fns, const uint8_t *bsics, int n, unsigned long long xts,
                                      uint8_t *bits, TrxProfiler *prof);
+// uplink stream decode (trxsig_fec_tch_decode_stream / _xcch_decode_stream): k_fec_rx_stream, then k_fec_rx_fold.  tch != 0:
+// TCH/FACCH (out_tch = 33 octets, out_l2 = the FACCH frame), 0: XCCH (out_l2 = the frame; out_tch and b0 unused)
+hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_slots, const float *soft, long long stride,
+                                    long long n_rows, const int32_t *index, const uint8_t *b0, int wire, uint8_t *state,
+                                    uint8_t *status, uint8_t *out_tch, uint8_t *out_l2, float *fer, TrxProfiler *prof);
