@@ -557,6 +557,8 @@ enum { TRXSIG_K_TSC_CORR = 0, TRXSIG_K_TSC_PEAK = 1, TRXSIG_K_DEMOD = 2, TRXSIG_
  * leaves them out; trxsig_profile_collect_n reports them, and trxsig_kernel_count() counts them. */
 enum { TRXSIG_K_FEC_TCH_ENC = 15, TRXSIG_K_FEC_SCH_ENC = 16, TRXSIG_K_FEC_TCH_RX = 17, TRXSIG_K_FEC_XCCH_RX = 18,
        TRXSIG_K_FEC_RX_FOLD = 19 };
+/* the uplink L1 demultiplexer's own kernels (trxsig_l1rx.h): k_l1rx_demux and k_l1rx_finish */
+enum { TRXSIG_K_L1RX_DEMUX = 20, TRXSIG_K_L1RX_FINISH = 21 };
 const char *trxsig_kernel_name(int kernel_id);
 int trxsig_profile_enable(trxsig_ctx *ctx, int on);
 int trxsig_profile_collect(trxsig_ctx *ctx, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]);

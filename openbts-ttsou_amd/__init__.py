@@ -884,3 +884,116 @@ class TrxGroup:
         v = C.c_double()
         self._chk(self.L.trxsig_trxgroup_energy_threshold(self.h, arfcn, C.byref(v)), "trxsig_trxgroup_energy_threshold")
         return v.value
+
+
+L1_TCH, L1_XCCH, L1_RACH = 0, 1, 2               # channel classes of trxsig_l1rx.h
+L1_TCHF, L1_SACCH_TF, L1_SDCCH8, L1_SACCH_C8, L1_SDCCH4, L1_SACCH_C4, L1_RACH_C5 = range(7)   # mapping kinds (TRXSIG_L1_*)
+
+
+class L1RxOut(C.Structure):
+    """trxsig_l1rx_out"""
+    _fields_ = [(n, C.c_int) for n in ("n_tch", "n_xcch", "nb_tch", "nb_xcch", "rach_cap")] + \
+               [(n, C.c_void_p) for n in ("d_tch_status", "d_tch_frames", "d_facch", "d_tch_fer", "d_tch_fn", "d_xcch_status",
+                                          "d_xcch_frames", "d_xcch_fer", "d_xcch_fn", "d_rach_count", "d_rach_fn", "d_rach_arfcn",
+                                          "d_rach_rssi", "d_rach_timing", "d_rach_ok", "d_rach_ra", "d_tch_rssi", "d_tch_timing",
+                                          "d_xcch_rssi", "d_xcch_timing", "d_ms_power", "d_ms_ta")]
+
+
+class L1Rx:
+    """ctypes view of include/trxsig_l1rx.h: a Transceiver group pull -> the logical channels' decoders, on the device.
+    comb: uint8 [n_arfcn, 8] in the CMD SETSLOT numbering (0 none, 1 = I, 5 = V on ARFCN 0 TN 0, 7 = VII)."""
+
+    def __init__(self, ctx, comb, bsic, band=900):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32 = C.c_void_p, C.c_int
+        L.trxsig_l1rx_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32]
+        L.trxsig_l1rx_destroy.argtypes = [vp]; L.trxsig_l1rx_destroy.restype = None
+        L.trxsig_l1rx_channels.argtypes = [vp, i32]
+        L.trxsig_l1rx_channel.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        L.trxsig_l1rx_open.argtypes = [vp, i32, i32]
+        L.trxsig_l1rx_close.argtypes = [vp, i32, i32]
+        L.trxsig_l1rx_state.argtypes = [vp, i32, C.POINTER(vp)]
+        L.trxsig_l1rx_decode.argtypes = [vp, C.POINTER(TrxGroupResult), i32, i32, C.POINTER(L1RxOut)]
+        self.comb = np.ascontiguousarray(comb, np.uint8)
+        self.h = vp()
+        rc = L.trxsig_l1rx_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1rx_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self.out = None
+
+    def destroy(self):
+        """trxsig_l1rx_destroy (channels are closed with close(cls, chan))."""
+        if self.h:
+            self.L.trxsig_l1rx_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def channels(self, cls):
+        return self._chk(self.L.trxsig_l1rx_channels(self.h, cls), "trxsig_l1rx_channels")
+
+    def channel(self, cls, chan):
+        """(arfcn, tn, kind, sub) of a channel"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.trxsig_l1rx_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1rx_channel")
+        return tuple(x.value for x in v)
+
+    def open(self, cls, chan):
+        """L1Decoder::open of one TCH / XCCH channel (FER reset; SACCH: power 40, TA 0)."""
+        self._chk(self.L.trxsig_l1rx_open(self.h, cls, chan), "trxsig_l1rx_open")
+
+    def close(self, cls, chan):
+        """L1Decoder::close of one TCH / XCCH channel: its bursts are ignored until it is opened again."""
+        self._chk(self.L.trxsig_l1rx_close(self.h, cls, chan), "trxsig_l1rx_close")
+
+    def decode(self, res, fn, wire=True):
+        """res: a TrxGroupResult (of trxsig_trxgroup_pull, or built from tensors); whole frames from (fn, TN 0)."""
+        out = L1RxOut()
+        self._chk(self.L.trxsig_l1rx_decode(self.h, C.byref(res), int(fn), int(bool(wire)), C.byref(out)), "trxsig_l1rx_decode")
+        self.out = out
+        return out
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._chk(self.L.trxsig_l1rx_state(self.h, cls, C.byref(p)), "trxsig_l1rx_state")
+        return p.value
+
+    def collect(self, state=True):
+        """The last decode's outputs as host numpy arrays (synchronises the context's stream)."""
+        import torch
+        from .frontend import _DevView
+        np, o = self.np, self.out
+        self.ctx.synchronize()
+
+        def get(p, shape, ts):
+            if p is None or int(np.prod(shape)) == 0:
+                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32, "<f4": np.float32}[ts])
+            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        T, X, bt, bx, R = o.n_tch, o.n_xcch, o.nb_tch, o.nb_xcch, o.rach_cap
+        r = dict(tch_status=get(o.d_tch_status, (T, bt), "|u1"), tch=get(o.d_tch_frames, (T, bt, 33), "|u1"),
+                 facch=get(o.d_facch, (T, bt, 23), "|u1"), tch_fer=get(o.d_tch_fer, (T, bt), "<f4"),
+                 tch_fn=get(o.d_tch_fn, (T, bt), "<i4"),
+                 xcch_status=get(o.d_xcch_status, (X, bx), "|u1"), xcch=get(o.d_xcch_frames, (X, bx, 23), "|u1"),
+                 xcch_fer=get(o.d_xcch_fer, (X, bx), "<f4"), xcch_fn=get(o.d_xcch_fn, (X, bx), "<i4"),
+                 tch_rssi=get(o.d_tch_rssi, (T,), "<i4"), tch_timing=get(o.d_tch_timing, (T,), "<i4"),
+                 xcch_rssi=get(o.d_xcch_rssi, (X,), "<i4"), xcch_timing=get(o.d_xcch_timing, (X,), "<i4"),
+                 ms_power=get(o.d_ms_power, (X,), "<i4"), ms_ta=get(o.d_ms_ta, (X,), "<i4"))
+        n = int(get(o.d_rach_count, (1,), "<i4")[0]) if R else 0
+        r["rach"] = dict(fn=get(o.d_rach_fn, (R,), "<i4")[:n], arfcn=get(o.d_rach_arfcn, (R,), "<i4")[:n],
+                         rssi=get(o.d_rach_rssi, (R,), "<i4")[:n], timing=get(o.d_rach_timing, (R,), "<i4")[:n],
+                         ok=get(o.d_rach_ok, (R,), "|u1")[:n], ra=get(o.d_rach_ra, (R,), "|u1")[:n])
+        if state:
+            r["tch_state"] = get(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
+            r["xcch_state"] = get(self.state(L1_XCCH), (X, XCCH_RX_STATE_BYTES), "|u1")
+        return r

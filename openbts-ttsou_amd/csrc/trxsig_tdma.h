@@ -1,0 +1,103 @@
+// trxsig_tdma.h -- internal: the uplink TDMA mappings of GSM 05.02 that the uplink L1 demultiplexer (trxsig_l1rx.cpp / .hip)
+// routes by: the numbers of GSM/GSMTDMA.cpp's uplink TDMAMapping tables (repeat length, frame list in reverse-mapping order).
+// tests/golden/tdma_uplink.npz records the same tables for the CPU model (tests/l1_demux_model.py); tests/test_gpu_l1rx.py
+// checks this routing against the model.
+//
+// Positions.  A mapping with n frames per repeat R numbers its bursts in time order: the burst of frame u (an unwrapped frame
+// count) sits at position p(u) = n * floor((u - f[0]) / R) + r, where f[r] == u mod R.  Because f[r] - f[0] (mod R) grows with r
+// (checked at create), positions grow with time and p mod n is reverseMapping(u) -- so p mod 4 is the XCCH decoders' B and, with
+// n = 24, p mod 8 the TCH decoder's.  R divides 5304 and 5304 divides the hyperframe, so the numbering is the same modulo the
+// hyperframe wrap up to a multiple of n * 5304 / R positions (a whole number of blocks).
+#pragma once
+#include <stdint.h>
+
+enum {
+  TRX_MAP_TCHF = 0,            // FACCH_TCHF
+  TRX_MAP_SACCH_TF = 1,        // + TN: SACCH_TF_T0..T7
+  TRX_MAP_SDCCH8 = 9,          // + sub-channel: SDCCH_8_0U..7U
+  TRX_MAP_SACCH_C8 = 17,       // + sub-channel: SACCH_C8_0U..7U
+  TRX_MAP_SDCCH4 = 25,         // + sub-channel: SDCCH_4_0U..3U
+  TRX_MAP_SACCH_C4 = 29,       // + sub-channel: SACCH_C4_0U..3U
+  TRX_MAP_RACH_C5 = 33,        // RACHC5
+  TRX_N_MAPS = 34
+};
+
+struct TrxTdmaMap {
+  int16_t R, n;
+  int16_t f[27];
+};
+
+#define TRX_M4(R, a, b, c, d) { R, 4, { a, b, c, d } }
+#define TRX_TDMA_MAPS_INIT                                                                                                   \
+  {                                                                                                                          \
+    { 26, 24, { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24 } },                    \
+    TRX_M4(104, 12, 38, 64, 90), TRX_M4(104, 25, 51, 77, 103), TRX_M4(104, 38, 64, 90, 12), TRX_M4(104, 51, 77, 103, 25),  \
+    TRX_M4(104, 64, 90, 12, 38), TRX_M4(104, 77, 103, 25, 51), TRX_M4(104, 90, 12, 38, 64), TRX_M4(104, 103, 25, 51, 77),  \
+    TRX_M4(51, 15, 16, 17, 18), TRX_M4(51, 19, 20, 21, 22), TRX_M4(51, 23, 24, 25, 26), TRX_M4(51, 27, 28, 29, 30),        \
+    TRX_M4(51, 31, 32, 33, 34), TRX_M4(51, 35, 36, 37, 38), TRX_M4(51, 39, 40, 41, 42), TRX_M4(51, 43, 44, 45, 46),        \
+    TRX_M4(102, 47, 48, 49, 50), TRX_M4(102, 51, 52, 53, 54), TRX_M4(102, 55, 56, 57, 58), TRX_M4(102, 59, 60, 61, 62),    \
+    TRX_M4(102, 98, 99, 100, 101), TRX_M4(102, 0, 1, 2, 3), TRX_M4(102, 4, 5, 6, 7), TRX_M4(102, 8, 9, 10, 11),            \
+    TRX_M4(51, 37, 38, 39, 40), TRX_M4(51, 41, 42, 43, 44), TRX_M4(51, 47, 48, 49, 50), TRX_M4(51, 0, 1, 2, 3),            \
+    TRX_M4(102, 57, 58, 59, 60), TRX_M4(102, 61, 62, 63, 64), TRX_M4(102, 6, 7, 8, 9), TRX_M4(102, 10, 11, 12, 13),        \
+    { 51, 27, { 4, 5, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 45, 46 } } \
+  }
+
+constexpr int kTrxHyperframe = 2715648;   // 2048 * 26 * 51
+
+// floor division for a positive divisor
+__host__ __device__ inline long long trx_fdiv(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// the frame (unwrapped) of position q of mapping m
+__host__ __device__ inline long long trx_map_frame(const TrxTdmaMap &m, long long q) {
+  const long long k = trx_fdiv(q, m.n), r = q - k * m.n;
+  return m.f[0] + k * m.R + ((m.f[r] - m.f[0] + m.R) % m.R);
+}
+
+// the number of positions of mapping m in frames before u (the position of the first burst at or after frame u)
+__host__ __device__ inline long long trx_map_count(const TrxTdmaMap &m, long long u) {
+  const long long d = u - m.f[0], k = trx_fdiv(d, m.R), rem = d - k * m.R;
+  long long c = k * m.n;
+  for (int r = 0; r < m.n; r++) c += ((m.f[r] - m.f[0] + m.R) % m.R) < rem;
+  return c;
+}
+
+// GSM 05.05 4.1.1 power control levels -> dBm, SACCHL1Decoder's decodePower (GSM/GSML1FEC.cpp): 0 = GSM850 / EGSM900,
+// 1 = DCS1800, 2 = PCS1900
+#define TRX_POWER_TABLES_INIT                                                                                     \
+  {                                                                                                               \
+    { 39, 39, 39, 37, 35, 33, 31, 29, 27, 25, 23, 21, 19, 17, 15, 13, 11, 9, 7, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5 }, \
+    { 30, 28, 26, 24, 22, 20, 18, 16, 14, 12, 10, 8, 6, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 36, 24, 23 },     \
+    { 30, 28, 26, 24, 22, 20, 18, 16, 14, 12, 10, 8, 6, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }         \
+  }
+
+// what the demux kernel and the fold need of one call (by value)
+struct TrxL1rxCall {
+  int fn, n_frames, n_arfcn, n_rows, soft_stride, sps;
+  int n_tch, n_xcch, n_rach, nb_tch, nb_xcch, rach_cap, band;
+  int32_t blk_first[TRX_N_MAPS];   // per mapping: floor(first position at or after fn / 4)
+  long long p_first[TRX_N_MAPS];   // per mapping: the first position at or after fn
+};
+
+// the device side of one object (pointers into its allocations)
+struct TrxL1rxDev {
+  const int32_t *chinfo;           // [n_all]: arfcn | tn << 16 | map << 20
+  const uint8_t *active;           // [n_all]
+  int32_t *rssi, *timing;          // [n_all]: the last accepted burst's, as the decoder records them
+  int32_t *ms_power, *ms_ta;       // [n_xcch]: SACCH actuals, -1 on channels that are not SACCH
+  int32_t *tch_index, *xcch_index; // [n_tch][4 nb_tch], [n_xcch][4 nb_xcch]
+  uint8_t *tch_b0;                 // [n_tch]
+  int32_t *tch_fn, *xcch_fn;       // closing frame numbers [..][nb]
+  const uint8_t *xcch_status, *xcch_frames;
+  float *rach_soft;                // [rach_cap][148] gathered rows
+  int32_t *rach_fn, *rach_arfcn, *rach_rssi, *rach_timing, *rach_count;
+  uint8_t *rach_tail, *rach_bsic, *rach_ra, *rach_ok;
+  int bsic;
+};
+
+hipError_t trx_launch_l1rx_demux(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, const int32_t *row,
+                                 const uint8_t *valid, const float *soft, const trx_c32 *amp, const float *toa, TrxProfiler *prof);
+hipError_t trx_launch_l1rx_finish(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, TrxProfiler *prof);
+// open (1) / close (0) channel `ch` of the object (index over all classes): the active flag; on open also FER = 0 (state_fer)
+// and, where `sacch`, power 40 / TA 0 (ms_power / ms_ta, unused otherwise)
+hipError_t trx_launch_l1rx_set(hipStream_t st, uint8_t *active, int ch, int open, uint8_t *state_fer, int32_t *ms_power,
+                               int32_t *ms_ta, int sacch);
