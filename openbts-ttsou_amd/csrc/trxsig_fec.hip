@@ -659,15 +659,16 @@ __device__ __forceinline__ int rx_pos(int j) { return j < 57 ? 3 + j : 88 + (j -
 __device__ __forceinline__ int rx_b0(const RxStream &a, int ch) { return a.b0 ? (int)a.b0[ch] : 0; }
 
 template <bool TCH>
-__global__ __launch_bounds__(64) void k_fec_rx_stream(RxStream a, const uint8_t *__restrict__ state, uint8_t *__restrict__ status,
-                                                      uint8_t *__restrict__ out_tch, uint8_t *__restrict__ out_l2) {
+__global__ __launch_bounds__(64) void k_fec_rx_stream(RxStream a, int blk0, const uint8_t *__restrict__ state,
+                                                      uint8_t *__restrict__ status, uint8_t *__restrict__ out_tch,
+                                                      uint8_t *__restrict__ out_l2) {
   constexpr int R = TCH ? 8 : 4, P = TCH ? 8 : 4;
   constexpr int kStateBytes = kRxHdr + R * 114 * 4;
   __shared__ float4 ktab[4][kChunk];
   __shared__ int srcd[4][8];
   const int lane = threadIdx.x & 63, row = lane >> 4, s = lane & 15;
   const int n_blocks = a.n_slots >> 2;
-  const int blk = blockIdx.x * 4 + row;                    // (channel, block) = blk; n_chan * n_blocks < 2^29
+  const int blk = blk0 + blockIdx.x * 4 + row;             // (channel, block) = blk; n_chan * n_blocks < 2^29
   const bool live = blk < a.n_chan * n_blocks;
   const int ch = live ? blk / n_blocks : 0, m = live ? blk - ch * n_blocks : 0;
   const int32_t *idx = a.index + (size_t)ch * a.n_slots;
@@ -743,12 +744,12 @@ __global__ __launch_bounds__(64) void k_fec_rx_stream(RxStream a, const uint8_t 
 // fec:390-405, in the reference's count order) and the new state -- mFER and the rows of mI after the call's last slot.
 // Every position of the state is read and rewritten by the same lane, so the update in place is race-free.
 template <bool TCH>
-__global__ __launch_bounds__(64) void k_fec_rx_fold(RxStream a, uint8_t *state, const uint8_t *__restrict__ status,
+__global__ __launch_bounds__(64) void k_fec_rx_fold(RxStream a, int ch0, uint8_t *state, const uint8_t *__restrict__ status,
                                                     uint8_t *__restrict__ fer_out) {
   constexpr int R = TCH ? 8 : 4, P = TCH ? 8 : 4;
   constexpr int kStateBytes = kRxHdr + R * 114 * 4;
   __shared__ int srcd[16];
-  const int lane = threadIdx.x, ch = blockIdx.x;
+  const int lane = threadIdx.x, ch = ch0 + blockIdx.x;
   const int n_blocks = a.n_slots >> 2, T = a.n_slots;
   const int32_t *idx = a.index + (size_t)ch * a.n_slots;
   const int b0 = TCH ? rx_b0(a, ch) : 0;
@@ -867,18 +868,27 @@ hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_s
   if (n_chan <= 0 || n_slots <= 0) return hipSuccess;
   if (n_slots & 3) return hipErrorInvalidValue;
   const RxStream a = { soft, stride, n_rows, index, tch ? b0 : nullptr, n_chan, n_slots, wire };
-  const long long nblk = (long long)n_chan * (n_slots / 4);
-  const dim3 grid((unsigned)((nblk + 3) / 4)), block(64);
+  // the host allows n_chan * n_blocks < 2^29 code words, 2^27 workgroups of 64: 2^33 work-items, but a dispatch counts its
+  // work-items in 32 bits.  So both kernels go out in slices of at most kRxSlice workgroups (one launch at any bench shape).
+  constexpr long long kRxSlice = 1LL << 24;
+  const long long nblk = (long long)n_chan * (n_slots / 4), ngrp = (nblk + 3) / 4;
+  const dim3 block(64);
   const int id = tch ? TRXSIG_K_FEC_TCH_RX : TRXSIG_K_FEC_XCCH_RX;
   if (prof) prof->begin(id, st);
-  if (tch) k_fec_rx_stream<true><<<grid, block, 0, st>>>(a, state, status, out_tch, out_l2);
-  else k_fec_rx_stream<false><<<grid, block, 0, st>>>(a, state, status, out_tch, out_l2);
+  for (long long g0 = 0; g0 < ngrp; g0 += kRxSlice) {
+    const dim3 grid((unsigned)(ngrp - g0 < kRxSlice ? ngrp - g0 : kRxSlice));
+    if (tch) k_fec_rx_stream<true><<<grid, block, 0, st>>>(a, (int)(4 * g0), state, status, out_tch, out_l2);
+    else k_fec_rx_stream<false><<<grid, block, 0, st>>>(a, (int)(4 * g0), state, status, out_tch, out_l2);
+  }
   if (prof) prof->end(id, st);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (prof) prof->begin(TRXSIG_K_FEC_RX_FOLD, st);
-  if (tch) k_fec_rx_fold<true><<<dim3((unsigned)n_chan), block, 0, st>>>(a, state, status, reinterpret_cast<uint8_t *>(fer));
-  else k_fec_rx_fold<false><<<dim3((unsigned)n_chan), block, 0, st>>>(a, state, status, reinterpret_cast<uint8_t *>(fer));
+  for (long long c0 = 0; c0 < n_chan; c0 += kRxSlice) {
+    const dim3 grid((unsigned)(n_chan - c0 < kRxSlice ? n_chan - c0 : kRxSlice));
+    if (tch) k_fec_rx_fold<true><<<grid, block, 0, st>>>(a, (int)c0, state, status, reinterpret_cast<uint8_t *>(fer));
+    else k_fec_rx_fold<false><<<grid, block, 0, st>>>(a, (int)c0, state, status, reinterpret_cast<uint8_t *>(fer));
+  }
   if (prof) prof->end(TRXSIG_K_FEC_RX_FOLD, st);
   return hipGetLastError();
 }

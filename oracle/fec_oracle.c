@@ -150,6 +150,11 @@ float fo_wire(float v) {
   return (float)(unsigned char)q / 256.0F;
 }
 
+/* fo_wire on n values (the models run it on every burst they take in) */
+void fo_wire_n(const float *v, float *out, int n) {
+  for (int i = 0; i < n; i++) out[i] = fo_wire(v[i]);
+}
+
 static uint64_t peek(const uint8_t *b, int at, int len) {   /* BitVector::peekField (bv:69-78) */
   uint64_t a = 0;
   for (int i = 0; i < len; i++) a = (a << 1) | (b[at + i] & 1u);

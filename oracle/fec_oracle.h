@@ -18,6 +18,7 @@ uint64_t fo_parity(uint64_t coeff, unsigned psize, const uint8_t *bits, int n);
 uint64_t fo_syndrome(uint64_t coeff, unsigned psize, const uint8_t *bits, int n);
 void fo_lsb8msb(uint8_t *bits, int n);
 float fo_wire(float v);
+void fo_wire_n(const float *v, float *out, int n);
 int fo_xcch_decode(const float *i4x114, uint8_t *u228, uint8_t *d184, uint64_t *syn);
 void fo_xcch_encode(const uint8_t *frame23, const uint8_t *tsc26, uint8_t *bursts4x148);
 int fo_rach_decode(const float *e36, uint8_t *u18, unsigned *bsic, unsigned *ra);

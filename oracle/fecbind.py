@@ -21,6 +21,7 @@ class FecOracle:
             getattr(L, n).restype = C.c_uint64
         L.fo_lsb8msb.argtypes = [u8p, C.c_int]
         L.fo_wire.argtypes = [C.c_float]; L.fo_wire.restype = C.c_float
+        L.fo_wire_n.argtypes = [f32p, f32p, C.c_int]
         L.fo_xcch_decode.argtypes = [f32p, u8p, u8p, C.POINTER(C.c_uint64)]
         L.fo_rach_decode.argtypes = [f32p, u8p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
         L.fo_xcch_encode.argtypes = [u8p, u8p, u8p]
@@ -55,7 +56,14 @@ class FecOracle:
         return b
 
     def wire(self, v):
-        return np.array([self.lib.fo_wire(float(x)) for x in np.asarray(v, np.float32).ravel()], np.float32).reshape(np.shape(v))
+        x = np.ascontiguousarray(np.asarray(v, np.float32).ravel())
+        out = np.empty_like(x)
+        self.lib.fo_wire_n(x, out, x.size)
+        return out.reshape(np.shape(v))
+
+    def wire1(self, x):
+        """fo_wire on one value, one call across the binding (the element form wire() is checked against)"""
+        return np.float32(self.lib.fo_wire(float(x)))
 
     def xcch_decode(self, i4x114):
         u = np.zeros(228, np.uint8); d = np.zeros(184, np.uint8); syn = C.c_uint64()

@@ -115,6 +115,24 @@ def test_batch_layout_and_wire(o, golden):
     assert np.array_equal(out[:, 1], g["rach_bsic_out"]) and np.array_equal(out[:, 2], g["rach_ra_out"])
 
 
+def test_wire_on_many_values_is_the_element_form(o):
+    """wire() quantises a whole array in one call; every value equals fo_wire on it alone, at the rounding midpoints, the
+    byte wrap (below 0, above 1) and in random shapes."""
+    rng = np.random.default_rng(5)
+    k = np.arange(-300, 600, dtype=np.float64)
+    mid = ((k + 0.5) / 255.0).astype(np.float32)
+    v = np.concatenate([mid, np.nextafter(mid, np.float32(np.inf)), np.nextafter(mid, np.float32(-np.inf)),
+                        (k / 255.0).astype(np.float32), rng.random(4000).astype(np.float32) * 4 - 2,
+                        np.float32([0.0, -0.0, 1.0, 255.0 / 256.0, 1e-30, -1e-30])])
+    one = np.array([o.wire1(x) for x in v], np.float32)
+    many = o.wire(v)
+    assert many.dtype == np.float32 and np.array_equal(many.view(np.uint32), one.view(np.uint32))
+    m = v[:1200].reshape(3, 400)
+    assert np.array_equal(o.wire(m), one[:1200].reshape(3, 400))
+    assert np.array_equal(o.wire(m[:, ::3]), one[:1200].reshape(3, 400)[:, ::3])
+    assert o.wire(np.float32(0.5)).shape == ()
+
+
 def test_random_vs_reference(o, refs):
     r = refs.fec()
     rng = np.random.default_rng(77)

@@ -379,3 +379,223 @@ def test_fed_from_a_transceiver_group_pull(pkg, t, prims):
     same(g, m, "group pull")
     assert (g["status"] & fsm.TCH_GOOD).any()
     grp.close(); ctx.close()
+
+
+# ---- production scale: the shapes tools/fec_stream_bench.py times, the ragged last workgroup, long gaps, index edges ----
+def long_stream(rng, tx, fo, tch, S, n_total):
+    """S channels x n_total blocks of bursts as one row buffer (rows in shuffled order) and the full index [S, 4 n_total]."""
+    if tch:
+        soft, _, _ = fsm.tch_bursts(rng, tx, S, n_total, noise=0.35, p_junk=0.05)
+    else:
+        soft, _ = fsm.xcch_bursts(rng, fo, S, n_total, noise=0.35)
+    T = 4 * n_total
+    perm = rng.permutation(S * T)
+    rows = soft.reshape(S * T, 148)[perm]
+    inv = np.empty_like(perm); inv[perm] = np.arange(S * T)
+    return rows, inv.reshape(S, T).astype(np.int64)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("tch", [True, False])
+@pytest.mark.parametrize("wire", [True, False])
+def test_production_shape_vs_model(t, tx, prims, tch, wire):
+    """1,024 channels x 16 blocks in one call (the bench's shape), from a state with random rows and FER, with the missing
+    patterns of stream_case and random drops."""
+    rng = np.random.default_rng(400 + 2 * tch + wire)
+    S, n = 1024, 16
+    rows, index = stream_case(rng, tx, prims.fo, tch, S, n, 0.1)
+    b0 = rng.choice([0, 4], S).astype(np.uint8) if tch else None
+    st = np.zeros((S, state_bytes(tch)), np.uint8)
+    st[:, fsm.HDR:] = rng.random((S, (state_bytes(tch) - fsm.HDR) // 4)).astype(np.float32).view(np.uint8)
+    st[:, :4] = rng.random(S).astype(np.float32).reshape(S, 1).view(np.uint8)
+    g = gpu_stream(t, tch, rows, index, st, b0=b0, wire=wire)
+    m = fsm.run(prims, tch, rows, index, st, b0=b0, wire=wire)
+    same(g, m, "production shape")
+    assert S * n == 16384 and (m["status"] & fsm.TCH_GOOD).mean() > 0.5 and not (m["status"] & fsm.DECODED).all()
+
+
+def gap_plan(rng, S, T, calls, P):
+    """Missing-burst gaps of 3..10 periods for most channels: across block and call boundaries, one ending on a closing slot
+    (its last missing slot has B % 4 == 3), one after which the first burst is a closing one, and one channel silent for a
+    whole call.  Returns a bool [S, T * calls] of missing slots and a description for the reach asserts."""
+    Tt = T * calls
+    miss = np.zeros((S, Tt), bool)
+    gaps = []
+    for s in range(S):
+        if s % 5 == 4:
+            continue                                           # some channels without a long gap
+        g = int(rng.integers(3, 11)) * P + int(rng.integers(0, P))
+        if s % 5 == 0:                                         # straddles a call boundary
+            b = T * int(rng.integers(1, calls))
+            lo = b - int(rng.integers(1, g))
+        else:
+            lo = int(rng.integers(0, Tt - g))
+        miss[s, lo:lo + g] = True
+        gaps.append((s, lo, lo + g))
+    s0, s1, s2 = 1, 2, 3
+    e0 = 4 * (T // 4 + 2)                                      # s0: missing up to and including closing slot e0 - 1
+    e1 = 4 * (2 * T // 4 - 1) + 3                              # s1: the first burst after the gap is closing slot e1
+    miss[s0] = False; miss[s0, e0 - 4 * P - 2:e0] = True
+    miss[s1] = False; miss[s1, e1 - 5 * P - 1:e1] = True
+    miss[s2] = False; miss[s2, 2 * T:3 * T] = True             # silent for the whole third call
+    assert (e0 - 1) % 4 == 3 and e1 % 4 == 3
+    gaps += [(s0, e0 - 4 * P - 2, e0), (s1, e1 - 5 * P - 1, e1), (s2, 2 * T, 3 * T)]
+    return miss, gaps
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("tch", [True, False])
+@pytest.mark.parametrize("wire", [True, False])
+def test_long_gaps_over_chained_calls_ragged(t, tx, prims, tch, wire):
+    """255 channels x 9 blocks per call (2,295 code words: the last workgroup holds 3), five chained calls; every channel's
+    bursts missing for 3 to 10 periods somewhere, so rx_source walks back over many periods, into earlier calls' state."""
+    rng = np.random.default_rng(500 + 2 * tch + wire)
+    S, n, calls = 255, 9, 5
+    P, T = (8 if tch else 4), 4 * n
+    assert (S * n) % 4 == 3
+    rows, full = long_stream(rng, tx, prims.fo, tch, S, n * calls)
+    miss, gaps = gap_plan(rng, S, T, calls, P)
+    orig = full.copy()
+    full[miss] = -1
+    full[rng.random(full.shape) < 0.03] = -1
+    (_, _, e0), (_, _, e1) = gaps[-3][:3], gaps[-2][:3]
+    full[1, e0:e0 + 8] = orig[1, e0:e0 + 8]                    # the bursts right after the two marked gaps are present
+    full[2, e1] = orig[2, e1]
+    assert max(hi - lo for _, lo, hi in gaps) >= 10 * P and min(hi - lo for _, lo, hi in gaps) >= 3 * P
+    assert any(lo // T != (hi - 1) // T for _, lo, hi in gaps)                          # a gap crossing a call boundary
+    assert (full[3, 2 * T:3 * T] < 0).all() and (full[3, :2 * T] >= 0).any()
+    b0 = rng.choice([0, 4], S).astype(np.uint8) if tch else None
+    st = np.zeros((S, state_bytes(tch)), np.uint8)
+    mst = st.copy()
+    for c in range(calls):
+        index = full[:, c * T:(c + 1) * T].astype(np.int32)
+        bc = None if b0 is None else ((b0.astype(int) + c * T) % 8).astype(np.uint8)
+        g = gpu_stream(t, tch, rows, index, st, b0=bc, wire=wire)
+        m = fsm.run(prims, tch, rows, index, mst, b0=bc, wire=wire)
+        same(g, m, ("call", c))
+        st, mst = g["state"], m["state"]
+        if c == 2:
+            assert not m["status"][3].any()
+    # the whole stream in one call decodes the same blocks (chaining is invisible)
+    one = gpu_stream(t, tch, rows, full.astype(np.int32), np.zeros_like(st), b0=b0, wire=wire)
+    assert np.array_equal(one["state"], st)
+
+
+@pytest.mark.timeout(300)
+def test_index_edges_and_a_large_soft_buffer(t, tx, prims):
+    """Rows at the end of a soft buffer of more than 2^31 floats (soft_stride 164 > 148), so the row offsets only fit in
+    size_t; indices -1, n_rows, n_rows - 1, INT32_MIN and INT32_MAX in one stream; TCH channels with b0 of 0, 4 and invalid
+    values in the same call; and the XCCH decoder on the same buffer."""
+    import torch
+    stride, n_rows = 164, 13_200_000
+    assert n_rows * stride > 2 ** 31
+    rng = np.random.default_rng(600)
+    S, n = 8, 8
+    T = 4 * n
+    soft, _, _ = fsm.tch_bursts(rng, tx, S, n, noise=0.35, p_junk=0.05)
+    xsoft, _ = fsm.xcch_bursts(rng, prims.fo, S, n, noise=0.35)
+    big = torch.empty((n_rows, stride), dtype=torch.float32, device="cuda")
+    base = n_rows - 2 * S * T                                    # TCH rows then XCCH rows, up to the buffer's last row
+    host = np.concatenate([soft.reshape(S * T, 148), xsoft.reshape(S * T, 148)])
+    pad = rng.random((2 * S * T, stride)).astype(np.float32)
+    pad[:, :148] = host
+    big[base:].copy_(torch.from_numpy(pad))
+    torch.cuda.synchronize()
+    for tch in (True, False):
+        index = (base + (0 if tch else S * T) + np.arange(S * T).reshape(S, T)).astype(np.int64)
+        perm = rng.permutation(S)
+        index = index[perm]
+        index[rng.random((S, T)) < 0.1] = -1
+        edges = [-1, n_rows, n_rows - 1, -2 ** 31, 2 ** 31 - 1]
+        for s in range(S):
+            for k, e in enumerate(edges):
+                index[s, (3 + 5 * k + s) % T] = e
+        index[0, 3::4] = n_rows - 1                               # closing bursts from the very last row
+        index = index.astype(np.int32)
+        b0 = np.array([0, 4, 2, 0, 4, 255, 1, 0], np.uint8) if tch else None
+        st = np.zeros((S, state_bytes(tch)), np.uint8)
+        st[:, fsm.HDR:] = rng.random((S, (state_bytes(tch) - fsm.HDR) // 4)).astype(np.float32).view(np.uint8)
+        g = gpu_stream(t, tch, big, index, st, b0=b0)
+        # the model on the rows the index reaches, renumbered (an index outside [0, n_rows) stays outside)
+        used = np.unique(index[(index >= 0) & (index < n_rows)])
+        rows = big[torch.from_numpy(used.astype(np.int64)).cuda()][:, :148].cpu().numpy()
+        mi = np.full(index.shape, -1, np.int64)
+        ok = (index >= 0) & (index < n_rows)
+        mi[ok] = np.searchsorted(used, index[ok])
+        m = fsm.run(prims, tch, rows, mi, st, b0=b0)
+        same(g, m, ("edges", tch))
+        assert (used >= base).all() and used.max() == n_rows - 1 and int(used.min()) * stride > 2 ** 31
+        assert g["status"][0].all() and (g["status"][0] & fsm.DECODED).all()             # every block closed by row n_rows-1
+        if tch:
+            bad = np.isin(b0, (0, 4), invert=True)
+            assert bad.any() and not g["status"][bad].any() and np.array_equal(g["state"][bad], st[bad])
+            assert (g["status"][~bad] & fsm.DECODED).any()
+    del big
+    torch.cuda.empty_cache()
+
+
+def test_host_refuses_the_kernels_block_limit(t):
+    """k_fec_rx_stream numbers (channel, block) code words in an int and assumes n_chan * n_blocks < 2^29, i.e.
+    n_chan * n_slots < 2^31: the host refuses every factoring that reaches it, before anything is launched."""
+    L, h, EINVAL = t.L, t.h, -1
+    fake = 256                                                      # never dereferenced: the call must fail on its sizes
+    for n_chan, n_slots in ((2 ** 29, 4), (2 ** 27, 16), (2 ** 14, 2 ** 17), (3, 715827884),
+                            (2, 2 ** 30), (2 ** 30, 2 ** 30 - 4), (2 ** 31 - 1, 4)):
+        assert n_chan * n_slots >= 2 ** 31 and n_slots % 4 == 0, (n_chan, n_slots)
+        for tch in (True, False):
+            if tch:
+                r = L.trxsig_fec_tch_decode_stream(h, n_chan, n_slots, fake, 148, 1, fake, None, 1, fake, fake, fake, fake, None)
+            else:
+                r = L.trxsig_fec_xcch_decode_stream(h, n_chan, n_slots, fake, 148, 1, fake, 1, fake, fake, fake, None)
+            assert r == EINVAL, (tch, n_chan, n_slots)
+
+
+@pytest.mark.timeout(600)
+def test_just_under_the_block_limit(t, prims):
+    """The largest kind of call the host accepts: 16,383 XCCH channels x 131,076 slots = 2^31 - 65,540 slots, 536,854,527
+    code words (the last workgroup holds 3, its last code word's number is just under 2^29).  Three channels carry bursts
+    (the first channel's first blocks, one in the middle, the last channel's last blocks, whose code words sit in the final
+    workgroup); every other channel sees none.  Those three equal the model over their whole streams; every other channel
+    reports nothing and keeps its state and FER."""
+    import torch
+    S, T = 16383, 131076
+    nb = T // 4
+    assert 2 ** 31 - 2 ** 17 < S * T < 2 ** 31 and (S * nb) % 4 == 3 and 2 ** 29 - S * nb < 2 ** 20
+    rng = np.random.default_rng(700)
+    xs, _ = fsm.xcch_bursts(rng, prims.fo, 3, 8, noise=0.35)
+    rows = xs.reshape(96, 148)
+    busy = {0: 0, S // 2: T // 2 + 1, S - 1: T - 32}              # channel -> first slot of its 32 bursts
+    index = torch.full((S, T), -1, dtype=torch.int32, device="cuda")
+    hidx = {}
+    for k, (ch, lo) in enumerate(busy.items()):
+        h = np.full(T, -1, np.int32)
+        h[lo:lo + 32] = 32 * k + np.arange(32)
+        h[lo + rng.choice(32, 3, replace=False)] = -1
+        index[ch] = torch.from_numpy(h).cuda()
+        hidx[ch] = h
+    st0 = rng.random((S, fsm.XCCH_STATE_BYTES // 4)).astype(np.float32).view(np.uint8)
+    st0[:, 4:fsm.HDR] = 0
+    st = dev(st0)
+    status = torch.full((S, nb), 0xEE, dtype=torch.uint8, device="cuda")
+    l2 = torch.full((S, nb, 23), 0xEE, dtype=torch.uint8, device="cuda")
+    fer = torch.full((S, nb), float("nan"), dtype=torch.float32, device="cuda")
+    t.fec_xcch_decode_stream(dev(rows), index, st, status, l2, fer=fer)
+    torch.cuda.synchronize()
+    del index
+    quiet = torch.ones(S, dtype=torch.bool, device="cuda")
+    quiet[list(busy)] = False
+    assert int(status.amax(dim=1)[quiet].max()) == 0
+    assert int(l2.view(S, nb * 23).amax(dim=1)[quiet].max()) == 0
+    fer0 = torch.from_numpy(st0[:, :4].copy().view(np.float32)).cuda()
+    assert bool((fer.view(torch.int32) == fer0.view(torch.int32)).all(dim=1)[quiet].all())
+    gst = st.cpu().numpy()
+    q = quiet.cpu().numpy()
+    assert np.array_equal(gst[q], st0[q])
+    for ch, h in hidx.items():
+        m = fsm.run(prims, False, rows, h.reshape(1, T), st0[ch:ch + 1])
+        g = dict(status=status[ch:ch + 1].cpu().numpy(), l2=l2[ch:ch + 1].cpu().numpy(), fer=fer[ch:ch + 1].cpu().numpy(),
+                 state=gst[ch:ch + 1])
+        same(g, m, ("busy channel", ch))
+        assert (m["status"] & fsm.DECODED).sum() >= 5
+    del status, l2, fer
+    torch.cuda.empty_cache()

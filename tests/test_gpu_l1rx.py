@@ -42,7 +42,9 @@ def dev(a):
 class Pull:
     """A trxsig_trxgroup_result built from tensors, and what trxsig_trxgroup_collect would report for it."""
 
-    def __init__(self, pkg, rng, model, fn, F, p_drop=0.15, sps=4):
+    def __init__(self, pkg, rng, model, fn, F, p_drop=0.15, sps=4, phy=None, rach_bsic=None):
+        """phy(rng, n_rows) -> (amp[n_rows, 2], toa[n_rows]) replaces the random amplitudes and TOAs; rach_bsic: access bursts
+        that carry a random RA, every other one with this BSIC, at the RACH positions (else noise)."""
         A = model.A
         T = 8 * F
         bits = {}
@@ -58,6 +60,10 @@ class Pull:
                             fr = rng.integers(0, 256, 23).astype(np.uint8)
                             bits[key] = model.p.fo.xcch_encode(fr, np.zeros(26, np.uint8)).reshape(4, 148)
                         soft[8 * k + tn, a] = fsm.soft_from_bits(rng, bits[key][c.m.reverse(u % HYPER) % 4], 0.3)
+                    elif c is not None and c.cls == ldm.RACH and rach_bsic is not None:
+                        soft[8 * k + tn, a] = rng.random(148).astype(np.float32)
+                        e = rach_e36(model.p.fo, int(rng.integers(0, 256)), rach_bsic if (k + a) % 2 == 0 else rach_bsic ^ 0x2A)
+                        soft[8 * k + tn, a, 49:85] = fsm.soft_from_bits(rng, e, 0.3)
                     else:
                         soft[8 * k + tn, a] = rng.random(148).astype(np.float32)
         present = rng.random((T, A)) >= p_drop
@@ -68,8 +74,11 @@ class Pull:
         rows = rng.random((n_rows, 160)).astype(np.float32)
         rows[row[present], :148] = soft[present]
         valid = (rng.random(n_rows) >= 0.1).astype(np.uint8) * pkg.F_DETECT
-        amp = (rng.standard_normal((n_rows, 2)) * 3000).astype(np.float32)
-        toa = (rng.standard_normal(n_rows) * 3).astype(np.float32)
+        if phy is None:
+            amp = (rng.standard_normal((n_rows, 2)) * 3000).astype(np.float32)
+            toa = (rng.standard_normal(n_rows) * 3).astype(np.float32)
+        else:
+            amp, toa = phy(rng, n_rows)
         self.t = dict(row=dev(row), valid=dev(valid), amp=dev(amp), toa=dev(toa), soft=dev(rows))
         self.res = pkg.TrxGroupResult(n_slots=T, n_arfcn=A, n_rows=n_rows, d_row=self.t["row"].data_ptr(),
                                       d_valid=self.t["valid"].data_ptr(), d_flags=None, d_amp=self.t["amp"].data_ptr(),
@@ -142,13 +151,20 @@ def test_chaining_across_the_wraps(pkg, ctx, prims, fn0):
     A, F = 2, 208
     comb = random_plan(rng, A)
     comb[1, 3] = 1
+    chain_vs_whole(pkg, ctx, prims, rng, comb, fn0, F)
+
+
+def chain_vs_whole(pkg, ctx, prims, rng, comb, fn0, F, n_cuts=4):
+    """One decode of F frames from fn0 against the model, then the same pull decoded in n_cuts + 1 pieces at random frame
+    cuts by a second L1Rx: every block, the final state and the RACH list equal the whole call's."""
+    A = comb.shape[0]
     model = ldm.Model(comb, bsic=7, prims=prims)
     p = Pull(pkg, rng, model, fn0, F)
     whole = pkg.L1Rx(ctx, comb, 7)
     whole.decode(p.res, fn0)
     gw = whole.collect()
     assert_same(gw, model.decode(p.col, fn0), "whole")
-    cuts = [0] + sorted(rng.choice(np.arange(1, F), 4, replace=False).tolist()) + [F]
+    cuts = [0] + sorted(rng.choice(np.arange(1, F), n_cuts, replace=False).tolist()) + [F]
     part = pkg.L1Rx(ctx, comb, 7)
     blocks = {}
     rach = []
@@ -178,6 +194,7 @@ def test_chaining_across_the_wraps(pkg, ctx, prims, fn0):
         assert np.array_equal(g[k], gw[k]), k
     for k in ("fn", "ok", "ra", "rssi", "timing"):
         assert np.array_equal(np.concatenate([r[k] for r in rach]), gw["rach"][k]), k
+    return whole, cuts, gw
 
 
 def test_bad_inputs(pkg, ctx):
@@ -374,4 +391,130 @@ def test_rssi_at_the_floor_boundaries(pkg, ctx):
         db = math.floor(20.0 * math.log10(9450.0 / a))
         assert g["tch_rssi"][c] == ldm.wire_phy(db, 0)[0], (c, mags[c], db)
     assert (g["tch_rssi"] > 0).any() and (g["tch_rssi"] < 0).any()
+    l1.destroy()
+
+
+# ---- production scale: the plan tools/l1rx_bench.py times, a RACH list past one k_l1rx_finish block, the wraps at that
+# scale, and RSSI / TOA values that wrap through the datagram's signed byte and int16 ----
+def big_plan(rng, A):
+    comb = rng.choice(np.array([0, 1, 1, 7], np.uint8), (A, 8))
+    comb[0, 0] = 5
+    return comb
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("wire", [True, False])
+def test_production_plan_over_consecutive_calls(pkg, ctx, prims, wire):
+    """128 ARFCNs x 104 frames (C0T0 combination V, the rest a mix of I, VII and unused slots), some channels closed and one
+    reopened between calls, three consecutive calls."""
+    rng = np.random.default_rng(800 + wire)
+    A, F = 128, 104
+    comb = big_plan(rng, A)
+    model = ldm.Model(comb, bsic=int(rng.integers(0, 64)), band=1800, prims=prims)
+    l1 = pkg.L1Rx(ctx, comb, model.bsic, model.band)
+    closed = {}
+    for cls in (0, 1):
+        closed[cls] = rng.choice(len(model.ch[cls]), len(model.ch[cls]) // 10, replace=False)
+        for i in closed[cls]:
+            l1.close(cls, int(i))
+            model.ch[cls][i].active = False
+    fn = int(rng.integers(0, HYPER - 3 * F))
+    for call in range(3):
+        p = Pull(pkg, rng, model, fn, F, rach_bsic=model.bsic)
+        l1.decode(p.res, fn, wire=wire)
+        g = l1.collect()
+        m = model.decode(p.col, fn, wire=wire)
+        assert_same(g, m, ("call", call))
+        if call == 0:
+            for cls in (0, 1):
+                i = int(closed[cls][0])
+                l1.open(cls, i)
+                model.ch[cls][i].open()
+        fn += F
+    o = l1.out
+    assert o.n_xcch > 256 and o.n_tch > 256 and o.n_xcch == len(model.ch[ldm.XCCH])
+    st = m["xcch"]["status"]
+    assert (st & fsm.TCH_GOOD).any() and (m["tch"]["status"] & fsm.DECODED).any() and m["rach"]["ok"].any()
+    assert (m["xcch"]["power"] != 40).any()
+    l1.destroy()
+
+
+@pytest.mark.timeout(600)
+def test_rach_list_past_one_finish_block(pkg, ctx, prims):
+    """680 frames: the C0T0 RACH positions number more than 256 (rach_cap > 256, so k_l1rx_demux builds its list over many
+    64-position chunks and k_l1rx_finish runs several blocks for it); access bursts at most of them, half with the cell's
+    BSIC."""
+    rng = np.random.default_rng(900)
+    A, F, bsic = 2, 680, 45
+    comb = big_plan(rng, A)
+    model = ldm.Model(comb, bsic=bsic, prims=prims)
+    l1 = pkg.L1Rx(ctx, comb, bsic)
+    fn = 5304 - 77
+    for call in range(2):
+        p = Pull(pkg, rng, model, fn, F, p_drop=0.1, rach_bsic=bsic)
+        l1.decode(p.res, fn)
+        g = l1.collect()
+        m = model.decode(p.col, fn)
+        assert_same(g, m, ("call", call))
+        assert l1.out.rach_cap > 256 and len(m["rach"]["fn"]) > 256
+        assert m["rach"]["ok"].sum() > 100 and not m["rach"]["ok"].all()
+        fn += F
+    l1.destroy()
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("fn0", [5304 * 7 - 61, HYPER - 53])
+def test_chaining_across_the_wraps_at_scale(pkg, ctx, prims, fn0):
+    """128 ARFCNs x 104 frames across the 5304 period / the hyperframe wrap, whole against the model and against six pieces cut
+    at random frames (not block-aligned)."""
+    rng = np.random.default_rng(fn0 % 997)
+    comb = big_plan(rng, 128)
+    whole, cuts, gw = chain_vs_whole(pkg, ctx, prims, rng, comb, fn0, 104, n_cuts=5)
+    wrap = (fn0 // 5304 + 1) * 5304                          # the next 5304 boundary (HYPER is one of them)
+    assert any((fn0 + lo) < wrap < (fn0 + hi) or fn0 + lo == wrap for lo, hi in zip(cuts, cuts[1:]))
+    assert any(c % 4 for c in cuts) and whole.out.n_xcch > 256
+
+
+def wild_phy(rng, n):
+    """amplitudes from 1e-18 to 1e18 (20 log10(9450 / |A|) from about -281 to 439, inside and outside the signed byte),
+    TOAs whose round(toa * 256 / sps) leaves int16 (and sits on its boundary: 32767.5 -> 32768 wraps)"""
+    mag = np.where(rng.random(n) < 0.2, rng.standard_normal(n) * 3000, 10.0 ** rng.uniform(-18, 18, n))
+    ph = rng.uniform(0.2, 1.37, n) + np.pi / 2 * rng.integers(0, 4, n)   # both components >= 0.2 |A|: no subnormal square
+    amp = np.stack([mag * np.cos(ph), mag * np.sin(ph)], 1).astype(np.float32)
+    x = np.where(rng.random(n) < 0.5, rng.standard_normal(n) * 3 * 64, rng.uniform(-4e7, 4e7, n))
+    edge = np.array([32767.4, 32767.5, 32768.0, 32768.5, -32768.4, -32768.5, -32769.0, 65535.5, 65536.5, -65536.5, 127.5, -128.5])
+    x[:len(edge) * 20] = np.tile(edge, 20)
+    toa = (x / 64.0).astype(np.float32)                       # sps = 4: round(toa * 64)
+    return amp, toa
+
+
+def test_rssi_and_toa_wrap_like_the_datagram(pkg, ctx, prims):
+    """RSSI / timing values outside the datagram's ranges on every channel kind (TCH and XCCH per-channel values, RACH list):
+    equal the model, whose narrowing tests/test_l1_demux_model.py checks against the reference's byte path."""
+    rng = np.random.default_rng(1000)
+    A, F = 4, 104
+    comb = big_plan(rng, A)
+    model = ldm.Model(comb, bsic=3, prims=prims)
+    l1 = pkg.L1Rx(ctx, comb, 3)
+    fn = 1234
+    wrapped_db = wrapped_t = 0
+    for call in range(3):
+        p = Pull(pkg, rng, model, fn, F, phy=wild_phy, rach_bsic=3)
+        l1.decode(p.res, fn)
+        g = l1.collect()
+        m = model.decode(p.col, fn)
+        assert_same(g, m, ("call", call))
+        routed = np.zeros_like(p.col["valid"])
+        for k in range(F):
+            for tn in range(8):
+                for a in range(A):
+                    routed[8 * k + tn, a] = model.table[a][tn][((fn + k) % HYPER) % ldm.MAX_MODULUS] is not None
+        on = p.col["valid"] & routed
+        db, tt = p.col["rssi"][on], p.col["timing"][on]
+        wrapped_db += int(((db > 127) | (db < -128)).sum())
+        wrapped_t += int(((tt > 32767) | (tt < -32768)).sum())
+        assert (db > 127).any() and (db < -128).any() and (tt > 32767).any() and (tt < -32768).any()
+        fn += F
+    r = m["rach"]
+    assert wrapped_db > 100 and wrapped_t > 100 and len(r["fn"]) > 0
     l1.destroy()

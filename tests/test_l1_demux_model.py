@@ -90,3 +90,35 @@ def test_wire_phy():
     assert ldm.wire_phy(37, 0) == (-37, 0)
     assert ldm.wire_phy(200, -255) == (56, 0) and ldm.wire_phy(5, -256) == (-5, -1) and ldm.wire_phy(5, 513) == (-5, 2)
     assert ldm.wire_phy(5, 70000) == (-5, 17)                # 70000 & 0xFFFF = 4464; 4464 / 256 = 17.4
+
+
+def datagram_phy(rssi, toa):
+    """The reference's byte path for one burst's RSSI and timing offset, restated step by step: Transceiver::driveReceiveFIFO
+    stores burstString[5] = RSSI (a char: the low byte), burstString[6] = (TOA >> 8) & 0xff, burstString[7] = TOA & 0xff
+    (Transceiver.cpp:663-665); ARFCNManager::driveRx reads RSSI = *(signed char *), timingError = (*(signed char *) << 8) |
+    next byte, and builds RxBurst(..., timingError / 256.0F, -RSSI) whose int parameter truncates the float (TRXManager.cpp:
+    220-233)."""
+    b5 = rssi & 0xFF
+    b6, b7 = (toa >> 8) & 0xFF, toa & 0xFF
+    r = b5 - 256 if b5 >= 128 else b5
+    hi = b6 - 256 if b6 >= 128 else b6
+    te = (hi << 8) | b7
+    q = np.float32(te) / np.float32(256.0)
+    return -r, int(q)                                         # C's float -> int conversion: toward zero
+
+
+def test_wire_narrowing_follows_the_datagram():
+    """ldm.wire_phy (what the model applies to collect()'s RSSI / timing) equals the reference's datagram byte path on values
+    inside and far outside the signed byte and int16: the boundaries, their wraps, and random values."""
+    rng = np.random.default_rng(11)
+    rs = list(range(-700, 700)) + [2 ** 31 - 1, -2 ** 31, 255, 256, -255, -256, 383, -385] + rng.integers(-10 ** 6, 10 ** 6, 2000).tolist()
+    ts = list(range(-1030, 1030)) + [32767, 32768, 32769, -32768, -32769, -32767, 65535, 65536, 65537, -65536, -65537,
+                                     2 ** 31 - 1, -2 ** 31, 98303, -98305] + rng.integers(-4 * 10 ** 7, 4 * 10 ** 7, 4000).tolist()
+    for i, t in enumerate(ts):
+        r = rs[i % len(rs)]
+        assert ldm.wire_phy(r, t) == datagram_phy(r, t), (r, t)
+    for r in rs:
+        assert ldm.wire_phy(r, 0)[0] == datagram_phy(r, 0)[0], r
+    # the signs the wraps produce: 128 dB below full scale reads back as -(-128) = +128, 127 as -127, 32768 / 256 as -128
+    assert ldm.wire_phy(128, 0)[0] == 128 and ldm.wire_phy(127, 0)[0] == -127 and ldm.wire_phy(0, 32768)[1] == -128
+    assert ldm.wire_phy(0, -255)[1] == 0 and ldm.wire_phy(0, -256)[1] == -1 and ldm.wire_phy(0, 65535)[1] == 0
