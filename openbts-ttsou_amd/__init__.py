@@ -997,3 +997,145 @@ class L1Rx:
             r["tch_state"] = get(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
             r["xcch_state"] = get(self.state(L1_XCCH), (X, XCCH_RX_STATE_BYTES), "|u1")
         return r
+
+
+L1_CCCH = 3                                      # the downlink's CCCH class (trxsig_l1tx.h)
+L1TX_STATE_BYTES = 160                           # TRXSIG_L1TX_STATE_BYTES
+L1TX_NONE, L1TX_FCCH, L1TX_SCH, L1TX_BCCH, L1TX_CCCH, L1TX_XCCH, L1TX_TCH, L1TX_IDLE = range(8)   # d_what codes
+
+
+class L1TxIn(C.Structure):
+    """trxsig_l1tx_in"""
+    _fields_ = [(n, C.c_void_p) for n in ("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_ccch_kind",
+                                          "d_ccch_payload")]
+
+
+class L1TxOut(C.Structure):
+    """trxsig_l1tx_out"""
+    _fields_ = [(n, C.c_int) for n in ("n_arfcn", "n_frames", "n_xcch")] + \
+               [(n, C.c_void_p) for n in ("d_bits", "d_what", "d_ms_power", "d_ms_ta")]
+
+
+class L1Tx:
+    """ctypes view of include/trxsig_l1tx.h: per-channel payloads for whole frames -> timed bursts, on the device.
+    comb as for L1Rx; rssi_target is GSM.RSSITarget."""
+
+    def __init__(self, ctx, comb, bsic, band=900, rssi_target=-15.0):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
+        L.trxsig_l1tx_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32, C.c_float]
+        L.trxsig_l1tx_destroy.argtypes = [vp]; L.trxsig_l1tx_destroy.restype = None
+        L.trxsig_l1tx_channels.argtypes = [vp, i32]
+        L.trxsig_l1tx_channel.argtypes = [vp, i32, i32, ip, ip, ip, ip]
+        L.trxsig_l1tx_open.argtypes = [vp, i32, i32]
+        L.trxsig_l1tx_close.argtypes = [vp, i32, i32]
+        L.trxsig_l1tx_set_si.argtypes = [vp, vp]
+        L.trxsig_l1tx_grid.argtypes = [vp, i32, i32, ip, ip, ip]
+        L.trxsig_l1tx_encode.argtypes = [vp, i32, i32, C.POINTER(L1TxIn), vp, C.POINTER(L1TxOut)]
+        L.trxsig_l1tx_datagrams.argtypes = [vp, vp, vp, i32, ip]
+        L.trxsig_l1tx_state.argtypes = [vp, i32, C.POINTER(vp)]
+        self.comb = np.ascontiguousarray(comb, np.uint8)
+        self.h = vp()
+        rc = L.trxsig_l1tx_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band),
+                                  float(rssi_target))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1tx_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self.out = None
+        self._keep = None
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_l1tx_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def channels(self, cls):
+        return self._chk(self.L.trxsig_l1tx_channels(self.h, cls), "trxsig_l1tx_channels")
+
+    def channel(self, cls, chan):
+        """(arfcn, tn, kind, sub) of a channel"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.trxsig_l1tx_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1tx_channel")
+        return tuple(x.value for x in v)
+
+    def open(self, cls, chan):
+        """L1Encoder::open of one TCH / XCCH / CCCH channel (SACCH: orders 40 dBm / TA 0; pending idle fill cancelled)."""
+        self._chk(self.L.trxsig_l1tx_open(self.h, cls, chan), "trxsig_l1tx_open")
+
+    def close(self, cls, chan):
+        """L1Encoder::close: nothing more is sent; the next numFrames positions carry the dummy burst."""
+        self._chk(self.L.trxsig_l1tx_close(self.h, cls, chan), "trxsig_l1tx_close")
+
+    def set_si(self, si):
+        """si: uint8 [4, 23], SI1..SI4."""
+        si = self.np.ascontiguousarray(si, self.np.uint8).reshape(4, 23)
+        self._chk(self.L.trxsig_l1tx_set_si(self.h, si.ctypes.data), "trxsig_l1tx_set_si")
+
+    def grid(self, fn, n_frames):
+        """(nb_tch, nb_xcch, nb_ccch) of a call"""
+        v = [C.c_int() for _ in range(3)]
+        self._chk(self.L.trxsig_l1tx_grid(self.h, int(fn), int(n_frames), *[C.byref(x) for x in v]), "trxsig_l1tx_grid")
+        return tuple(x.value for x in v)
+
+    def encode(self, fn, n_frames, tch_kind=None, tch_payload=None, xcch_kind=None, xcch_payload=None, ccch_kind=None,
+               ccch_payload=None, sibling=None):
+        """Grids as torch uint8 tensors on the context's device (or None for a class without channels)."""
+        ins = L1TxIn()
+        keep = (tch_kind, tch_payload, xcch_kind, xcch_payload, ccch_kind, ccch_payload)
+        for name, t in zip(("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_ccch_kind", "d_ccch_payload"), keep):
+            if t is not None:
+                assert t.is_contiguous() and t.dtype.itemsize == 1
+                setattr(ins, name, t.data_ptr() if t.numel() else 1)
+        out = L1TxOut()
+        self._chk(self.L.trxsig_l1tx_encode(self.h, int(fn), int(n_frames), C.byref(ins), sibling.h if sibling is not None else None,
+                                            C.byref(out)), "trxsig_l1tx_encode")
+        self._keep = keep
+        self.out = out
+        return out
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._chk(self.L.trxsig_l1tx_state(self.h, cls, C.byref(p)), "trxsig_l1tx_state")
+        return p.value
+
+    def collect(self, state=True):
+        """The last encode's outputs as host numpy arrays (synchronises the context's stream)."""
+        import torch
+        from .frontend import _DevView
+        np, o = self.np, self.out
+        self.ctx.synchronize()
+
+        def get(p, shape, ts):
+            if p is None or int(np.prod(shape)) == 0:
+                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32, "<f4": np.float32}[ts])
+            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        A, F, X = o.n_arfcn, o.n_frames, o.n_xcch
+        r = dict(bits=get(o.d_bits, (A, 8 * F, 148), "|u1"), what=get(o.d_what, (A, 8 * F), "|u1"),
+                 ms_power=get(o.d_ms_power, (X,), "<i4"), ms_ta=get(o.d_ms_ta, (X,), "<f4"))
+        if state:
+            for cls, key in ((L1_TCH, "tch_state"), (L1_XCCH, "xcch_state"), (L1_CCCH, "ccch_state")):
+                r[key] = get(self.state(cls), (self.channels(cls), L1TX_STATE_BYTES), "|u1")
+        return r
+
+    def datagrams(self, cap=None):
+        """(datagrams uint8 [n, 154], arfcn int32 [n]) of the last encode's non-empty slots, in (FN, TN, ARFCN) order."""
+        np = self.np
+        n = C.c_int()
+        if cap is None:
+            o = self.out
+            cap = o.n_arfcn * 8 * o.n_frames
+        d = np.zeros((max(cap, 1), 154), np.uint8); a = np.zeros(max(cap, 1), np.int32)
+        self._chk(self.L.trxsig_l1tx_datagrams(self.h, d.ctypes.data, a.ctypes.data, int(cap), C.byref(n)), "trxsig_l1tx_datagrams")
+        return d[:n.value], a[:n.value]

@@ -20,7 +20,7 @@
 #include "trxsig_tablegen.h"
 
 // kernel ids the profiler knows: the TRXSIG_K_COUNT of ABI 2, then the ones appended since (trxsig.h)
-constexpr int kKernels = TRXSIG_K_L1RX_FINISH + 1;
+constexpr int kKernels = TRXSIG_K_L1TX_COMMIT + 1;
 
 struct EventProfiler : TrxProfiler {
   struct Rec { int id; hipEvent_t a, b; };
@@ -1166,7 +1166,8 @@ const char *trxsig_kernel_name(int id) {
                                                "k_modulate", "k_resample", "k_eq_detect", "k_convert", "k_normal_fused", "k_fec_viterbi",
                                                "k_normal_chain", "k_eq_delay", "k_eq_dfe", "k_group_replay",
                                                "k_fec_tch_encode", "k_fec_sch_encode", "k_fec_rx_stream_tch",
-                                               "k_fec_rx_stream_xcch", "k_fec_rx_fold", "k_l1rx_demux", "k_l1rx_finish" };
+                                               "k_fec_rx_stream_xcch", "k_fec_rx_fold", "k_l1rx_demux", "k_l1rx_finish",
+                                               "k_l1tx_encode", "k_l1tx_mux", "k_l1tx_datagrams", "k_l1tx_commit" };
   return (id >= 0 && id < kKernels) ? names[id] : "?";
 }
 int trxsig_fec_xcch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n_blocks, int wire,
@@ -1212,6 +1213,10 @@ int alloc_tch_filler(trxsig_ctx *c) {
   return TRXSIG_OK;
 }
 }  // namespace
+const uint8_t *trx_ctx_tch_filler(trxsig_ctx *c) {
+  TrxDeviceGuard g(c->device);
+  return alloc_tch_filler(c) == TRXSIG_OK ? c->d_tch_filler : nullptr;
+}
 int trxsig_fec_xcch_encode_batch(trxsig_ctx *c, const uint8_t *d_frames, int n_blocks, int tsc, uint8_t *d_bits) {
   if (!c) return TRXSIG_EINVAL;
   if (n_blocks < 0 || tsc < 0 || tsc > 7 || (n_blocks > 0 && (!d_frames || !d_bits)))

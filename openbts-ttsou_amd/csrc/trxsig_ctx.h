@@ -135,6 +135,8 @@ struct TrxPinRing {
   }
 };
 TrxProfiler *trx_ctx_profiler(trxsig_ctx *c);
+// the context's TCH filler c[456] on the device (allocated, all zero, on first use; trxsig_fec_tch_set_filler), or null
+extern "C" const uint8_t *trx_ctx_tch_filler(trxsig_ctx *c);   // defined in trxsig_api.cpp's C block
 // the normal-burst leg on bursts computed from the raw int16 stream (trxsig_rxfe_push_detect_demod_normal)
 // (on != nullptr: launched on that stream instead of the context's; the caller orders it against the context's stream)
 int trx_ctx_rx_normal(trxsig_ctx *c, const TrxRxGen &gen, int B, int tsc, float detect_thresh, float energy_thresh, uint8_t *d_flags,

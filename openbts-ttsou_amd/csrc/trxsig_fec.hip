@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "trxsig_fec_enc.h"
 #include "trxsig_launch.h"
 
 namespace {
@@ -26,20 +27,6 @@ namespace {
 constexpr int kDeferral = 24;                              // 6*mOrder (bh:138)
 constexpr int kChunk = 64;                                 // trellis steps per table refill (8 positions per lane)
 
-// coder output for the 5-bit input history idx: generator 0x19 in bit 1, 0x1b in bit 0 (bv:306-330),
-// two bits per entry, 32 entries
-constexpr unsigned apply_poly(unsigned val, unsigned poly) {
-  unsigned prod = val & poly, sum = prod;
-  for (unsigned i = 1; i < 5; i++) sum ^= prod >> i;
-  return sum & 1u;
-}
-constexpr unsigned long long gen_table() {
-  unsigned long long t = 0;
-  for (unsigned idx = 0; idx < 32; idx++)
-    t |= (unsigned long long)((apply_poly(idx, 0x19) << 1) | apply_poly(idx, 0x1b)) << (2 * idx);
-  return t;
-}
-constexpr unsigned long long kGen = gen_table();
 
 // The syndrome / parity registers are linear over GF(2) (they start from zero), so the word for a
 // bit string is the XOR of the words of its set bits.  XcchSyn::v[i] = syndromeShift response
@@ -71,21 +58,6 @@ struct RachPar {
     }
   }
 };
-struct TchPar {                                            // encoderShift response, 50 bits, generator 0x0b (3 bits)
-  unsigned v[50];
-  constexpr TchPar() : v() {
-    for (int i = 0; i < 50; i++) {
-      unsigned st = 0;
-      for (int k = 0; k < 50; k++) {
-        const unsigned fb = ((st >> 2) ^ (k == i ? 1u : 0u)) & 1u;
-        st <<= 1;
-        if (fb) st ^= 0x0bu;
-      }
-      v[i] = st & 7u;
-    }
-  }
-};
-__device__ __constant__ const TchPar kTchPar;
 __device__ __constant__ const XcchSyn kXcchSyn;
 __device__ __constant__ const RachPar kRachPar;
 
@@ -94,11 +66,6 @@ __device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
 
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the soft value as the GSM side sees it after the UDP hop
 __device__ __forceinline__ float wire_value(float v) {
@@ -324,19 +291,6 @@ __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ so
 // every burst: zero tails, both stealing flags set (fec:713-717) and the training sequence at 61..86.
 // All integer work; the parity word uses the register's GF(2) linearity (XOR of unit responses).
 // ---------------------------------------------------------------------------------------------
-struct XcchPar {                                           // encoderShift response (bh:80-85) to a 1 at position i of 184
-  unsigned long long v[184];
-  constexpr XcchPar() : v() {
-    unsigned long long st = 0x10004820009ULL & ((1ULL << 40) - 1);   // the bit just went in: fb = 1, state = coeff
-    for (int i = 183; i >= 0; i--) {
-      v[i] = st & ((1ULL << 40) - 1);
-      const unsigned long long fb = (st >> 39) & 1ULL;     // one more zero behind it
-      st <<= 1;
-      if (fb) st ^= 0x10004820009ULL;
-    }
-  }
-};
-__device__ __constant__ const XcchPar kXcchPar;
 
 __global__ __launch_bounds__(64) void k_fec_xcch_encode(const uint8_t *__restrict__ frames, int nblk,
                                                         const uint8_t *__restrict__ tsc_bits /* 26 */, uint8_t *__restrict__ bits) {
@@ -397,72 +351,7 @@ __global__ __launch_bounds__(64) void k_fec_xcch_encode(const uint8_t *__restric
 // filler = the caller's c[] (fec:1346-1350), any other kind = zeros.  The output is gathered: each lane forms 16
 // consecutive bytes of the block's 592 through an inverse interleaver table and stores them at once.
 // ---------------------------------------------------------------------------------------------
-struct TchInv {                                            // (burst b, e-bit j) -> k; j even: c_m[k], j odd: c_{m-1}[k]
-  uint16_t k[4][114];
-  constexpr TchInv() : k() {
-    for (int c = 0; c < 456; c++) k[(c % 8) & 3][2 * ((49 * c) % 57) + ((c % 8) / 4)] = (uint16_t)c;
-  }
-};
-__device__ __constant__ const TchInv kTchInv;
 
-enum { TCH_FILLER = 0, TCH_SPEECH = 1, TCH_FACCH = 2 };
-constexpr int kTchState = 32;                              // TRXSIG_TCH_TX_STATE_BYTES
-constexpr int kTchOddBytes = 29;                           // 228 bits of c[k], k mod 8 >= 4, bit i = (byte i/8 >> i%8) & 1
-
-// c[456] of one block into LDS (one byte per bit); the whole wave calls it with the same kind.  pl: the block's 33
-// payload octets (global), u: 232 bytes of LDS scratch.
-__device__ void tch_form_c(int kind, const uint8_t *__restrict__ pl, const uint8_t *__restrict__ filler, uint8_t *u,
-                           uint8_t *c, uint8_t *pls, int lane) {
-  if (kind == TCH_SPEECH || kind == TCH_FACCH) {
-    if (lane < 33) pls[lane] = pl[lane];
-    wave_fence();
-  }
-  if (kind == TCH_SPEECH) {
-    auto dq = [&](int q) { return (unsigned)(pls[q >> 3] >> (7 - (q & 7))) & 1u; };   // d[q], octets MSB first
-    unsigned par = (lane < 50 && dq(lane)) ? kTchPar.v[lane] : 0u;                     // encoderShift over d[0..50)
-    for (int m = 1; m < 64; m <<= 1) par ^= (unsigned)__shfl_xor((int)par, m, 64);
-    par = ~par & 7u;                                                                   // writeParityWord inverts (bv:413)
-    for (int i = lane; i < 189; i += 64) {
-      unsigned v = 0;
-      if (i <= 90) v = dq(2 * i);                                                      // u[k] = d[2k]
-      else if (i <= 93) v = (par >> (93 - i)) & 1u;                                    // u[91..93] = parity, MSB first
-      else if (i <= 184) v = dq(2 * (184 - i) + 1);                                    // u[184-k] = d[2k+1]
-      u[i] = (uint8_t)v;                                                               // u[185..188] = 0
-    }
-    for (int i = lane; i < 78; i += 64) c[378 + i] = (uint8_t)dq(182 + i);             // class 2 copied
-    wave_fence();
-    for (int k = lane; k < 189; k += 64) {
-      unsigned idx = 0;
-      for (int h = 0; h < 5; h++) idx |= (k - h >= 0 ? (unsigned)u[k - h] : 0u) << h;
-      const unsigned g = (unsigned)(kGen >> (2 * idx)) & 3u;
-      c[2 * k] = (uint8_t)(g >> 1); c[2 * k + 1] = (uint8_t)(g & 1u);
-    }
-  } else if (kind == TCH_FACCH) {
-    // d[] = the L2 frame after LSB8MSB: u[8o + b] = bit b of octet o; 40 inverted Fire parity bits; 4 zero tail bits
-    unsigned long long par = 0;
-    for (int i = lane; i < 184; i += 64)
-      if ((pls[i >> 3] >> (i & 7)) & 1u) par ^= kXcchPar.v[i];
-    unsigned lo = (unsigned)par, hi = (unsigned)(par >> 32);
-    for (int m = 1; m < 64; m <<= 1) { lo ^= (unsigned)__shfl_xor((int)lo, m, 64); hi ^= (unsigned)__shfl_xor((int)hi, m, 64); }
-    const unsigned long long pw = ~(((unsigned long long)hi << 32) | lo) & ((1ULL << 40) - 1);
-    for (int i = lane; i < 228; i += 64) {
-      unsigned v = 0;
-      if (i < 184) v = (pls[i >> 3] >> (i & 7)) & 1u;
-      else if (i < 224) v = (unsigned)(pw >> (39 - (i - 184))) & 1u;
-      u[i] = (uint8_t)v;
-    }
-    wave_fence();
-    for (int k = lane; k < 228; k += 64) {
-      unsigned idx = 0;
-      for (int h = 0; h < 5; h++) idx |= (k - h >= 0 ? (unsigned)u[k - h] : 0u) << h;
-      const unsigned g = (unsigned)(kGen >> (2 * idx)) & 3u;
-      c[2 * k] = (uint8_t)(g >> 1); c[2 * k + 1] = (uint8_t)(g & 1u);
-    }
-  } else {
-    for (int i = lane; i < 456; i += 64) c[i] = kind == TCH_FILLER ? (uint8_t)(filler[i] & 1u) : (uint8_t)0;
-  }
-  wave_fence();
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(64) void k_fec_tch_encode(int n_blocks, const uint8_t *__restrict__ kinds,

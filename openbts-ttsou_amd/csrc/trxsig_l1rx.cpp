@@ -36,11 +36,13 @@ struct trxsig_l1rx {
   int A = 0, bsic = 0, band = 0;
   int n_tch = 0, n_xcch = 0, n_rach = 0;
   std::vector<int32_t> chinfo;         // host copy: arfcn | tn << 16 | map << 20
+  std::vector<uint8_t> comb;           // the plan, [A * 8]
   bool map_used[2][TRX_N_MAPS] = {};   // [TCH, XCCH]
   // persistent device state
   void *d_persist = nullptr;
   uint8_t *d_tch_state = nullptr, *d_xcch_state = nullptr, *d_active = nullptr;
   int32_t *d_chinfo = nullptr, *d_rssi = nullptr, *d_timing = nullptr, *d_power = nullptr, *d_ta = nullptr;
+  uint32_t *d_accepted = nullptr;
   // per-call workspace
   void *d_work = nullptr;
   size_t work_bytes = 0;
@@ -161,15 +163,15 @@ int trxsig_l1rx_create(trxsig_l1rx **out, trxsig_ctx *c, int n_arfcn, const uint
     map_kind(xcch[i] >> 20, &kind, &sub);
     if (kind == TRXSIG_L1_SACCH_TF || kind == TRXSIG_L1_SACCH_C8 || kind == TRXSIG_L1_SACCH_C4) { power[i] = 40; ta[i] = 0; }
   }
-  const size_t sz[] = { T * TRXSIG_TCH_RX_STATE_BYTES, X * TRXSIG_XCCH_RX_STATE_BYTES, N, N * 4, N * 4, N * 4, X * 4, X * 4 };
-  size_t off[8], total = 0;
-  for (int i = 0; i < 8; i++) { off[i] = total; total += al(sz[i]); }
+  const size_t sz[] = { T * TRXSIG_TCH_RX_STATE_BYTES, X * TRXSIG_XCCH_RX_STATE_BYTES, N, N * 4, N * 4, N * 4, X * 4, X * 4, N * 4 };
+  size_t off[9], total = 0;
+  for (int i = 0; i < 9; i++) { off[i] = total; total += al(sz[i]); }
   TrxDeviceGuard g(trxsig_device(c));
   if (hipMalloc(&l1->d_persist, total) != hipSuccess) { delete l1; return trx_ctx_fail(c, TRXSIG_ENOMEM, "trxsig_l1rx_create: device allocation", hipSuccess); }
   char *b = (char *)l1->d_persist;
   l1->d_tch_state = (uint8_t *)(b + off[0]); l1->d_xcch_state = (uint8_t *)(b + off[1]); l1->d_active = (uint8_t *)(b + off[2]);
   l1->d_chinfo = (int32_t *)(b + off[3]); l1->d_rssi = (int32_t *)(b + off[4]); l1->d_timing = (int32_t *)(b + off[5]);
-  l1->d_power = (int32_t *)(b + off[6]); l1->d_ta = (int32_t *)(b + off[7]);
+  l1->d_power = (int32_t *)(b + off[6]); l1->d_ta = (int32_t *)(b + off[7]); l1->d_accepted = (uint32_t *)(b + off[8]);
   std::vector<uint8_t> ones(N, 1);
   hipError_t e = hipMemset(l1->d_persist, 0, total);
   if (e == hipSuccess && N) e = hipMemcpy(l1->d_active, ones.data(), N, hipMemcpyHostToDevice);
@@ -183,7 +185,8 @@ int trxsig_l1rx_create(trxsig_l1rx **out, trxsig_ctx *c, int n_arfcn, const uint
   }
   TrxL1rxDev &d = l1->dv;
   d.chinfo = l1->d_chinfo; d.active = l1->d_active; d.rssi = l1->d_rssi; d.timing = l1->d_timing;
-  d.ms_power = l1->d_power; d.ms_ta = l1->d_ta; d.bsic = bsic;
+  d.ms_power = l1->d_power; d.ms_ta = l1->d_ta; d.accepted = l1->d_accepted; d.bsic = bsic;
+  l1->comb.assign(h_comb, h_comb + 8 * (size_t)n_arfcn);
   trx_ctx_retain(c);
   *out = l1;
   return TRXSIG_OK;
@@ -275,4 +278,10 @@ int trxsig_l1rx_decode(trxsig_l1rx *l1, const trxsig_trxgroup_result *res, int f
   out->d_tch_rssi = d.rssi; out->d_tch_timing = d.timing; out->d_xcch_rssi = d.rssi + k.n_tch; out->d_xcch_timing = d.timing + k.n_tch;
   out->d_ms_power = d.ms_power; out->d_ms_ta = d.ms_ta;
   return TRXSIG_OK;
+}
+
+void trx_l1rx_sibling(const trxsig_l1rx *l1, TrxL1rxSib *o) {
+  o->n_arfcn = l1->A; o->n_tch = l1->n_tch; o->n_xcch = l1->n_xcch; o->comb = l1->comb.data();
+  o->rssi = l1->d_rssi + l1->n_tch; o->timing = l1->d_timing + l1->n_tch; o->power = l1->d_power; o->ta = l1->d_ta;
+  o->accepted = l1->d_accepted + l1->n_tch;
 }

@@ -92,6 +92,7 @@ __global__ __launch_bounds__(256) void k_l1rx_demux(TrxL1rxCall c, TrxL1rxDev d,
   const long long q0 = 4LL * c.blk_first[m];
   const bool act = d.active[ch] != 0;
   int last = -1;
+  unsigned n_acc = 0;
   for (int s0 = 0; s0 < T; s0 += 64) {
     const int s = s0 + lane;
     int r = -1;
@@ -100,9 +101,11 @@ __global__ __launch_bounds__(256) void k_l1rx_demux(TrxL1rxCall c, TrxL1rxDev d,
       idx[s] = r;
     }
     const unsigned long long bal = __ballot(r >= 0);
+    n_acc += (unsigned)__popcll(bal);
     if (bal) last = __shfl(r, 63 - __clzll((long long)bal));
   }
   if (lane == 0 && last >= 0) burst_phy(amp, toa, last, c.sps, &d.rssi[ch], &d.timing[ch]);
+  if (lane == 0 && n_acc) d.accepted[ch] += n_acc;
   if (tch && lane == 0) d.tch_b0[ci] = (uint8_t)(((q0 % 8) + 8) % 8);
   int32_t *fno = (tch ? d.tch_fn : d.xcch_fn) + (size_t)ci * nb;
   for (int b = lane; b < nb; b += 64) fno[b] = (int32_t)(trx_map_frame(M, q0 + 4LL * b + 3) % kTrxHyperframe);

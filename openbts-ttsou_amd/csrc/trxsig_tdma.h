@@ -91,6 +91,7 @@ struct TrxL1rxDev {
   float *rach_soft;                // [rach_cap][148] gathered rows
   int32_t *rach_fn, *rach_arfcn, *rach_rssi, *rach_timing, *rach_count;
   uint8_t *rach_tail, *rach_bsic, *rach_ra, *rach_ok;
+  uint32_t *accepted;              // [n_all]: bursts each channel has accepted since create (the downlink's phyNew, trxsig_l1tx)
   int bsic;
 };
 
@@ -101,3 +102,100 @@ hipError_t trx_launch_l1rx_finish(hipStream_t st, const TrxL1rxCall &call, const
 // and, where `sacch`, power 40 / TA 0 (ms_power / ms_ta, unused otherwise)
 hipError_t trx_launch_l1rx_set(hipStream_t st, uint8_t *active, int ch, int open, uint8_t *state_fer, int32_t *ms_power,
                                int32_t *ms_ta, int sacch);
+
+// ---- the downlink (trxsig_l1tx.h) ----------------------------------------------------------------------------------------
+// GSM/GSMTDMA.cpp's downlink TDMAMapping tables: the *D tables of SDCCH/8, SACCH/C8, SDCCH/4 and SACCH/C4, FACCH_TCHF and
+// SACCH_TF_Tn (which serve both directions), and combination V's beacon: CCCH_0..2, BCCH, SCH, FCCH.  Ids 0..32 name the same
+// logical channels as the uplink ids above (TRX_MAP_TCHF .. TRX_MAP_SACCH_C4 + 3); positions are numbered as above.
+// tests/golden/tdma_downlink.npz records the same tables for the CPU model (tests/l1_mux_model.py).
+enum {
+  TRX_DL_CCCH = 33,            // + sub-channel: CCCH_0..2
+  TRX_DL_BCCH = 36,
+  TRX_DL_SCH = 37,
+  TRX_DL_FCCH = 38,
+  TRX_N_DL_MAPS = 39
+};
+
+#define TRX_M5(R, a, b, c, d, e) { R, 5, { a, b, c, d, e } }
+#define TRX_TDMA_DL_MAPS_INIT                                                                                                \
+  {                                                                                                                          \
+    { 26, 24, { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24 } },                    \
+    TRX_M4(104, 12, 38, 64, 90), TRX_M4(104, 25, 51, 77, 103), TRX_M4(104, 38, 64, 90, 12), TRX_M4(104, 51, 77, 103, 25),  \
+    TRX_M4(104, 64, 90, 12, 38), TRX_M4(104, 77, 103, 25, 51), TRX_M4(104, 90, 12, 38, 64), TRX_M4(104, 103, 25, 51, 77),  \
+    TRX_M4(51, 0, 1, 2, 3), TRX_M4(51, 4, 5, 6, 7), TRX_M4(51, 8, 9, 10, 11), TRX_M4(51, 12, 13, 14, 15),                  \
+    TRX_M4(51, 16, 17, 18, 19), TRX_M4(51, 20, 21, 22, 23), TRX_M4(51, 24, 25, 26, 27), TRX_M4(51, 28, 29, 30, 31),        \
+    TRX_M4(102, 32, 33, 34, 35), TRX_M4(102, 36, 37, 38, 39), TRX_M4(102, 40, 41, 42, 43), TRX_M4(102, 44, 45, 46, 47),    \
+    TRX_M4(102, 83, 84, 85, 86), TRX_M4(102, 87, 88, 89, 90), TRX_M4(102, 91, 92, 93, 94), TRX_M4(102, 95, 96, 97, 98),    \
+    TRX_M4(51, 22, 23, 24, 25), TRX_M4(51, 26, 27, 28, 29), TRX_M4(51, 32, 33, 34, 35), TRX_M4(51, 36, 37, 38, 39),        \
+    TRX_M4(102, 42, 43, 44, 45), TRX_M4(102, 46, 47, 48, 49), TRX_M4(102, 93, 94, 95, 96), TRX_M4(102, 97, 98, 99, 100),   \
+    TRX_M4(51, 6, 7, 8, 9), TRX_M4(51, 12, 13, 14, 15), TRX_M4(51, 16, 17, 18, 19), TRX_M4(51, 2, 3, 4, 5),                \
+    TRX_M5(51, 1, 11, 21, 31, 41), TRX_M5(51, 0, 10, 20, 30, 40)                                                           \
+  }
+
+// what one encode needs of its call (by value).  Per mapping m: p_first = the first position at or after fn, p_end = the
+// first position at or after fn + n_frames, base = p_first minus the mapping's positions in frames [fn - fn % R, fn) -- so
+// the frame fn + k, k = q * R + rem - fn % R, is position base + n * q + cnt[m][rem] (cnt: the host's table of frames below
+// rem), no division by a variable.
+struct TrxL1txCall {
+  int fn, n_frames, n_arfcn, n_tch, n_xcch, n_ccch, n_bcch, n_all;
+  int nb[4];                         // per class (TCH, XCCH, CCCH, BCCH): the most blocks any channel opens
+  long long unit0[4];                // per class: the first scratch unit ([n_chan][nb] after it)
+  int r104, r102, r51, r26;          // fn mod 104 / 102 / 51 / 26
+  int cur, has_sib, band, bsic;
+  float rssi_target;
+  long long p_first[TRX_N_DL_MAPS], p_end[TRX_N_DL_MAPS], base[TRX_N_DL_MAPS];
+};
+
+// a channel's record in the object (two copies: the call reads copy `cur`, the mux writes copy `cur ^ 1`)
+struct TrxL1txChan {
+  uint32_t last_c[16];               // c[456] of the last block the channel encoded, bit i = word i/32 bit i%32
+  uint32_t prev_c[16];               // ... and of the one before it (TCH: the odd half interleaves into the next block)
+  uint8_t last_f, prev_f;            // their FACCH flags
+  uint8_t pend;                      // the last block's last burst lies after the last call: its tail goes out next
+  uint8_t active;
+  int32_t idle_left;                 // dummy bursts still to send (close)
+  int32_t ord_pow;                   // SACCH orders (dBm), -1 on channels that are not SACCH
+  float ord_ta;
+  uint32_t seen;                     // the sibling's accepted-burst count when the orders were last decided
+  uint32_t pad[3];
+};
+static_assert(sizeof(TrxL1txChan) == 160, "TrxL1txChan layout");
+
+struct TrxL1txDev {
+  const int32_t *chinfo;             // [n_all]: arfcn | tn << 16 | map << 20
+  const int32_t *slot;               // [n_arfcn * 8]: combination | the slot's TCH channel << 4
+  const int32_t *slot_x;             // [n_arfcn * 8]: the slot's first XCCH channel (index over all classes)
+  const int8_t *writer;              // [3][8][104]: the mapping that owns (combination I / V / VII, TN, fn mod 104 or 102)
+  const int16_t *cnt;                // [TRX_N_DL_MAPS][105]
+  TrxL1txChan *st;                   // [2][n_all]
+  uint32_t *c;                       // scratch [units][16]
+  uint8_t *flag;                     // scratch [units]: 1 encoded, 2 FACCH
+  const uint8_t *kind[3], *payload[3];   // TCH / XCCH / CCCH grids
+  const uint8_t *si;                 // [4][23] + [92] = 1 once set
+  const uint8_t *filler;             // the context's TCH filler c[456]
+  int32_t *ord_pow;                  // [n_xcch] out
+  float *ord_ta;                     // [n_xcch] out
+  uint8_t *bits, *what;              // [n_arfcn][8 F][148], [n_arfcn][8 F]
+  // sibling (trxsig_l1rx) device state, or null
+  const int32_t *sib_rssi, *sib_timing, *sib_power, *sib_ta;   // XCCH-indexed
+  const uint32_t *sib_count;         // XCCH-indexed accepted-burst counters
+};
+
+// what trxsig_l1tx reads of a sibling trxsig_l1rx (trxsig_l1rx.cpp): its plan and its XCCH channels' device state
+struct trxsig_l1rx;
+struct TrxL1rxSib {
+  int n_arfcn, n_tch, n_xcch;
+  const uint8_t *comb;               // [n_arfcn * 8] (host)
+  const int32_t *rssi, *timing, *power, *ta;   // XCCH-indexed device arrays
+  const uint32_t *accepted;          // XCCH-indexed
+};
+void trx_l1rx_sibling(const trxsig_l1rx *l1, TrxL1rxSib *out);
+
+hipError_t trx_launch_l1tx_encode(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);
+hipError_t trx_launch_l1tx_mux(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);
+// open (1) / close (0) of global channel ch on copy `cur`: open sets active, cancels idle fill and, where sacch, orders 40 / 0;
+// close clears active and queues idle_fill dummy bursts
+hipError_t trx_launch_l1tx_set(hipStream_t st, TrxL1txChan *rec, int open, int sacch, int idle_fill);
+// compaction of the slots d_what != 0 into datagrams, in (FN, TN, ARFCN) order: counts [n_wg], then the datagrams
+hipError_t trx_launch_l1tx_dgram(hipStream_t st, const uint8_t *what, const uint8_t *bits, int n_arfcn, int n_frames, int fn,
+                                 int32_t *wg_count, int32_t *total, uint8_t *dgram, int32_t *arfcn, int cap, TrxProfiler *prof);

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "trxsig_bursts.h"
 #include "trxsig_ctx.h"
 #include "trxsig_transceiver.h"
 #include "trxsig_trxstate.h"
@@ -37,10 +38,7 @@ bool time_less(const Time &a, const Time &b) { return a.fn == b.fn ? a.tn < b.tn
 bool time_equal(const Time &a, const Time &b) { return a.fn == b.fn && a.tn == b.tn; }
 int time_minus(const Time &a, const Time &b) { return fn_delta(a.fn, b.fn); }        // operator-(Time): frames
 
-// the dummy burst of GSM 05.02 5.2.6 (gDummyBurst, GSM/GSMCommon.cpp)
-const char kDummyBurst[149] =
-    "0001111101101110110000010100100111000001001000100000001111100011100010111000101110001010111010010100"
-    "011001100111001111010011111000100101111101010000";
+const char kDummyBurst[149] = TRX_DUMMY_BURST_BITS;   // trxsig_bursts.h
 
 bool time_greater(const Time &a, const Time &b) { return a.fn == b.fn ? a.tn > b.tn : fn_compare(a.fn, b.fn) > 0; }   // GSMCommon.h:431-435
 Time time_plus(const Time &a, const Time &b) {               // Time::operator+(const Time&) (GSMCommon.h:405-410)
