@@ -561,6 +561,8 @@ enum { TRXSIG_K_FEC_TCH_ENC = 15, TRXSIG_K_FEC_SCH_ENC = 16, TRXSIG_K_FEC_TCH_RX
 enum { TRXSIG_K_L1RX_DEMUX = 20, TRXSIG_K_L1RX_FINISH = 21 };
 /* the downlink L1 multiplexer's (trxsig_l1tx.h): k_l1tx_encode, k_l1tx_mux, the datagram compaction, k_l1tx_commit */
 enum { TRXSIG_K_L1TX_ENCODE = 22, TRXSIG_K_L1TX_MUX = 23, TRXSIG_K_L1TX_DGRAM = 24, TRXSIG_K_L1TX_COMMIT = 25 };
+/* the wideband transmit synthesiser's (trxsig_frontend.h, trxsig_txbe_create_wideband): k_tx_wideband */
+enum { TRXSIG_K_TXWB = 26 };
 const char *trxsig_kernel_name(int kernel_id);
 int trxsig_profile_enable(trxsig_ctx *ctx, int on);
 int trxsig_profile_collect(trxsig_ctx *ctx, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]);

@@ -125,6 +125,42 @@ int trxsig_txbe_streams(const trxsig_txbe *be);
 int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_stride, int *n_samples);
 int trxsig_txbe_pending(const trxsig_txbe *be);   /* modulated samples per stream waiting for a whole chunk */
 
+/* ---- wideband transmit synthesiser: the transmit mirror of trxsig_rxfe_create_wideband ------------------------------------------
+ * A trxsig_txbe whose S = n_wide_streams * n_carriers ARFCN streams are summed into n_wide_streams int16 streams at
+ * rate_factor (R) x 400 kS/s.  ARFCN stream s = w * C + c is carrier c of wideband stream w (the channeliser's numbering: one
+ * Transceiver group of Sw * C ARFCNs and one plan serve both directions; trxsig_trxgroup_push_txbe takes it as it is).
+ * trxsig_txbe_push_bursts / _can_push / _pending / _destroy keep their meanings; trxsig_txbe_streams returns Sw * C;
+ * trxsig_txbe_pop returns n_wide_streams int16 I/Q streams of 864 R samples per whole chunk (stream w at *d_iq + w * *stream_stride
+ * pairs).  Only the fused form exists: trxsig_txbe_set_fused(be, 0) returns TRXSIG_EINVAL.
+ * h_carrier_freq[c]: the array trxsig_rxfe_create_wideband takes -- radians per wideband sample, the value that brings carrier c to
+ * 0 on receive; the synthesiser moves carrier c from 0 to -h_carrier_freq[c].  h_lpf: L taps for interpolation by P = 96 R, DC
+ * gain P.  gain replaces the narrowband 13500 (with C carriers, e.g. 13500 / C).
+ * Numerical contract (IEEE equality; tests/test_gpu_txwideband.py).  For every ARFCN stream s:
+ *   1. the send stream x_s is the narrowband back end's: modulateBurst with the burst's guard, times its gain when d_gain is given,
+ *      behind INHISTORY = 130 sps zero samples;
+ *   2. a pop of nch whole chunks forms y_s = polyphaseResampleVector([history | nch * 585 sps samples], P = 96 R, Q = 65 sps, h_lpf)
+ *      and keeps outputs [192 R, 192 R + 864 R nch);
+ *   3. the history moves on as in pushBuffer.
+ * For every wideband stream w and output k (a 64-bit count of the int16 samples emitted on w, from 0):
+ *   m_c[k] = expjLookup(phi_c[k]), phi_c[k] = (float)(t - 2 pi floor(t / 2 pi)), t = (double) k * (double)(-h_carrier_freq[c])
+ *            (the channeliser's mixer convention);
+ *   z = ((0 + y_{w,0}[k] m_0[k]) + y_{w,1}[k] m_1[k]) + ...   in carrier order, each product Complex<float>'s multiply, no fused
+ *            multiply-adds;
+ *   int16 pair = (sat(trunc(z.r * gain)), sat(trunc(z.i * gain))), I first as the narrowband back end writes it, sat clamping to
+ *            [-32768, 32767] (a sum of carriers can exceed the range; a DAC clips.  The narrowband conversion is unchanged).
+ * So for the same chunks per pop the output depends only on the concatenated bursts, not on how pushes split them (a pop's last
+ * outputs skip the taps that reach past its window's end, as pushBuffer's do), and with C = 1, R = 1, f = 0 and samples in range
+ * it equals the narrowband back end's.
+ * Limits (TRXSIG_EINVAL before anything is allocated; the context keeps no reference): 1 <= C <= 64, 1 <= R <= 64, h_carrier_freq
+ * non-NULL with |f| <= pi, Sw * C <= 65535, max_bursts >= 1, h_lpf non-NULL, L >= 1; at most 32 taps per output (L <= 32 * 96 R);
+ * the branch-major tap table, P / gcd(P, Q) rows of (ceil(L / P) | 1) floats, at most 32 KiB; 192 R + 864 R * (the chunks one pop
+ * can carry) below 2^31.
+ * The kernel (k_tx_wideband, csrc/trxsig_txwb.hip): one launch per pop, a workgroup per (tile of 1,024 outputs, wideband stream);
+ * carrier by carrier it stages the tile's modulated window from the bit ring, resamples from branch-major taps in LDS, mixes and
+ * accumulates in registers; the int16 is written once. */
+int trxsig_txbe_create_wideband(trxsig_txbe **out, trxsig_ctx *ctx, int n_wide_streams, int n_carriers, const float *h_carrier_freq,
+                                int rate_factor, int max_bursts, const float *h_lpf, int L, float gain);
+
 #ifdef __cplusplus
 }
 #endif

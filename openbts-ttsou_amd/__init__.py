@@ -794,11 +794,13 @@ class TrxGroup:
         return res
 
     def pull_rxfe(self, fe, iq, fn):
-        """fe: frontend.RxFrontEnd on the same context; iq: int16 device tensor [S, K*864, 2].  Returns (slots completed, result)."""
+        """fe: frontend.RxFrontEnd on the same context; iq: int16 device tensor [S, K*864, 2] ([Sw, K*864*R, 2] for a wideband front
+        end, whose Sw * C streams are the group's ARFCNs).  Returns (slots completed, result)."""
         iq = iq.contiguous()
         res = TrxGroupResult()
         n = C.c_int()
-        self._chk(self.L.trxsig_trxgroup_pull_rxfe(self.h, fe.h, iq.data_ptr(), iq.shape[1] // 864, fn, C.byref(n), C.byref(res)),
+        chunk = 864 * max(1, getattr(fe, "rate_factor", 0) or 1)   # (a wideband front end: iq [Sw, K*864*R, 2])
+        self._chk(self.L.trxsig_trxgroup_pull_rxfe(self.h, fe.h, iq.data_ptr(), iq.shape[1] // chunk, fn, C.byref(n), C.byref(res)),
                   "trxsig_trxgroup_pull_rxfe")
         fe._keep = iq
         self.n_slots = n.value

@@ -164,6 +164,7 @@ void trx_ctx_release(trxsig_ctx *c);
 struct trxsig_txbe;
 trxsig_ctx *trx_txbe_context(const trxsig_txbe *be);         // the context a transmit back end was created on (trxsig_frontend.cpp)
 trxsig_ctx *trx_rxfe_ctx(trxsig_rxfe *fe);
+int trx_rxfe_rate_factor(const trxsig_rxfe *fe);            // 0: a narrowband front end; else the channeliser's rate factor
 int trx_rxfe_streams(const trxsig_rxfe *fe);
 int trx_rxfe_next_tn(const trxsig_rxfe *fe);
 // Transceiver group (trxsig_trxgroup.cpp), equalising TSC leg (sps = 1):

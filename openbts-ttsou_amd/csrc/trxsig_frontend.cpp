@@ -69,6 +69,14 @@ struct trxsig_txbe {
   float *d_lpf = nullptr;
   short2 *d_iq = nullptr;
   int32_t *d_meta = nullptr;                                // guard[S*nb] then off[S*nb]
+  // wideband (trxsig_txbe_create_wideband): the S = Sw * C ARFCN streams are summed into Sw int16 streams at Cw x 400 kS/s by
+  // k_tx_wideband (trxsig_txwb.hip); ARFCN stream w*C + c = carrier c of wideband stream w.  Fused only: d_send is not allocated.
+  int Cw = 0, C = 0, Sw = 0;
+  int KT = 0, Pr = 0, pitch = 0, step_r = 0, step_i = 0, n_tiles_max = 0, xcap = 0;
+  float *d_freq = nullptr, *d_tpb = nullptr;                // -h_carrier_freq [C]; branch-major taps [Pr][pitch]
+  int2 *d_lane = nullptr;                                   // [256] (row, input offset) of lane t's first output, relative to the tile's
+  int4 *d_tiles = nullptr;                                  // [n_tiles_max] (row, input offset) of the tile's first output, its last input
+  long long k_out = 0;                                      // int16 samples emitted per wideband stream so far (the mixer's count)
 };
 
 extern "C" {
@@ -338,6 +346,7 @@ int trxsig_rxfe_pop(trxsig_rxfe *fe, const trxsig_c32 **d_samples, const int32_t
 trxsig_ctx *trx_rxfe_ctx(trxsig_rxfe *fe) { return fe ? fe->c : nullptr; }
 int trx_rxfe_streams(const trxsig_rxfe *fe) { return fe ? fe->S : 0; }
 int trx_rxfe_next_tn(const trxsig_rxfe *fe) { return fe ? fe->tn : 0; }   // TN of the next burst a pop will cut
+int trx_rxfe_rate_factor(const trxsig_rxfe *fe) { return fe ? fe->Cw : 0; }   // 0: narrowband; else the channeliser's rate factor
 
 // the bursts a fused push completes and where the kernels find their samples
 int trx_rxfe_fused_begin(trxsig_rxfe *fe, const int16_t *d_iq, int n_chunks, TrxRxfePush *out) {
@@ -451,12 +460,99 @@ int trxsig_txbe_create(trxsig_txbe **out, trxsig_ctx *c, int n_streams, int max_
   return TRXSIG_OK;
 }
 
+int trxsig_txbe_create_wideband(trxsig_txbe **out, trxsig_ctx *c, int n_wide_streams, int n_carriers, const float *h_carrier_freq,
+                                int rate_factor, int max_bursts, const float *h_lpf, int L, float gain) {
+  if (!out) return TRXSIG_EINVAL;
+  *out = nullptr;
+  if (!c) return TRXSIG_EINVAL;
+  // every refusal comes before anything is allocated or the context is retained
+  if (n_wide_streams <= 0 || n_carriers <= 0 || n_carriers > 64 || rate_factor <= 0 || rate_factor > 64 || !h_carrier_freq ||
+      (long long)n_wide_streams * n_carriers > 65535 || max_bursts <= 0 || !h_lpf || L <= 0)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_txbe_create_wideband: bad argument", hipSuccess);
+  for (int k = 0; k < n_carriers; k++)
+    if (!(h_carrier_freq[k] >= -3.2f && h_carrier_freq[k] <= 3.2f))
+      return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_txbe_create_wideband: carrier frequencies are radians per wideband sample, |f| <= pi", hipSuccess);
+  const int R = rate_factor, sps = trxsig_sps(c), P = TRXSIG_OUTRATE * R, Q = 65 * sps;
+  const int KT = (L + P - 1) / P;
+  if (KT > TRX_TXWB_KT)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_txbe_create_wideband: at most 32 taps per output (L <= 32 * 96 * rate_factor)", hipSuccess);
+  int g = P, r = Q % P;
+  while (r) { const int t = g % r; g = r; r = t; }          // gcd(P, Q)
+  const int Pr = P / g, Qr = Q / g, pitch = KT | 1;
+  if (sizeof(float) * (size_t)Pr * pitch > TRX_TXWB_TAPB)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_txbe_create_wideband: the branch-major tap table (P / gcd(P, Q) rows of (taps per output | 1) floats) exceeds 32 KiB", hipSuccess);
+  const int inchunk = 9 * Q, inhist = 2 * Q;
+  const long long cap = (long long)inchunk + (long long)max_bursts * 157 * sps;
+  const long long stride = (inhist + cap + 63) & ~63LL;
+  const long long nch_max = (stride - inhist) / inchunk;
+  const long long kept_max = (long long)TRXSIG_OUTCHUNK * R * nch_max;
+  if ((long long)TRXSIG_OUTHISTORY * R + kept_max + TRX_TXWB_OB > 0x7fffffffLL || stride > 0x7fffffffLL)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_txbe_create_wideband: max_bursts x rate_factor too large (outputs per pop exceed 2^31)", hipSuccess);
+  // the tiles' tables: (row, input offset) of each tile's first output, and the last input any of its outputs reaches
+  const int o_skip = TRXSIG_OUTHISTORY * R, D = (L - 1) / 2 / Q;   // :1177
+  const int n_tiles_max = (int)((kept_max + TRX_TXWB_OB - 1) / TRX_TXWB_OB);
+  std::vector<int4> tiles((size_t)n_tiles_max);
+  int xcap = 1;
+  for (int t = 0; t < n_tiles_max; t++) {
+    const long long oq = ((long long)o_skip + (long long)t * TRX_TXWB_OB + D) * Qr;
+    const long long hi = (((long long)o_skip + (long long)t * TRX_TXWB_OB + TRX_TXWB_OB - 1 + D) * Qr) / Pr;
+    tiles[(size_t)t] = make_int4((int)(oq % Pr), (int)(oq / Pr), (int)hi, 0);
+    const long long span = hi - (oq / Pr - (KT - 1)) + 1;
+    if (span > xcap) xcap = (int)span;
+  }
+  if (xcap > TRX_TXWB_XCAP)                                 // (cannot happen for rate_factor >= 1: at most 1023 * 260 / 96 + 32 samples)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_txbe_create_wideband: a tile's input span exceeds the kernel's staging", hipSuccess);
+  std::vector<int2> lane(256);
+  for (int t = 0; t < 256; t++) lane[(size_t)t] = make_int2((int)(((long long)t * Qr) % Pr), (int)(((long long)t * Qr) / Pr));
+  std::vector<float> tpb((size_t)Pr * pitch, 0.0f);
+  for (int row = 0; row < Pr; row++)
+    for (int k = 0; k < KT; k++) {
+      const long long fi = (long long)row * g + (long long)P * k;
+      if (fi < L) tpb[(size_t)row * pitch + k] = h_lpf[fi];
+    }
+  std::vector<float> fneg((size_t)n_carriers);
+  for (int k = 0; k < n_carriers; k++) fneg[(size_t)k] = -h_carrier_freq[k];   // the synthesiser moves carrier c from 0 to -f_c
+  trxsig_txbe *be = new (std::nothrow) trxsig_txbe;
+  if (!be) return TRXSIG_ENOMEM;
+  be->c = c; trx_ctx_retain(c);
+  be->S = n_wide_streams * n_carriers; be->Sw = n_wide_streams; be->C = n_carriers; be->Cw = R;
+  be->sps = sps; be->Q = Q; be->L = L; be->gain = gain; be->inchunk = inchunk; be->inhist = inhist; be->max_bursts = max_bursts;
+  be->stride = stride; be->fused = 1;
+  be->KT = KT; be->Pr = Pr; be->pitch = pitch; be->n_tiles_max = n_tiles_max; be->xcap = xcap;
+  be->step_r = (int)((256LL * Qr) % Pr); be->step_i = (int)((256LL * Qr) / Pr);
+  be->iq_stride = (kept_max + 63) & ~63LL;
+  be->ring_cap = max_bursts + (be->inchunk + be->inhist) / (148 * be->sps) + 4;
+  be->tab_cap = be->ring_cap + 2;
+  TrxDeviceGuard gd(trxsig_device(c));
+  const bool ok = be->ring_cap < 65536 &&
+       hipMalloc((void **)&be->d_iq, sizeof(short2) * (size_t)be->iq_stride * be->Sw) == hipSuccess &&
+       hipMalloc((void **)&be->d_ring, (size_t)148 * be->ring_cap * be->S) == hipSuccess &&
+       hipMalloc((void **)&be->d_rgain, sizeof(float) * (size_t)be->ring_cap * be->S) == hipSuccess &&
+       hipMalloc((void **)&be->d_tab, sizeof(int32_t) * 2 * (size_t)be->tab_cap) == hipSuccess &&
+       hipMalloc((void **)&be->d_freq, sizeof(float) * fneg.size()) == hipSuccess &&
+       hipMemcpy(be->d_freq, fneg.data(), sizeof(float) * fneg.size(), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMalloc((void **)&be->d_tpb, sizeof(float) * tpb.size()) == hipSuccess &&
+       hipMemcpy(be->d_tpb, tpb.data(), sizeof(float) * tpb.size(), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMalloc((void **)&be->d_lane, sizeof(int2) * lane.size()) == hipSuccess &&
+       hipMemcpy(be->d_lane, lane.data(), sizeof(int2) * lane.size(), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMalloc((void **)&be->d_tiles, sizeof(int4) * tiles.size()) == hipSuccess &&
+       hipMemcpy(be->d_tiles, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    const int rc = trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_txbe_create_wideband: device allocation failed", hipSuccess);   // (first the error text: the release below may be the context's end)
+    trxsig_txbe_destroy(be);
+    return rc;
+  }
+  *out = be;
+  return TRXSIG_OK;
+}
+
 void trxsig_txbe_destroy(trxsig_txbe *be) {
   if (!be) return;
   {
     TrxDeviceGuard g(trxsig_device(be->c));
     (void)hipFree(be->d_send[0]); (void)hipFree(be->d_send[1]); (void)hipFree(be->d_lpf); (void)hipFree(be->d_iq); (void)hipFree(be->d_meta);
     (void)hipFree(be->d_ring); (void)hipFree(be->d_rgain); (void)hipFree(be->d_tab);
+    (void)hipFree(be->d_freq); (void)hipFree(be->d_tpb); (void)hipFree(be->d_lane); (void)hipFree(be->d_tiles);
     be->tab_up.release();
   }
   trx_ctx_release(be->c);
@@ -468,6 +564,7 @@ int trxsig_txbe_pending(const trxsig_txbe *be) { return be ? be->fill : TRXSIG_E
 int trxsig_txbe_set_fused(trxsig_txbe *be, int fused) {
   if (!be) return TRXSIG_EINVAL;
   if (be->started) return trx_ctx_fail(be->c, TRXSIG_EINVAL, "trxsig_txbe_set_fused: the back end is in use", hipSuccess);
+  if (be->Cw && !fused) return trx_ctx_fail(be->c, TRXSIG_EINVAL, "trxsig_txbe_set_fused: a wideband back end has only the fused form", hipSuccess);
   be->fused = fused != 0;
   return TRXSIG_OK;
 }
@@ -547,7 +644,8 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
   if (nch == 0) return TRXSIG_OK;
   const int ntr = nch * be->inchunk;                        // truncatedBuffer (:131-132)
   const int n_in = be->inhist + ntr;                        // signalVector(*sendHistory, *truncatedBuffer) (:141)
-  const int n_out = trxsig_resample_out_len(n_in, TRXSIG_OUTRATE, be->Q);
+  // the wideband synthesiser keeps 864 R outputs per chunk: n_in * 96 R / (65 sps) = (2 + 9 nch) * 96 R exactly
+  const int n_out = be->Cw ? TRXSIG_OUTHISTORY * be->Cw + TRXSIG_OUTCHUNK * be->Cw * nch : trxsig_resample_out_len(n_in, TRXSIG_OUTRATE, be->Q);
   TrxDeviceGuard g(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   TrxResampleArgs a = {};
@@ -572,10 +670,24 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
       m_used++;
     }
     TRX_HIPCHK(c, be->tab_up.upload(tab_slot, be->d_tab, sizeof(int32_t) * 2 * (size_t)be->tab_cap, st));
-    a.in = be->d_ring; a.in_stride = be->ring_cap;
-    a.tx_tables = (const TrxTables *)trxsig_tables_device(c); a.tx_gain = be->d_rgain; a.tx_start = be->d_tab; a.tx_meta = be->d_tab + be->tab_cap;
-    a.tx_n = m_used; a.tx_sps = be->sps;
-    TRX_HIPCHK(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c), true));
+    if (be->Cw) {
+      const int o_skip = TRXSIG_OUTHISTORY * be->Cw, kept = n_out - o_skip;
+      TrxTxwbArgs w = {};
+      w.T = (const TrxTables *)trxsig_tables_device(c);
+      w.ring = be->d_ring; w.gring = be->d_rgain; w.cap = be->ring_cap;
+      w.tx_start = be->d_tab; w.tx_meta = be->d_tab + be->tab_cap; w.tx_n = m_used;
+      w.tpb = be->d_tpb; w.Pr = be->Pr; w.pitch = be->pitch; w.KT = be->KT;
+      w.lane = be->d_lane; w.step_r = be->step_r; w.step_i = be->step_i; w.tiles = be->d_tiles;
+      w.n = n_in; w.o_skip = o_skip; w.n_out = n_out; w.C = be->C; w.xcap = be->xcap;
+      w.freq = be->d_freq; w.k0 = be->k_out; w.gain = be->gain; w.out = be->d_iq; w.out_stride = be->iq_stride;
+      TRX_HIPCHK(c, trx_launch_tx_wideband(st, w, be->sps, be->Sw, (kept + TRX_TXWB_OB - 1) / TRX_TXWB_OB, trx_ctx_profiler(c)));
+      be->k_out += kept;
+    } else {
+      a.in = be->d_ring; a.in_stride = be->ring_cap;
+      a.tx_tables = (const TrxTables *)trxsig_tables_device(c); a.tx_gain = be->d_rgain; a.tx_start = be->d_tab; a.tx_meta = be->d_tab + be->tab_cap;
+      a.tx_n = m_used; a.tx_sps = be->sps;
+      TRX_HIPCHK(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c), true));
+    }
     // sendHistory = the last INHISTORY samples sent, the rest of sendBuffer follows it (:183-191): the window's origin moves on
     // by ntr samples; bursts that end before it are done
     size_t keep_from = 0;
@@ -585,7 +697,7 @@ int trxsig_txbe_pop(trxsig_txbe *be, const int16_t **d_iq, int64_t *stream_strid
     }
     be->live.erase(be->live.begin(), be->live.begin() + (long)keep_from);
     be->fill -= ntr;
-    *n_samples = n_out - TRXSIG_OUTHISTORY;
+    *n_samples = n_out - TRXSIG_OUTHISTORY * (be->Cw ? be->Cw : 1);
     return TRXSIG_OK;
   }
   TRX_HIPCHK(c, trx_launch_resample_ex(st, a, be->S, 1, false, true, trx_ctx_profiler(c)));

@@ -153,6 +153,30 @@ hipError_t trx_launch_channelise16(hipStream_t st, TrxResampleArgs a, int S_wide
 // what trx_launch_channelise16 can launch, apart from the carriers' grid: C in {1, 2, 4, 8, 16}, at most 32 taps per output, the tile's span of
 // the window (xcap) inside the kernel's staging and its LDS inside 64 KiB.  trxsig_rxfe_set_shared_filter refuses the rest with it.
 bool trx_channelise16_fits(int P, int Q, int L, int C);
+// The wideband transmit synthesiser (trxsig_txbe_create_wideband; k_tx_wideband, trxsig_txwb.hip): for every wideband stream w and
+// tile of TRX_TXWB_OB outputs, carrier by carrier, the modulated window of ARFCN stream w*C + c is staged from its bit ring,
+// resampled P : Q with the branch-major taps, mixed by expjLookup(phase of output k) and summed in carrier order; int16 out once.
+// Tables built by the host at create time: tpb [Pr][pitch] (Pr = P / gcd(P, Q); row r holds lpf[r gcd + P k], zero past L),
+// lane[256] = ((t Q') mod Pr, (t Q') / Pr) for t = 0..255 (Q' = Q / gcd), tiles[t] = (row, inOff) of the tile's first output and the
+// last input its outputs reach;
+// freq[C] = -h_carrier_freq.
+#define TRX_TXWB_OB 1024                                   // outputs per workgroup (four per lane)
+#define TRX_TXWB_KT 32                                     // taps per output at most
+#define TRX_TXWB_TAPB 32768                                // bytes of the branch-major tap table at most
+#define TRX_TXWB_XCAP 3584                                 // staged samples per carrier and tile at most
+struct TrxTxwbArgs {
+  const TrxTables *T;
+  const uint8_t *ring; const float *gring; int cap;        // bit ring [S][cap][148], gains [S][cap]
+  const int32_t *tx_start, *tx_meta; int tx_n;             // the window's bursts (as TrxResampleArgs)
+  const float *tpb; int Pr, pitch, KT;                     // branch-major taps
+  const int2 *lane; int step_r, step_i;                    // a lane's first output; 256 outputs on: rows / input offsets further
+  const int4 *tiles; int tile0;                            // (row, inOff, hi) of every tile: its first output's, the last input it
+                                                           // can reach; this slice's first tile
+  int n, o_skip, n_out, C, xcap;                           // window length, first kept output, outputs, carriers, staged samples
+  const float *freq; long long k0;                         // mixer frequencies; wideband sample count of output o_skip
+  float gain; short2 *out; long long out_stride;           // int16 out: stream w at out + w*out_stride
+};
+hipError_t trx_launch_tx_wideband(hipStream_t st, TrxTxwbArgs a, int sps, int Sw, int n_tiles, TrxProfiler *prof);
 hipError_t trx_launch_tx_ring_store(hipStream_t st, const uint8_t *bits, const float *gain, int S, int nb, int head, int cap, uint8_t *ring,
                                     float *gring);
 hipError_t trx_launch_burst_index(hipStream_t st, int S, int nb, long long stride, int rd, int tn0, int sps, int32_t *off,

@@ -556,12 +556,14 @@ int trxsig_trxgroup_pull_rxfe(trxsig_trxgroup *g, trxsig_rxfe *fe, const int16_t
   trxsig_ctx *c = g->c;
   if (!fe || !n_slots || fn < 0 || fn >= kHyperframe) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_rxfe: bad argument", hipSuccess);
   if (trx_rxfe_ctx(fe) != c) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_rxfe: the front end lives on another context", hipSuccess);
-  if (g->leg != TRXSIG_TSCLEG_DEMOD || g->sps != 4) {
+  const bool wide = trx_rxfe_rate_factor(fe) > 0;
+  if (g->leg != TRXSIG_TSCLEG_DEMOD || g->sps != 4 || wide) {
     // The fused front end is the 260 : 96 resampler feeding the demodulating leg.  Everything else -- the equalising leg at one
-    // sample per symbol, the reference's own configuration -- goes through the resampled stream: push, pop, and the group on the
-    // bursts the pop lists (same results as the fused form where both exist: tests/test_gpu_trxgroup.py).
+    // sample per symbol, the reference's own configuration, and the wideband channeliser -- goes through the resampled stream:
+    // push, pop, and the group on the bursts the pop lists (same results as the fused form where both exist:
+    // tests/test_gpu_trxgroup.py).
     if (trx_rxfe_streams(fe) != g->S) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_rxfe: one stream per ARFCN, please", hipSuccess);
-    G_LIB(trxsig_rxfe_push(fe, d_iq, n_chunks));
+    G_LIB(wide ? trxsig_rxfe_push_wideband(fe, d_iq, n_chunks) : trxsig_rxfe_push(fe, d_iq, n_chunks));
     const trxsig_c32 *xs = nullptr;
     const int32_t *off = nullptr, *len = nullptr;
     const int tn0 = trx_rxfe_next_tn(fe);

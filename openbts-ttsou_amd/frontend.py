@@ -39,6 +39,8 @@ def _bind(L):
     L.trxsig_txbe_pop.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(i32)]
     L.trxsig_txbe_pending.argtypes = [vp]
     L.trxsig_txbe_set_fused.argtypes = [vp, i32]
+    L.trxsig_txbe_create_wideband.argtypes = [C.POINTER(vp), vp, i32, i32, vp, i32, i32, vp, i32, C.c_float]
+    L.trxsig_txbe_streams.argtypes = [vp]
     L._frontend_bound = True
 
 
@@ -154,21 +156,33 @@ class RxFrontEnd:
 
 
 class TxBackEnd:
-    def __init__(self, ctx, n_streams, lpf_taps, gain=13500.0, device="cuda:0", max_bursts=64, fused=True):
+    def __init__(self, ctx, n_streams, lpf_taps, gain=13500.0, device="cuda:0", max_bursts=64, fused=True, carrier_freq=None, rate_factor=0):
+        """carrier_freq (radians per wideband sample, one per carrier: the array RxFrontEnd takes) + rate_factor: the wideband
+        synthesiser -- n_streams WIDEBAND int16 streams at rate_factor x 400 kS/s, each the sum of len(carrier_freq) ARFCNs;
+        bursts go in per (stream, carrier), .S = n_streams * C of them, and pop_samples returns [n_streams, n, 2]."""
         import torch
         self.torch = torch
         self.ctx = ctx
         self.L = ctx.L
         _bind(self.L)
-        self.S = n_streams
         self.sps = ctx.sps
         self.dev = torch.device(device)
+        self.rate_factor = rate_factor
         lpf = np.ascontiguousarray(lpf_taps, np.float32)
         h = C.c_void_p()
-        ctx._chk(self.L.trxsig_txbe_create(C.byref(h), ctx.h, n_streams, max_bursts, lpf.ctypes.data, lpf.size, float(gain)),
-                 "trxsig_txbe_create")
+        if carrier_freq is not None:
+            fr = np.ascontiguousarray(carrier_freq, np.float32)
+            ctx._chk(self.L.trxsig_txbe_create_wideband(C.byref(h), ctx.h, n_streams, fr.size, fr.ctypes.data, rate_factor, max_bursts,
+                                                        lpf.ctypes.data, lpf.size, float(gain)), "trxsig_txbe_create_wideband")
+            self.S = n_streams * fr.size
+            self.Sw = n_streams
+        else:
+            ctx._chk(self.L.trxsig_txbe_create(C.byref(h), ctx.h, n_streams, max_bursts, lpf.ctypes.data, lpf.size, float(gain)),
+                     "trxsig_txbe_create")
+            self.S = self.Sw = n_streams
         self.h = h
-        ctx._chk(self.L.trxsig_txbe_set_fused(h, int(fused)), "trxsig_txbe_set_fused")
+        if carrier_freq is None or not fused:                 # (the wideband form is fused only: asking for the other is refused)
+            ctx._chk(self.L.trxsig_txbe_set_fused(h, int(fused)), "trxsig_txbe_set_fused")
 
     def close(self):
         if self.h:
@@ -197,7 +211,7 @@ class TxBackEnd:
         self._keep = (d_bits, d_gain)
 
     def pop_samples(self):
-        """int16 tensor [S, n, 2] for the radio (a strided view of the library's output buffer, valid until the next pop),
+        """int16 tensor [Sw, n, 2] for the radio (Sw = S for a narrowband back end) (a strided view of the library's output buffer, valid until the next pop),
         or None while less than one chunk is buffered."""
         p = C.c_void_p(); stride = C.c_int64(); n = C.c_int()
         self.ctx._chk(self.L.trxsig_txbe_pop(self.h, C.byref(p), C.byref(stride), C.byref(n)), "trxsig_txbe_pop")
@@ -207,7 +221,7 @@ class TxBackEnd:
         #  object asks the runtime about the pointer, which took ~0.4 ms per call whenever the device was busy)
         key = (p.value, stride.value)
         if getattr(self, "_iq_key", None) != key:
-            self._iq_full = self.torch.as_tensor(_DevView(p.value, (self.S, stride.value, 2), "<i2"), device=self.dev)
+            self._iq_full = self.torch.as_tensor(_DevView(p.value, (self.Sw, stride.value, 2), "<i2"), device=self.dev)
             self._iq_key = key
         return self._iq_full[:, :n.value]
 
