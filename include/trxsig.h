@@ -563,6 +563,9 @@ enum { TRXSIG_K_L1RX_DEMUX = 20, TRXSIG_K_L1RX_FINISH = 21 };
 enum { TRXSIG_K_L1TX_ENCODE = 22, TRXSIG_K_L1TX_MUX = 23, TRXSIG_K_L1TX_DGRAM = 24, TRXSIG_K_L1TX_COMMIT = 25 };
 /* the wideband transmit synthesiser's (trxsig_frontend.h, trxsig_txbe_create_wideband): k_tx_wideband */
 enum { TRXSIG_K_TXWB = 26 };
+/* the device-to-device hand-off of the multiplexer's bursts to a group's transmit queues (trxsig_trxgroup_add_l1tx):
+ * k_group_tx_arrive_grid */
+enum { TRXSIG_K_GROUP_TX_GRID = 27 };
 const char *trxsig_kernel_name(int kernel_id);
 int trxsig_profile_enable(trxsig_ctx *ctx, int on);
 int trxsig_profile_collect(trxsig_ctx *ctx, float total_ms[TRXSIG_K_COUNT], int launches[TRXSIG_K_COUNT]);

@@ -108,6 +108,17 @@ int trxsig_l1tx_encode(trxsig_l1tx *l1, int fn, int n_frames, const trxsig_l1tx_
  * 148 bits), in (FN, TN, ARFCN) order, with each one's ARFCN: what trxsig_trxgroup_add_bursts takes.  Compacted on the device
  * and copied down once; synchronises.  *n = the count; if cap is smaller, TRXSIG_EINVAL with *n the count needed. */
 int trxsig_l1tx_datagrams(trxsig_l1tx *l1, uint8_t *h_dgram, int32_t *h_arfcn, int cap, int *n);
+/* addRadioVector for every non-empty slot of l1's LAST encode, device to device.  Same effect on g as
+ * trxsig_l1tx_datagrams + trxsig_trxgroup_add_bursts of what it returns (power byte 0, gain 1.0), without the copy down, the
+ * host parse or the upload: per ARFCN the bursts enter in (FN, TN) order, a full queue or payload pool accepts the same prefix
+ * and marks the same ARFCNs dropped.  Enqueues only (k_group_tx_arrive_grid on the context's stream, behind the encode; the
+ * payloads move into the group's own memory there, so l1 may encode again at once); never synchronises; copies nothing to the
+ * host.  The ingest stays pending exactly as after trxsig_trxgroup_add_bursts: the push that follows takes it into its launch.
+ * Only a call larger than any before allocates (and waits for the group's earlier transmit work while it does).
+ * TRXSIG_EINVAL, with nothing queued: g or l1 NULL, different contexts, l1's n_arfcn is not g's, no encode yet (or none since
+ * l1's workspace last grew), a staging block lent out by trxsig_trxgroup_tx_staging and not yet added.  An encode whose slots
+ * are all empty is TRXSIG_OK and queues nothing. */
+int trxsig_trxgroup_add_l1tx(trxsig_trxgroup *g, trxsig_l1tx *l1);
 /* the channel records of a class, [n_chan][TRXSIG_L1TX_STATE_BYTES] (device; opaque; for tests and checkpoints) */
 int trxsig_l1tx_state(trxsig_l1tx *l1, int cls, void **d_state);
 

@@ -752,6 +752,7 @@ class TrxGroup:
         L.trxsig_trxgroup_add_bursts.argtypes = [vp, vp, vp, i32]
         L.trxsig_trxgroup_tx_staging.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp)]
         L.trxsig_trxgroup_add_staged.argtypes = [vp, i32]
+        L.trxsig_trxgroup_add_l1tx.argtypes = [vp, vp]
         L.trxsig_trxgroup_push.argtypes = [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.trxsig_trxgroup_push_txbe.argtypes = [vp, vp, i32, i32, i32]
         L.trxsig_trxgroup_tx_queue_size.argtypes = [vp, i32, C.POINTER(i32)]
@@ -827,6 +828,11 @@ class TrxGroup:
     def add_staged(self, n):
         """The first n datagrams of the staging block: header check on the host, one upload, one kernel."""
         self._chk(self.L.trxsig_trxgroup_add_staged(self.h, int(n)), "trxsig_trxgroup_add_staged")
+
+    def add_l1tx(self, l1):
+        """Every non-empty slot of l1's (an L1Tx on the same context) last encode into the queues, device to device: the effect of
+        add_bursts(*l1.datagrams()) without the copy down, the host's header loop and the upload.  Enqueues only."""
+        self._chk(self.L.trxsig_trxgroup_add_l1tx(self.h, l1.h if l1 is not None else None), "trxsig_trxgroup_add_l1tx")
 
     def push(self, fn, tn, n_slots, device="cuda:0"):
         """pushRadioVector for n_slots timeslots from (fn, tn): (bits uint8 [S, n, 148], gain float32 [S, n], from_queue uint8 [S, n])

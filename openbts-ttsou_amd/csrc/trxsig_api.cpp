@@ -20,7 +20,7 @@
 #include "trxsig_tablegen.h"
 
 // kernel ids the profiler knows: the TRXSIG_K_COUNT of ABI 2, then the ones appended since (trxsig.h)
-constexpr int kKernels = TRXSIG_K_TXWB + 1;
+constexpr int kKernels = TRXSIG_K_GROUP_TX_GRID + 1;
 
 struct EventProfiler : TrxProfiler {
   struct Rec { int id; hipEvent_t a, b; };
@@ -1168,7 +1168,7 @@ const char *trxsig_kernel_name(int id) {
                                                "k_fec_tch_encode", "k_fec_sch_encode", "k_fec_rx_stream_tch",
                                                "k_fec_rx_stream_xcch", "k_fec_rx_fold", "k_l1rx_demux", "k_l1rx_finish",
                                                "k_l1tx_encode", "k_l1tx_mux", "k_l1tx_datagrams", "k_l1tx_commit",
-                                               "k_tx_wideband" };
+                                               "k_tx_wideband", "k_group_tx_arrive_grid" };
   return (id >= 0 && id < kKernels) ? names[id] : "?";
 }
 int trxsig_fec_xcch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n_blocks, int wire,

@@ -110,7 +110,15 @@ size_t trx_group_tx_arrive_ints(int S, int n, size_t *tot_ints);
 hipError_t trx_launch_group_tx_arrive(hipStream_t st, int S, int n, const uint8_t *dgram, const int32_t *arfcn, int32_t *a_lf, int32_t *a_lk,
                                       int32_t *a_tot);
 hipError_t trx_launch_group_tx_ingest(hipStream_t st, const TrxGroupTx &x, int n, const uint8_t *dgram, const int32_t *a_lf, const int32_t *a_lk,
-                                      const int32_t *a_tot, const float *gain_tab26, int ref_fn, int far);
+                                      const int32_t *a_tot, const float *gain_tab26, int ref_fn, int far, int grid = 0);
+// The arrival half of trxsig_trxgroup_add_l1tx: the same lists straight from the downlink multiplexer's grid (what [S][8 n_frames],
+// bits [S][8 n_frames][148], frames [fn, fn + n_frames)), a round = 64 frames, and the payloads into dgram -- trx_group_tx_grid_bytes
+// bytes, a block per arrival group -- in datagram layout.  The lists take trx_group_tx_arrive_ints(S, n, &t) ints with n =
+// trx_group_tx_grid_rounds(n_frames) * 8192: the n (and grid = 1) the ingest launchers are then given.
+int trx_group_tx_grid_rounds(int n_frames);
+size_t trx_group_tx_grid_bytes(int S, int n_frames);
+hipError_t trx_launch_group_tx_arrive_grid(hipStream_t st, int S, int n_frames, int fn, const uint8_t *what, const uint8_t *bits, int32_t *a_lf,
+                                           int32_t *a_lk, int32_t *a_tot, uint8_t *dgram, TrxProfiler *prof);
 // pushRadioVector for n_slots timeslots from (fn0, tn0) on every ARFCN: bits_out [S][n_slots][148], gain_out [S][n_slots], fq_out
 // [S][n_slots] (1 = the burst came from the queue)
 hipError_t trx_launch_group_tx_push(hipStream_t st, const TrxGroupTx &x, int fn0, int tn0, int n_slots, uint8_t *bits_out, float *gain_out,
@@ -119,4 +127,4 @@ hipError_t trx_launch_group_tx_push(hipStream_t st, const TrxGroupTx &x, int fn0
 // of the add call lies TRXQ_PK_WIN frames or more from fn0
 hipError_t trx_launch_group_tx_both(hipStream_t st, const TrxGroupTx &x, int n, const uint8_t *dgram, const int32_t *a_lf, const int32_t *a_lk,
                                     const int32_t *a_tot, const float *gain_tab26, int far_add, int fn0, int tn0, int n_slots, uint8_t *bits_out,
-                                    float *gain_out, uint8_t *fq_out);
+                                    float *gain_out, uint8_t *fq_out, int grid = 0);

@@ -5,6 +5,10 @@
 //                       their ARFCN ids, as they arrived -- everything that needs no queue state, so it runs on the uploads' stream: a
 //                       workgroup owns sixteen ARFCNs, finds its datagrams (a stable counting sort by wave ballots: arrival order is
 //                       kept inside an ARFCN) and parses TN / big-endian FN / RSSI into per-ARFCN lists;
+//   k_group_tx_arrive_grid : the same lists straight from the downlink multiplexer's slot grid (trxsig_trxgroup_add_l1tx: d_what /
+//                       d_bits of the last trxsig_l1tx_encode, device to device) -- no headers to parse and nothing to sort, the grid is
+//                       ARFCN by ARFCN in (FN, TN) order already: a workgroup per (ARFCN, round of 64 frames) compacts its non-empty
+//                       slots and moves their payloads into the group's own block, so the grid is free for the next encode;
 //   k_group_tx<INGEST, WALK> : the queues' kernel, a workgroup of four waves for four ARFCNs, in three forms -- the add call's part
 //                       alone, the push's alone, or both in one launch (the add call's part stays pending until the push that follows):
 //     INGEST            addRadioVector (:100-113) for those lists: WAVE k enters ARFCN k's bursts in its queue -- the queue sits in LDS
@@ -88,6 +92,9 @@ struct TxArrive {
   int32_t *lf, *lk;                                         // [workgroups][n_pad]
   int32_t *tot;                                             // [workgroups][rounds][16]
   int n_pad, rounds;                                        // n_pad = rounds * kTxWin
+  size_t dg_stride;                                         // 0: ONE datagram block, a round's positions count through it (k_group_tx_arrive); else every
+                                                            // arrival workgroup has its own block of this many bytes (k_group_tx_arrive_grid), the
+                                                            // position = the entry's place in the workgroup's list of the round
 };
 __global__ __launch_bounds__(1024) void k_group_tx_arrive(int S, int n, const uint8_t *__restrict__ dgram, const int32_t *__restrict__ arfcn, TxArrive ar) {
   __shared__ int32_t cnt[kTxChunks][kTxA];
@@ -162,6 +169,67 @@ __global__ __launch_bounds__(1024) void k_group_tx_arrive(int S, int n, const ui
       olk[w0 + lp] = (tn & 7) | (gi << 3) | (k << 8) | ((my_i[cc] - w0) << 12);   // (13 bits of position: a round is 8,192 datagrams)
     }
     __syncthreads();                                        // cnt / tot / lbase are the next round's
+  }
+}
+
+// ---- the arrival half of trxsig_trxgroup_add_l1tx: TxArrive's lists from the downlink multiplexer's grid, what [S][8 F] (0 = an empty
+// slot) and bits [S][8 F][148], frames [fn0, fn0 + F) modulo the hyperframe.  A ROUND is 64 frames: sixteen ARFCNs x 64 frames x 8
+// timeslots = kTxWin, so an arrival group's sixteen ARFCNs never exceed the ingest's window whatever the grid holds.  A workgroup
+// per (ARFCN, round), a thread per slot row of the round (512): the non-empty rows are compacted by wave ballots in row order = (FN,
+// TN) order, the order the datagram route delivers an ARFCN's bursts in; where the ARFCN's entries start in its group's list is the
+// count of the group's EARLIER ARFCNs' non-empty rows, which the workgroup counts itself from `what` (at most 15 x 512 bytes: cheaper
+// than a pass of its own and a dependent launch).  Every entry: gain index 12 (power byte 0: pow(10, 0)), position = its place in the
+// group's list of the round, and its 148 payload bytes in datagram layout (154 p + 6) in the GROUP'S block dg + group * ar.dg_stride,
+// which the ingest reads exactly as it reads an uploaded block (the headers' six bytes are not written: nothing reads them).
+constexpr int kTxGridF = kTxWin / (kTxA * 8);               // frames a round
+constexpr int kTxGridT = kTxGridF * 8;                      // threads: a slot row of the round each
+__global__ __launch_bounds__(kTxGridT) void k_group_tx_arrive_grid(int S, int F, int fn0, int r0, const uint8_t *__restrict__ what,
+                                                                   const uint8_t *__restrict__ bits, TxArrive ar, uint8_t *__restrict__ dg) {
+  static_assert(kTxGridF * 8 * kTxA == kTxWin && kTxGridT % 64 == 0, "a round of sixteen ARFCNs fills the ingest's window exactly");
+  constexpr int NW = kTxGridT / 64;
+  __shared__ int w_own[NW], w_before[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int a = blockIdx.x, g16 = a / kTxA, k = a - g16 * kTxA, round = r0 + blockIdx.y;
+  const int f0 = round * kTxGridF;
+  const int rows = 8 * min(kTxGridF, F - f0);               // (round < ar.rounds = ceil(F / 64): at least one frame)
+  const size_t F8 = (size_t)8 * F, row0 = (size_t)8 * f0 + tid;
+  const bool in = tid < rows;
+  const bool on = in && what[(size_t)a * F8 + row0] != 0;
+  int before = 0;                                           // the group's earlier ARFCNs' non-empty slots at this row
+  for (int kk = 0; kk < k; kk++) before += (in && what[(size_t)(g16 * kTxA + kk) * F8 + row0] != 0) ? 1 : 0;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
+  const unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+  if (lane == 0) { w_own[wave] = __builtin_popcountll(m); w_before[wave] = before; }
+  __syncthreads();
+  int lp = __builtin_popcountll(m & ((1ull << lane) - 1ull)), own = 0;
+  for (int w = 0; w < NW; w++) {
+    lp += w_before[w] + (w < wave ? w_own[w] : 0);
+    own += w_own[w];
+  }
+  int32_t *const tot = ar.tot + ((size_t)g16 * ar.rounds + round) * kTxA;
+  if (tid == 0) tot[k] = own;
+  if (k == 0 && tid >= 1 && tid < kTxA && a + tid >= S) tot[tid] = 0;   // (the last group's ARFCNs past S: nobody else writes their counts)
+  if (!on) return;
+  const size_t li = (size_t)g16 * ar.n_pad + (size_t)round * kTxWin + lp;
+  ar.lf[li] = (int32_t)(((long long)fn0 + f0 + (tid >> 3)) % TRXQ_HYPERFRAME);
+  ar.lk[li] = (tid & 7) | (12 << 3) | (k << 8) | (lp << 12);              // (lp < kTxWin: 13 bits)
+  // the payload: 37 aligned words in, to byte 154 p + 6 of the group's block -- on a multiple of four for odd p, two past one for even p
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(bits + ((size_t)a * F8 + row0) * 148);
+  uint32_t v[37];
+#pragma unroll
+  for (int w = 0; w < 37; w++) v[w] = src[w];
+  uint8_t *dst = dg + (size_t)g16 * ar.dg_stride + ((size_t)round * kTxWin + lp) * 154 + 6;
+  if (lp & 1) {
+    uint32_t *d4 = reinterpret_cast<uint32_t *>(dst);
+#pragma unroll
+    for (int w = 0; w < 37; w++) d4[w] = v[w];
+  } else {
+    *reinterpret_cast<uint16_t *>(dst) = (uint16_t)v[0];
+    uint32_t *d4 = reinterpret_cast<uint32_t *>(dst + 2);
+#pragma unroll
+    for (int w = 0; w < 36; w++) d4[w] = __builtin_amdgcn_alignbyte(v[w + 1], v[w], 2);
+    *reinterpret_cast<uint16_t *>(dst + 146) = (uint16_t)(v[36] >> 16);
   }
 }
 
@@ -328,6 +396,7 @@ __global__ __launch_bounds__(64 * kTxI) void k_group_tx(TrxGroupTx x, int n, con
     // ================= addRadioVector for what k_group_tx_arrive sorted =================
     const int g16 = a0 / kTxA, k0 = a0 - g16 * kTxA;        // the arrival workgroup whose lists hold this workgroup's ARFCNs, and where in its sixteen
     const int32_t *const ilf = ar.lf + (size_t)g16 * ar.n_pad, *const ilk = ar.lk + (size_t)g16 * ar.n_pad;
+    const uint8_t *const dgb = dgram + (size_t)g16 * ar.dg_stride;   // (the arrival group's own block when the lists came from the grid)
     int round = 0;
     for (int w0 = 0; w0 < n; w0 += kTxWin, round++) {         // rounds of 8,192 datagrams (LDS is sized for one)
       if (tid == 0) {                                         // this workgroup's part of the arrival workgroup's lists
@@ -370,7 +439,7 @@ __global__ __launch_bounds__(64 * kTxI) void k_group_tx(TrxGroupTx x, int n, con
           if (e - lbase[kk] >= acc[kk]) return;               // dropped
           const size_t pb = (size_t)src * 154 + 6;
           odd2 = (pb & 2) != 0;
-          const uint32_t *pa = reinterpret_cast<const uint32_t *>(dgram + (pb & ~(size_t)3));
+          const uint32_t *pa = reinterpret_cast<const uint32_t *>(dgb + (pb & ~(size_t)3));
   #pragma unroll
           for (int w = 0; w < 36; w += 4) __builtin_memcpy(&aw[w], pa + w, 16);
           __builtin_memcpy(&aw[36], pa + 36, 8);              // (up to four bytes past the last datagram's end: the array is allocated eight longer)
@@ -590,12 +659,32 @@ size_t trx_group_tx_arrive_ints(int S, int n, size_t *tot_ints) {
   return nblk * rounds * kTxWin;
 }
 
-static TxArrive tx_arrive_args(int n, int32_t *a_lf, int32_t *a_lk, int32_t *a_tot) {
+static TxArrive tx_arrive_args(int n, int32_t *a_lf, int32_t *a_lk, int32_t *a_tot, int grid = 0) {
   TxArrive ar;
   ar.lf = a_lf; ar.lk = a_lk; ar.tot = a_tot;
   ar.rounds = (n + kTxWin - 1) / kTxWin;
   ar.n_pad = ar.rounds * kTxWin;
+  ar.dg_stride = grid ? (size_t)ar.n_pad * 154 : 0;
   return ar;
+}
+
+int trx_group_tx_grid_rounds(int n_frames) { return (n_frames + kTxGridF - 1) / kTxGridF; }
+size_t trx_group_tx_grid_bytes(int S, int n_frames) {
+  return (size_t)((S + kTxA - 1) / kTxA) * (size_t)trx_group_tx_grid_rounds(n_frames) * kTxWin * 154 + 8;
+}
+
+hipError_t trx_launch_group_tx_arrive_grid(hipStream_t st, int S, int n_frames, int fn, const uint8_t *what, const uint8_t *bits, int32_t *a_lf,
+                                           int32_t *a_lk, int32_t *a_tot, uint8_t *dgram, TrxProfiler *prof) {
+  if (n_frames <= 0) return hipSuccess;
+  const int rounds = trx_group_tx_grid_rounds(n_frames);
+  if (S > 65535 || (long long)rounds * kTxWin > 0x7fffffffLL) return hipErrorInvalidValue;
+  const TxArrive ar = tx_arrive_args(rounds * kTxWin, a_lf, a_lk, a_tot, 1);
+  if (prof) prof->begin(TRXSIG_K_GROUP_TX_GRID, st);
+  constexpr int kMaxY = 65535;                              // a dispatch's y-dimension: more rounds go out in slices
+  for (int r0 = 0; r0 < rounds; r0 += kMaxY)
+    k_group_tx_arrive_grid<<<dim3((unsigned)S, (unsigned)(rounds - r0 < kMaxY ? rounds - r0 : kMaxY)), dim3(kTxGridT), 0, st>>>(S, n_frames, fn, r0, what, bits, ar, dgram);
+  if (prof) prof->end(TRXSIG_K_GROUP_TX_GRID, st);
+  return hipGetLastError();
 }
 
 hipError_t trx_launch_group_tx_arrive(hipStream_t st, int S, int n, const uint8_t *dgram, const int32_t *arfcn, int32_t *a_lf, int32_t *a_lk,
@@ -606,13 +695,13 @@ hipError_t trx_launch_group_tx_arrive(hipStream_t st, int S, int n, const uint8_
 }
 
 hipError_t trx_launch_group_tx_ingest(hipStream_t st, const TrxGroupTx &x, int n, const uint8_t *dgram, const int32_t *a_lf, const int32_t *a_lk,
-                                      const int32_t *a_tot, const float *gain_tab26, int ref_fn, int far) {
+                                      const int32_t *a_tot, const float *gain_tab26, int ref_fn, int far, int grid) {
   if (n <= 0) return hipSuccess;
   if (x.qcap != kTxQ || x.npool > TRXQ_PK_IDS) return hipErrorInvalidValue;   // (the kernel's LDS copy of a queue, a packed entry's id field)
   TxGainTab gt;
   for (int q = 0; q < 26; q++) gt.v[q] = gain_tab26[q];
   k_group_tx<true, false><<<dim3((x.S + kTxI - 1) / kTxI), dim3(64 * kTxI), 0, st>>>(
-      x, n, dgram, tx_arrive_args(n, (int32_t *)a_lf, (int32_t *)a_lk, (int32_t *)a_tot), gt, ref_fn, 0, 0, 0, nullptr, nullptr, nullptr, far);
+      x, n, dgram, tx_arrive_args(n, (int32_t *)a_lf, (int32_t *)a_lk, (int32_t *)a_tot, grid), gt, ref_fn, 0, 0, 0, nullptr, nullptr, nullptr, far);
   return hipGetLastError();
 }
 
@@ -632,13 +721,13 @@ hipError_t trx_launch_group_tx_push(hipStream_t st, const TrxGroupTx &x, int fn0
 // relative to fn0: the caller has seen to it that every datagram of the add call lies within TRXQ_PK_WIN frames of fn0 (else far).
 hipError_t trx_launch_group_tx_both(hipStream_t st, const TrxGroupTx &x, int n, const uint8_t *dgram, const int32_t *a_lf, const int32_t *a_lk,
                                     const int32_t *a_tot, const float *gain_tab26, int far_add, int fn0, int tn0, int n_slots, uint8_t *bits_out,
-                                    float *gain_out, uint8_t *fq_out) {
+                                    float *gain_out, uint8_t *fq_out, int grid) {
   if (n <= 0 || n_slots <= 0) return hipErrorInvalidValue;
   if (x.qcap != kTxQ || x.npool > TRXQ_PK_IDS) return hipErrorInvalidValue;
   const int far = far_add || (long long)tn0 + n_slots >= 8LL * TRXQ_PK_WIN;
   TxGainTab gt;
   for (int q = 0; q < 26; q++) gt.v[q] = gain_tab26[q];
   k_group_tx<true, true><<<dim3((x.S + kTxI - 1) / kTxI), dim3(64 * kTxI), 0, st>>>(
-      x, n, dgram, tx_arrive_args(n, (int32_t *)a_lf, (int32_t *)a_lk, (int32_t *)a_tot), gt, fn0, fn0, tn0, n_slots, (uint32_t *)bits_out, gain_out, fq_out, far);
+      x, n, dgram, tx_arrive_args(n, (int32_t *)a_lf, (int32_t *)a_lk, (int32_t *)a_tot, grid), gt, fn0, fn0, tn0, n_slots, (uint32_t *)bits_out, gain_out, fq_out, far);
   return hipGetLastError();
 }

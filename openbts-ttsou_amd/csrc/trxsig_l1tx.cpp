@@ -356,6 +356,13 @@ int trxsig_l1tx_encode(trxsig_l1tx *l1, int fn, int F, const trxsig_l1tx_in *in,
   return TRXSIG_OK;
 }
 
+void trx_l1tx_last(const trxsig_l1tx *l1, TrxL1txLast *o) {
+  const bool have = l1->last_fn >= 0 && l1->dv.what && l1->dv.bits;
+  o->ctx = l1->c; o->n_arfcn = l1->A;
+  o->fn = have ? l1->last_fn : 0; o->n_frames = have ? l1->last_F : 0;
+  o->what = have ? l1->dv.what : nullptr; o->bits = have ? l1->dv.bits : nullptr;
+}
+
 int trxsig_l1tx_datagrams(trxsig_l1tx *l1, uint8_t *h_dgram, int32_t *h_arfcn, int cap, int *n) {
   if (!l1) return TRXSIG_EINVAL;
   if (!n || cap < 0 || (cap > 0 && (!h_dgram || !h_arfcn)) || l1->last_fn < 0)

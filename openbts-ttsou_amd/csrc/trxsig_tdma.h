@@ -191,6 +191,15 @@ struct TrxL1rxSib {
 };
 void trx_l1rx_sibling(const trxsig_l1rx *l1, TrxL1rxSib *out);
 
+// what trxsig_trxgroup_add_l1tx reads of a trxsig_l1tx (trxsig_l1tx.cpp): its last encode, as left on the context's stream
+struct trxsig_l1tx;
+struct TrxL1txLast {
+  trxsig_ctx *ctx;
+  int n_arfcn, fn, n_frames;         // n_frames = 0: no encode yet (or the workspace that held it is gone)
+  const uint8_t *what, *bits;        // [n_arfcn][8 n_frames], [n_arfcn][8 n_frames][148] (device)
+};
+void trx_l1tx_last(const trxsig_l1tx *l1, TrxL1txLast *out);
+
 hipError_t trx_launch_l1tx_encode(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);
 hipError_t trx_launch_l1tx_mux(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);
 // open (1) / close (0) of global channel ch on copy `cur`: open sets active, cancels idle fill and, where sacch, orders 40 / 0;

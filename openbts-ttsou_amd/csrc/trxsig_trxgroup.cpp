@@ -13,6 +13,8 @@
 
 #include "trxsig_ctx.h"
 #include "trxsig_group.h"
+#include "trxsig_l1tx.h"
+#include "trxsig_tdma.h"
 #include "trxsig_trxgroup.h"
 #include "trxsig_trxstate.h"
 #include "trxsig_txq_lds.h"
@@ -123,6 +125,7 @@ struct trxsig_trxgroup {
   // launches it on its own first (tx_flush_pending)
   bool tx_pend = false;
   int tx_pend_k = 0, tx_pend_n = 0, tx_pend_ref = 0, tx_pend_far = 0;
+  int tx_pend_grid = 0;              // the pending lists came from a multiplexer's grid (trxsig_trxgroup_add_l1tx): a payload block per arrival group
   uint8_t *tx_pin[kTxSets] = {};     // pinned staging blocks the caller receives into (trxsig_trxgroup_tx_staging), in turn
   int tx_pin_cap[kTxSets] = {};
   bool tx_stage_held = false;        // the current set has been handed out and not yet added
@@ -806,7 +809,7 @@ int tx_flush_pending(trxsig_trxgroup *g) {
   g->tx_pend = false;
   G_LIB(tx_wait_arrival(g, k));
   TRX_HIPCHK(g->c, trx_launch_group_tx_ingest(g->tx_q, g->tx, g->tx_pend_n, g->tx_dgram[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->gain_tab,
-                                      g->tx_pend_ref, g->tx_pend_far));
+                                      g->tx_pend_ref, g->tx_pend_far, g->tx_pend_grid));
   G_LIB(tx_q_mark(g, g->tx_read_ev[k]));                   // (the set's device arrays are free behind it; the context's stream joins on it)
   g->tx_read_armed[k] = true;
   return TRXSIG_OK;
@@ -892,7 +895,7 @@ static int tx_add_staged(trxsig_trxgroup *g, int n) {
   g->tx_stage_held = false;
   (void)q;
   G_LIB(tx_flush_pending(g));                               // (an add behind an add: the earlier one's ingest goes first)
-  g->tx_pend = true; g->tx_pend_k = k; g->tx_pend_n = n; g->tx_pend_ref = ref_fn; g->tx_pend_far = far;
+  g->tx_pend = true; g->tx_pend_k = k; g->tx_pend_n = n; g->tx_pend_ref = ref_fn; g->tx_pend_far = far; g->tx_pend_grid = 0;
   return TRXSIG_OK;
 }
 
@@ -918,6 +921,53 @@ int trxsig_trxgroup_add_bursts(trxsig_trxgroup *g, const uint8_t *h_datagrams, c
   std::memcpy(pd, h_datagrams, (size_t)n * TRXSIG_TX_DATAGRAM_BYTES);
   TrxDeviceGuard gd(trxsig_device(c));
   return tx_add_staged(g, n);
+}
+
+// The device-to-device add (include/trxsig_l1tx.h).  The arrival half runs on the CONTEXT'S stream, right behind the encode whose
+// grid it reads: it needs no event to see that grid, and since it moves the payloads into the set's own block an encode enqueued
+// next is ordered behind the last read of the grid by the stream itself.  The set is the next of the staging sets, as for a host
+// add, but where tx_take_set holds the HOST until the set's last readers have run, here the context's stream is made to wait
+// for them; from the seal on (tx_ev[k] behind the arrival kernel) the add is a pending ingest like any other.
+int trxsig_trxgroup_add_l1tx(trxsig_trxgroup *g, trxsig_l1tx *l1) {
+  if (!g || !l1) return TRXSIG_EINVAL;
+  trxsig_ctx *c = g->c;
+  TrxL1txLast e;
+  trx_l1tx_last(l1, &e);
+  if (e.ctx != c) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_add_l1tx: the multiplexer lives on another context (another stream: its grid would be read unordered)", hipSuccess);
+  if (e.n_arfcn != g->S) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_add_l1tx: the multiplexer's ARFCN count is not the group's", hipSuccess);
+  if (e.n_frames <= 0) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_add_l1tx: no encode yet", hipSuccess);
+  if (g->tx_stage_held)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_add_l1tx: a staging block is lent out (trxsig_trxgroup_add_staged first)", hipSuccess);
+  const int S = g->S, F = e.n_frames;
+  const long long n_ll = (long long)trx_group_tx_grid_rounds(F) * 8192;   // the ingest's count: whole rounds of its window
+  if (n_ll > std::numeric_limits<int32_t>::max() / 2)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_add_l1tx: too many frames in one encode (split it)", hipSuccess);
+  const int n = (int)n_ll;
+  TrxDeviceGuard gd(trxsig_device(c));
+  hipStream_t st = (hipStream_t)trxsig_get_stream(c);
+  G_LIB(tx_setup(g));
+  G_LIB(tx_streams(g));
+  const int k = g->tx_set = (g->tx_set + 1) % trxsig_trxgroup::kTxSets;
+  size_t tot_ints = 0;
+  const size_t list_ints = trx_group_tx_arrive_ints(S, n, &tot_ints), dg_bytes = trx_group_tx_grid_bytes(S, F);
+  if (dg_bytes > g->tx_dgram[k].cap || list_ints > g->tx_alf[k].cap || list_ints > g->tx_alk[k].cap || tot_ints > g->tx_atot[k].cap) {
+    // a larger call than any before: the set's arrays are replaced, once whoever may still use the old ones has run
+    if (g->tx_ev_armed[k]) { TRX_HIPCHK(c, hipEventSynchronize(g->tx_ev[k])); g->tx_ev_armed[k] = false; }
+    if (g->tx_read_armed[k]) { TRX_HIPCHK(c, hipEventSynchronize(g->tx_read_ev[k])); g->tx_read_armed[k] = false; }
+    TRX_HIPCHK(c, g->tx_dgram[k].need(dg_bytes, st));
+    TRX_HIPCHK(c, g->tx_alf[k].need(list_ints, st)); TRX_HIPCHK(c, g->tx_alk[k].need(list_ints, st)); TRX_HIPCHK(c, g->tx_atot[k].need(tot_ints, st));
+  }
+  // set k's last upload and arrival kernel (tx_up) and the ingest that read its arrays (tx_q), three adds ago
+  if (g->tx_ev_armed[k]) { TRX_HIPCHK(c, hipStreamWaitEvent(st, g->tx_ev[k], 0)); g->tx_ev_armed[k] = false; }
+  if (g->tx_read_armed[k]) { TRX_HIPCHK(c, hipStreamWaitEvent(st, g->tx_read_ev[k], 0)); g->tx_read_armed[k] = false; }
+  TRX_HIPCHK(c, trx_launch_group_tx_arrive_grid(st, S, F, e.fn, e.what, e.bits, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->tx_dgram[k].p,
+                                                trx_ctx_profiler(c)));
+  G_LIB(tx_seal_set(g, k, st));
+  G_LIB(tx_flush_pending(g));                               // (an add behind an add: the earlier one's ingest goes first)
+  // ref and far as tx_add_staged derives them from the headers: the frames are [fn, fn + F) -- every one within half the packed
+  // entries' window of the first unless the call is that long
+  g->tx_pend = true; g->tx_pend_k = k; g->tx_pend_n = n; g->tx_pend_ref = e.fn; g->tx_pend_far = F - 1 >= TRXQ_PK_WIN / 2; g->tx_pend_grid = 1;
+  return TRXSIG_OK;
 }
 
 int trxsig_trxgroup_push(trxsig_trxgroup *g, int fn, int tn, int n_slots, const uint8_t **d_bits, const float **d_gain,
@@ -957,7 +1007,7 @@ int trxsig_trxgroup_push(trxsig_trxgroup *g, int fn, int tn, int n_slots, const 
     g->tx_pend = false;
     G_LIB(tx_wait_arrival(g, k));
     TRX_HIPCHK(g->c, trx_launch_group_tx_both(q, g->tx, g->tx_pend_n, g->tx_dgram[k].p, g->tx_alf[k].p, g->tx_alk[k].p, g->tx_atot[k].p, g->gain_tab,
-                                      g->tx_pend_far, fn, tn, n_slots, g->tx_bits[o].p, g->tx_gain[o].p, g->tx_fq[o].p));
+                                      g->tx_pend_far, fn, tn, n_slots, g->tx_bits[o].p, g->tx_gain[o].p, g->tx_fq[o].p, g->tx_pend_grid));
     G_LIB(tx_q_mark(g, g->tx_read_ev[k]));
     g->tx_read_armed[k] = true;
   } else {
