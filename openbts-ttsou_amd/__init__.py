@@ -1147,3 +1147,153 @@ class L1Tx:
         d = np.zeros((max(cap, 1), 154), np.uint8); a = np.zeros(max(cap, 1), np.int32)
         self._chk(self.L.trxsig_l1tx_datagrams(self.h, d.ctypes.data, a.ctypes.data, int(cap), C.byref(n)), "trxsig_l1tx_datagrams")
         return d[:n.value], a[:n.value]
+
+
+L1MS_STATE_BYTES = 160                           # TRXSIG_L1MS_STATE_BYTES
+L1MS_NONE, L1MS_TCH, L1MS_XCCH, L1MS_ACCESS = range(4)   # d_what codes of trxsig_l1ms.h
+
+
+class L1MsIn(C.Structure):
+    """trxsig_l1ms_in"""
+    _fields_ = [(n, C.c_void_p) for n in ("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_rach_kind",
+                                          "d_rach_ra", "d_rach_bsic")]
+
+
+class L1MsOut(C.Structure):
+    """trxsig_l1ms_out"""
+    _fields_ = [(n, C.c_int) for n in ("n_arfcn", "n_frames", "n_xcch")] + \
+               [(n, C.c_void_p) for n in ("d_bits", "d_what", "d_ms_power", "d_ms_ta")]
+
+
+class L1MsAir(C.Structure):
+    """trxsig_l1ms_air"""
+    _fields_ = [(n, C.c_void_p) for n in ("d_tch_gain", "d_tch_delay", "d_xcch_gain", "d_xcch_delay", "d_rach_gain",
+                                          "d_rach_delay", "d_amp_of_power")]
+
+
+class L1Ms:
+    """ctypes view of include/trxsig_l1ms.h: the handsets of a cell -- per-channel uplink payloads for whole frames -> timed
+    uplink bursts -> the samples TrxGroup.pull takes, on the device.  comb as for L1Rx."""
+
+    def __init__(self, ctx, comb, bsic, band=900):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, ip, i64 = C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int64
+        L.trxsig_l1ms_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32]
+        L.trxsig_l1ms_destroy.argtypes = [vp]; L.trxsig_l1ms_destroy.restype = None
+        L.trxsig_l1ms_channels.argtypes = [vp, i32]
+        L.trxsig_l1ms_channel.argtypes = [vp, i32, i32, ip, ip, ip, ip]
+        L.trxsig_l1ms_open.argtypes = [vp, i32, i32]
+        L.trxsig_l1ms_close.argtypes = [vp, i32, i32]
+        L.trxsig_l1ms_set_phy.argtypes = [vp, i32, i32, i32]
+        L.trxsig_l1ms_grid.argtypes = [vp, i32, i32, ip, ip, ip]
+        L.trxsig_l1ms_encode.argtypes = [vp, i32, i32, C.POINTER(L1MsIn), vp, C.POINTER(L1MsOut)]
+        L.trxsig_l1ms_radiate.argtypes = [vp, C.POINTER(L1MsAir), vp, i64, i64]
+        L.trxsig_l1ms_state.argtypes = [vp, i32, C.POINTER(vp)]
+        self.comb = np.ascontiguousarray(comb, np.uint8)
+        self.h = vp()
+        rc = L.trxsig_l1ms_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1ms_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self.out = None
+        self._keep = None
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_l1ms_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def channels(self, cls):
+        return self._chk(self.L.trxsig_l1ms_channels(self.h, cls), "trxsig_l1ms_channels")
+
+    def channel(self, cls, chan):
+        """(arfcn, tn, kind, sub) of a channel"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.trxsig_l1ms_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1ms_channel")
+        return tuple(x.value for x in v)
+
+    def open(self, cls, chan):
+        """open of one TCH / XCCH channel (SACCH: the handset back at the band's level nearest 40 dBm, TA 0)."""
+        self._chk(self.L.trxsig_l1ms_open(self.h, cls, chan), "trxsig_l1ms_open")
+
+    def close(self, cls, chan):
+        """close: no new block of the channel is sent until it is opened again."""
+        self._chk(self.L.trxsig_l1ms_close(self.h, cls, chan), "trxsig_l1ms_close")
+
+    def set_phy(self, xcch_chan, power_dbm, ta):
+        """The handset of a SACCH channel: power (0..40 dBm, taken to the band's nearest level) and TA (0..63)."""
+        self._chk(self.L.trxsig_l1ms_set_phy(self.h, int(xcch_chan), int(power_dbm), int(ta)), "trxsig_l1ms_set_phy")
+
+    def grid(self, fn, n_frames):
+        """(nb_tch, nb_xcch, n_rach) of a call"""
+        v = [C.c_int() for _ in range(3)]
+        self._chk(self.L.trxsig_l1ms_grid(self.h, int(fn), int(n_frames), *[C.byref(x) for x in v]), "trxsig_l1ms_grid")
+        return tuple(x.value for x in v)
+
+    def encode(self, fn, n_frames, tch_kind=None, tch_payload=None, xcch_kind=None, xcch_payload=None, rach_kind=None,
+               rach_ra=None, rach_bsic=None, sibling=None):
+        """Grids as torch uint8 tensors on the context's device (or None for a class without channels); sibling: an L1Tx."""
+        ins = L1MsIn()
+        keep = (tch_kind, tch_payload, xcch_kind, xcch_payload, rach_kind, rach_ra, rach_bsic)
+        for name, t in zip(("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_rach_kind", "d_rach_ra",
+                            "d_rach_bsic"), keep):
+            if t is not None:
+                assert t.is_contiguous() and t.dtype.itemsize == 1
+                setattr(ins, name, t.data_ptr() if t.numel() else 1)
+        out = L1MsOut()
+        self._chk(self.L.trxsig_l1ms_encode(self.h, int(fn), int(n_frames), C.byref(ins), sibling.h if sibling is not None else None,
+                                            C.byref(out)), "trxsig_l1ms_encode")
+        self._keep = keep
+        self.out = out
+        return out
+
+    def radiate(self, samples, slot_stride, arfcn_stride, tch_gain=None, tch_delay=None, xcch_gain=None, xcch_delay=None,
+                rach_gain=None, rach_delay=None, amp_of_power=None):
+        """The last encode as samples into `samples` (a complex64 / float32 tensor or a device address), strides in complex
+        samples.  Gains: complex64 (or float32 [n, 2]) tensors, delays float32 (symbols), amp_of_power float32 [41]."""
+        air = L1MsAir()
+        keep = (tch_gain, tch_delay, xcch_gain, xcch_delay, rach_gain, rach_delay, amp_of_power)
+        for name, t in zip(("d_tch_gain", "d_tch_delay", "d_xcch_gain", "d_xcch_delay", "d_rach_gain", "d_rach_delay",
+                            "d_amp_of_power"), keep):
+            if t is not None:
+                assert t.is_contiguous()
+                setattr(air, name, t.data_ptr() if t.numel() else 1)
+        self._chk(self.L.trxsig_l1ms_radiate(self.h, C.byref(air), _ptr(samples), int(slot_stride), int(arfcn_stride)),
+                  "trxsig_l1ms_radiate")
+        self._keep_air = keep
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._chk(self.L.trxsig_l1ms_state(self.h, cls, C.byref(p)), "trxsig_l1ms_state")
+        return p.value
+
+    def collect(self, state=True):
+        """The last encode's outputs as host numpy arrays (synchronises the context's stream)."""
+        import torch
+        from .frontend import _DevView
+        np, o = self.np, self.out
+        self.ctx.synchronize()
+
+        def get(p, shape, ts):
+            if p is None or int(np.prod(shape)) == 0:
+                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32}[ts])
+            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        A, F, X = o.n_arfcn, o.n_frames, o.n_xcch
+        r = dict(bits=get(o.d_bits, (A, 8 * F, 148), "|u1"), what=get(o.d_what, (A, 8 * F), "|u1"),
+                 ms_power=get(o.d_ms_power, (X,), "<i4"), ms_ta=get(o.d_ms_ta, (X,), "<i4"))
+        if state:
+            for cls, key in ((L1_TCH, "tch_state"), (L1_XCCH, "xcch_state")):
+                r[key] = get(self.state(cls), (self.channels(cls), L1MS_STATE_BYTES), "|u1")
+        return r

@@ -1,6 +1,6 @@
-// trxsig_fec_enc.h -- internal: the downlink block coders' device routines, shared by trxsig_fec.hip (k_fec_xcch_encode,
-// k_fec_tch_encode) and trxsig_l1tx.hip (k_l1tx_encode, k_l1tx_mux).  Moved here unchanged; each including file gets its own
-// copy of the constant tables.
+// trxsig_fec_enc.h -- internal: the block coders' device routines, shared by trxsig_fec.hip (k_fec_xcch_encode,
+// k_fec_tch_encode), trxsig_l1tx.hip (k_l1tx_encode, k_l1tx_mux) and trxsig_l1ms.hip (k_l1ms_encode, k_l1ms_mux; the access
+// burst's coder rach_e36 is used there alone).  Each including file gets its own copy of the constant tables.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +65,30 @@ struct TchInv {                                            // (burst b, e-bit j)
   }
 };
 __device__ __constant__ const TchInv kTchInv;
+
+// The access burst's 36 coded bits (GSM 05.03 4.6; the inverse of RACHL1Decoder::writeLowSide, GSML1FEC.cpp:470-510), bit i of
+// the result = e[i]: u[0..7] = the RA, LSB first (the decoder's LSB8MSB reads it back MSB first); u[8..13] = ~(bsic ^ parity),
+// MSB first, parity = the 6-bit encoderShift register (generator 0x6f) over u[0..7]; u[14..17] = 0; the rate-1/2 coder.
+__device__ __forceinline__ unsigned long long rach_e36(unsigned ra, unsigned bsic) {
+  unsigned st = 0;
+  for (int k = 0; k < 8; k++) {
+    const unsigned fb = ((st >> 5) ^ (ra >> k)) & 1u;
+    st <<= 1;
+    if (fb) st ^= 0x6fu;
+  }
+  const unsigned p = ~(bsic ^ st) & 0x3fu;
+  unsigned u = ra & 0xffu;
+  for (int i = 0; i < 6; i++) u |= ((p >> (5 - i)) & 1u) << (8 + i);
+  unsigned long long e = 0;
+  unsigned acc = 0;
+  for (int q = 0; q < 18; q++) {
+    acc = (acc << 1) | ((u >> q) & 1u);
+    const unsigned long long gg = (kGen >> (2 * (acc & 31u))) & 3ULL;
+    e |= (gg >> 1) << (2 * q);
+    e |= (gg & 1ULL) << (2 * q + 1);
+  }
+  return e;
+}
 
 enum { TCH_FILLER = 0, TCH_SPEECH = 1, TCH_FACCH = 2 };
 constexpr int kTchState = 32;                              // TRXSIG_TCH_TX_STATE_BYTES

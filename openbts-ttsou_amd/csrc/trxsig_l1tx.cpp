@@ -8,7 +8,7 @@
 
 #include "trxsig_ctx.h"
 #include "trxsig_l1tx.h"
-#include "trxsig_tdma.h"
+#include "trxsig_l1ms_dev.h"
 
 namespace {
 const TrxTdmaMap kDl[TRX_N_DL_MAPS] = TRX_TDMA_DL_MAPS_INIT;
@@ -361,6 +361,11 @@ void trx_l1tx_last(const trxsig_l1tx *l1, TrxL1txLast *o) {
   o->ctx = l1->c; o->n_arfcn = l1->A;
   o->fn = have ? l1->last_fn : 0; o->n_frames = have ? l1->last_F : 0;
   o->what = have ? l1->dv.what : nullptr; o->bits = have ? l1->dv.bits : nullptr;
+}
+
+void trx_l1tx_sibling(const trxsig_l1tx *l1, TrxL1txSib *o) {
+  o->ctx = l1->c; o->n_arfcn = l1->A; o->n_xcch = l1->n[1]; o->comb = l1->comb.data();
+  o->xcch = l1->d_st + (size_t)l1->cur * l1->n_all + l1->n[0];
 }
 
 int trxsig_l1tx_datagrams(trxsig_l1tx *l1, uint8_t *h_dgram, int32_t *h_arfcn, int cap, int *n) {
