@@ -35,7 +35,8 @@
  * trxsig_l1ms_set_phy sets power POWER[band][encodePower(band, power_dbm)] and the TA.  With a sibling trxsig_l1tx, every open
  * SACCH channel takes the sibling's current orders for the same channel number at the start of the call: power =
  * POWER[band][encodePower(band, ordered)], TA = (int)(orderedTA + 0.5F) -- what the header trxsig_l1tx writes decodes to.  Every
- * block of the call sees that one snapshot.  Without a sibling only set_phy and open move the state.
+ * block of the call sees that one snapshot.  Without a sibling only set_phy and open move the state -- unless the object follows
+ * a trxsig_l1msrx (trxsig_l1ms_follow): then the orders are the ones that object DECODED from the downlink's SACCH headers.
  *
  * Open / close.  A new object has every channel open.  A closed channel's grid entries are ignored and nothing new of it is
  * sent (a block already begun goes out to its end); its encoder state is left as it is.  The RACH has no active flag.
@@ -118,6 +119,15 @@ int trxsig_l1ms_radiate(trxsig_l1ms *ms, const trxsig_l1ms_air *air, trxsig_c32 
                         int64_t arfcn_stride);
 /* the channel records of a class (TCH / XCCH), [n_chan][TRXSIG_L1MS_STATE_BYTES] (device; opaque; for tests and checkpoints) */
 int trxsig_l1ms_state(trxsig_l1ms *ms, int cls, void **d_state);
+
+/* Follow the SACCH orders a trxsig_l1msrx (trxsig_l1msrx.h) decodes.  rx must have ms's context and plan (n_arfcn, h_comb,
+ * bsic, band), else TRXSIG_EINVAL; rx = NULL stops following.  While following, an encode with sibling == NULL gives every open
+ * SACCH channel, at the start of the call, power POWER[band][encodePower(band, ord_power)] and TA ord_ta, read from rx's device
+ * state in stream order: one snapshot per call, what trxsig_l1ms_set_phy(chan, ord_power, ord_ta) before the encode would
+ * give.  An encode with a non-NULL sibling while following is TRXSIG_EINVAL.  The caller stops following before it destroys
+ * rx.  No launch. */
+struct trxsig_l1msrx;
+int trxsig_l1ms_follow(trxsig_l1ms *ms, const struct trxsig_l1msrx *rx);
 
 #ifdef __cplusplus
 }

@@ -1192,6 +1192,7 @@ class L1Ms:
         L.trxsig_l1ms_encode.argtypes = [vp, i32, i32, C.POINTER(L1MsIn), vp, C.POINTER(L1MsOut)]
         L.trxsig_l1ms_radiate.argtypes = [vp, C.POINTER(L1MsAir), vp, i64, i64]
         L.trxsig_l1ms_state.argtypes = [vp, i32, C.POINTER(vp)]
+        L.trxsig_l1ms_follow.argtypes = [vp, vp]
         self.comb = np.ascontiguousarray(comb, np.uint8)
         self.h = vp()
         rc = L.trxsig_l1ms_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
@@ -1274,6 +1275,11 @@ class L1Ms:
                   "trxsig_l1ms_radiate")
         self._keep_air = keep
 
+    def follow(self, rx):
+        """Follow the SACCH orders an L1MsRx decodes (same context and plan); None stops following."""
+        self._chk(self.L.trxsig_l1ms_follow(self.h, rx.h if rx is not None else None), "trxsig_l1ms_follow")
+        self._follow = rx
+
     def state(self, cls):
         p = C.c_void_p()
         self._chk(self.L.trxsig_l1ms_state(self.h, cls, C.byref(p)), "trxsig_l1ms_state")
@@ -1296,4 +1302,126 @@ class L1Ms:
         if state:
             for cls, key in ((L1_TCH, "tch_state"), (L1_XCCH, "xcch_state")):
                 r[key] = get(self.state(cls), (self.channels(cls), L1MS_STATE_BYTES), "|u1")
+        return r
+
+
+L1_BCCH, L1_SCH, L1_FCCH = 4, 5, 6               # the downlink-only classes of trxsig_l1msrx.h
+L1_CCCH_C5, L1_BCCH_C5, L1_SCH_C5, L1_FCCH_C5 = 7, 8, 9, 10   # mapping kinds (TRXSIG_L1_*)
+
+
+class L1MsRxOut(C.Structure):
+    """trxsig_l1msrx_out"""
+    _fields_ = [(n, C.c_int) for n in ("n_tch", "n_xcch", "n_ccch", "n_bcch", "nb_tch", "nb_ctl", "sch_cap", "fcch_cap")] + \
+               [(n, C.c_void_p) for n in ("d_tch_status", "d_tch_frames", "d_facch", "d_tch_fer", "d_tch_fn",
+                                          "d_xcch_status", "d_xcch_frames", "d_xcch_fer", "d_xcch_fn",
+                                          "d_ccch_status", "d_ccch_frames", "d_ccch_fer", "d_ccch_fn",
+                                          "d_bcch_status", "d_bcch_frames", "d_bcch_fer", "d_bcch_fn", "d_bcch_tc",
+                                          "d_sch_fn", "d_sch_rfn", "d_sch_present", "d_sch_ok", "d_sch_bsic", "d_sch_sync",
+                                          "d_fcch_fn", "d_fcch_ones",
+                                          "d_tch_rssi", "d_tch_timing", "d_xcch_rssi", "d_xcch_timing", "d_ccch_rssi",
+                                          "d_ccch_timing", "d_bcch_rssi", "d_bcch_timing", "d_ord_power", "d_ord_ta")]
+
+
+class L1MsRx:
+    """ctypes view of include/trxsig_l1msrx.h: the handsets' receive side -- downlink bursts (a TrxGroupResult of whole frames)
+    -> the logical channels' payloads, the SCH's frame number and BSIC, the FCCH, and the SACCH orders, on the device.  comb as
+    for L1Rx."""
+
+    def __init__(self, ctx, comb, bsic, band=900):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
+        L.trxsig_l1msrx_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32]
+        L.trxsig_l1msrx_destroy.argtypes = [vp]; L.trxsig_l1msrx_destroy.restype = None
+        L.trxsig_l1msrx_channels.argtypes = [vp, i32]
+        L.trxsig_l1msrx_channel.argtypes = [vp, i32, i32, ip, ip, ip, ip]
+        L.trxsig_l1msrx_open.argtypes = [vp, i32, i32]
+        L.trxsig_l1msrx_close.argtypes = [vp, i32, i32]
+        L.trxsig_l1msrx_state.argtypes = [vp, i32, C.POINTER(vp)]
+        L.trxsig_l1msrx_decode.argtypes = [vp, C.POINTER(TrxGroupResult), i32, i32, C.POINTER(L1MsRxOut)]
+        self.comb = np.ascontiguousarray(comb, np.uint8)
+        self.h = vp()
+        rc = L.trxsig_l1msrx_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1msrx_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self.out = None
+
+    def destroy(self):
+        """trxsig_l1msrx_destroy (an L1Ms that follows this object stops following first)."""
+        if self.h:
+            self.L.trxsig_l1msrx_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def channels(self, cls):
+        return self._chk(self.L.trxsig_l1msrx_channels(self.h, cls), "trxsig_l1msrx_channels")
+
+    def channel(self, cls, chan):
+        """(arfcn, tn, kind, sub) of a channel"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.trxsig_l1msrx_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1msrx_channel")
+        return tuple(x.value for x in v)
+
+    def open(self, cls, chan):
+        """open of one TCH / XCCH / CCCH / BCCH channel (FER reset; SACCH: orders 40 dBm / TA 0)."""
+        self._chk(self.L.trxsig_l1msrx_open(self.h, cls, chan), "trxsig_l1msrx_open")
+
+    def close(self, cls, chan):
+        """close: the channel's bursts are ignored until it is opened again."""
+        self._chk(self.L.trxsig_l1msrx_close(self.h, cls, chan), "trxsig_l1msrx_close")
+
+    def decode(self, res, fn, wire=True):
+        """res: a TrxGroupResult (of a pull of downlink samples, or built from tensors); whole frames from (fn, TN 0)."""
+        out = L1MsRxOut()
+        self._chk(self.L.trxsig_l1msrx_decode(self.h, C.byref(res), int(fn), int(bool(wire)), C.byref(out)), "trxsig_l1msrx_decode")
+        self.out = out
+        return out
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._chk(self.L.trxsig_l1msrx_state(self.h, cls, C.byref(p)), "trxsig_l1msrx_state")
+        return p.value
+
+    def collect(self, state=True):
+        """The last decode's outputs as host numpy arrays (synchronises the context's stream)."""
+        import torch
+        from .frontend import _DevView
+        np, o = self.np, self.out
+        self.ctx.synchronize()
+
+        def get(p, shape, ts):
+            if p is None or int(np.prod(shape)) == 0:
+                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32, "<f4": np.float32}[ts])
+            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        T, bt, bx, S, Fc = o.n_tch, o.nb_tch, o.nb_ctl, o.sch_cap, o.fcch_cap
+        r = dict(tch_status=get(o.d_tch_status, (T, bt), "|u1"), tch=get(o.d_tch_frames, (T, bt, 33), "|u1"),
+                 facch=get(o.d_facch, (T, bt, 23), "|u1"), tch_fer=get(o.d_tch_fer, (T, bt), "<f4"),
+                 tch_fn=get(o.d_tch_fn, (T, bt), "<i4"), tch_rssi=get(o.d_tch_rssi, (T,), "<i4"),
+                 tch_timing=get(o.d_tch_timing, (T,), "<i4"))
+        for key, n in (("xcch", o.n_xcch), ("ccch", o.n_ccch), ("bcch", o.n_bcch)):
+            f = lambda name: getattr(o, "d_%s_%s" % (key, name))
+            r.update({key + "_status": get(f("status"), (n, bx), "|u1"), key: get(f("frames"), (n, bx, 23), "|u1"),
+                      key + "_fer": get(f("fer"), (n, bx), "<f4"), key + "_fn": get(f("fn"), (n, bx), "<i4"),
+                      key + "_rssi": get(f("rssi"), (n,), "<i4"), key + "_timing": get(f("timing"), (n,), "<i4")})
+        r["bcch_tc"] = get(o.d_bcch_tc, (o.n_bcch, bx), "<i4")
+        r["ord_power"] = get(o.d_ord_power, (o.n_xcch,), "<i4")
+        r["ord_ta"] = get(o.d_ord_ta, (o.n_xcch,), "<i4")
+        r["sch"] = dict(fn=get(o.d_sch_fn, (S,), "<i4"), present=get(o.d_sch_present, (S,), "|u1"), ok=get(o.d_sch_ok, (S,), "|u1"),
+                        bsic=get(o.d_sch_bsic, (S,), "|u1"), rfn=get(o.d_sch_rfn, (S,), "<i4"), sync=get(o.d_sch_sync, (S,), "|u1"))
+        r["fcch"] = dict(fn=get(o.d_fcch_fn, (Fc,), "<i4"), ones=get(o.d_fcch_ones, (Fc,), "<i4"))
+        if state:
+            r["tch_state"] = get(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
+            for cls, key, n in ((L1_XCCH, "xcch", o.n_xcch), (L1_CCCH, "ccch", o.n_ccch), (L1_BCCH, "bcch", o.n_bcch)):
+                r[key + "_state"] = get(self.state(cls), (n, XCCH_RX_STATE_BYTES), "|u1")
         return r

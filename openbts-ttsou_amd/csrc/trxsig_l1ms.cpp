@@ -11,6 +11,7 @@
 #include "trxsig_ctx.h"
 #include "trxsig_l1ms.h"
 #include "trxsig_l1ms_dev.h"
+#include "trxsig_l1msrx_dev.h"
 
 namespace {
 const TrxTdmaMap kUl[TRX_N_MAPS] = TRX_TDMA_MAPS_INIT;
@@ -64,6 +65,7 @@ struct trxsig_l1ms {
   size_t work_bytes = 0;
   TrxL1msDev dv{};
   int last_F = 0, last_rach = 0;        // the last encode (radiate); 0: none
+  const trxsig_l1msrx *fol = nullptr;   // the trxsig_l1msrx whose decoded orders the handsets follow, or null
 };
 
 namespace {
@@ -299,6 +301,19 @@ int trxsig_l1ms_state(trxsig_l1ms *ms, int cls, void **d_state) {
   return TRXSIG_OK;
 }
 
+int trxsig_l1ms_follow(trxsig_l1ms *ms, const trxsig_l1msrx *rx) {
+  if (!ms) return TRXSIG_EINVAL;
+  if (rx) {
+    TrxL1msrxFollow fo{};
+    trx_l1msrx_follow(rx, &fo);
+    if (fo.ctx != ms->c || fo.n_arfcn != ms->A || fo.bsic != ms->bsic || fo.band != ms->band || fo.n_xcch != ms->n[1] ||
+        std::memcmp(fo.comb, ms->comb.data(), ms->comb.size()) != 0)
+      return fail(ms, "trxsig_l1ms_follow: the trxsig_l1msrx's plan (or context) is not this object's");
+  }
+  ms->fol = rx;
+  return TRXSIG_OK;
+}
+
 int trxsig_l1ms_encode(trxsig_l1ms *ms, int fn, int F, const trxsig_l1ms_in *in, const trxsig_l1tx *sib, trxsig_l1ms_out *out) {
   if (!ms) return TRXSIG_EINVAL;
   if (!in || !out || fn < 0 || fn >= kTrxHyperframe || F <= 0)
@@ -309,6 +324,7 @@ int trxsig_l1ms_encode(trxsig_l1ms *ms, int fn, int F, const trxsig_l1ms_in *in,
   if ((ms->n[0] && (!in->d_tch_kind || !in->d_tch_payload)) || (ms->n[1] && (!in->d_xcch_kind || !in->d_xcch_payload)) ||
       (k.n_rach && (!in->d_rach_kind || !in->d_rach_ra)))
     return fail(ms, "trxsig_l1ms_encode: NULL grid for a class that has channels");
+  if (sib && ms->fol) return fail(ms, "trxsig_l1ms_encode: a sibling while following a trxsig_l1msrx");
   TrxL1txSib sb{};
   if (sib) {
     trx_l1tx_sibling(sib, &sb);
@@ -339,8 +355,14 @@ int trxsig_l1ms_encode(trxsig_l1ms *ms, int fn, int F, const trxsig_l1ms_in *in,
   d.kind[0] = in->d_tch_kind; d.payload[0] = in->d_tch_payload;
   d.kind[1] = in->d_xcch_kind; d.payload[1] = in->d_xcch_payload;
   d.rach_kind = in->d_rach_kind; d.rach_ra = in->d_rach_ra; d.rach_bsic = in->d_rach_bsic;
-  k.has_sib = sib ? 1 : 0;
+  k.has_sib = sib ? 1 : ms->fol ? 2 : 0;
   d.sib = sb.xcch;
+  d.fol_power = d.fol_ta = nullptr;
+  if (ms->fol) {
+    TrxL1msrxFollow fo{};
+    trx_l1msrx_follow(ms->fol, &fo);
+    d.fol_power = fo.ord_power; d.fol_ta = fo.ord_ta;
+  }
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   TRX_HIPCHK(c, trx_launch_l1ms_encode(st, k, d));
   TRX_HIPCHK(c, trx_launch_l1ms_mux(st, k, d));

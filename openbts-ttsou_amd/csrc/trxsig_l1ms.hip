@@ -68,11 +68,13 @@ __device__ int encode_power(int band, int power) {
   return (int)code;
 }
 
-// the handset of XCCH channel ci during the call: the sibling's current orders as its header decodes them, else the record's
+// the handset of XCCH channel ci during the call: the sibling's current orders as its header decodes them (or the orders the
+// followed trxsig_l1msrx decoded from that header), else the record's
 struct Phy { int power, ta; };
 __device__ Phy call_phy(const TrxL1msCall &c, const TrxL1msDev &d, const TrxL1msChan &S, int ci, bool sacch) {
   if (!sacch) return Phy{ -1, -1 };
   if (!c.has_sib || !S.active) return Phy{ S.power, S.ta };
+  if (c.has_sib == 2) return Phy{ c_pw[c.band][encode_power(c.band, d.fol_power[ci])], d.fol_ta[ci] };
   const TrxL1txChan &o = d.sib[ci];
   return Phy{ c_pw[c.band][encode_power(c.band, o.ord_pow)], (int)__fadd_rn(o.ord_ta, 0.5F) };
 }

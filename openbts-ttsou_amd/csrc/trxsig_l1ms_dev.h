@@ -12,7 +12,7 @@ struct TrxL1msCall {
   int n_rach;                        // RACH frames of the call (0 without a combination-V slot)
   long long unit0[2];                // per class: the first scratch unit ([n_chan][nb] after it)
   int r104, r102, r51, r26;          // fn mod 104 / 102 / 51 / 26
-  int cur, has_sib, band, bsic;
+  int cur, has_sib, band, bsic;      // has_sib: 0 none, 1 a sibling trxsig_l1tx's orders, 2 a followed trxsig_l1msrx's
   long long p_first[TRX_N_MAPS], p_end[TRX_N_MAPS], base[TRX_N_MAPS];
 };
 
@@ -45,6 +45,7 @@ struct TrxL1msDev {
   uint8_t *bits, *what;              // [n_arfcn][8 F][148], [n_arfcn][8 F]
   int32_t *who;                      // [n_arfcn][8 F]: the slot's channel within its class, or its RACH entry
   const TrxL1txChan *sib;            // the sibling's XCCH records (current copy), or null
+  const int32_t *fol_power, *fol_ta; // the followed trxsig_l1msrx's decoded SACCH orders (XCCH-indexed), or null
 };
 
 // what trxsig_l1ms reads of a sibling trxsig_l1tx (trxsig_l1tx.cpp): its plan and its XCCH channels' current records

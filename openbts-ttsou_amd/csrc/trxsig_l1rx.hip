@@ -11,6 +11,7 @@
 //   verdict ok = tail_ok && BSIC == the cell's (RACHL1Decoder::writeLowSide), a thread per list entry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "trxsig_l1_phy.h"
 #include "trxsig_launch.h"
 #include "trxsig_tdma.h"
 
@@ -18,28 +19,6 @@ namespace {
 
 __constant__ TrxTdmaMap c_maps[TRX_N_MAPS] = TRX_TDMA_MAPS_INIT;
 __constant__ int8_t c_power[3][32] = TRX_POWER_TABLES_INIT;
-
-// the burst's RSSI and timing as the decoder records them: trxsig_trxgroup_collect's integers (Transceiver.cpp:400-402) through
-// the datagram (one signed byte of RSSI, negated by TRXManager; timing as int16, / 256.0F, into an int parameter)
-__device__ inline void burst_phy(const trx_c32 *amp, const float *toa, int r, int sps, int32_t *rssi, int32_t *timing) {
-  const trx_c32 a = amp[r];
-  const float n2 = __fadd_rn(__fmul_rn(a.i, a.i), __fmul_rn(a.r, a.r));
-  const float absA = (float)sqrt((double)n2);
-  const double x = 9450.0 / (double)absA;
-  double l = log10(x);
-  // where x is an exact power of ten the host's log10 returns the integer exactly and floor() sits on it: pin the device's
-  // value there too, so the floor boundary is decided the same way (tests/test_gpu_l1rx.py, test_rssi_at_the_floor_boundaries)
-  const double ri = rint(l);
-  if (ri >= 0.0 && ri <= 22.0 && fabs(l - ri) < 1e-9) {
-    double p = 1.0;
-    for (int i = 0; i < (int)ri; i++) p *= 10.0;              // exact up to 1e22
-    if (p == x) l = ri;
-  }
-  const int db = (int)floor(20.0 * l);
-  const int t = (int)round((double)toa[r] * 256.0 / (double)sps);
-  *rssi = -(int)(signed char)db;
-  *timing = (int)(int16_t)t / 256;
-}
 
 __global__ __launch_bounds__(256) void k_l1rx_demux(TrxL1rxCall c, TrxL1rxDev d, const int32_t *__restrict__ row,
                                                     const uint8_t *__restrict__ valid, const float *__restrict__ soft,
@@ -138,6 +117,17 @@ __global__ __launch_bounds__(256) void k_l1rx_finish(TrxL1rxCall c, TrxL1rxDev d
   }
 }
 
+// burst_phy for a list of rows, a lane per channel: last[ch] is the row of the last burst channel ch accepted in the call, or
+// -1 (its RSSI / timing stay).  The handsets' demultiplexer (trxsig_l1msrx.hip) records the rows and leaves the arithmetic here,
+// beside k_l1rx_demux's: the device library's double log10 stays in this file's kernels (tests/test_no_fma_contraction.py).
+__global__ __launch_bounds__(256) void k_l1rx_demux_phy(const int32_t *__restrict__ last, int n, const trx_c32 *__restrict__ amp,
+                                                        const float *__restrict__ toa, int sps, int32_t *rssi, int32_t *timing) {
+  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ch >= n) return;
+  const int r = last[ch];
+  if (r >= 0) burst_phy(amp, toa, r, sps, &rssi[ch], &timing[ch]);
+}
+
 __global__ void k_l1rx_set(uint8_t *active, int ch, int open, uint8_t *state_fer, int32_t *ms_power, int32_t *ms_ta, int sacch) {
   if (threadIdx.x != 0) return;
   active[ch] = open ? 1 : 0;
@@ -164,6 +154,13 @@ hipError_t trx_launch_l1rx_finish(hipStream_t st, const TrxL1rxCall &call, const
   if (prof) prof->begin(TRXSIG_K_L1RX_FINISH, st);
   k_l1rx_finish<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(call, dv);
   if (prof) prof->end(TRXSIG_K_L1RX_FINISH, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_l1rx_phy(hipStream_t st, const int32_t *last, int n, const trx_c32 *amp, const float *toa, int sps,
+                               int32_t *rssi, int32_t *timing) {
+  if (n <= 0) return hipSuccess;
+  k_l1rx_demux_phy<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(last, n, amp, toa, sps, rssi, timing);
   return hipGetLastError();
 }
 

@@ -98,6 +98,9 @@ struct TrxL1rxDev {
 hipError_t trx_launch_l1rx_demux(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, const int32_t *row,
                                  const uint8_t *valid, const float *soft, const trx_c32 *amp, const float *toa, TrxProfiler *prof);
 hipError_t trx_launch_l1rx_finish(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, TrxProfiler *prof);
+// burst_phy (trxsig_l1_phy.h) for n channels: channel ch's RSSI / timing from row last[ch] of amp / toa; last[ch] < 0 keeps them
+hipError_t trx_launch_l1rx_phy(hipStream_t st, const int32_t *last, int n, const trx_c32 *amp, const float *toa, int sps,
+                               int32_t *rssi, int32_t *timing);
 // open (1) / close (0) channel `ch` of the object (index over all classes): the active flag; on open also FER = 0 (state_fer)
 // and, where `sacch`, power 40 / TA 0 (ms_power / ms_ta, unused otherwise)
 hipError_t trx_launch_l1rx_set(hipStream_t st, uint8_t *active, int ch, int open, uint8_t *state_fer, int32_t *ms_power,
