@@ -622,8 +622,9 @@ int trxsig_kernel_count(void);
  *     estimate runs a lane per burst instead of a wave per burst (default 4096).  TRXSIG_TUNE_RXRES_WPB: windows per workgroup of the
  *     receive resampler (0 = chosen from the launch size); TRXSIG_TUNE_RXRES_ROWS: 1 = its tap rows in visiting order (default),
  *     0 = in branch order.  TRXSIG_TUNE_CHAN_TPW: tiles per workgroup of the shared-filter channeliser (0 = chosen from the launch size).
- *   TRXSIG_TUNE_GROUP_REPLAY: the Transceiver group's receive state machine (trxsig_trxgroup.h).  0 = a wave per ARFCN and 64-timeslot
- *     segment that visits only the timeslots at which the state can move (calls of up to 1,024 timeslots; the default), 1 = a lane per
+ *   TRXSIG_TUNE_GROUP_REPLAY: the Transceiver group's receive state machine (trxsig_trxgroup.h).  0 = a wave per ARFCN and segment
+ *     (32 timeslots in calls of up to 512, 64 in longer ones: at most 16 segments) that visits only the timeslots at which the state
+ *     can move (calls of up to 1,024 timeslots; the default), 1 = a lane per
  *     ARFCN (and segment) stepping through every timeslot (round 4's kernels, also what longer calls take). */
 enum { TRXSIG_TUNE_NORMAL_PATH = 0, TRXSIG_TUNE_RACH_PATH = 1, TRXSIG_TUNE_GENERIC_TAPS = 2, TRXSIG_TUNE_SPECULATIVE_PEAK = 3,
        TRXSIG_TUNE_CHAIN_LAG = 4, TRXSIG_TUNE_CHAIN_SPIN = 5, TRXSIG_TUNE_DEMOD_BESIDE = 7, TRXSIG_TUNE_BESIDE_DET_CUS = 8,

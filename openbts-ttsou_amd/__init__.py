@@ -742,6 +742,7 @@ class TrxGroup:
         L.trxsig_trxgroup_expected_corr_type.argtypes = [vp, i32, i32, i32]
         L.trxsig_trxgroup_pull.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(TrxGroupResult)]
         L.trxsig_trxgroup_pull_host.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32]
+        L.trxsig_trxgroup_pull_bursts.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(TrxGroupResult)]
         L.trxsig_trxgroup_pull_rxfe.argtypes = [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(TrxGroupResult)]
         L.trxsig_trxgroup_collect.argtypes = [vp, vp, vp, vp, vp, vp]
         L.trxsig_trxgroup_energy_threshold.argtypes = [vp, i32, C.POINTER(C.c_double)]
@@ -792,6 +793,15 @@ class TrxGroup:
         self._chk(self.L.trxsig_trxgroup_pull(self.h, _ptr(samples), slot_stride, arfcn_stride, burst_len, fn, tn, n_slots, C.byref(res)),
                   "trxsig_trxgroup_pull")
         self.n_slots = n_slots
+        return res
+
+    def pull_bursts(self, samples, offset, length, n_per_arfcn, fn, tn):
+        """pull on LISTED bursts: burst t of ARFCN a is entry a*n_per_arfcn + t of offset / length (int32 device tensors or addresses,
+        samples into `samples`); (fn, tn) = the time of burst 0.  The samples are only read: entries may share a burst."""
+        res = TrxGroupResult()
+        self._chk(self.L.trxsig_trxgroup_pull_bursts(self.h, _ptr(samples), _ptr(offset), _ptr(length), n_per_arfcn, fn, tn, C.byref(res)),
+                  "trxsig_trxgroup_pull_bursts")
+        self.n_slots = n_per_arfcn
         return res
 
     def pull_rxfe(self, fe, iq, fn):
