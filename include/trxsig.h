@@ -439,6 +439,15 @@ int trxsig_fec_tch_set_filler(trxsig_ctx *ctx, const uint8_t *h_c456);
 int trxsig_fec_tch_encode_batch(trxsig_ctx *ctx, int n_chan, int n_blocks, const uint8_t *d_kind, const uint8_t *d_payload,
                                 const uint8_t *d_tsc, void *d_state, uint8_t *d_bits);
 int trxsig_fec_sch_encode_batch(trxsig_ctx *ctx, const uint32_t *d_fn, const uint8_t *d_bsic, int n, uint8_t *d_bits);
+/* SCH decoder, the inverse of trxsig_fec_sch_encode_batch (the reference, a base station, has none: the arithmetic is the one
+ * trxsig_l1msrx.h states for its SCH entries, and the device code is shared with it).  Row i = the burst's 148 soft values at
+ * d_soft + i * soft_stride, as they are (no UDP hop): e[0..39) = values 3..41, e[39..78) = 106..144; SoftVector::decode gives
+ * u[39]; d_ok[i] = the four tail bits are zero and u[25..35) is the inverted parity (generator 0x575) of u[0..25); LSB8MSB is
+ * undone on the first three octets; d_bsic[i] = BSIC (6 bits), and d_rfn[i] = 1326 T1 + 51 ((T3 - T2) mod 26) + T3 with T3 =
+ * 10 T3' + 1 from T1 (11) T2 (5) T3' (3), all MSB first -- written whether or not the parity holds.  soft_stride >= 148;
+ * d_rfn 4-byte aligned; n == 0 is a no-op. */
+int trxsig_fec_sch_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft_stride, int n, uint8_t *d_ok, uint8_t *d_bsic,
+                                int32_t *d_rfn);
 
 /* ---- the free-standing vector primitives of sigProcLib.h (csrc/trxsig_prim.hip) -------------------------------
  * On the burst path these only run fused into the burst kernels above; the stand-alone forms complete the

@@ -8,10 +8,10 @@
  * The decoder here is the inverse of trxsig_fec_sch_encode_batch as trxsig.h states that encoder, built from the reference's
  * generic SoftVector::decode; it is pinned by this project's own model (tests/l1_msrx_model.py), not by the reference.
  *
- * Not here: acquisition.  Finding SCH / FCCH bursts in samples (a synchronisation-burst correlator, frequency estimation from
- * the FCCH) is not part of this object; the normal-burst detector of a group pull does not find them, so a caller that wants
- * their slots decoded supplies the rows itself.  Combination IV is not supported.  The group's detectors and tables are used
- * as they are.
+ * Acquisition -- finding the FCCH and SCH bursts in raw samples, the frequency offset, the frame grid, the frame number and the
+ * BSIC -- is trxsig_l1acq.h; the normal-burst detector of a group pull does not find those bursts, so a caller that wants their
+ * slots decoded here supplies the rows (trxsig_l1acq_detect_sch_batch produces SCH rows).  Combination IV is not supported.
+ * The group's detectors and tables are used as they are.
  *
  * Plan and channels.  h_comb, bsic and band mean what they mean for trxsig_l1rx_create: h_comb[a][tn] in 0 / 1 (I) / 5 (V, on
  * ARFCN 0 TN 0 only) / 7 (VII); anything else is TRXSIG_EINVAL.  Classes: TRXSIG_L1_TCH and TRXSIG_L1_XCCH numbered exactly as

@@ -120,6 +120,7 @@ def _load(path):
         L.trxsig_fec_tch_set_filler.argtypes = [vp, vp]
         L.trxsig_fec_tch_encode_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
         L.trxsig_fec_sch_encode_batch.argtypes = [vp, vp, vp, i32, vp]
+        L.trxsig_fec_sch_decode_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp]
         L.trxsig_fec_tch_decode_stream.argtypes = [vp, i32, i32, vp, i32, C.c_int64, vp, vp, i32, vp, vp, vp, vp, vp]
         L.trxsig_fec_xcch_decode_stream.argtypes = [vp, i32, i32, vp, i32, C.c_int64, vp, i32, vp, vp, vp, vp]
         # sigProcLib.h's free-standing primitives
@@ -505,6 +506,11 @@ class TrxSig:
         """SCH bursts for fn[n] (uint32 / int32) and bsic[n] (uint8) -> bits[n, 148] (all device)."""
         self._chk(self.L.trxsig_fec_sch_encode_batch(self.h, _ptr(fn), _ptr(bsic), fn.numel(), _ptr(bits)),
                   "trxsig_fec_sch_encode_batch")
+
+    def fec_sch_decode(self, soft, n, ok, bsic, rfn, soft_stride=None):
+        """The inverse of fec_sch_encode: soft[n, >= 148] float32 -> ok[n], bsic[n] (uint8), rfn[n] (int32) (all device)."""
+        self._chk(self.L.trxsig_fec_sch_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n, _ptr(ok), _ptr(bsic),
+                                                     _ptr(rfn)), "trxsig_fec_sch_decode_batch")
 
     def fec_tch_decode(self, soft, n_bursts, tch, tch_good, stolen, facch=None, facch_ok=None, wire=True, soft_stride=None):
         self._chk(self.L.trxsig_fec_tch_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n_bursts, int(wire),
@@ -1434,4 +1440,94 @@ class L1MsRx:
             r["tch_state"] = get(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
             for cls, key, n in ((L1_XCCH, "xcch", o.n_xcch), (L1_CCCH, "ccch", o.n_ccch), (L1_BCCH, "bcch", o.n_bcch)):
                 r[key + "_state"] = get(self.state(cls), (n, XCCH_RX_STATE_BYTES), "|u1")
+        return r
+
+
+ACQ_FCCH, ACQ_WINDOW, ACQ_SCH, ACQ_DECODED = 1, 2, 4, 8   # trxsig_l1acq_out.d_state bits (TRXSIG_ACQ_*)
+ACQ_FCCH_THRESH, ACQ_SCH_THRESH = 0.5, 8.0                # TRXSIG_L1ACQ_FCCH_THRESH / _SCH_THRESH
+ACQ_MAX_WINDOW = 256                                      # TRXSIG_L1ACQ_MAX_WINDOW (symbols)
+
+
+class L1AcqOut(C.Structure):
+    """trxsig_l1acq_out"""
+    _fields_ = [("n_streams", C.c_int), ("soft_stride", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("d_state", "d_fcch_k", "d_fcch_metric", "d_fcch_c", "d_fcch_e", "d_arg", "d_omega",
+                                          "d_sch_w0", "d_sch_ptm", "d_sch_amp", "d_sch_toa", "d_soft", "d_ok", "d_bsic", "d_rfn")]
+
+
+class L1Acq:
+    """ctypes view of include/trxsig_l1acq.h: mobile-side acquisition -- raw downlink samples of a C0 carrier -> the FCCH's
+    position and frequency offset, the SCH burst's soft values, FN and BSIC, and where the frame grid lies, on the device."""
+
+    def __init__(self, ctx, max_streams, max_samples):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
+        L.trxsig_l1acq_create.argtypes = [C.POINTER(vp), vp, i32, i32]
+        L.trxsig_l1acq_destroy.argtypes = [vp]; L.trxsig_l1acq_destroy.restype = None
+        L.trxsig_l1acq_search.argtypes = [vp, vp, C.c_int64, i32, i32, f32, f32, C.POINTER(L1AcqOut)]
+        L.trxsig_l1acq_detect_sch_batch.argtypes = [vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, i32]
+        L.trxsig_l1acq_sequence.argtypes = [vp, vp, vp, vp]
+        self.h = vp()
+        rc = L.trxsig_l1acq_create(C.byref(self.h), ctx.h, int(max_streams), int(max_samples))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1acq_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self.out = None
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_l1acq_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def sequence(self):
+        """(seq[64 sps] complex64, gain complex64, toa float32): the SCH correlation sequence as built at create."""
+        np = self.np
+        seq = np.zeros(64 * self.ctx.sps, np.complex64); gain = np.zeros(1, np.complex64); toa = np.zeros(1, np.float32)
+        self._chk(self.L.trxsig_l1acq_sequence(self.h, seq.ctypes.data, gain.ctypes.data, toa.ctypes.data), "trxsig_l1acq_sequence")
+        return seq, gain[0], toa[0]
+
+    def search(self, samples, stream_stride, n_samples, n_streams, fcch_thresh=ACQ_FCCH_THRESH, sch_thresh=ACQ_SCH_THRESH):
+        """samples: device tensor (complex64, or float32 pairs) holding n_streams streams stream_stride samples apart."""
+        out = L1AcqOut()
+        self._chk(self.L.trxsig_l1acq_search(self.h, _ptr(samples), int(stream_stride), int(n_samples), int(n_streams),
+                                             float(fcch_thresh), float(sch_thresh), C.byref(out)), "trxsig_l1acq_search")
+        self.out = out
+        return out
+
+    def detect_sch(self, samples, offset, length, flags, amp, toa, soft, omega=None, ptm=None, hard=None,
+                   detect_thresh=ACQ_SCH_THRESH, soft_stride=None):
+        """Stage 2 on caller-chosen windows (all device tensors): offset / length int32 [B]; flags uint8 [B], amp [B, 2], toa [B],
+        soft [B, >= 148] are written; omega float32 [B] (None: no frequency shift), ptm float32 [B], hard uint8 [B, stride]."""
+        self._chk(self.L.trxsig_l1acq_detect_sch_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), offset.numel(), _ptr(omega),
+                                                       float(detect_thresh), _ptr(flags), _ptr(amp), _ptr(toa), _ptr(ptm), _ptr(soft),
+                                                       _ptr(hard), soft_stride or soft.shape[-1]), "trxsig_l1acq_detect_sch_batch")
+
+    def collect(self):
+        """The last search's outputs as host numpy arrays (synchronises the context's stream)."""
+        import torch
+        from .frontend import _DevView
+        np, o = self.np, self.out
+        self.ctx.synchronize()
+        S = o.n_streams
+
+        def get(p, shape, ts):
+            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        r = dict(state=get(o.d_state, (S,), "|u1"), fcch_k=get(o.d_fcch_k, (S,), "<i4"), fcch_metric=get(o.d_fcch_metric, (S,), "<f4"),
+                 fcch_c=get(o.d_fcch_c, (S, 2), "<f4").view(np.complex64).ravel(), fcch_e=get(o.d_fcch_e, (S,), "<f4"),
+                 arg=get(o.d_arg, (S,), "<f4"), omega=get(o.d_omega, (S,), "<f4"), sch_w0=get(o.d_sch_w0, (S,), "<i4"),
+                 sch_ptm=get(o.d_sch_ptm, (S,), "<f4"), sch_amp=get(o.d_sch_amp, (S, 2), "<f4").view(np.complex64).ravel(),
+                 sch_toa=get(o.d_sch_toa, (S,), "<f4"), soft=get(o.d_soft, (S, o.soft_stride), "<f4"),
+                 ok=get(o.d_ok, (S,), "|u1"), bsic=get(o.d_bsic, (S,), "|u1"), rfn=get(o.d_rfn, (S,), "<i4"))
         return r

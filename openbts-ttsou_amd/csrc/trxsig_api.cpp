@@ -1284,6 +1284,17 @@ int trxsig_fec_sch_encode_batch(trxsig_ctx *c, const uint32_t *d_fn, const uint8
   TRX_HIPCHK(c, trx_launch_fec_sch_encode(c->stream, d_fn, d_bsic, n, xts, d_bits, c->prof));
   return TRXSIG_OK;
 }
+int trxsig_fec_sch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int n, uint8_t *d_ok, uint8_t *d_bsic,
+                                int32_t *d_rfn) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n < 0 || soft_stride < 148 || (n > 0 && (!d_soft || !d_ok || !d_bsic || !d_rfn)) || ((uintptr_t)d_rfn & 3))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_sch_decode_batch: bad argument");
+  if (n == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec(c->stream, TRX_FEC_MODE_SCH, d_soft, soft_stride, 78, 39, n, 0, d_ok, d_bsic, reinterpret_cast<uint8_t *>(d_rfn), 0,
+                           c->prof));
+  return TRXSIG_OK;
+}
 namespace {
 int fec_rx_stream(trxsig_ctx *c, const char *what, int tch, int n_chan, int n_slots, const float *d_soft, int soft_stride,
                   int64_t n_rows, const int32_t *d_index, const uint8_t *d_b0, int wire, void *d_state, uint8_t *d_status,

@@ -21,6 +21,7 @@
 
 #include "trxsig_fec_enc.h"
 #include "trxsig_launch.h"
+#include "trxsig_sch_dec.h"
 
 namespace {
 
@@ -73,7 +74,7 @@ __device__ __forceinline__ float wire_value(float v) {
   return (float)(unsigned char)q / 256.0F;                 // TRXManager.cpp:231
 }
 
-enum { FEC_GENERIC = 0, FEC_XCCH = 1, FEC_RACH = 2, FEC_TCH = 3 };
+enum { FEC_GENERIC = 0, FEC_XCCH = 1, FEC_RACH = 2, FEC_TCH = 3, FEC_SCH = TRX_FEC_MODE_SCH };
 
 // The trellis of SoftVector::decode (bv:334-399, metric tables bv:462-485) for the code word of this lane's 16-lane row:
 // lane s IS survivor s.  fetch(p) loads soft value p of the row's code word (called for p < n of a live row, eight loads
@@ -216,6 +217,8 @@ __device__ __forceinline__ bool tch_finish(const unsigned *uw, int s, CBit cbit,
 // MODE FEC_TCH    : block b = bursts 4b..4b+7 (diagonal deinterleaver, fec:1108-1116), class 1 = c[0..378) decoded,
 //                   class 2 = c[378..456) sliced (fec:1133-1163); out0 = d[260] packed MSB first (33 octets),
 //                   out1 = good (parity of class 1a and tail), out2 = stolen (Hl of the block's last burst, fec:1077).
+// MODE FEC_SCH    : block b = burst b, e = burst[3..42) + burst[106..145) (the inverse of trxsig_fec_sch_encode_batch); out0 = ok,
+//                   out1 = BSIC, out2 = the decoded frame number as int32 (trx_sch_verdict, trxsig_sch_dec.h).
 // ilv8 (FEC_XCCH only): read c[] through the TCH deinterleaver instead -- the FACCH decode of a stolen block.
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ soft, long long in_stride, int n, int nout,
@@ -235,12 +238,26 @@ __global__ __launch_bounds__(64) void k_fec_viterbi(const float *__restrict__ so
       return soft[(size_t)(4 * blk + B) * in_stride + (j < 57 ? 3 + j : 88 + (j - 57))];
     } else if (MODE == FEC_RACH) {
       return soft[(size_t)blk * in_stride + 49 + p];
+    } else if (MODE == FEC_SCH) {
+      return soft[(size_t)blk * in_stride + (p < 39 ? 3 + p : 106 + (p - 39))];
     } else {
       return soft[(size_t)blk * in_stride + p];
     }
   };
   auto finish = [&](float v, int) -> float { return wire ? wire_value(v) : v; };
   const unsigned outw = fec_trellis(ktab[row], n, nout + kDeferral, live, lane, fetch, finish);
+  if (MODE == FEC_SCH) {                                   // u[39]: bits 0..31 in the row's lane 0, 32..38 in its lane 1
+    const unsigned lo = __shfl(outw, 16 * row, 64), hi = __shfl(outw, 16 * row + 1, 64);
+    if (live && s == 0) {
+      unsigned ok, bsic;
+      int rfn;
+      trx_sch_verdict([&](int q) -> unsigned { return q < 32 ? (lo >> q) & 1u : (hi >> (q - 32)) & 1u; }, &ok, &bsic, &rfn);
+      out0[blk] = (uint8_t)ok;
+      out1[blk] = (uint8_t)bsic;
+      reinterpret_cast<int32_t *>(out2)[blk] = rfn;
+    }
+    return;
+  }
   if (!live) return;
 
   if (MODE == FEC_GENERIC) {
@@ -718,6 +735,7 @@ hipError_t trx_launch_fec(hipStream_t st, int mode, const float *soft, long long
     case FEC_XCCH: k_fec_viterbi<FEC_XCCH><<<grid, block, 0, st>>>(soft, in_stride, n, nout, nblk, wire, ilv8, out0, out1, out2, out_stride); break;
     case FEC_RACH: k_fec_viterbi<FEC_RACH><<<grid, block, 0, st>>>(soft, in_stride, n, nout, nblk, wire, ilv8, out0, out1, out2, out_stride); break;
     case FEC_TCH: k_fec_viterbi<FEC_TCH><<<grid, block, 0, st>>>(soft, in_stride, n, nout, nblk, wire, ilv8, out0, out1, out2, out_stride); break;
+    case FEC_SCH: k_fec_viterbi<FEC_SCH><<<grid, block, 0, st>>>(soft, in_stride, n, nout, nblk, wire, ilv8, out0, out1, out2, out_stride); break;
     default: return hipErrorInvalidValue;
   }
   if (prof) prof->end(TRXSIG_K_FEC, st);

@@ -1,0 +1,212 @@
+// trxsig_l1acq.cpp -- the acquisition object's host side (include/trxsig_l1acq.h): the SCH correlation sequence built once with
+// the table generator's restatements, the per-stream arrays and the stage-2 workspace on the device, and per call the launches
+// on the context's stream: k_l1acq_fcch, k_l1acq_pick, k_l1acq_shift, the correlation over every lag and peakDetect
+// (trxsig_prim.hip), k_l1acq_verdict, the exact demodulator, the SCH decode (k_fec_viterbi's SCH mode), k_l1acq_finish.
+#include <hip/hip_runtime_api.h>
+
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "trxsig_ctx.h"
+#include "trxsig_l1acq_dev.h"
+#include "trxsig_tablegen.h"
+
+namespace {
+inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+constexpr int kSoft = 148;
+}  // namespace
+
+struct trxsig_l1acq {
+  trxsig_ctx *c = nullptr;
+  int sps = 0, max_streams = 0, max_samples = 0, max_tiles = 0;
+  std::vector<trx_c32> h_seq;          // 64 * sps
+  trx_c32 gain{};
+  float seq_toa = 0.0f;
+  // persistent: the sequence, the per-stream arrays of a search, the tiles' records
+  void *d_persist = nullptr;
+  trx_c32 *d_seq = nullptr;
+  TrxAcqStreams sv{};
+  float *ptm = nullptr, *toa = nullptr, *soft = nullptr;
+  trx_c32 *amp = nullptr;
+  uint8_t *ok = nullptr, *bsic = nullptr, *flags = nullptr;
+  int32_t *rfn = nullptr;
+  float *tile_m = nullptr, *tile_e = nullptr;
+  int32_t *tile_k = nullptr;
+  trx_c32 *tile_c = nullptr;
+  // stage-2 workspace for `cap` windows; grows only
+  void *d_work = nullptr;
+  int cap = 0;
+  trx_c32 *y = nullptr, *corr = nullptr, *peak = nullptr;
+  float *pidx = nullptr, *dtoa = nullptr;
+  int32_t *woff = nullptr, *wlen = nullptr, *doff = nullptr, *dlen = nullptr;
+};
+
+namespace {
+int fail(trxsig_l1acq *a, const char *what) { return trx_ctx_fail(a ? a->c : nullptr, TRXSIG_EINVAL, what, hipSuccess); }
+
+// the stage-2 workspace for B windows (a growth waits for the stream first); the caller holds the TrxDeviceGuard
+int ensure_work(trxsig_l1acq *a, int B) {
+  if (B <= a->cap) return TRXSIG_OK;
+  trxsig_ctx *c = a->c;
+  const size_t n = (size_t)B;
+  const size_t sizes[] = { n * TRX_ACQ_WMAX * sizeof(trx_c32), n * TRX_ACQ_WMAX * sizeof(trx_c32), n * sizeof(trx_c32),   // y, corr, peak
+                           n * 4, n * 4, n * 4, n * 4, n * 4, n * 4 };                                                     // pidx, dtoa, woff, wlen, doff, dlen
+  constexpr int k = sizeof sizes / sizeof sizes[0];
+  size_t off[k], total = 0;
+  for (int i = 0; i < k; i++) { off[i] = total; total += al(sizes[i]); }
+  TRX_HIPCHK(c, hipStreamSynchronize((hipStream_t)trxsig_get_stream(c)));
+  if (a->d_work) { TRX_HIPCHK(c, hipFree(a->d_work)); a->d_work = nullptr; a->cap = 0; }
+  TRX_HIPCHK(c, hipMalloc(&a->d_work, total));
+  TRX_HIPCHK(c, hipMemset(a->d_work, 0, total));
+  char *b = (char *)a->d_work;
+  a->y = (trx_c32 *)(b + off[0]); a->corr = (trx_c32 *)(b + off[1]); a->peak = (trx_c32 *)(b + off[2]);
+  a->pidx = (float *)(b + off[3]); a->dtoa = (float *)(b + off[4]);
+  a->woff = (int32_t *)(b + off[5]); a->wlen = (int32_t *)(b + off[6]); a->doff = (int32_t *)(b + off[7]); a->dlen = (int32_t *)(b + off[8]);
+  a->cap = B;
+  return TRXSIG_OK;
+}
+
+// stage 2 on B windows already described by (base64 | off32, len): everything after the window set-up
+int stage2(trxsig_l1acq *a, const trxsig_c32 *d_samples, const long long *base64, const int32_t *off32, const int32_t *len,
+           const float *omega, int B, float thresh, int search, uint8_t *flags, trxsig_c32 *amp, float *toa, float *ptm, float *soft,
+           uint8_t *hard, int soft_stride, uint8_t *state) {
+  trxsig_ctx *c = a->c;
+  hipStream_t st = (hipStream_t)trxsig_get_stream(c);
+  const TrxTables *dT = (const TrxTables *)trxsig_tables_device(c);
+  TrxProfiler *prof = trx_ctx_profiler(c);
+  const int sps = a->sps;
+  TRX_HIPCHK(c, trx_launch_l1acq_shift(st, sps, dT, (const trx_c32 *)d_samples, base64, off32, len, omega, B, a->y, a->woff, a->wlen));
+  TRX_HIPCHK(c, trx_launch_convolve(st, a->y, a->woff, a->wlen, B, TRXSIG_L1ACQ_MAX_WINDOW * sps, a->d_seq, 64 * sps, TRXSIG_NO_DELAY, 0,
+                                    1, 0, 0, a->corr, a->woff));
+  TRX_HIPCHK(c, trx_launch_peak_detect(st, dT, a->corr, a->woff, a->wlen, B, a->peak, a->pidx, nullptr));
+  TRX_HIPCHK(c, trx_launch_l1acq_verdict(st, sps, a->corr, a->wlen, a->peak, a->pidx, B, a->gain, a->seq_toa, thresh, search, flags,
+                                         (trx_c32 *)amp, toa, ptm, a->doff, a->dlen, a->dtoa, state));
+  // acquisition always demodulates with the exact arithmetic, whatever trxsig_set_soft_mode says
+  TRX_HIPCHK(c, trx_launch_demod(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, soft,
+                                 hard, kSoft, soft_stride, prof, TRXSIG_SOFT_EXACT));
+  return TRXSIG_OK;
+}
+}  // namespace
+
+int trxsig_l1acq_create(trxsig_l1acq **out, trxsig_ctx *c, int max_streams, int max_samples) {
+  if (!out || !c) return TRXSIG_EINVAL;
+  *out = nullptr;
+  if (max_streams < 1 || max_streams > 65535 || max_samples < 1 || (long long)max_streams * max_samples > 0x7fffffffLL)
+    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1acq_create: bad argument", hipSuccess);
+  trxsig_l1acq *a = new (std::nothrow) trxsig_l1acq;
+  if (!a) return TRXSIG_ENOMEM;
+  a->c = c; a->sps = trxsig_sps(c); a->max_streams = max_streams; a->max_samples = max_samples;
+  a->max_tiles = trx_acq_tiles(a->sps, max_samples);
+  {
+    std::unique_ptr<TrxTables> T(new (std::nothrow) TrxTables);
+    a->h_seq.resize(64 * (size_t)a->sps);
+    if (!T || trx_build_tables(T.get(), a->sps) != 0 || trx_build_sch_sequence(T.get(), a->h_seq.data(), &a->gain, &a->seq_toa) != 0) {
+      delete a;
+      return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1acq_create: the correlation sequence", hipSuccess);
+    }
+  }
+  const size_t S = (size_t)max_streams, NT = S * (size_t)(a->max_tiles > 0 ? a->max_tiles : 1);
+  const size_t sz[] = { a->h_seq.size() * sizeof(trx_c32),
+                        S, S * 4, S * 4, S * 8, S * 4, S * 4, S * 4, S * 4, S * 8, S * 4,        // state, k, m, c, e, arg, omega, w0, base, wlen
+                        S * 4, S * 4, S * 8, S * kSoft * 4, S, S, S, S * 4,                       // ptm, toa, amp, soft, ok, bsic, flags, rfn
+                        NT * 4, NT * 4, NT * 8, NT * 4 };                                         // tiles: m, k, c, e
+  constexpr int n = sizeof sz / sizeof sz[0];
+  size_t off[n], total = 0;
+  for (int i = 0; i < n; i++) { off[i] = total; total += al(sz[i]); }
+  TrxDeviceGuard g(trxsig_device(c));
+  if (hipMalloc(&a->d_persist, total) != hipSuccess) {
+    delete a;
+    return trx_ctx_fail(c, TRXSIG_ENOMEM, "trxsig_l1acq_create: device allocation", hipSuccess);
+  }
+  char *b = (char *)a->d_persist;
+  a->d_seq = (trx_c32 *)(b + off[0]);
+  TrxAcqStreams &s = a->sv;
+  s.state = (uint8_t *)(b + off[1]); s.fcch_k = (int32_t *)(b + off[2]); s.fcch_m = (float *)(b + off[3]);
+  s.fcch_c = (trx_c32 *)(b + off[4]); s.fcch_e = (float *)(b + off[5]); s.arg = (float *)(b + off[6]); s.omega = (float *)(b + off[7]);
+  s.w0 = (int32_t *)(b + off[8]); s.base = (long long *)(b + off[9]); s.wlen = (int32_t *)(b + off[10]);
+  a->ptm = (float *)(b + off[11]); a->toa = (float *)(b + off[12]); a->amp = (trx_c32 *)(b + off[13]); a->soft = (float *)(b + off[14]);
+  a->ok = (uint8_t *)(b + off[15]); a->bsic = (uint8_t *)(b + off[16]); a->flags = (uint8_t *)(b + off[17]); a->rfn = (int32_t *)(b + off[18]);
+  a->tile_m = (float *)(b + off[19]); a->tile_k = (int32_t *)(b + off[20]); a->tile_c = (trx_c32 *)(b + off[21]); a->tile_e = (float *)(b + off[22]);
+  hipError_t e = hipMemset(a->d_persist, 0, total);
+  if (e == hipSuccess) e = hipMemcpy(a->d_seq, a->h_seq.data(), sz[0], hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(a->d_persist);
+    delete a;
+    return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_l1acq_create: upload", e);
+  }
+  const int rc = ensure_work(a, max_streams);
+  if (rc != TRXSIG_OK) {
+    if (a->d_work) (void)hipFree(a->d_work);
+    (void)hipFree(a->d_persist);
+    delete a;
+    return rc;
+  }
+  trx_ctx_retain(c);
+  *out = a;
+  return TRXSIG_OK;
+}
+
+void trxsig_l1acq_destroy(trxsig_l1acq *a) {
+  if (!a) return;
+  {
+    TrxDeviceGuard g(trxsig_device(a->c));
+    (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(a->c));
+    if (a->d_work) (void)hipFree(a->d_work);
+    if (a->d_persist) (void)hipFree(a->d_persist);
+  }
+  trx_ctx_release(a->c);
+  delete a;
+}
+
+int trxsig_l1acq_sequence(const trxsig_l1acq *a, trxsig_c32 *h_seq, trxsig_c32 *h_gain, float *h_toa) {
+  if (!a) return TRXSIG_EINVAL;
+  if (h_seq) std::memcpy(h_seq, a->h_seq.data(), a->h_seq.size() * sizeof(trx_c32));
+  if (h_gain) { h_gain->re = a->gain.r; h_gain->im = a->gain.i; }
+  if (h_toa) *h_toa = a->seq_toa;
+  return TRXSIG_OK;
+}
+
+int trxsig_l1acq_search(trxsig_l1acq *a, const trxsig_c32 *d_samples, int64_t stream_stride, int n_samples, int n_streams,
+                        float fcch_thresh, float sch_thresh, trxsig_l1acq_out *out) {
+  if (!a) return TRXSIG_EINVAL;
+  if (!d_samples || !out || n_streams < 1 || n_streams > a->max_streams || n_samples < 1 || n_samples > a->max_samples ||
+      stream_stride < n_samples)
+    return fail(a, "trxsig_l1acq_search: bad argument");
+  trxsig_ctx *c = a->c;
+  TrxDeviceGuard g(trxsig_device(c));
+  hipStream_t st = (hipStream_t)trxsig_get_stream(c);
+  const int n_tiles = trx_acq_tiles(a->sps, n_samples);
+  const TrxAcqStreams &s = a->sv;
+  TRX_HIPCHK(c, trx_launch_l1acq_fcch(st, a->sps, (const trx_c32 *)d_samples, stream_stride, n_samples, n_streams, n_tiles, a->tile_m,
+                                      a->tile_k, a->tile_c, a->tile_e));
+  TRX_HIPCHK(c, trx_launch_l1acq_pick(st, a->sps, stream_stride, n_samples, n_streams, n_tiles, a->tile_m, a->tile_k, a->tile_c,
+                                      a->tile_e, fcch_thresh, s));
+  const int rc = stage2(a, d_samples, s.base, nullptr, s.wlen, s.omega, n_streams, sch_thresh, 1, a->flags, (trxsig_c32 *)a->amp, a->toa,
+                        a->ptm, a->soft, nullptr, kSoft, s.state);
+  if (rc != TRXSIG_OK) return rc;
+  TRX_HIPCHK(c, trx_launch_fec(st, TRX_FEC_MODE_SCH, a->soft, kSoft, 78, 39, n_streams, 0, a->ok, a->bsic, reinterpret_cast<uint8_t *>(a->rfn), 0,
+                               trx_ctx_profiler(c)));
+  TRX_HIPCHK(c, trx_launch_l1acq_finish(st, n_streams, a->ok, s.state));
+  out->n_streams = n_streams; out->soft_stride = kSoft;
+  out->d_state = s.state; out->d_fcch_k = s.fcch_k; out->d_fcch_metric = s.fcch_m; out->d_fcch_c = (const trxsig_c32 *)s.fcch_c;
+  out->d_fcch_e = s.fcch_e; out->d_arg = s.arg; out->d_omega = s.omega; out->d_sch_w0 = s.w0; out->d_sch_ptm = a->ptm;
+  out->d_sch_amp = (const trxsig_c32 *)a->amp; out->d_sch_toa = a->toa; out->d_soft = a->soft; out->d_ok = a->ok; out->d_bsic = a->bsic;
+  out->d_rfn = a->rfn;
+  return TRXSIG_OK;
+}
+
+int trxsig_l1acq_detect_sch_batch(trxsig_l1acq *a, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                                  const float *d_omega, float detect_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa,
+                                  float *d_ptm, float *d_soft, uint8_t *d_hard, int soft_stride) {
+  if (!a) return TRXSIG_EINVAL;
+  if (B < 0 || B > 65535 || soft_stride < kSoft || (B > 0 && (!d_samples || !d_offset || !d_length || !d_flags || !d_amp || !d_toa || !d_soft)))
+    return fail(a, "trxsig_l1acq_detect_sch_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(trxsig_device(a->c));
+  const int rc = ensure_work(a, B);
+  if (rc != TRXSIG_OK) return rc;
+  return stage2(a, d_samples, nullptr, d_offset, d_length, d_omega, B, detect_thresh, 0, d_flags, d_amp, d_toa, d_ptm, d_soft, d_hard,
+                soft_stride, nullptr);
+}

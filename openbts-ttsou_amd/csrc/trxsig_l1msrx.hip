@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "trxsig_l1msrx_dev.h"
+#include "trxsig_sch_dec.h"
 
 namespace {
 
@@ -147,25 +148,7 @@ __global__ __launch_bounds__(256) void k_l1msrx_finish(TrxL1msrxCall c, TrxL1msr
     int rfn = 0;
     if (d.sch_present[i]) {
       const uint8_t *u = d.sch_u + (size_t)i * 39;
-      unsigned dw = 0, par = 0, sent = 0;                     // dw: bit 24 - q = u[q]
-      for (int q = 0; q < 25; q++) {
-        const unsigned b = u[q] & 1u;
-        dw = (dw << 1) | b;
-        const unsigned fb = ((par >> 9) ^ b) & 1u;            // the encoder's parity register, generator 0x575
-        par <<= 1;
-        if (fb) par ^= 0x575u;
-      }
-      for (int k = 0; k < 10; k++) sent = (sent << 1) | (u[25 + k] & 1u);
-      const unsigned tail = (u[35] | u[36] | u[37] | u[38]) & 1u;
-      ok = (tail == 0 && sent == (~par & 0x3ffu)) ? 1u : 0u;
-      unsigned D = 0;                                         // LSB8MSB undone on the first three octets: bit 24 stays
-      for (int q = 0; q < 25; q++) {
-        const int src = q < 24 ? 8 * (q >> 3) + 7 - (q & 7) : 24;
-        D |= ((dw >> (24 - src)) & 1u) << (24 - q);
-      }
-      bsic = (D >> 19) & 63u;
-      const int t1 = (int)((D >> 8) & 2047u), t2 = (int)((D >> 3) & 31u), t3 = 10 * (int)(D & 7u) + 1;
-      rfn = 1326 * t1 + 51 * ((((t3 - t2) % 26) + 26) % 26) + t3;
+      trx_sch_verdict([&](int q) -> unsigned { return u[q]; }, &ok, &bsic, &rfn);   // trxsig_sch_dec.h
       sync = (ok && rfn == d.sch_fn[i] && bsic == (unsigned)c.bsic) ? 1u : 0u;
     }
     d.sch_ok[i] = (uint8_t)ok; d.sch_bsic[i] = (uint8_t)bsic; d.sch_sync[i] = (uint8_t)sync; d.sch_rfn[i] = rfn;

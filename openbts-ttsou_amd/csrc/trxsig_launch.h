@@ -227,7 +227,9 @@ inline bool trx_eq52_geometry(const TrxTables *hT, int tsc) {
 // L1 FEC soft decode (trxsig_fec.hip).  mode 0: generic SoftVector::decode of nblk blocks of n soft values ->
 // nout bits (one byte each) at out0 + b*out_stride; mode 1: XCCH (four bursts per block, in_stride = floats per
 // burst): out0 = 23 octets per block, out1 = parity ok; mode 2: RACH (one burst per block): out0 = tail ok,
-// out1 = BSIC, out2 = RA.  wire != 0: the UDP hop's 8-bit quantisation of the soft values first.
+// out1 = BSIC, out2 = RA; mode 4: SCH (one burst per block, n = 78, nout = 39): out0 = ok, out1 = BSIC, out2 = the decoded
+// frame number, an int32 array.  wire != 0: the UDP hop's 8-bit quantisation of the soft values first.
+#define TRX_FEC_MODE_SCH 4   // what the SCH callers pass (trxsig_fec_sch_decode_batch, trxsig_l1acq_search); FEC_SCH in trxsig_fec.hip
 hipError_t trx_launch_fec(hipStream_t st, int mode, const float *soft, long long in_stride, int n, int nout, int nblk,
                           int wire, uint8_t *out0, uint8_t *out1, uint8_t *out2, long long out_stride, TrxProfiler *prof,
                           int ilv8 = 0 /* mode 1 through the 8-burst TCH deinterleaver (FACCH); mode 3 = TCH: out0 = 33

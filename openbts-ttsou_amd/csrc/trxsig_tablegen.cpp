@@ -201,3 +201,20 @@ int trx_build_tables(TrxTables *T, int sps) {
 // the 26 training-sequence bits of TSC 0..7 as '0'/'1' characters (GSM 05.02 5.2.3; GSM/GSMCommon.cpp:44-53)
 const char *trx_training_sequence(int tsc) { return (tsc >= 0 && tsc < 8) ? kTSC[tsc] : nullptr; }
 const char *trx_sch_extended_training_sequence() { return kXTS; }
+
+// The SCH correlation sequence of include/trxsig_l1acq.h from the restatements above: modulateBurst(XTS, gsmPulse, 0, sps),
+// scaleVector by (-1, 0) (the sequence starts at bit 42 of its burst and j^42 = -1: generateMidamble's reasoning for bit 66),
+// gain = peakDetect(correlate(seq, seq, NO_DELAY), &toa).  seq: 64 * sps entries.
+int trx_build_sch_sequence(const TrxTables *T, trx_c32 *seq, trx_c32 *gain, float *toa) {
+  if (!T || !seq || !gain || !toa || !(T->sps == 1 || T->sps == 2 || T->sps == 4)) return -1;
+  const int sps = (int)T->sps;
+  Trig tr = { T->cosT, T->sinT };
+  cvec pulse(2 * sps + 1);
+  for (int i = 0; i < 2 * sps + 1; i++) pulse[i] = mk(T->pulse[i], 0.0f);
+  cvec s = modulate(*T, kXTS, 64, pulse, true);
+  for (auto &z : s) z = mul(z, mk(-1.0f, 0.0f));
+  cvec ac = correlateNoDelay(s, s);
+  *gain = peakDetect(tr, ac, toa);
+  std::memcpy(seq, s.data(), s.size() * sizeof(cx));
+  return 0;
+}
