@@ -34,6 +34,22 @@ def fcch_tol(sps):
 
 
 # ---- stage 1 ---------------------------------------------------------------------------------------------------------------
+def _window_sums(v, L):
+    """sum(v[k : k + L]) for every k in float64 WITHOUT A SUBTRACTION: per-segment inclusive suffix and prefix scans, a window is
+    one suffix plus one prefix (the header's scheme).  A differenced running sum is not good enough for a reference even in
+    float64: beside slots 90 dB up it errs by 1.9e-4 (sps 1) and 4.3e-4 (sps 4) on the metric of a quiet frequency burst --
+    beyond fcch_tol -- where direct window sums and these scans agree to 1e-13."""
+    n = len(v)
+    nseg = (n + L - 1) // L + 1
+    pad = np.zeros(nseg * L, v.dtype); pad[:n] = v
+    seg = pad.reshape(nseg, L)
+    pre = np.cumsum(seg, axis=1)
+    suf = np.cumsum(seg[:, ::-1], axis=1)[:, ::-1]
+    k = np.arange(n - L + 1)
+    j, r = k // L, k % L
+    return suf[j, r] + np.where(r > 0, pre[j + 1, np.maximum(r - 1, 0)], 0)
+
+
 def fcch_metric64(x, sps):
     """(C[k], E[k], m[k]) for k in [0, N - sps - L], float64; empty where the stream has no window"""
     x = np.asarray(x).astype(np.complex128)
@@ -45,10 +61,9 @@ def fcch_metric64(x, sps):
         d = x[sps:] * np.conj(x[:-sps]) * (-1j)
         e = 0.5 * (np.abs(x[:-sps]) ** 2 + np.abs(x[sps:]) ** 2)
         bad = ~(np.isfinite(d.real) & np.isfinite(d.imag) & np.isfinite(e))
-        cs = np.concatenate([[0], np.cumsum(np.where(bad, 0, d))])
-        es = np.concatenate([[0], np.cumsum(np.where(bad, 0, e))])
+        C, E = _window_sums(np.where(bad, 0, d), L), _window_sums(np.where(bad, 0, e), L)
         nb = np.concatenate([[0], np.cumsum(bad)])
-        C, E, nbad = cs[L:] - cs[:-L], es[L:] - es[:-L], nb[L:] - nb[:-L]
+        nbad = nb[L:] - nb[:-L]
         m = np.where((C.real > 0) & (E > 0) & (nbad == 0), np.abs(C) ** 2 / np.where(E > 0, E, 1) ** 2, 0.0)
     return C, E, m
 

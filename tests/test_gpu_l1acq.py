@@ -9,7 +9,8 @@
             trxsig_fec_sch_decode_batch against the l1msrx model
   truth     16 seeded streams per sps at 20 dB, |f| <= 0.1 cycle / symbol: state 15, BSIC, FN, the SCH start within 0.25 sample,
             the offset within 2e-3 cycle / symbol; the negative families
-  closed loop   the reported frame grid -> the SCH slots of the following multiframe -> detect_sch -> L1MsRx.decode: all sync"""
+  closed loop   the reported frame grid -> the SCH slots of the following multiframe -> detect_sch -> L1MsRx.decode: all sync
+Exact ties, every angle, sps 2 and a reused object: tests/test_gpu_acq_family.py on the family of tests/acq_family.py."""
 import numpy as np
 import pytest
 
