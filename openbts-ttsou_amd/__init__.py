@@ -1531,3 +1531,88 @@ class L1Acq:
                  sch_toa=get(o.d_sch_toa, (S,), "<f4"), soft=get(o.d_soft, (S, o.soft_stride), "<f4"),
                  ok=get(o.d_ok, (S,), "|u1"), bsic=get(o.d_bsic, (S,), "|u1"), rfn=get(o.d_rfn, (S,), "<i4"))
         return r
+
+
+AIR_MAX_TAPS = 32                                         # TRXSIG_AIR_MAX_TAPS
+
+
+class AirCellParams(C.Structure):
+    """trxsig_air_cell_params"""
+    _fields_ = [("d_taps", C.c_void_p), ("n_taps", C.c_int), ("d_step", C.c_void_p), ("d_phase", C.c_void_p), ("d_sigma", C.c_void_p)]
+
+
+class AirStreamParams(C.Structure):
+    """trxsig_air_stream_params"""
+    _fields_ = [("n_arfcn", C.c_int)] + [(n, C.c_void_p) for n in ("d_arfcn", "d_cut", "d_delay", "d_step", "d_phase", "d_gain",
+                                                                   "d_sigma", "d_n0")]
+
+
+class Air:
+    """ctypes view of include/trxsig_air.h: the radio channel on the device -- multipath, oscillator offset and counter-based
+    Gaussian noise, slot cells -> slot cells (cells) or a carrier's cells -> one stream per handset (stream)."""
+
+    def __init__(self, ctx, max_taps=AIR_MAX_TAPS):
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, i64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
+        L.trxsig_air_create.argtypes = [C.POINTER(vp), vp, i32]
+        L.trxsig_air_destroy.argtypes = [vp]; L.trxsig_air_destroy.restype = None
+        L.trxsig_air_cells.argtypes = [vp, i32, i32, i32, u64, vp, i64, i64, C.POINTER(AirCellParams), vp, i64, i64, i32]
+        L.trxsig_air_stream.argtypes = [vp, i32, u64, vp, i64, i64, i32, C.POINTER(AirStreamParams), i32, vp, i64]
+        self.h = vp()
+        rc = L.trxsig_air_create(C.byref(self.h), ctx.h, int(max_taps))
+        if rc != 0:
+            raise TrxSigError("trxsig_air_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self._keep = None
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_air_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def cells(self, fn, n_arfcn, n_frames, seed, x, slot_stride, arfcn_stride, out=None, out_slot_stride=None, out_arfcn_stride=None,
+              taps=None, step=None, phase=None, sigma=None, accumulate=False):
+        """x / out: device tensors (complex64 or float32 pairs) or addresses, strides in complex samples; out None: in place.
+        taps complex64 [a][t][Lh] (or float32 [a][t][Lh][2]: give n_taps through its shape), step / phase int32-sized words,
+        sigma float32, all [a][t] device tensors or None (the stage is skipped)."""
+        p = AirCellParams()
+        if taps is not None:
+            assert taps.is_contiguous()
+            p.d_taps = taps.data_ptr()
+            p.n_taps = taps.shape[2]
+        for name, t in (("d_step", step), ("d_phase", phase), ("d_sigma", sigma)):
+            if t is not None:
+                assert t.is_contiguous() and t.element_size() == 4
+                setattr(p, name, t.data_ptr())
+        if out is None:
+            out, out_slot_stride, out_arfcn_stride = x, slot_stride, arfcn_stride
+        self._chk(self.L.trxsig_air_cells(self.h, int(fn), int(n_arfcn), int(n_frames), int(seed), _ptr(x), int(slot_stride),
+                                          int(arfcn_stride), C.byref(p), _ptr(out), int(out_slot_stride), int(out_arfcn_stride),
+                                          int(bool(accumulate))), "trxsig_air_cells")
+        self._keep = (taps, step, phase, sigma)
+
+    def stream(self, n_arfcn, n_cells, seed, x, slot_stride, arfcn_stride, out, out_stride, length, arfcn, cut, delay=None, step=None,
+               phase=None, gain=None, sigma=None, n0=None):
+        """x: the carriers' cells, out: [n_handsets][out_stride] complex samples; arfcn int32, cut int64, delay / sigma float32,
+        step / phase / n0 32-bit words, gain complex64 -- device tensors of one entry per handset, or None where optional."""
+        p = AirStreamParams()
+        p.n_arfcn = int(n_arfcn)
+        assert arfcn.element_size() == 4 and cut.element_size() == 8
+        keep = (arfcn, cut, delay, step, phase, gain, sigma, n0)
+        for name, t in zip(("d_arfcn", "d_cut", "d_delay", "d_step", "d_phase", "d_gain", "d_sigma", "d_n0"), keep):
+            if t is not None:
+                assert t.is_contiguous()
+                setattr(p, name, t.data_ptr())
+        self._chk(self.L.trxsig_air_stream(self.h, int(n_cells), int(seed), _ptr(x), int(slot_stride), int(arfcn_stride),
+                                           int(arfcn.numel()), C.byref(p), int(length), _ptr(out), int(out_stride)), "trxsig_air_stream")
+        self._keep = keep

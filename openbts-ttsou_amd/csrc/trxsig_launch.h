@@ -272,3 +272,25 @@ hipError_t trx_launch_fec_sch_encode(hipStream_t st, const uint32_t *fns, const 
 hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_slots, const float *soft, long long stride,
                                     long long n_rows, const int32_t *index, const uint8_t *b0, int wire, uint8_t *state,
                                     uint8_t *status, uint8_t *out_tch, uint8_t *out_l2, float *fer, TrxProfiler *prof);
+
+// the air (include/trxsig_air.h; trxsig_air.hip): k_air_cells, k_air_stream.  NULL arrays skip their stage, as the header says.
+struct TrxAirCells {
+  const trx_c32 *in; long long in_slot, in_arfcn;          // cell (t, a) at in + t * in_slot + a * in_arfcn
+  trx_c32 *out; long long out_slot, out_arfcn;
+  const trx_c32 *taps; int n_taps;                         // [a][t][n_taps]
+  const uint32_t *step, *phase; const float *sigma;        // [a][t]
+  long long rows; int n_arfcn;                             // rows: 8 n_frames
+  unsigned row0;                                           // 8 fn: the noise counter's row of slot 0
+  unsigned key0, key1;                                     // the seed
+  int accumulate;
+};
+hipError_t trx_launch_air_cells(hipStream_t st, int sps, const TrxTables *dT, const TrxAirCells &p);
+struct TrxAirStream {
+  const trx_c32 *in; long long in_slot, in_arfcn; int n_arfcn, n_cells;
+  const int32_t *arfcn; const long long *cut; const float *delay; const uint32_t *step, *phase; const trx_c32 *gain;
+  const float *sigma; const uint32_t *n0;
+  int n_handsets, len; trx_c32 *out; long long out_stride;
+  unsigned key0, key1;
+};
+#define TRX_AIR_TILE 512                                   // outputs per workgroup of k_air_stream
+hipError_t trx_launch_air_stream(hipStream_t st, int sps, const TrxTables *dT, const TrxAirStream &p);
