@@ -1616,3 +1616,114 @@ class Air:
         self._chk(self.L.trxsig_air_stream(self.h, int(n_cells), int(seed), _ptr(x), int(slot_stride), int(arfcn_stride),
                                            int(arfcn.numel()), C.byref(p), int(length), _ptr(out), int(out_stride)), "trxsig_air_stream")
         self._keep = keep
+
+
+TRK_CLIPPED, TRK_UNLOCKED = 1, 2                          # trxsig_l1trk_meas.d_status bits (TRXSIG_TRK_*)
+TRK_MAX_FRAMES, TRK_MAX_GATE = 65536, 1 << 24             # TRXSIG_L1TRK_MAX_FRAMES / _MAX_GATE
+
+
+class L1TrkView(C.Structure):
+    """trxsig_l1trk_view"""
+    _fields_ = [("n_phones", C.c_int), ("n_cols", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("d_fn", "d_pos", "d_phase", "d_step", "d_locked", "d_quiet", "d_toa_sum", "d_toa_n", "d_adj",
+                                          "d_afc_n", "d_afc_delta")]
+
+
+class L1TrkMeas(C.Structure):
+    """trxsig_l1trk_meas"""
+    _fields_ = [("n_phones", C.c_int), ("n_cols", C.c_int), ("n_fcch", C.c_int), ("fcch_stride", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("d_status", "d_fcch_fn", "d_fcch_c", "d_fcch_e", "d_fcch_ok")]
+
+
+class L1Trk:
+    """ctypes view of include/trxsig_l1trk.h: the handset's tracking receiver -- acquired streams -> the slot cells TrxGroup.pull
+    reads, derotated by an exact NCO (slice), with the AFC measured on every frequency burst passed and the grid moved by the
+    TOAs the pull reports (update)."""
+
+    def __init__(self, ctx, phone, c0, max_frames, afc_shift=1, toa_gate=512, fcch_thresh=ACQ_FCCH_THRESH):
+        """phone: the phone of every column; c0: every phone's C0 column, -1: none"""
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, i64, u32, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float
+        L.trxsig_l1trk_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp, vp, i32, i32, i32, f32]
+        L.trxsig_l1trk_destroy.argtypes = [vp]; L.trxsig_l1trk_destroy.restype = None
+        L.trxsig_l1trk_seed.argtypes = [vp, C.POINTER(L1AcqOut), vp]
+        L.trxsig_l1trk_set.argtypes = [vp, i32, i32, i32, i64, u32, u32]
+        L.trxsig_l1trk_state.argtypes = [vp, C.POINTER(L1TrkView)]
+        L.trxsig_l1trk_slice.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, i64, i64, C.POINTER(L1TrkMeas)]
+        L.trxsig_l1trk_update.argtypes = [vp, C.POINTER(TrxGroupResult), i32, vp]
+        phone, c0 = np.ascontiguousarray(phone, np.int32), np.ascontiguousarray(c0, np.int32)
+        self.n_cols, self.n_phones = len(phone), len(c0)
+        self.h = vp()
+        rc = L.trxsig_l1trk_create(C.byref(self.h), ctx.h, self.n_phones, self.n_cols, phone.ctypes.data, c0.ctypes.data, int(max_frames),
+                                   int(afc_shift), int(toa_gate), float(fcch_thresh))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1trk_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self.meas = None
+        self._keep = None
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_l1trk_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def seed(self, acq_out, src):
+        """acq_out: the L1AcqOut of a search; src: device int32 [n_phones], the stream each phone was acquired on, -1: leave"""
+        assert src.element_size() == 4 and src.numel() == self.n_phones
+        self._chk(self.L.trxsig_l1trk_seed(self.h, C.byref(acq_out), _ptr(src)), "trxsig_l1trk_seed")
+        self._keep = src
+
+    def set(self, phone, locked, fn, pos, step, phase):
+        self._chk(self.L.trxsig_l1trk_set(self.h, int(phone), int(bool(locked)), int(fn), int(pos), int(step) & 0xffffffff,
+                                          int(phase) & 0xffffffff), "trxsig_l1trk_set")
+
+    def slice(self, streams, stream_stride, n0, n_samples, fn, n_frames, cells, slot_stride, col_stride):
+        """streams / cells: device tensors (complex64 or float32 pairs) or addresses; strides in complex samples"""
+        out = L1TrkMeas()
+        self._chk(self.L.trxsig_l1trk_slice(self.h, _ptr(streams), int(stream_stride), int(n0), int(n_samples), int(fn), int(n_frames),
+                                            _ptr(cells), int(slot_stride), int(col_stride), C.byref(out)), "trxsig_l1trk_slice")
+        self.meas = out
+        return out
+
+    def update(self, res, fn, use=None):
+        """res: the TrxGroupResult of the pull of the cells just sliced; use: device uint8 [n_slots][n_cols] or None"""
+        self._chk(self.L.trxsig_l1trk_update(self.h, C.byref(res), int(fn), _ptr(use)), "trxsig_l1trk_update")
+        self._keep = use
+
+    def state(self):
+        v = L1TrkView()
+        self._chk(self.L.trxsig_l1trk_state(self.h, C.byref(v)), "trxsig_l1trk_state")
+        return v
+
+    def collect(self):
+        """The state, what the last update did and the last slice's records as host numpy arrays (synchronises the stream)."""
+        import torch
+        from .frontend import _DevView
+        np, v, m = self.np, self.state(), self.meas
+        self.ctx.synchronize()
+        P = v.n_phones
+
+        def get(p, shape, ts):
+            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        r = dict(fn=get(v.d_fn, (P,), "<i4"), pos=get(v.d_pos, (P,), "<i8"), phase=get(v.d_phase, (P,), "<i4").view(np.uint32),
+                 step=get(v.d_step, (P,), "<i4").view(np.uint32), locked=get(v.d_locked, (P,), "|u1"), quiet=get(v.d_quiet, (P,), "<i4"),
+                 toa_sum=get(v.d_toa_sum, (P,), "<i8"), toa_n=get(v.d_toa_n, (P,), "<i4"), adj=get(v.d_adj, (P,), "<i8"),
+                 afc_n=get(v.d_afc_n, (P,), "<i4"), afc_delta=get(v.d_afc_delta, (P,), "<i8"))
+        if m is not None:
+            K, n = m.fcch_stride, m.n_fcch
+            r.update(status=get(m.d_status, (v.n_cols,), "|u1"), n_fcch=n, fcch_fn=get(m.d_fcch_fn, (P, K), "<i4")[:, :n],
+                     fcch_c=get(m.d_fcch_c, (P, K, 2), "<f8")[:, :n].copy().view(np.complex128)[..., 0],
+                     fcch_e=get(m.d_fcch_e, (P, K), "<f8")[:, :n], fcch_ok=get(m.d_fcch_ok, (P, K), "|u1")[:, :n])
+        return r

@@ -151,30 +151,7 @@ __global__ __launch_bounds__(kAcqThreads) void k_l1acq_fcch(const cx *__restrict
   }
 }
 
-// atan2(y, x) in plain float32 multiplies, adds and divisions: lo / hi in [0, 1]; above tan(pi / 8) the identity
-// atan t = pi / 4 + atan((t - 1) / (t + 1)) brings |t| below 0.4143, where the odd series to t^17 is within 3e-9; the octant
-// is undone by reflections.  Within a few float32 steps at pi of the true angle (the tests allow 2e-6).
-__device__ __forceinline__ float acq_atan2(float y, float x) {
-  const float ax = fabsf(x), ay = fabsf(y);
-  const float hi = ax > ay ? ax : ay, lo = ax > ay ? ay : ax;
-  if (!(hi > 0.0f)) return 0.0f;
-  float t = lo / hi, off = 0.0f;
-  if (t > 0.41421356f) { t = (t - 1.0f) / (t + 1.0f); off = 0.78539816f; }
-  const float z = t * t;
-  float p = 1.0f / 17.0f;
-  p = p * z - 1.0f / 15.0f;
-  p = p * z + 1.0f / 13.0f;
-  p = p * z - 1.0f / 11.0f;
-  p = p * z + 1.0f / 9.0f;
-  p = p * z - 1.0f / 7.0f;
-  p = p * z + 1.0f / 5.0f;
-  p = p * z - 1.0f / 3.0f;
-  p = p * z + 1.0f;
-  float r = off + t * p;
-  if (ay > ax) r = 1.57079633f - r;
-  if (x < 0.0f) r = 3.14159265f - r;
-  return y < 0.0f ? -r : r;
-}
+// acq_atan2 (the angle of C): trxsig_l1acq_dev.h -- the tracking receiver's AFC uses it too
 
 __global__ __launch_bounds__(64) void k_l1acq_pick(int sps, long long stride, int N, int n_streams, int n_tiles,
                                                    const float *__restrict__ tile_m, const int32_t *__restrict__ tile_k,

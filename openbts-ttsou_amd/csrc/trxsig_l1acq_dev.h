@@ -45,3 +45,33 @@ hipError_t trx_launch_l1acq_verdict(hipStream_t st, int sps, const trx_c32 *c, c
                                     trx_c32 *amp, float *toa, float *ptm, int32_t *doff, int32_t *dlen, float *dtoa, uint8_t *state);
 // state[s] |= TRXSIG_ACQ_DECODED where ok[s]
 hipError_t trx_launch_l1acq_finish(hipStream_t st, int n_streams, const uint8_t *ok, uint8_t *state);
+
+// device code shared by trxsig_l1acq.hip (k_l1acq_pick) and trxsig_l1trk.hip (k_l1trk_update)
+namespace {
+
+// atan2(y, x) in plain float32 multiplies, adds and divisions: lo / hi in [0, 1]; above tan(pi / 8) the identity
+// atan t = pi / 4 + atan((t - 1) / (t + 1)) brings |t| below 0.4143, where the odd series to t^17 is within 3e-9; the octant
+// is undone by reflections.  Within a few float32 steps at pi of the true angle (the tests allow 2e-6).
+__device__ __forceinline__ float acq_atan2(float y, float x) {
+  const float ax = fabsf(x), ay = fabsf(y);
+  const float hi = ax > ay ? ax : ay, lo = ax > ay ? ay : ax;
+  if (!(hi > 0.0f)) return 0.0f;
+  float t = lo / hi, off = 0.0f;
+  if (t > 0.41421356f) { t = (t - 1.0f) / (t + 1.0f); off = 0.78539816f; }
+  const float z = t * t;
+  float p = 1.0f / 17.0f;
+  p = p * z - 1.0f / 15.0f;
+  p = p * z + 1.0f / 13.0f;
+  p = p * z - 1.0f / 11.0f;
+  p = p * z + 1.0f / 9.0f;
+  p = p * z - 1.0f / 7.0f;
+  p = p * z + 1.0f / 5.0f;
+  p = p * z - 1.0f / 3.0f;
+  p = p * z + 1.0f;
+  float r = off + t * p;
+  if (ay > ax) r = 1.57079633f - r;
+  if (x < 0.0f) r = 3.14159265f - r;
+  return y < 0.0f ? -r : r;
+}
+
+}  // namespace
