@@ -52,6 +52,9 @@
  * in float32, unfused, as trxsig_l1acq.h's stage 1 forms them (three roundings per component); C = sum d and E = sum e in
  * float64, in any order.  Record j of the phone (j counts the call's FCCH frames) carries the frame, C, E and
  *   ok = Re C > 0 and E > 0 and C, E finite and |C|^2 / E^2 > fcch_thresh   (in double)
+ * C and E are the sums of the float32 terms, not of exact ones: a term that is not finite in float32 (a sample above about
+ * 1.8e19 in modulus overflows e[n]; a NaN or Inf sample) makes its sum Inf or NaN and gives ok = 0 even where the exact sum
+ * would be finite, and terms that underflow to 0 give E = 0 and ok = 0.
  * A phone that is not locked gets C = E = 0, ok = 0; a phone without a C0 column has no records (its entries stay zero).
  *
  * Update.  res is the pull of the cells just sliced (res->n_arfcn == n_cols; fn and res->n_slots those of the last slice, and

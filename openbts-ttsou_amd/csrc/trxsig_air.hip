@@ -78,19 +78,7 @@ __device__ __forceinline__ cx air_gauss(unsigned wa, unsigned wb) {
 __device__ __forceinline__ cx air_rot(const TrxTables *__restrict__ T, unsigned ph) {
   return dev_expj_lookup(T, (float)(ph >> 8) * 5.9604644775390625e-8f * TRX_2PI_F);
 }
-// Complex<float>::operator* with the real part's difference formed as a sum: x.r a.r + x.i (-a.i).  For every pair of numbers
-// that is the same value as x.r a.r - x.i a.i (negation is exact, and a - b is a + (-b) by definition, signed zeros included).
-// For a NaN it is not the same word: where only x.i is a NaN, v_sub_f32 hands it on with its sign flipped (the negation of the
-// second operand is applied to the NaN), while the reference's subss hands it on as it is.  With the negation moved onto the
-// factor -- nai = -a.i, made where the compiler cannot fold it back into a subtraction -- a NaN sample leaves the kernel with
-// the words the reference gives it, which is how the tests compare cells that hold one.
-__device__ __forceinline__ cx air_cmul(cx x, cx a, float nai) { return mk(x.r * a.r + x.i * nai, x.r * a.i + x.i * a.r); }
-__device__ __forceinline__ float air_neg(float v) {
-  float r = -v;
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ cx air_cmul(cx x, cx a) { return air_cmul(x, a, air_neg(a.i)); }
+// (the complex products are trxsig_dev.h's cmul_sum: a NaN sample leaves with the reference's words)
 __device__ __forceinline__ cx air_add_noise(cx v, float sigma, cx g) { return mk(v.r + sigma * g.r, v.i + sigma * g.i); }
 
 // ---------------------------------------------------------------------------------------------
@@ -104,7 +92,7 @@ template <int SPS>
 __global__ __launch_bounds__(256) void k_air_cells(const TrxTables *__restrict__ T, TrxAirCells p) {
   __shared__ cx row[kAirPad + 157 * SPS + 1];
   __shared__ cx hs[32];
-  __shared__ float hni[32];                                  // -h.i (air_cmul)
+  __shared__ float hni[32];                                  // -h.i (cmul_sum)
   const int a = blockIdx.y;
   if (threadIdx.x < kAirPad) row[threadIdx.x] = mk(0, 0);
   if (threadIdx.x == 0) row[kAirPad + 157 * SPS] = mk(0, 0);
@@ -134,8 +122,8 @@ __global__ __launch_bounds__(256) void k_air_cells(const TrxTables *__restrict__
           const cx xb = row[kAirPad + i - j];
           const cx h = hs[j];
           const float nh = hni[j];
-          u1 = cadd(u1, air_cmul(xa, h, nh));
-          u0 = cadd(u0, air_cmul(xb, h, nh));
+          u1 = cadd(u1, cmul_sum(xa, h, nh));
+          u0 = cadd(u0, cmul_sum(xb, h, nh));
           xa = xb;
         }
       } else {
@@ -143,8 +131,8 @@ __global__ __launch_bounds__(256) void k_air_cells(const TrxTables *__restrict__
       }
       if (p.step) {                                          // frequencyShift: (*xP) * expjLookup(phase)
         const unsigned ph = phase + (unsigned)i * step;
-        u0 = air_cmul(u0, air_rot(T, ph));
-        u1 = air_cmul(u1, air_rot(T, ph + step));
+        u0 = cmul_sum(u0, air_rot(T, ph));
+        u1 = cmul_sum(u1, air_rot(T, ph + step));
       }
       if (p.sigma) {
         unsigned w[4];
@@ -211,7 +199,7 @@ __global__ __launch_bounds__(256) void k_air_stream(const TrxTables *__restrict_
   const unsigned step = p.step ? p.step[h] : 0u;
   const unsigned phase = (p.step && p.phase) ? p.phase[h] : 0u;
   const cx gain = p.gain ? p.gain[h] : mk(1, 0);
-  const float ngi = air_neg(gain.i);
+  const float ngi = neg_opaque(gain.i);
   const float sigma = p.sigma ? p.sigma[h] : 0.0f;
   const unsigned n0 = p.n0 ? p.n0[h] : 0u;
   for (int l = threadIdx.x; l < TRX_AIR_TILE; l += 256) {
@@ -228,8 +216,8 @@ __global__ __launch_bounds__(256) void k_air_stream(const TrxTables *__restrict_
         r = xs[l + 10];
       }
     }
-    if (p.step) r = air_cmul(r, air_rot(T, phase + (unsigned)n * step));
-    if (p.gain) r = air_cmul(r, gain, ngi);                           // scaleVector (:719)
+    if (p.step) r = cmul_sum(r, air_rot(T, phase + (unsigned)n * step));
+    if (p.gain) r = cmul_sum(r, gain, ngi);                           // scaleVector (:719)
     if (p.sigma) {
       const unsigned i = n0 + (unsigned)n;
       unsigned w[4];

@@ -37,6 +37,20 @@ typedef trx_c32 cx;
 __device__ __forceinline__ cx mk(float r, float i) { cx z; z.r = r; z.i = i; return z; }
 // Complex<float>::operator* (Transceiver/Complex.h:83): (r*a.r - i*a.i, r*a.i + i*a.r)
 __device__ __forceinline__ cx cmul(cx x, cx a) { return mk(x.r * a.r - x.i * a.i, x.r * a.i + x.i * a.r); }
+// Complex<float>::operator* with the real part's difference formed as a sum: x.r a.r + x.i (-a.i).  For every pair of numbers
+// that is the same value as x.r a.r - x.i a.i (negation is exact, and a - b is a + (-b) by definition, signed zeros included).
+// For a NaN it is not the same word: where only x.i is a NaN, v_sub_f32 hands it on with its sign flipped (the negation of the
+// second operand is applied to the NaN), while the reference's subss hands it on as it is.  With the negation moved onto the
+// factor -- nai = -a.i, made where the compiler cannot fold it back into a subtraction -- a NaN sample leaves the kernel with
+// the words the reference gives it, which is how the tests compare cells that hold one (trxsig_air.hip's channel and
+// trxsig_l1trk.hip's slice, which reads the channel's streams).
+__device__ __forceinline__ cx cmul_sum(cx x, cx a, float nai) { return mk(x.r * a.r + x.i * nai, x.r * a.i + x.i * a.r); }
+__device__ __forceinline__ float neg_opaque(float v) {
+  float r = -v;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+__device__ __forceinline__ cx cmul_sum(cx x, cx a) { return cmul_sum(x, a, neg_opaque(a.i)); }
 __device__ __forceinline__ cx cmulr(cx x, float a) { return mk(x.r * a, x.i * a); }       // Complex.h:84
 __device__ __forceinline__ cx cadd(cx x, cx a) { return mk(x.r + a.r, x.i + a.i); }
 __device__ __forceinline__ float norm2(cx x) { return x.i * x.i + x.r * x.r; }            // Complex.h:119

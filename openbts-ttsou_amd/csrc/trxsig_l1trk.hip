@@ -1,6 +1,7 @@
 // trxsig_l1trk.hip -- the tracking receiver's kernels (include/trxsig_l1trk.h, host side in trxsig_l1trk.cpp).
 // k_l1trk_slice: workgroup (x, y) forms column y's cells x, x + gridDim.x, ... (k_air_cells' grid): the stream samples of the cell
-//   come in coalesced, are turned by the NCO (expjLookup of the top 24 phase bits, Complex<float>::operator*) and go out.  A cell
+//   come in coalesced, are turned by the NCO (expjLookup of the top 24 phase bits, Complex<float>::operator* in trxsig_dev.h's
+//   cmul_sum form, which hands a NaN sample on with the model's words) and go out.  A cell
 //   that holds a frequency burst stays in LDS as well: the workgroup forms d[] and e[] from it in float32, sums them in float64
 //   (lane, wave, workgroup) and writes the phone's record -- no second pass over HBM.  Workgroup (0, y) also writes column y's
 //   status and advances the anchors of phones y, y + gridDim.y, ... from the set the launch reads into the other set.
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void k_l1trk_slice(const TrxTables *__restrict
       cx v = mk(0, 0);
       if (locked && q >= 0 && q < (long long)p.n_samples) {
         const unsigned ph = PH + (unsigned)(st + i) * step;
-        v = cmul(x[q], dev_expj_lookup(T, (float)(ph >> 8) * 5.9604644775390625e-8f * TRX_2PI_F));
+        v = cmul_sum(x[q], dev_expj_lookup(T, (float)(ph >> 8) * 5.9604644775390625e-8f * TRX_2PI_F));
       }
       o[i] = v;
       if (fcch) y[i] = v;
