@@ -1727,3 +1727,105 @@ class L1Trk:
                      fcch_c=get(m.d_fcch_c, (P, K, 2), "<f8")[:, :n].copy().view(np.complex128)[..., 0],
                      fcch_e=get(m.d_fcch_e, (P, K), "<f8")[:, :n], fcch_ok=get(m.d_fcch_ok, (P, K), "|u1")[:, :n])
         return r
+
+
+A5_OFF, A5_1 = 0, 1                                      # trxsig_l1ciph_set's algo (TRXSIG_A5_*)
+L1CIPH_STATE_BYTES = 16                                  # TRXSIG_L1CIPH_STATE_BYTES: uint32 algo, R1, R2, R3
+
+
+def a5_1_blocks(ctx, kc, count, block1=None, block2=None):
+    """trxsig_a5_1_blocks_batch: kc device uint8 [n][8], count device int32 / uint32 [n] -> BLOCK1 / BLOCK2 device uint8
+    [n][114], one bit per byte (either may be None).  Enqueued on the context's stream."""
+    L = ctx.L
+    vp = C.c_void_p
+    L.trxsig_a5_1_blocks_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    n = int(count.numel()) if hasattr(count, "numel") else 0
+    rc = L.trxsig_a5_1_blocks_batch(ctx.h, n, _ptr(kc), _ptr(count), _ptr(block1), _ptr(block2))
+    if rc < 0:
+        raise TrxSigError("trxsig_a5_1_blocks_batch: %d (%s)" % (rc, L.trxsig_last_error(ctx.h).decode()))
+
+
+class L1Ciph:
+    """ctypes view of include/trxsig_l1ciph.h: A5/1 ciphering of the dedicated channels' bursts -- bits() on an encoder's burst
+    grid before it is sent, soft() on a pull's rows before they are decoded; a key per TCH / XCCH channel (set).
+    comb: uint8 [n_arfcn, 8] as L1Rx takes it."""
+
+    def __init__(self, ctx, comb):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, u32 = C.c_void_p, C.c_int, C.c_uint32
+        L.trxsig_l1ciph_create.argtypes = [C.POINTER(vp), vp, i32, vp]
+        L.trxsig_l1ciph_destroy.argtypes = [vp]; L.trxsig_l1ciph_destroy.restype = None
+        L.trxsig_l1ciph_channels.argtypes = [vp, i32]
+        L.trxsig_l1ciph_channel.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        L.trxsig_l1ciph_set.argtypes = [vp, i32, i32, i32, vp]
+        L.trxsig_l1ciph_state.argtypes = [vp, i32, C.POINTER(vp)]
+        L.trxsig_l1ciph_bits.argtypes = [vp, i32, i32, i32, vp, vp, u32]
+        L.trxsig_l1ciph_soft.argtypes = [vp, i32, C.POINTER(TrxGroupResult), i32]
+        self.comb = np.ascontiguousarray(comb, np.uint8)
+        self.h = vp()
+        rc = L.trxsig_l1ciph_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data)
+        if rc != 0:
+            raise TrxSigError("trxsig_l1ciph_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_l1ciph_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def channels(self, cls):
+        return self._chk(self.L.trxsig_l1ciph_channels(self.h, cls), "trxsig_l1ciph_channels")
+
+    def channel(self, cls, chan):
+        """(arfcn, tn, kind, sub) of a channel"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self.L.trxsig_l1ciph_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1ciph_channel")
+        return tuple(x.value for x in v)
+
+    def set(self, cls, chan, algo, kc=None):
+        """algo: A5_OFF or A5_1; kc: 8 key bytes (host).  Takes effect in stream order."""
+        key = None if kc is None else (C.c_uint8 * 8)(*[int(x) & 0xff for x in kc])
+        self._chk(self.L.trxsig_l1ciph_set(self.h, int(cls), int(chan), int(algo), key), "trxsig_l1ciph_set")
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._chk(self.L.trxsig_l1ciph_state(self.h, cls, C.byref(p)), "trxsig_l1ciph_state")
+        return p.value
+
+    def bits(self, uplink, fn, n_frames, bits, what=None, what_mask=0):
+        """bits: device uint8 [n_arfcn][8 n_frames][148] (a tensor or an address: an encoder's d_bits), ciphered in place; what:
+        its [n_arfcn][8 n_frames] map or None"""
+        self._chk(self.L.trxsig_l1ciph_bits(self.h, int(bool(uplink)), int(fn), int(n_frames), _ptr(bits), _ptr(what),
+                                            int(what_mask) & 0xffffffff), "trxsig_l1ciph_bits")
+
+    def soft(self, uplink, res, fn):
+        """res: a TrxGroupResult of whole frames from (fn, TN 0); its soft rows are deciphered in place, once"""
+        self._chk(self.L.trxsig_l1ciph_soft(self.h, int(bool(uplink)), C.byref(res), int(fn)), "trxsig_l1ciph_soft")
+
+    def collect(self):
+        """The channels' records as host numpy arrays uint32 [n_chan][4] per class (synchronises the context's stream)."""
+        import torch
+        from .frontend import _DevView
+        np = self.np
+        self.ctx.synchronize()
+        r = {}
+        for name, cls in (("tch", L1_TCH), ("xcch", L1_XCCH)):
+            n = self.channels(cls)
+            if n == 0:
+                r[name] = np.zeros((0, 4), np.uint32)
+            else:
+                t = torch.as_tensor(_DevView(self.state(cls), (n, 4), "<i4"), device="cuda:%d" % self.ctx.device)
+                r[name] = t.cpu().numpy().view(np.uint32)
+        return r
