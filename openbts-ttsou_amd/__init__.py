@@ -1829,3 +1829,106 @@ class L1Ciph:
                 t = torch.as_tensor(_DevView(self.state(cls), (n, 4), "<i4"), device="cuda:%d" % self.ctx.device)
                 r[name] = t.cpu().numpy().view(np.uint32)
         return r
+
+
+L1HOP_MAX_N = 64                                         # TRXSIG_L1HOP_MAX_N
+
+
+def hop_mai(ctx, fn, hsn, maio, n, mai):
+    """trxsig_hop_mai_batch: device int32 arrays of equal length, mai[i] = MAI(fn[i], hsn[i], maio[i], n[i]) (GSM 05.02 6.2.3).
+    Entries out of range are undefined.  Enqueued on the context's stream."""
+    L = ctx.L
+    vp = C.c_void_p
+    L.trxsig_hop_mai_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    cnt = int(fn.numel()) if hasattr(fn, "numel") else 0
+    rc = L.trxsig_hop_mai_batch(ctx.h, cnt, _ptr(fn), _ptr(hsn), _ptr(maio), _ptr(n), _ptr(mai))
+    if rc < 0:
+        raise TrxSigError("trxsig_hop_mai_batch: %d (%s)" % (rc, L.trxsig_last_error(ctx.h).decode()))
+
+
+class L1Hop:
+    """ctypes view of include/trxsig_l1hop.h: slow frequency hopping of the dedicated channels -- bits() on an encoder's burst
+    grid (in place), cells() on sample cells (out of place), result() on a pull (indices only), map() the radio row of every
+    channel row.  comb: uint8 [n_arfcn, 8] as L1Rx takes it; group: int8 [n_arfcn, 8], -1 or a group id; hsn: one per group;
+    max_frames: the longest map() / result() call."""
+
+    def __init__(self, ctx, comb, group, hsn, max_frames=104):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = L = ctx.L
+        vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
+        L.trxsig_l1hop_create.argtypes = [C.POINTER(vp), vp, i32, vp, vp, i32, vp, i32]
+        L.trxsig_l1hop_destroy.argtypes = [vp]; L.trxsig_l1hop_destroy.restype = None
+        L.trxsig_l1hop_groups.argtypes = [vp]
+        L.trxsig_l1hop_members.argtypes = [vp, i32, i32, vp]
+        L.trxsig_l1hop_map.argtypes = [vp, i32, i32, C.POINTER(vp)]
+        L.trxsig_l1hop_bits.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.trxsig_l1hop_cells.argtypes = [vp, i32, i32, i32, vp, i64, i64, vp, i64, i64]
+        L.trxsig_l1hop_result.argtypes = [vp, i32, C.POINTER(TrxGroupResult), C.POINTER(TrxGroupResult)]
+        self.comb = np.ascontiguousarray(comb, np.uint8)
+        self.group = np.ascontiguousarray(group, np.int8)
+        self.hsn = np.ascontiguousarray(hsn, np.uint8).reshape(-1)
+        if self.group.shape != self.comb.shape:
+            raise TrxSigError("L1Hop: comb and group differ in shape")
+        self.n_arfcn = self.comb.shape[0]
+        self.h = vp()
+        rc = L.trxsig_l1hop_create(C.byref(self.h), ctx.h, self.n_arfcn, self.comb.ctypes.data, self.group.ctypes.data,
+                                   len(self.hsn), self.hsn.ctypes.data if len(self.hsn) else None, int(max_frames))
+        if rc != 0:
+            raise TrxSigError("trxsig_l1hop_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+
+    def destroy(self):
+        if self.h:
+            self.L.trxsig_l1hop_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
+        return rc
+
+    def groups(self):
+        return self._chk(self.L.trxsig_l1hop_groups(self.h), "trxsig_l1hop_groups")
+
+    def members(self, g, tn):
+        """the rows of group g on timeslot tn, ascending: a row's place in the list is its MAIO"""
+        rows = (C.c_int32 * L1HOP_MAX_N)()
+        n = self._chk(self.L.trxsig_l1hop_members(self.h, int(g), int(tn), rows), "trxsig_l1hop_members")
+        return list(rows[:n])
+
+    def map(self, fn, n_frames):
+        """device int32 [8 n_frames][n_arfcn] (a view of the object's array, valid until the next map): the radio row of channel
+        row a in slot t"""
+        import torch
+        from .frontend import _DevView
+        p = C.c_void_p()
+        self._chk(self.L.trxsig_l1hop_map(self.h, int(fn), int(n_frames), C.byref(p)), "trxsig_l1hop_map")
+        return torch.as_tensor(_DevView(p.value, (8 * int(n_frames), self.n_arfcn), "<i4"), device="cuda:%d" % self.ctx.device)
+
+    def bits(self, to_radio, fn, n_frames, bits, what=None):
+        """bits: device uint8 [n_arfcn][8 n_frames][148] (a tensor or an address: an encoder's d_bits), hopped in place together
+        with what, its [n_arfcn][8 n_frames] map (or None)"""
+        self._chk(self.L.trxsig_l1hop_bits(self.h, int(bool(to_radio)), int(fn), int(n_frames), _ptr(bits), _ptr(what)),
+                  "trxsig_l1hop_bits")
+
+    def cells(self, to_radio, fn, n_frames, src, in_slot_stride, in_arfcn_stride, dst, out_slot_stride, out_arfcn_stride):
+        """src, dst: device complex64 cells (tensors or addresses), strides in samples; out of place"""
+        self._chk(self.L.trxsig_l1hop_cells(self.h, int(bool(to_radio)), int(fn), int(n_frames), _ptr(src), int(in_slot_stride),
+                                            int(in_arfcn_stride), _ptr(dst), int(out_slot_stride), int(out_arfcn_stride)),
+                  "trxsig_l1hop_cells")
+
+    def result(self, res, fn):
+        """res: a TrxGroupResult of whole frames from (fn, TN 0) -> a copy whose d_row is in the channel domain (the object's
+        array, valid until the next result; self.row is that array as a tensor)"""
+        import torch
+        from .frontend import _DevView
+        out = TrxGroupResult()
+        self._chk(self.L.trxsig_l1hop_result(self.h, int(fn), C.byref(res), C.byref(out)), "trxsig_l1hop_result")
+        self.row = torch.as_tensor(_DevView(out.d_row, (out.n_slots, out.n_arfcn), "<i4"), device="cuda:%d" % self.ctx.device)
+        return out
