@@ -63,7 +63,7 @@ typedef struct {
  * Empty cells (zeros in) still receive noise.  d_out may be exactly d_in with d_in's strides; otherwise the two regions (first
  * cell to the end of the last) must not overlap.  One launch (k_air_cells).  TRXSIG_EINVAL before any launch: NULL object, params
  * or buffers, n_arfcn outside 1..65535, n_frames outside 1..2^24, fn outside [0, 2715648), n_taps out of range, strides under which
- * cells overlap (trxsig_l1ms_radiate's rule: slot_stride and arfcn_stride at least 157 sps apart, in either nesting), out
+ * cells overlap (the rule trxsig_l1ms_radiate, trxsig_l1trk_slice and trxsig_l1hop_cells share: slot_stride and arfcn_stride at least 157 sps apart, in either nesting), out
  * overlapping in without being identical. */
 int trxsig_air_cells(trxsig_air *air, int fn, int n_arfcn, int n_frames, uint64_t seed, const trxsig_c32 *d_in, int64_t in_slot_stride,
                      int64_t in_arfcn_stride, const trxsig_air_cell_params *params, trxsig_c32 *d_out, int64_t out_slot_stride,

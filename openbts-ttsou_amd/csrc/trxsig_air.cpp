@@ -6,7 +6,7 @@
 
 #include "trxsig_air.h"
 #include "trxsig_ctx.h"
-#include "trxsig_tdma.h"
+#include "trxsig_plan.h"
 
 struct trxsig_air {
   trxsig_ctx *c = nullptr;
@@ -15,27 +15,6 @@ struct trxsig_air {
 
 namespace {
 int fail(trxsig_air *a, const char *what) { return trx_ctx_fail(a ? a->c : nullptr, TRXSIG_EINVAL, what, hipSuccess); }
-
-// trxsig_l1ms_radiate's rule: T slots of A ARFCNs, cells of `cell` samples, must not overlap in either nesting
-bool strides_ok(long long T, long long A, long long cell, long long slot_stride, long long arfcn_stride) {
-  const bool slot_major = arfcn_stride >= cell && (T == 1 || (slot_stride >= cell && slot_stride / A >= arfcn_stride));
-  const bool arfcn_major = slot_stride >= cell && (A == 1 || (arfcn_stride >= cell && arfcn_stride / T >= slot_stride));
-  return slot_major || arfcn_major;
-}
-// one past the last sample of the last cell, from the base (strides already known to be positive and overflow-free by strides_ok's
-// divisions: the larger stride is at least the smaller times the other dimension)
-bool extent(long long T, long long A, long long cell, long long slot_stride, long long arfcn_stride, long long *out) {
-  long long x = 0, y = 0;
-  if (__builtin_mul_overflow(T - 1, slot_stride, &x) || __builtin_mul_overflow(A - 1, arfcn_stride, &y) ||
-      __builtin_add_overflow(x, y, &x) || __builtin_add_overflow(x, cell, &x) || x > (1LL << 58))
-    return false;
-  *out = x;
-  return true;
-}
-bool overlap(const trxsig_c32 *p, long long np, const trxsig_c32 *q, long long nq) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)nq * sizeof(trxsig_c32) && b < a + (uintptr_t)np * sizeof(trxsig_c32);
-}
 }  // namespace
 
 int trxsig_air_create(trxsig_air **out, trxsig_ctx *c, int max_taps) {
@@ -53,11 +32,7 @@ int trxsig_air_create(trxsig_air **out, trxsig_ctx *c, int max_taps) {
 
 void trxsig_air_destroy(trxsig_air *a) {
   if (!a) return;
-  {
-    TrxDeviceGuard g(trxsig_device(a->c));
-    (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(a->c));
-  }
-  trx_ctx_release(a->c);
+  trx_object_destroy(a->c, {});
   delete a;
 }
 

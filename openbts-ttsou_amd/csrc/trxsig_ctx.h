@@ -1,7 +1,10 @@
 // trxsig_ctx.h -- internal: what the other host translation units of the library (trxsig_frontend.cpp, trxsig_trxgroup.cpp,
 // trxsig_transceiver.cpp) may ask of a context (trxsig_api.cpp owns struct trxsig_ctx).
 #pragma once
+#include <cassert>
 #include <cstring>
+#include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "trxsig.h"
@@ -179,3 +182,67 @@ int trx_ctx_group_estimate(trxsig_ctx *c, const trxsig_c32 *d_samples, const int
 int trx_ctx_group_equalize(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                            const trxsig_c32 *d_amp, const float *d_toa_eq, const uint8_t *d_gate, const trxsig_c32 *d_w_tab,
                            const trxsig_c32 *d_b_tab, const int32_t *d_tap_ix, float *d_soft, int nsoft, int soft_stride);
+
+// ---- what every object that lives on a context does the same way (trxsig_l1*.cpp, trxsig_air.cpp) ---------------------------
+#pragma GCC visibility push(hidden)
+inline size_t trx_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// One device block carved into regions that each start on a 256-byte boundary: sizes in (the list, or add() one by one, which
+// returns the region's handle: its place in the order), `total` and, once the block is there, typed pointers out.
+struct TrxCarve {
+  static constexpr int kMax = 32;
+  size_t off[kMax] = {}, total = 0;
+  int n = 0;
+  TrxCarve() = default;
+  TrxCarve(std::initializer_list<size_t> sizes) { for (size_t s : sizes) add(s); }
+  int add(size_t bytes) { assert(n < kMax); off[n] = total; total += trx_align256(bytes); return n++; }
+  template <class T> T *at(void *base, int region) const { return (T *)((char *)base + off[region]); }
+};
+
+// An object's persistent block: `total` bytes, zero-filled, then the pieces copied from the host in the order given (empty
+// ones skipped).  On failure nothing stays allocated, *out is null and the context's last error is "<who>: device allocation"
+// (TRXSIG_ENOMEM) or "<who>: upload" (TRXSIG_EHIP).  The caller holds the TrxDeviceGuard.
+struct TrxUpload { size_t off; const void *src; size_t bytes; };
+inline int trx_device_block(trxsig_ctx *c, const char *who, size_t total, std::initializer_list<TrxUpload> pieces, void **out) {
+  *out = nullptr;
+  if (hipMalloc(out, total) != hipSuccess) {
+    *out = nullptr;
+    return trx_ctx_fail(c, TRXSIG_ENOMEM, (std::string(who) + ": device allocation").c_str(), hipSuccess);
+  }
+  hipError_t e = hipMemset(*out, 0, total);
+  for (const TrxUpload &u : pieces)
+    if (e == hipSuccess && u.bytes) e = hipMemcpy((char *)*out + u.off, u.src, u.bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) return TRXSIG_OK;
+  (void)hipFree(*out);
+  *out = nullptr;
+  return trx_ctx_fail(c, TRXSIG_EHIP, (std::string(who) + ": upload").c_str(), e);
+}
+
+// A per-call workspace that only grows.  A growth waits for the context's stream first (the old block may still be read), and
+// from then on the old contents are gone (*gone = true, also where the growth then fails).  oom: the last-error text of a
+// failed allocation, reported as TRXSIG_ENOMEM; null: it is reported as any failed HIP call (TRXSIG_EHIP).
+struct TrxWork { void *p = nullptr; size_t bytes = 0; };
+inline int trx_work_ensure(trxsig_ctx *c, TrxWork &w, size_t need, bool zero, const char *oom, bool *gone = nullptr) {
+  if (need <= w.bytes) return TRXSIG_OK;
+  TRX_HIPCHK(c, hipStreamSynchronize((hipStream_t)trxsig_get_stream(c)));
+  if (gone) *gone = true;
+  if (w.p) { TRX_HIPCHK(c, hipFree(w.p)); w.p = nullptr; w.bytes = 0; }
+  if (!oom) TRX_HIPCHK(c, hipMalloc(&w.p, need));
+  else if (hipMalloc(&w.p, need) != hipSuccess) return trx_ctx_fail(c, TRXSIG_ENOMEM, oom, hipSuccess);
+  if (zero) TRX_HIPCHK(c, hipMemset(w.p, 0, need));
+  w.bytes = need;
+  return TRXSIG_OK;
+}
+
+// An object's end: wait for the context's stream, free its device blocks (null ones skipped), give the context back (which
+// destroys a context whose trxsig_destroy waited for this object).  The caller deletes the object afterwards.
+inline void trx_object_destroy(trxsig_ctx *c, std::initializer_list<void *> blocks) {
+  {
+    TrxDeviceGuard g(trxsig_device(c));
+    (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(c));
+    for (void *p : blocks)
+      if (p) (void)hipFree(p);
+  }
+  trx_ctx_release(c);
+}
+#pragma GCC visibility pop

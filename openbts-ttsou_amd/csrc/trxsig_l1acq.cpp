@@ -14,7 +14,6 @@
 #include "trxsig_tablegen.h"
 
 namespace {
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr int kSoft = 148;
 }  // namespace
 
@@ -36,7 +35,7 @@ struct trxsig_l1acq {
   int32_t *tile_k = nullptr;
   trx_c32 *tile_c = nullptr;
   // stage-2 workspace for `cap` windows; grows only
-  void *d_work = nullptr;
+  TrxWork work;
   int cap = 0;
   trx_c32 *y = nullptr, *corr = nullptr, *peak = nullptr;
   float *pidx = nullptr, *dtoa = nullptr;
@@ -51,19 +50,14 @@ int ensure_work(trxsig_l1acq *a, int B) {
   if (B <= a->cap) return TRXSIG_OK;
   trxsig_ctx *c = a->c;
   const size_t n = (size_t)B;
-  const size_t sizes[] = { n * TRX_ACQ_WMAX * sizeof(trx_c32), n * TRX_ACQ_WMAX * sizeof(trx_c32), n * sizeof(trx_c32),   // y, corr, peak
-                           n * 4, n * 4, n * 4, n * 4, n * 4, n * 4 };                                                     // pidx, dtoa, woff, wlen, doff, dlen
-  constexpr int k = sizeof sizes / sizeof sizes[0];
-  size_t off[k], total = 0;
-  for (int i = 0; i < k; i++) { off[i] = total; total += al(sizes[i]); }
-  TRX_HIPCHK(c, hipStreamSynchronize((hipStream_t)trxsig_get_stream(c)));
-  if (a->d_work) { TRX_HIPCHK(c, hipFree(a->d_work)); a->d_work = nullptr; a->cap = 0; }
-  TRX_HIPCHK(c, hipMalloc(&a->d_work, total));
-  TRX_HIPCHK(c, hipMemset(a->d_work, 0, total));
-  char *b = (char *)a->d_work;
-  a->y = (trx_c32 *)(b + off[0]); a->corr = (trx_c32 *)(b + off[1]); a->peak = (trx_c32 *)(b + off[2]);
-  a->pidx = (float *)(b + off[3]); a->dtoa = (float *)(b + off[4]);
-  a->woff = (int32_t *)(b + off[5]); a->wlen = (int32_t *)(b + off[6]); a->doff = (int32_t *)(b + off[7]); a->dlen = (int32_t *)(b + off[8]);
+  const TrxCarve cv = { n * TRX_ACQ_WMAX * sizeof(trx_c32), n * TRX_ACQ_WMAX * sizeof(trx_c32), n * sizeof(trx_c32),   // y, corr, peak
+                        n * 4, n * 4, n * 4, n * 4, n * 4, n * 4 };                                                        // pidx, dtoa, woff, wlen, doff, dlen
+  const int rc = trx_work_ensure(c, a->work, cv.total, true, nullptr);
+  if (rc != TRXSIG_OK) { a->cap = 0; return rc; }
+  void *b = a->work.p;
+  a->y = cv.at<trx_c32>(b, 0); a->corr = cv.at<trx_c32>(b, 1); a->peak = cv.at<trx_c32>(b, 2);
+  a->pidx = cv.at<float>(b, 3); a->dtoa = cv.at<float>(b, 4);
+  a->woff = cv.at<int32_t>(b, 5); a->wlen = cv.at<int32_t>(b, 6); a->doff = cv.at<int32_t>(b, 7); a->dlen = cv.at<int32_t>(b, 8);
   a->cap = B;
   return TRXSIG_OK;
 }
@@ -108,37 +102,25 @@ int trxsig_l1acq_create(trxsig_l1acq **out, trxsig_ctx *c, int max_streams, int 
     }
   }
   const size_t S = (size_t)max_streams, NT = S * (size_t)(a->max_tiles > 0 ? a->max_tiles : 1);
-  const size_t sz[] = { a->h_seq.size() * sizeof(trx_c32),
+  const TrxCarve cv = { a->h_seq.size() * sizeof(trx_c32),
                         S, S * 4, S * 4, S * 8, S * 4, S * 4, S * 4, S * 4, S * 8, S * 4,        // state, k, m, c, e, arg, omega, w0, base, wlen
                         S * 4, S * 4, S * 8, S * kSoft * 4, S, S, S, S * 4,                       // ptm, toa, amp, soft, ok, bsic, flags, rfn
                         NT * 4, NT * 4, NT * 8, NT * 4 };                                         // tiles: m, k, c, e
-  constexpr int n = sizeof sz / sizeof sz[0];
-  size_t off[n], total = 0;
-  for (int i = 0; i < n; i++) { off[i] = total; total += al(sz[i]); }
   TrxDeviceGuard g(trxsig_device(c));
-  if (hipMalloc(&a->d_persist, total) != hipSuccess) {
-    delete a;
-    return trx_ctx_fail(c, TRXSIG_ENOMEM, "trxsig_l1acq_create: device allocation", hipSuccess);
-  }
-  char *b = (char *)a->d_persist;
-  a->d_seq = (trx_c32 *)(b + off[0]);
+  int rc = trx_device_block(c, "trxsig_l1acq_create", cv.total, { { cv.off[0], a->h_seq.data(), a->h_seq.size() * sizeof(trx_c32) } }, &a->d_persist);
+  if (rc != TRXSIG_OK) { delete a; return rc; }
+  void *b = a->d_persist;
+  a->d_seq = cv.at<trx_c32>(b, 0);
   TrxAcqStreams &s = a->sv;
-  s.state = (uint8_t *)(b + off[1]); s.fcch_k = (int32_t *)(b + off[2]); s.fcch_m = (float *)(b + off[3]);
-  s.fcch_c = (trx_c32 *)(b + off[4]); s.fcch_e = (float *)(b + off[5]); s.arg = (float *)(b + off[6]); s.omega = (float *)(b + off[7]);
-  s.w0 = (int32_t *)(b + off[8]); s.base = (long long *)(b + off[9]); s.wlen = (int32_t *)(b + off[10]);
-  a->ptm = (float *)(b + off[11]); a->toa = (float *)(b + off[12]); a->amp = (trx_c32 *)(b + off[13]); a->soft = (float *)(b + off[14]);
-  a->ok = (uint8_t *)(b + off[15]); a->bsic = (uint8_t *)(b + off[16]); a->flags = (uint8_t *)(b + off[17]); a->rfn = (int32_t *)(b + off[18]);
-  a->tile_m = (float *)(b + off[19]); a->tile_k = (int32_t *)(b + off[20]); a->tile_c = (trx_c32 *)(b + off[21]); a->tile_e = (float *)(b + off[22]);
-  hipError_t e = hipMemset(a->d_persist, 0, total);
-  if (e == hipSuccess) e = hipMemcpy(a->d_seq, a->h_seq.data(), sz[0], hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(a->d_persist);
-    delete a;
-    return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_l1acq_create: upload", e);
-  }
-  const int rc = ensure_work(a, max_streams);
+  s.state = cv.at<uint8_t>(b, 1); s.fcch_k = cv.at<int32_t>(b, 2); s.fcch_m = cv.at<float>(b, 3);
+  s.fcch_c = cv.at<trx_c32>(b, 4); s.fcch_e = cv.at<float>(b, 5); s.arg = cv.at<float>(b, 6); s.omega = cv.at<float>(b, 7);
+  s.w0 = cv.at<int32_t>(b, 8); s.base = cv.at<long long>(b, 9); s.wlen = cv.at<int32_t>(b, 10);
+  a->ptm = cv.at<float>(b, 11); a->toa = cv.at<float>(b, 12); a->amp = cv.at<trx_c32>(b, 13); a->soft = cv.at<float>(b, 14);
+  a->ok = cv.at<uint8_t>(b, 15); a->bsic = cv.at<uint8_t>(b, 16); a->flags = cv.at<uint8_t>(b, 17); a->rfn = cv.at<int32_t>(b, 18);
+  a->tile_m = cv.at<float>(b, 19); a->tile_k = cv.at<int32_t>(b, 20); a->tile_c = cv.at<trx_c32>(b, 21); a->tile_e = cv.at<float>(b, 22);
+  rc = ensure_work(a, max_streams);
   if (rc != TRXSIG_OK) {
-    if (a->d_work) (void)hipFree(a->d_work);
+    if (a->work.p) (void)hipFree(a->work.p);
     (void)hipFree(a->d_persist);
     delete a;
     return rc;
@@ -150,13 +132,7 @@ int trxsig_l1acq_create(trxsig_l1acq **out, trxsig_ctx *c, int max_streams, int 
 
 void trxsig_l1acq_destroy(trxsig_l1acq *a) {
   if (!a) return;
-  {
-    TrxDeviceGuard g(trxsig_device(a->c));
-    (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(a->c));
-    if (a->d_work) (void)hipFree(a->d_work);
-    if (a->d_persist) (void)hipFree(a->d_persist);
-  }
-  trx_ctx_release(a->c);
+  trx_object_destroy(a->c, { a->work.p, a->d_persist });
   delete a;
 }
 

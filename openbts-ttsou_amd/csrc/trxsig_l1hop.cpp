@@ -1,4 +1,4 @@
-// trxsig_l1hop.cpp -- the hopping stage's host side (include/trxsig_l1hop.h): the plan and its rules, the allocations of every
+// trxsig_l1hop.cpp -- the hopping stage's host side (include/trxsig_l1hop.h): the plan and its rules (placement: trxsig_plan.h), the allocations of every
 // (TN, group) on the device, the two object-owned index arrays, argument checks, and per call one launch on the context's stream
 // (k_hop_mai, k_hop_map, k_hop_bits, k_hop_cells, k_hop_result).  The host keeps nothing between calls but the plan.
 #include <hip/hip_runtime_api.h>
@@ -9,7 +9,7 @@
 #include "trxsig_ctx.h"
 #include "trxsig_l1hop.h"
 #include "trxsig_hop_dev.h"
-#include "trxsig_tdma.h"
+#include "trxsig_plan.h"
 
 static_assert(TRXSIG_L1HOP_MAX_N == kHopMaxN, "one limit");
 
@@ -24,30 +24,10 @@ struct trxsig_l1hop {
 };
 
 namespace {
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr long long kMaxSlots = 1LL << 30;
 
 int fail(trxsig_l1hop *o, const char *what) { return trx_ctx_fail(o ? o->c : nullptr, TRXSIG_EINVAL, what, hipSuccess); }
 
-// trxsig_air_cells' rules: T slots of A rows, cells of `cell` samples, must not overlap in either nesting
-bool strides_ok(long long T, long long A, long long cell, long long slot_stride, long long arfcn_stride) {
-  const bool slot_major = arfcn_stride >= cell && (T == 1 || (slot_stride >= cell && slot_stride / A >= arfcn_stride));
-  const bool arfcn_major = slot_stride >= cell && (A == 1 || (arfcn_stride >= cell && arfcn_stride / T >= slot_stride));
-  return slot_major || arfcn_major;
-}
-// one past the last sample of the last cell, from the base
-bool extent(long long T, long long A, long long cell, long long slot_stride, long long arfcn_stride, long long *out) {
-  long long x = 0, y = 0;
-  if (__builtin_mul_overflow(T - 1, slot_stride, &x) || __builtin_mul_overflow(A - 1, arfcn_stride, &y) ||
-      __builtin_add_overflow(x, y, &x) || __builtin_add_overflow(x, cell, &x) || x > (1LL << 58))
-    return false;
-  *out = x;
-  return true;
-}
-bool overlap(const trxsig_c32 *p, long long np, const trxsig_c32 *q, long long nq) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)nq * sizeof(trxsig_c32) && b < a + (uintptr_t)np * sizeof(trxsig_c32);
-}
 bool call_ok(const trxsig_l1hop *o, int fn, int n_frames) {
   return fn >= 0 && fn < kTrxHyperframe && n_frames >= 1 && 8LL * n_frames * o->A <= kMaxSlots;
 }
@@ -80,7 +60,7 @@ int trxsig_l1hop_create(trxsig_l1hop **out, trxsig_ctx *c, int n_arfcn, const ui
   for (int a = 0; a < A; a++)                                // ascending a: a row's rank is the count before it
     for (int tn = 0; tn < 8; tn++) {
       const int k = h_comb[8 * a + tn], g = h_group[8 * a + tn];
-      if (!(k == 0 || k == 1 || k == 7 || (k == 5 && a == 0 && tn == 0)))
+      if (!trx_plan_slot_ok(k, a, tn))
         return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1hop_create: unsupported channel combination or placement", hipSuccess);
       if (g < -1 || g >= G) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1hop_create: group id outside -1..n_groups-1", hipSuccess);
       if (g < 0) continue;
@@ -100,32 +80,19 @@ int trxsig_l1hop_create(trxsig_l1hop **out, trxsig_ctx *c, int n_arfcn, const ui
   o->c = c; o->A = A; o->G = G; o->max_frames = max_frames;
   o->count = count; o->member = member;
   const size_t rows = (size_t)8 * max_frames * A * sizeof(int32_t);
-  const size_t sz[] = { group.size(), rank.size(), count.size(), member.size() * 4, (size_t)(G ? G : 1), rows, rows };
-  constexpr int nsz = sizeof sz / sizeof sz[0];
-  size_t off[nsz], total = 0;
-  for (int i = 0; i < nsz; i++) { off[i] = total; total += al(sz[i]); }
+  const TrxCarve cv = { group.size(), rank.size(), count.size(), member.size() * 4, (size_t)(G ? G : 1), rows, rows };
   TrxDeviceGuard g(trxsig_device(c));
-  if (hipMalloc(&o->d_mem, total) != hipSuccess) {
-    delete o;
-    return trx_ctx_fail(c, TRXSIG_ENOMEM, "trxsig_l1hop_create: device allocation", hipSuccess);
-  }
-  char *b = (char *)o->d_mem;
+  const int rc = trx_device_block(c, "trxsig_l1hop_create", cv.total,
+                                  { { cv.off[0], group.data(), group.size() }, { cv.off[1], rank.data(), rank.size() },
+                                    { cv.off[2], count.data(), count.size() }, { cv.off[3], member.data(), member.size() * 4 },
+                                    { cv.off[4], h_hsn, (size_t)G } }, &o->d_mem);
+  if (rc != TRXSIG_OK) { delete o; return rc; }
+  void *b = o->d_mem;
   TrxHopDev &d = o->dv;
   d.n_arfcn = A; d.n_groups = G;
-  d.group = (const int8_t *)(b + off[0]); d.rank = (const uint8_t *)(b + off[1]); d.count = (const uint8_t *)(b + off[2]);
-  d.member = (const int32_t *)(b + off[3]); d.hsn = (const uint8_t *)(b + off[4]);
-  o->d_map = (int32_t *)(b + off[5]); o->d_row = (int32_t *)(b + off[6]);
-  hipError_t e = hipMemset(o->d_mem, 0, total);
-  if (e == hipSuccess) e = hipMemcpy(b + off[0], group.data(), sz[0], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + off[1], rank.data(), sz[1], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + off[2], count.data(), sz[2], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + off[3], member.data(), sz[3], hipMemcpyHostToDevice);
-  if (e == hipSuccess && G > 0) e = hipMemcpy(b + off[4], h_hsn, (size_t)G, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(o->d_mem);
-    delete o;
-    return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_l1hop_create: upload", e);
-  }
+  d.group = cv.at<int8_t>(b, 0); d.rank = cv.at<uint8_t>(b, 1); d.count = cv.at<uint8_t>(b, 2);
+  d.member = cv.at<int32_t>(b, 3); d.hsn = cv.at<uint8_t>(b, 4);
+  o->d_map = cv.at<int32_t>(b, 5); o->d_row = cv.at<int32_t>(b, 6);
   trx_ctx_retain(c);
   *out = o;
   return TRXSIG_OK;
@@ -133,12 +100,7 @@ int trxsig_l1hop_create(trxsig_l1hop **out, trxsig_ctx *c, int n_arfcn, const ui
 
 void trxsig_l1hop_destroy(trxsig_l1hop *o) {
   if (!o) return;
-  {
-    TrxDeviceGuard g(trxsig_device(o->c));
-    (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(o->c));
-    if (o->d_mem) (void)hipFree(o->d_mem);
-  }
-  trx_ctx_release(o->c);
+  trx_object_destroy(o->c, { o->d_mem });
   delete o;
 }
 

@@ -8,7 +8,7 @@
 
 #include "trxsig_ctx.h"
 #include "trxsig_l1trk_dev.h"
-#include "trxsig_tdma.h"
+#include "trxsig_plan.h"
 
 struct trxsig_l1trk {
   trxsig_ctx *c = nullptr;
@@ -24,28 +24,7 @@ struct trxsig_l1trk {
 };
 
 namespace {
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 int fail(trxsig_l1trk *t, const char *what) { return trx_ctx_fail(t ? t->c : nullptr, TRXSIG_EINVAL, what, hipSuccess); }
-
-// trxsig_l1ms_radiate's rule: T slots of A columns, cells of `cell` samples, must not overlap in either nesting
-bool strides_ok(long long T, long long A, long long cell, long long slot_stride, long long col_stride) {
-  const bool slot_major = col_stride >= cell && (T == 1 || (slot_stride >= cell && slot_stride / A >= col_stride));
-  const bool col_major = slot_stride >= cell && (A == 1 || (col_stride >= cell && col_stride / T >= slot_stride));
-  return slot_major || col_major;
-}
-// one past the last sample of the last cell, from the base
-bool extent(long long T, long long A, long long cell, long long slot_stride, long long col_stride, long long *out) {
-  long long x = 0, y = 0;
-  if (__builtin_mul_overflow(T - 1, slot_stride, &x) || __builtin_mul_overflow(A - 1, col_stride, &y) ||
-      __builtin_add_overflow(x, y, &x) || __builtin_add_overflow(x, cell, &x) || x > (1LL << 58))
-    return false;
-  *out = x;
-  return true;
-}
-bool overlap(const trxsig_c32 *p, long long np, const trxsig_c32 *q, long long nq) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)nq * sizeof(trxsig_c32) && b < a + (uintptr_t)np * sizeof(trxsig_c32);
-}
 }  // namespace
 
 int trxsig_l1trk_create(trxsig_l1trk **out, trxsig_ctx *c, int n_phones, int n_cols, const int32_t *h_phone, const int32_t *h_c0,
@@ -75,42 +54,28 @@ int trxsig_l1trk_create(trxsig_l1trk **out, trxsig_ctx *c, int n_phones, int n_c
     for (int i = 0; i < n_cols; i++) list[(size_t)fill[(size_t)h_phone[i]]++] = i;
   }
   const size_t P = (size_t)n_phones, C = (size_t)n_cols, R = P * (size_t)cap;
-  const size_t sz[] = { C * 4, P * 4, (P + 1) * 4, C * 4,                             // phone, c0, col_start, col_list
+  const TrxCarve cv = { C * 4, P * 4, (P + 1) * 4, C * 4,                             // phone, c0, col_start, col_list
                         P * 4, P * 4, P * 8, P * 8, P * 4, P * 4, P * 4, P, P * 4,     // fn x2, pos x2, phase x2, step, locked, quiet
                         P * 8, P * 8, P * 8, P * 4, P * 4,                             // toa_sum, adj, afc_delta, toa_n, afc_n
                         C, R * 4, R * 16, R * 8, R };                                  // status, fcch fn / c / e / ok
-  constexpr int n = sizeof sz / sizeof sz[0];
-  size_t off[n], total = 0;
-  for (int i = 0; i < n; i++) { off[i] = total; total += al(sz[i]); }
   TrxDeviceGuard g(trxsig_device(c));
-  if (hipMalloc(&t->d_mem, total) != hipSuccess) {
-    delete t;
-    return trx_ctx_fail(c, TRXSIG_ENOMEM, "trxsig_l1trk_create: device allocation", hipSuccess);
-  }
-  char *b = (char *)t->d_mem;
-  hipError_t e = hipMemset(t->d_mem, 0, total);
-  if (e == hipSuccess) e = hipMemcpy(b + off[0], h_phone, sz[0], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + off[1], h_c0, sz[1], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + off[2], start.data(), sz[2], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(b + off[3], list.data(), sz[3], hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(t->d_mem);
-    delete t;
-    return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_l1trk_create: upload", e);
-  }
+  const int rc = trx_device_block(c, "trxsig_l1trk_create", cv.total, { { cv.off[0], h_phone, C * 4 }, { cv.off[1], h_c0, P * 4 },
+                                  { cv.off[2], start.data(), (P + 1) * 4 }, { cv.off[3], list.data(), C * 4 } }, &t->d_mem);
+  if (rc != TRXSIG_OK) { delete t; return rc; }
+  void *b = t->d_mem;
   t->plan.n_phones = n_phones; t->plan.n_cols = n_cols;
-  t->plan.phone = (const int32_t *)(b + off[0]); t->plan.c0 = (const int32_t *)(b + off[1]);
-  t->plan.col_start = (const int32_t *)(b + off[2]); t->plan.col_list = (const int32_t *)(b + off[3]);
+  t->plan.phone = cv.at<const int32_t>(b, 0); t->plan.c0 = cv.at<const int32_t>(b, 1);
+  t->plan.col_start = cv.at<const int32_t>(b, 2); t->plan.col_list = cv.at<const int32_t>(b, 3);
   TrxTrkState &s = t->st;
-  s.fn[0] = (int32_t *)(b + off[4]); s.fn[1] = (int32_t *)(b + off[5]);
-  s.pos[0] = (long long *)(b + off[6]); s.pos[1] = (long long *)(b + off[7]);
-  s.phase[0] = (uint32_t *)(b + off[8]); s.phase[1] = (uint32_t *)(b + off[9]);
-  s.step = (uint32_t *)(b + off[10]); s.locked = (uint8_t *)(b + off[11]); s.quiet = (int32_t *)(b + off[12]);
-  s.toa_sum = (long long *)(b + off[13]); s.adj = (long long *)(b + off[14]); s.afc_delta = (long long *)(b + off[15]);
-  s.toa_n = (int32_t *)(b + off[16]); s.afc_n = (int32_t *)(b + off[17]);
+  s.fn[0] = cv.at<int32_t>(b, 4); s.fn[1] = cv.at<int32_t>(b, 5);
+  s.pos[0] = cv.at<long long>(b, 6); s.pos[1] = cv.at<long long>(b, 7);
+  s.phase[0] = cv.at<uint32_t>(b, 8); s.phase[1] = cv.at<uint32_t>(b, 9);
+  s.step = cv.at<uint32_t>(b, 10); s.locked = cv.at<uint8_t>(b, 11); s.quiet = cv.at<int32_t>(b, 12);
+  s.toa_sum = cv.at<long long>(b, 13); s.adj = cv.at<long long>(b, 14); s.afc_delta = cv.at<long long>(b, 15);
+  s.toa_n = cv.at<int32_t>(b, 16); s.afc_n = cv.at<int32_t>(b, 17);
   TrxTrkMeas &m = t->meas;
-  m.status = (uint8_t *)(b + off[18]); m.fcch_fn = (int32_t *)(b + off[19]); m.fcch_c = (double *)(b + off[20]);
-  m.fcch_e = (double *)(b + off[21]); m.fcch_ok = (uint8_t *)(b + off[22]); m.cap = cap;
+  m.status = cv.at<uint8_t>(b, 18); m.fcch_fn = cv.at<int32_t>(b, 19); m.fcch_c = cv.at<double>(b, 20);
+  m.fcch_e = cv.at<double>(b, 21); m.fcch_ok = cv.at<uint8_t>(b, 22); m.cap = cap;
   trx_ctx_retain(c);
   *out = t;
   return TRXSIG_OK;
@@ -118,12 +83,7 @@ int trxsig_l1trk_create(trxsig_l1trk **out, trxsig_ctx *c, int n_phones, int n_c
 
 void trxsig_l1trk_destroy(trxsig_l1trk *t) {
   if (!t) return;
-  {
-    TrxDeviceGuard g(trxsig_device(t->c));
-    (void)hipStreamSynchronize((hipStream_t)trxsig_get_stream(t->c));
-    if (t->d_mem) (void)hipFree(t->d_mem);
-  }
-  trx_ctx_release(t->c);
+  trx_object_destroy(t->c, { t->d_mem });
   delete t;
 }
 

@@ -11,6 +11,13 @@
 #pragma once
 #include <stdint.h>
 
+// TRX_TDMA_TABLES_ONLY (trxsig_plan.cpp, which a plain host compiler builds too): the tables, the position arithmetic and the
+// structs, without the launch declarations -- those need trxsig_launch.h before this file
+#if defined(TRX_TDMA_TABLES_ONLY) && !defined(__HIPCC__)
+#define __host__
+#define __device__
+#endif
+
 enum {
   TRX_MAP_TCHF = 0,            // FACCH_TCHF
   TRX_MAP_SACCH_TF = 1,        // + TN: SACCH_TF_T0..T7
@@ -95,6 +102,7 @@ struct TrxL1rxDev {
   int bsic;
 };
 
+#ifndef TRX_TDMA_TABLES_ONLY
 hipError_t trx_launch_l1rx_demux(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, const int32_t *row,
                                  const uint8_t *valid, const float *soft, const trx_c32 *amp, const float *toa, TrxProfiler *prof);
 hipError_t trx_launch_l1rx_finish(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, TrxProfiler *prof);
@@ -105,6 +113,7 @@ hipError_t trx_launch_l1rx_phy(hipStream_t st, const int32_t *last, int n, const
 // and, where `sacch`, power 40 / TA 0 (ms_power / ms_ta, unused otherwise)
 hipError_t trx_launch_l1rx_set(hipStream_t st, uint8_t *active, int ch, int open, uint8_t *state_fer, int32_t *ms_power,
                                int32_t *ms_ta, int sacch);
+#endif
 
 // ---- the downlink (trxsig_l1tx.h) ----------------------------------------------------------------------------------------
 // GSM/GSMTDMA.cpp's downlink TDMAMapping tables: the *D tables of SDCCH/8, SACCH/C8, SDCCH/4 and SACCH/C4, FACCH_TCHF and
@@ -203,6 +212,7 @@ struct TrxL1txLast {
 };
 void trx_l1tx_last(const trxsig_l1tx *l1, TrxL1txLast *out);
 
+#ifndef TRX_TDMA_TABLES_ONLY
 hipError_t trx_launch_l1tx_encode(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);
 hipError_t trx_launch_l1tx_mux(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);
 // open (1) / close (0) of global channel ch on copy `cur`: open sets active, cancels idle fill and, where sacch, orders 40 / 0;
@@ -211,3 +221,4 @@ hipError_t trx_launch_l1tx_set(hipStream_t st, TrxL1txChan *rec, int open, int s
 // compaction of the slots d_what != 0 into datagrams, in (FN, TN, ARFCN) order: counts [n_wg], then the datagrams
 hipError_t trx_launch_l1tx_dgram(hipStream_t st, const uint8_t *what, const uint8_t *bits, int n_arfcn, int n_frames, int fn,
                                  int32_t *wg_count, int32_t *total, uint8_t *dgram, int32_t *arfcn, int cap, TrxProfiler *prof);
+#endif

@@ -468,3 +468,40 @@ def test_bad_inputs(pkg, ctx):
     ctx.synchronize()
     assert (d.cpu().numpy() != src).any() and (t["soft"].cpu().numpy() != 1.0).any()
     ci.destroy()
+
+
+# ---- 7: one numbering for every stage ----
+def test_one_numbering_across_the_stages(pkg):
+    """The five stages that number a plan's channels take the numbering from one place (csrc/trxsig_plan.h): on one plan, the
+    TCH and XCCH classes are the same channels in the same order in all five, the CCCH in both downlink stages and the RACH in
+    both uplink stages.  And the objects' common end (trx_object_destroy): a context destroyed while an object still lives on it
+    goes when that object goes, not before."""
+    comb = np.array([[5, 7, 1, 0, 1, 7, 0, 1], [7, 1, 1, 0, 0, 1, 7, 0]], np.uint8)
+    ctx = pkg.TrxSig(4, 0)
+    rx, tx, ms = pkg.L1Rx(ctx, comb, 1), pkg.L1Tx(ctx, comb, 1), pkg.L1Ms(ctx, comb, 1)
+    mr, ci = pkg.L1MsRx(ctx, comb, 1), pkg.L1Ciph(ctx, comb)
+    objs = (rx, tx, ms, mr, ci)
+    ones, fives, sevens = [int((comb == k).sum()) for k in (1, 5, 7)]
+    for cls, n in ((pkg.L1_TCH, ones), (pkg.L1_XCCH, 8 * fives + 16 * sevens + ones)):
+        assert [o.channels(cls) for o in objs] == [n] * 5
+        for i in range(n):
+            want = rx.channel(cls, i)
+            assert [o.channel(cls, i) for o in objs] == [want] * 5, (cls, i)
+    assert tx.channels(pkg.L1_CCCH) == mr.channels(pkg.L1_CCCH) == 3
+    assert [tx.channel(pkg.L1_CCCH, i) for i in range(3)] == [mr.channel(pkg.L1_CCCH, i) for i in range(3)] == \
+        [(0, 0, pkg.L1_CCCH_C5, i) for i in range(3)]
+    assert rx.channels(pkg.L1_RACH) == ms.channels(pkg.L1_RACH) == 1
+    assert rx.channel(pkg.L1_RACH, 0) == ms.channel(pkg.L1_RACH, 0) == (0, 0, pkg.L1_RACH_C5, 0)
+    # a second context, destroyed under a live object: the object's next call (a launch on that context's stream) succeeds
+    import torch
+    ctx2 = pkg.TrxSig(4, 0)
+    held = pkg.L1Ciph(ctx2, comb)
+    ctx2.close()
+    key = (C.c_uint8 * 8)(*range(1, 9))
+    assert ctx.L.trxsig_l1ciph_set(held.h, pkg.L1_XCCH, 5, pkg.A5_1, key) == 0
+    torch.cuda.synchronize()
+    assert held.channel(pkg.L1_XCCH, 5) == ci.channel(pkg.L1_XCCH, 5)
+    held.destroy()                                           # the context goes with it
+    for o in objs:                                           # creation order, the context last
+        o.destroy()
+    ctx.close()
