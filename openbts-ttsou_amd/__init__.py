@@ -9,6 +9,9 @@ import ctypes as C
 import os
 import subprocess
 
+from ._abi import (TrxSigError, bind, C32, TrxGroupResult, L1RxOut, L1TxIn, L1TxOut, L1MsIn, L1MsOut, L1MsAir,  # noqa: F401
+                   L1MsRxOut, L1AcqOut, AirCellParams, AirStreamParams, L1TrkView, L1TrkMeas)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRXSIG_LIB", os.path.join(_HERE, "libtrxsig.so"))   # TRXSIG_LIB: tuning builds
 
@@ -19,15 +22,6 @@ TCH_FILLER, TCH_SPEECH, TCH_FACCH = 0, 1, 2      # block kinds of trxsig_fec_tch
 TCH_TX_STATE_BYTES = 32                          # TRXSIG_TCH_TX_STATE_BYTES
 FEC_DECODED, FEC_STOLEN, FEC_FACCH_OK, FEC_TCH_GOOD = 1, 2, 4, 8   # status bits of the stream decoders (TRXSIG_FEC_*)
 TCH_RX_STATE_BYTES, XCCH_RX_STATE_BYTES = 3664, 1840              # TRXSIG_TCH_RX_STATE_BYTES, TRXSIG_XCCH_RX_STATE_BYTES
-
-
-class TrxSigError(RuntimeError):
-    pass
-
-
-class C32(C.Structure):
-    """trxsig_c32 by value."""
-    _fields_ = [("re", C.c_float), ("im", C.c_float)]
 
 
 def build(verbose=False):
@@ -58,12 +52,7 @@ def lib(path=None):
     global _lib
     if path is not None:
         if path not in _libs:
-            saved = _lib
-            _lib = None
-            try:
-                _libs[path] = _load(path)
-            finally:
-                _lib = saved
+            _libs[path] = _load(path)
         return _libs[path]
     if _lib is None:
         _lib = _load(LIB_PATH)
@@ -71,104 +60,13 @@ def lib(path=None):
 
 
 def _load(path):
-    global _lib
-    if True:
-        if not os.path.exists(path):
-            raise TrxSigError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "or `make -C openbts-ttsou_amd/csrc` (there is no CPU fallback)" % os.path.basename(path))
-        L = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-        L.trxsig_abi_version.restype = i32
-        L.trxsig_create.argtypes = [C.POINTER(vp), i32, i32]
-        L.trxsig_create_from_tables.argtypes = [C.POINTER(vp), i32, vp, C.c_size_t]
-        L.trxsig_destroy.argtypes = [vp]; L.trxsig_destroy.restype = None
-        L.trxsig_sps.argtypes = [vp]; L.trxsig_device.argtypes = [vp]
-        L.trxsig_set_stream.argtypes = [vp, vp]
-        L.trxsig_synchronize.argtypes = [vp]
-        L.trxsig_last_error.argtypes = [vp]; L.trxsig_last_error.restype = C.c_char_p
-        L.trxsig_reserve.argtypes = [vp, i32]
-        L.trxsig_tables_bytes.argtypes = [i32]; L.trxsig_tables_bytes.restype = C.c_size_t
-        L.trxsig_tables_device.argtypes = [vp]; L.trxsig_tables_device.restype = vp
-        L.trxsig_tables_build_host.argtypes = [i32, vp, C.c_size_t]
-        L.trxsig_tables_export.argtypes = [vp, vp, C.c_size_t]
-        L.trxsig_detect_demod_normal_batch.argtypes = [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp,
-                                                       i32, i32]
-        L.trxsig_detect_demod_rach_batch.argtypes = [vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, i32, i32]
-        L.trxsig_detect_demod_normal_host.argtypes = [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, i32, i32]
-        L.trxsig_detect_demod_rach_host.argtypes = [vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, i32, i32]
-        L.trxsig_demodulate_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32]
-        L.trxsig_equalize_normal_batch.argtypes = [vp, vp, vp, vp, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp,
-                                                   vp, vp, i32, i32]
-        L.trxsig_equalize_normal_batch_fmt.argtypes = [vp, vp, i32, vp, vp, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp,
-                                                       vp, vp, i32, i32]
-        L.trxsig_modulate_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-        L.trxsig_modulate_host.argtypes = [vp, vp, vp, vp, i32, vp, vp, C.c_int64]
-        L.trxsig_resample_batch.argtypes = [vp, vp, i32, C.c_int64, i32, i32, i32, vp, i32, vp, C.c_int64]
-        L.trxsig_resample_out_len.argtypes = [i32, i32, i32]
-        L.trxsig_unpack_int16.argtypes = [vp, vp, C.c_int64, i32, vp]
-        L.trxsig_pack_int16.argtypes = [vp, vp, C.c_int64, vp]
-        L.trxsig_unpack_half.argtypes = [vp, vp, C.c_int64, vp]
-        L.trxsig_pack_int16_scaled.argtypes = [vp, vp, C.c_int64, C.c_float, vp]
-        L.trxsig_fec_xcch_decode_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-        L.trxsig_fec_rach_decode_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-        L.trxsig_channel_estimate_batch.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, i32, i32, vp, vp, vp, vp, vp]
-        L.trxsig_estimate_dfe_batch.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp]
-        L.trxsig_design_dfe_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-        L.trxsig_fec_xcch_encode_batch.argtypes = [vp, vp, i32, i32, vp]
-        L.trxsig_fec_tch_decode_batch.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
-        L.trxsig_fec_viterbi_batch.argtypes = [vp, vp, i32, C.c_int64, i32, vp, C.c_int64]
-        L.trxsig_fec_tch_set_filler.argtypes = [vp, vp]
-        L.trxsig_fec_tch_encode_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-        L.trxsig_fec_sch_encode_batch.argtypes = [vp, vp, vp, i32, vp]
-        L.trxsig_fec_sch_decode_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-        L.trxsig_fec_tch_decode_stream.argtypes = [vp, i32, i32, vp, i32, C.c_int64, vp, vp, i32, vp, vp, vp, vp, vp]
-        L.trxsig_fec_xcch_decode_stream.argtypes = [vp, i32, i32, vp, i32, C.c_int64, vp, i32, vp, vp, vp, vp]
-        # sigProcLib.h's free-standing primitives
-        L.trxsig_convolve_out_len.argtypes = [i32, i32, i32, i32]
-        L.trxsig_convolve_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-        L.trxsig_convolve_host.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32]
-        L.trxsig_delay_vector_batch.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
-        L.trxsig_delay_vector_host.argtypes = [vp, vp, i32, f32, i32]
-        L.trxsig_interpolate_point_batch.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
-        L.trxsig_interpolate_point_host.argtypes = [vp, vp, i32, f32, i32, vp]
-        L.trxsig_peak_detect_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
-        L.trxsig_peak_detect_host.argtypes = [vp, vp, i32, vp, vp, vp]
-        L.trxsig_scale_vector_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32]
-        L.trxsig_gmsk_rotate_batch.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32]
-        L.trxsig_vector_slicer_batch.argtypes = [vp, vp, vp, vp, i32, i32]
-        L.trxsig_decimate_batch.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
-        L.trxsig_elementwise_host.argtypes = [vp, i32, vp, i32, C32, i32]
-        L.trxsig_decimate_host.argtypes = [vp, vp, i32, i32, vp]
-        L.trxsig_energy_detect_batch.argtypes = [vp, vp, vp, vp, i32, C.c_uint, i32, f32, vp, vp]
-        L.trxsig_energy_detect_host.argtypes = [vp, vp, i32, C.c_uint, i32, f32, vp]
-        L.trxsig_db.argtypes = [f32]; L.trxsig_db.restype = f32
-        L.trxsig_dbinv.argtypes = [f32]; L.trxsig_dbinv.restype = f32
-        L.trxsig_sinc_host.argtypes = [vp, f32, C.POINTER(f32)]
-        L.trxsig_gaussian_noise_host.argtypes = [i32, f32, C32, vp]
-        L.trxsig_vector_norm2_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-        L.trxsig_vector_norm2_host.argtypes = [vp, vp, i32, C.POINTER(f32), C.POINTER(f32)]
-        L.trxsig_frequency_shift_batch.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]
-        L.trxsig_frequency_shift_host.argtypes = [vp, vp, i32, f32, f32, i32, vp, C.POINTER(f32)]
-        L.trxsig_add_vector_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32]
-        L.trxsig_add_vector_host.argtypes = [vp, vp, i32, vp, i32]
-        L.trxsig_offset_vector_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32]
-        L.trxsig_resample_linear_out_len.argtypes = [i32, f32]
-        L.trxsig_resample_linear_batch.argtypes = [vp, vp, vp, vp, i32, f32, vp, vp, vp]
-        L.trxsig_resample_linear_host.argtypes = [vp, vp, i32, f32, C32, vp, i32]
-        L.trxsig_timer_start.argtypes = [vp]
-        L.trxsig_timer_stop.argtypes = [vp, C.POINTER(f32)]
-        L.trxsig_kernel_name.argtypes = [i32]; L.trxsig_kernel_name.restype = C.c_char_p
-        L.trxsig_profile_enable.argtypes = [vp, i32]
-        L.trxsig_set_tuning.argtypes = [vp, i32, i32]
-        L.trxsig_set_soft_mode.argtypes = [vp, i32]
-        L.trxsig_get_soft_mode.argtypes = [vp]
-        L.trxsig_profile_collect.argtypes = [vp, C.POINTER(f32), C.POINTER(i32)]
-        L.trxsig_profile_collect_n.argtypes = [vp, i32, C.POINTER(f32), C.POINTER(i32)]
-        L.trxsig_kernel_count.restype = i32
-        if L.trxsig_abi_version() != ABI_VERSION:
-            raise TrxSigError("%s speaks ABI %d, this binding was written for %d" % (path, L.trxsig_abi_version(), ABI_VERSION))
-        L.trxsig_tables_validate_host.argtypes = [vp, C.c_size_t]
-        return L
+    if not os.path.exists(path):
+        raise TrxSigError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                          "or `make -C openbts-ttsou_amd/csrc` (there is no CPU fallback)" % os.path.basename(path))
+    L = C.CDLL(path, mode=C.RTLD_GLOBAL)
+    if hasattr(L, "trxsig_abi_version") and L.trxsig_abi_version() != ABI_VERSION:   # (said before a symbol of the other ABI is missed)
+        raise TrxSigError("%s speaks ABI %d, this binding was written for %d" % (path, L.trxsig_abi_version(), ABI_VERSION))
+    return bind(L, path)
 
 
 def tables_dtype():
@@ -205,6 +103,115 @@ def _ptr(t):
     if isinstance(t, int):
         return t
     return t.data_ptr()
+
+
+class _DevView:
+    """A device buffer owned by the library, presented to torch (zero copy) through __cuda_array_interface__."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = dict(data=(int(ptr), False), shape=tuple(shape), typestr=typestr, version=2)
+
+
+def _dev_tensor(ctx, ptr, shape, typestr):
+    """A device buffer owned by the library as a torch tensor on the context's device (a view: no copy)."""
+    import torch
+    return torch.as_tensor(_DevView(ptr, shape, typestr), device="cuda:%d" % ctx.device)
+
+
+def _to_host(ctx, ptr, shape, typestr):
+    """The same buffer as a host numpy array; zeros of that shape where there is nothing to read (no pointer, or no elements)."""
+    import numpy as np
+    if ptr is None or int(np.prod(shape)) == 0:
+        return np.zeros(shape, np.dtype(typestr))
+    return _dev_tensor(ctx, ptr, shape, typestr).cpu().numpy()
+
+
+def _fill(struct, names, tensors, itemsize=None, empty_as_one=False):
+    """Optional device tensors into a struct of device pointers (names: its fields, None: every pointer field in order); a None
+    tensor leaves its field NULL.  itemsize: what an element of each must measure.  empty_as_one: an empty tensor is "given, no rows"
+    (the address 1) and not NULL.  Returns the tensors, which the caller keeps alive while the launch may read them."""
+    if names is None:
+        names = [n for n, t in struct._fields_ if t is C.c_void_p]
+    for name, t in zip(names, tensors):
+        if t is not None:
+            assert t.is_contiguous() and (itemsize is None or t.element_size() == itemsize)
+            setattr(struct, name, 1 if empty_as_one and not t.numel() else t.data_ptr())
+    return tuple(tensors)
+
+
+class _Object:
+    """A library object made on a context by <_prefix>_create and released by <_prefix>_destroy.  Calls raise on rc < 0 with the
+    context's last error and return rc; destroy() is idempotent and runs at collection."""
+    _prefix = None
+
+    def __init__(self, ctx):
+        import numpy as np
+        self.np = np
+        self.ctx = ctx
+        self.L = ctx.L
+        self.h = C.c_void_p()
+
+    def _create(self, *args, name="create"):
+        name = "%s_%s" % (self._prefix, name)
+        rc = getattr(self.L, name)(C.byref(self.h), self.ctx.h, *args)
+        if rc != 0:
+            raise TrxSigError("%s failed (%d): %s" % (name, rc, self._last_error()))
+
+    def destroy(self):
+        if self.h:
+            getattr(self.L, self._prefix + "_destroy")(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _last_error(self):
+        return self.L.trxsig_last_error(self.ctx.h).decode()
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise TrxSigError("%s: %d (%s)" % (what, rc, self._last_error()))
+        return rc
+
+    def _call(self, name, *args):
+        name = "%s_%s" % (self._prefix, name)
+        return self._chk(getattr(self.L, name)(self.h, *args), name)
+
+
+class _PlanView(_Object):
+    """An object built on a channel plan (comb: uint8 [n_arfcn, 8] in the CMD SETSLOT numbering -- 0 none, 1 = I, 5 = V on ARFCN 0
+    TN 0, 7 = VII): its channels per class, where each lies, and the device array of their state records."""
+
+    def __init__(self, ctx, comb, *args):
+        super().__init__(ctx)
+        self.comb = self.np.ascontiguousarray(comb, self.np.uint8)
+        self._create(self.comb.shape[0], self.comb.ctypes.data, *args)
+
+    def channels(self, cls):
+        return self._call("channels", cls)
+
+    def channel(self, cls, chan):
+        """(arfcn, tn, kind, sub) of a channel"""
+        v = [C.c_int() for _ in range(4)]
+        self._call("channel", cls, chan, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._call("state", cls, C.byref(p))
+        return p.value
+
+
+class _PlanObject(_PlanView):
+    """A plan object whose channels are opened and closed one by one (what that means: each class's docstring)."""
+
+    def open(self, cls, chan):
+        self._call("open", cls, chan)
+
+    def close(self, cls, chan):
+        self._call("close", cls, chan)
 
 
 class TrxSig:
@@ -610,56 +617,32 @@ class TrxSig:
         return ms.value
 
 
-class TrxHost:
+class TrxHost(_Object):
     """ctypes view of include/trxsig_transceiver.h: the per-ARFCN Transceiver orchestration (pullRadioVector,
-    addRadioVector / pushRadioVector, control commands, UDP datagram codecs) on top of the GPU library."""
+    addRadioVector / pushRadioVector, control commands, UDP datagram codecs) on top of the GPU library.  It makes its own
+    context: errors are read from its own handle, and close() releases it."""
+    _prefix = "trxsig_trx"
 
     def __init__(self, sps, device=0, start=(0, 0), tsc_leg=0):
         import numpy as np
         self.np = np
-        self.L = L = lib()
-        vp, i32 = C.c_void_p, C.c_int
-        L.trxsig_trx_create.argtypes = [C.POINTER(vp), i32, i32, i32, i32]
-        L.trxsig_trx_destroy.argtypes = [vp]; L.trxsig_trx_destroy.restype = None
-        L.trxsig_trx_last_error.argtypes = [vp]; L.trxsig_trx_last_error.restype = C.c_char_p
-        L.trxsig_trx_control.argtypes = [vp, C.c_char_p, C.c_char_p, i32]
-        L.trxsig_trx_expected_corr_type.argtypes = [vp, i32, i32]
-        L.trxsig_trx_pull_radio_vector.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-        L.trxsig_trx_encode_rx_datagram.argtypes = [i32, i32, i32, i32, vp, i32, vp]
-        L.trxsig_trx_decode_tx_datagram.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]
-        L.trxsig_trx_add_radio_vector.argtypes = [vp, vp, i32, i32, i32]
-        L.trxsig_trx_push_radio_vector.argtypes = [vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
-        L.trxsig_trx_energy_threshold.argtypes = [vp]; L.trxsig_trx_energy_threshold.restype = C.c_double
-        L.trxsig_trx_filler_modulus.argtypes = [vp, i32]
-        L.trxsig_trx_queue_size.argtypes = [vp]
-        L.trxsig_create_lpf_host.argtypes = [vp, i32, C.c_float, vp]
-        L.trxsig_trx_set_tsc_leg.argtypes = [vp, i32]
+        self.L = lib()
         self.sps = sps
-        self.h = vp()
-        rc = L.trxsig_trx_create(C.byref(self.h), device, sps, start[0], start[1])
+        self.h = C.c_void_p()
+        rc = self.L.trxsig_trx_create(C.byref(self.h), device, sps, start[0], start[1])
         if rc != 0:
             raise RuntimeError("trxsig_trx_create failed: %d" % rc)
         if tsc_leg:
-            self._chk(L.trxsig_trx_set_tsc_leg(self.h, tsc_leg), "trxsig_trx_set_tsc_leg")
+            self._call("set_tsc_leg", tsc_leg)
 
-    def close(self):
-        if self.h:
-            self.L.trxsig_trx_destroy(self.h); self.h = None
+    close = _Object.destroy
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_trx_last_error(self.h).decode()))
-        return rc
+    def _last_error(self):
+        return self.L.trxsig_trx_last_error(self.h).decode()
 
     def control(self, msg):
         buf = C.create_string_buffer(128)
-        self._chk(self.L.trxsig_trx_control(self.h, msg.encode(), buf, 128), "trxsig_trx_control")
+        self._call("control", msg.encode(), buf, 128)
         return buf.value.decode()
 
     def expected_corr_type(self, tn, fn):
@@ -670,8 +653,7 @@ class TrxHost:
         x = np.ascontiguousarray(x, np.complex64)
         soft = np.zeros(160, np.float32)
         ns, rssi, toa = C.c_int(), C.c_int(), C.c_int()
-        rc = self._chk(self.L.trxsig_trx_pull_radio_vector(self.h, x.ctypes.data, len(x), tn, fn, soft.ctypes.data,
-                                                           C.byref(ns), C.byref(rssi), C.byref(toa)), "trxsig_trx_pull_radio_vector")
+        rc = self._call("pull_radio_vector", x.ctypes.data, len(x), tn, fn, soft.ctypes.data, C.byref(ns), C.byref(rssi), C.byref(toa))
         if rc == 0:
             return None
         return soft[:ns.value].copy(), rssi.value, toa.value
@@ -696,7 +678,7 @@ class TrxHost:
     def add_radio_vector(self, bits, rssi, tn, fn):
         np = self.np
         bits = np.ascontiguousarray(bits, np.uint8)
-        self._chk(self.L.trxsig_trx_add_radio_vector(self.h, bits.ctypes.data, rssi, tn, fn), "trxsig_trx_add_radio_vector")
+        self._call("add_radio_vector", bits.ctypes.data, rssi, tn, fn)
 
     def push_radio_vector(self, tn, fn):
         np = self.np
@@ -726,68 +708,22 @@ class TrxHost:
 TSCLEG_EQUALIZE, TSCLEG_DEMOD = 0, 1
 
 
-class TrxGroupResult(C.Structure):
-    """trxsig_trxgroup_result"""
-    _fields_ = [("n_slots", C.c_int), ("n_arfcn", C.c_int), ("n_rows", C.c_int), ("d_row", C.c_void_p), ("d_valid", C.c_void_p),
-                ("d_flags", C.c_void_p), ("d_amp", C.c_void_p), ("d_toa", C.c_void_p), ("d_avgpwr", C.c_void_p),
-                ("d_threshold", C.c_void_p), ("d_soft", C.c_void_p), ("soft_stride", C.c_int)]
-
-
-class TrxGroup:
-    """ctypes view of include/trxsig_trxgroup.h: S Transceivers' pullRadioVector per call, state machine on the device."""
+class TrxGroup(_Object):
+    """ctypes view of include/trxsig_trxgroup.h: S Transceivers' pullRadioVector per call, state machine on the device.
+    close() releases it."""
+    _prefix = "trxsig_trxgroup"
 
     def __init__(self, ctx, n_arfcn, tsc_leg=TSCLEG_EQUALIZE, start=(0, 0)):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-        L.trxsig_trxgroup_create.argtypes = [C.POINTER(vp), vp, i32, i32, i32, i32]
-        L.trxsig_trxgroup_destroy.argtypes = [vp]; L.trxsig_trxgroup_destroy.restype = None
-        L.trxsig_trxgroup_control.argtypes = [vp, i32, C.c_char_p, C.c_char_p, i32]
-        L.trxsig_trxgroup_expected_corr_type.argtypes = [vp, i32, i32, i32]
-        L.trxsig_trxgroup_pull.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(TrxGroupResult)]
-        L.trxsig_trxgroup_pull_host.argtypes = [vp, vp, i64, i64, i32, i32, i32, i32]
-        L.trxsig_trxgroup_pull_bursts.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(TrxGroupResult)]
-        L.trxsig_trxgroup_pull_rxfe.argtypes = [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(TrxGroupResult)]
-        L.trxsig_trxgroup_collect.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.trxsig_trxgroup_energy_threshold.argtypes = [vp, i32, C.POINTER(C.c_double)]
-        L.trxsig_trxgroup_set_pipelined.argtypes = [vp, i32]
-        L.trxsig_trxgroup_set_beside_rows.argtypes = [vp, i32]
-        L.trxsig_trxgroup_set_split_rows.argtypes = [vp, i32]
-        L.trxsig_trxgroup_sync.argtypes = [vp]
-        L.trxsig_trxgroup_add_bursts.argtypes = [vp, vp, vp, i32]
-        L.trxsig_trxgroup_tx_staging.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp)]
-        L.trxsig_trxgroup_add_staged.argtypes = [vp, i32]
-        L.trxsig_trxgroup_add_l1tx.argtypes = [vp, vp]
-        L.trxsig_trxgroup_push.argtypes = [vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-        L.trxsig_trxgroup_push_txbe.argtypes = [vp, vp, i32, i32, i32]
-        L.trxsig_trxgroup_tx_queue_size.argtypes = [vp, i32, C.POINTER(i32)]
+        super().__init__(ctx)
         self.S = n_arfcn
-        self.h = vp()
-        rc = L.trxsig_trxgroup_create(C.byref(self.h), ctx.h, n_arfcn, tsc_leg, start[0], start[1])
-        if rc != 0:
-            raise TrxSigError("trxsig_trxgroup_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self._create(n_arfcn, tsc_leg, start[0], start[1])
         self.n_slots = 0
 
-    def close(self):
-        if self.h:
-            self.L.trxsig_trxgroup_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
+    close = _Object.destroy
 
     def control(self, arfcn, msg):
         buf = C.create_string_buffer(128)
-        self._chk(self.L.trxsig_trxgroup_control(self.h, arfcn, msg.encode(), buf, 128), "trxsig_trxgroup_control")
+        self._call("control", arfcn, msg.encode(), buf, 128)
         return buf.value.decode()
 
     def expected_corr_type(self, arfcn, tn, fn):
@@ -796,8 +732,7 @@ class TrxGroup:
     def pull(self, samples, slot_stride, arfcn_stride, fn, tn, n_slots, burst_len=0):
         """samples: torch complex64-as-float32 device tensor (or a device address)."""
         res = TrxGroupResult()
-        self._chk(self.L.trxsig_trxgroup_pull(self.h, _ptr(samples), slot_stride, arfcn_stride, burst_len, fn, tn, n_slots, C.byref(res)),
-                  "trxsig_trxgroup_pull")
+        self._call("pull", _ptr(samples), slot_stride, arfcn_stride, burst_len, fn, tn, n_slots, C.byref(res))
         self.n_slots = n_slots
         return res
 
@@ -805,8 +740,7 @@ class TrxGroup:
         """pull on LISTED bursts: burst t of ARFCN a is entry a*n_per_arfcn + t of offset / length (int32 device tensors or addresses,
         samples into `samples`); (fn, tn) = the time of burst 0.  The samples are only read: entries may share a burst."""
         res = TrxGroupResult()
-        self._chk(self.L.trxsig_trxgroup_pull_bursts(self.h, _ptr(samples), _ptr(offset), _ptr(length), n_per_arfcn, fn, tn, C.byref(res)),
-                  "trxsig_trxgroup_pull_bursts")
+        self._call("pull_bursts", _ptr(samples), _ptr(offset), _ptr(length), n_per_arfcn, fn, tn, C.byref(res))
         self.n_slots = n_per_arfcn
         return res
 
@@ -817,8 +751,7 @@ class TrxGroup:
         res = TrxGroupResult()
         n = C.c_int()
         chunk = 864 * max(1, getattr(fe, "rate_factor", 0) or 1)   # (a wideband front end: iq [Sw, K*864*R, 2])
-        self._chk(self.L.trxsig_trxgroup_pull_rxfe(self.h, fe.h, iq.data_ptr(), iq.shape[1] // chunk, fn, C.byref(n), C.byref(res)),
-                  "trxsig_trxgroup_pull_rxfe")
+        self._call("pull_rxfe", fe.h, iq.data_ptr(), iq.shape[1] // chunk, fn, C.byref(n), C.byref(res))
         fe._keep = iq
         self.n_slots = n.value
         return n.value, res
@@ -829,52 +762,50 @@ class TrxGroup:
         np = self.np
         d = np.ascontiguousarray(datagrams, np.uint8); a = np.ascontiguousarray(arfcn, np.int32)
         assert d.ndim == 2 and d.shape[1] == 154 and a.shape == (d.shape[0],)
-        self._chk(self.L.trxsig_trxgroup_add_bursts(self.h, d.ctypes.data, a.ctypes.data, d.shape[0]), "trxsig_trxgroup_add_bursts")
+        self._call("add_bursts", d.ctypes.data, a.ctypes.data, d.shape[0])
 
     def tx_staging(self, n_max):
         """The pinned block to RECEIVE the next batch into: (datagrams uint8 [n_max, 154], arfcn int32 [n_max]) as numpy views of the
         library's memory; valid until add_staged."""
         np = self.np
         pd, pa = C.c_void_p(), C.c_void_p()
-        self._chk(self.L.trxsig_trxgroup_tx_staging(self.h, int(n_max), C.byref(pd), C.byref(pa)), "trxsig_trxgroup_tx_staging")
+        self._call("tx_staging", int(n_max), C.byref(pd), C.byref(pa))
         d = np.ctypeslib.as_array(C.cast(pd, C.POINTER(C.c_uint8)), shape=(n_max, 154))
         a = np.ctypeslib.as_array(C.cast(pa, C.POINTER(C.c_int32)), shape=(n_max,))
         return d, a
 
     def add_staged(self, n):
         """The first n datagrams of the staging block: header check on the host, one upload, one kernel."""
-        self._chk(self.L.trxsig_trxgroup_add_staged(self.h, int(n)), "trxsig_trxgroup_add_staged")
+        self._call("add_staged", int(n))
 
     def add_l1tx(self, l1):
         """Every non-empty slot of l1's (an L1Tx on the same context) last encode into the queues, device to device: the effect of
         add_bursts(*l1.datagrams()) without the copy down, the host's header loop and the upload.  Enqueues only."""
-        self._chk(self.L.trxsig_trxgroup_add_l1tx(self.h, l1.h if l1 is not None else None), "trxsig_trxgroup_add_l1tx")
+        self._call("add_l1tx", l1.h if l1 is not None else None)
 
     def push(self, fn, tn, n_slots, device="cuda:0"):
         """pushRadioVector for n_slots timeslots from (fn, tn): (bits uint8 [S, n, 148], gain float32 [S, n], from_queue uint8 [S, n])
         as torch views of the group's device buffers (valid until the next push)."""
         import torch
-        from .frontend import _DevView
         pb, pg, pq = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        self._chk(self.L.trxsig_trxgroup_push(self.h, fn, tn, n_slots, C.byref(pb), C.byref(pg), C.byref(pq)), "trxsig_trxgroup_push")
+        self._call("push", fn, tn, n_slots, C.byref(pb), C.byref(pg), C.byref(pq))
         dev = torch.device(device)
         return (torch.as_tensor(_DevView(pb.value, (self.S, n_slots, 148), "|u1"), device=dev),
                 torch.as_tensor(_DevView(pg.value, (self.S, n_slots), "<f4"), device=dev),
                 torch.as_tensor(_DevView(pq.value, (self.S, n_slots), "|u1"), device=dev))
 
     def push_txbe(self, be, fn, tn, n_slots):
-        self._chk(self.L.trxsig_trxgroup_push_txbe(self.h, be.h, fn, tn, n_slots), "trxsig_trxgroup_push_txbe")
+        self._call("push_txbe", be.h, fn, tn, n_slots)
 
     def tx_queue_size(self, arfcn):
         dropped = C.c_int()
-        n = self._chk(self.L.trxsig_trxgroup_tx_queue_size(self.h, arfcn, C.byref(dropped)), "trxsig_trxgroup_tx_queue_size")
+        n = self._call("tx_queue_size", arfcn, C.byref(dropped))
         return n, bool(dropped.value)
 
     def pull_host(self, x, slot_stride, arfcn_stride, fn, tn, n_slots, burst_len=0):
         np = self.np
         x = np.ascontiguousarray(x, np.complex64)
-        self._chk(self.L.trxsig_trxgroup_pull_host(self.h, x.ctypes.data, slot_stride, arfcn_stride, burst_len, fn, tn, n_slots),
-                  "trxsig_trxgroup_pull_host")
+        self._call("pull_host", x.ctypes.data, slot_stride, arfcn_stride, burst_len, fn, tn, n_slots)
         self.n_slots = n_slots
 
     def collect(self, soft=True):
@@ -883,30 +814,29 @@ class TrxGroup:
         n = self.n_slots * self.S
         valid = np.zeros(n, np.uint8); rssi = np.zeros(n, np.int32); timing = np.zeros(n, np.int32); thr = np.zeros(n, np.float64)
         sb = np.zeros((n, 148), np.float32) if soft else None
-        self._chk(self.L.trxsig_trxgroup_collect(self.h, valid.ctypes.data, sb.ctypes.data if soft else None, rssi.ctypes.data,
-                                                 timing.ctypes.data, thr.ctypes.data), "trxsig_trxgroup_collect")
+        self._call("collect", valid.ctypes.data, sb.ctypes.data if soft else None, rssi.ctypes.data, timing.ctypes.data, thr.ctypes.data)
         sh = (self.n_slots, self.S)
         return dict(valid=valid.reshape(sh).astype(bool), soft=None if sb is None else sb.reshape(sh + (148,)), rssi=rssi.reshape(sh),
                     timing=timing.reshape(sh), threshold=thr.reshape(sh))
 
     def set_pipelined(self, on=True):
         """Large pulls return without joining the side stream the state machine replays on (see trxsig_trxgroup.h)."""
-        self._chk(self.L.trxsig_trxgroup_set_pipelined(self.h, 1 if on else 0), "trxsig_trxgroup_set_pipelined")
+        self._call("set_pipelined", 1 if on else 0)
 
     def set_beside_rows(self, rows):
         """Pulls with at least `rows` rows replay the state machine on the group's side stream (0 = never, the default)."""
-        self._chk(self.L.trxsig_trxgroup_set_beside_rows(self.h, int(rows)), "trxsig_trxgroup_set_beside_rows")
+        self._call("set_beside_rows", int(rows))
 
     def set_split_rows(self, rows):
         """Fused pulls with at least `rows` rows and both kinds of burst detect the access bursts beside the normal ones (0 = never)."""
-        self._chk(self.L.trxsig_trxgroup_set_split_rows(self.h, int(rows)), "trxsig_trxgroup_set_split_rows")
+        self._call("set_split_rows", int(rows))
 
     def sync(self):
-        self._chk(self.L.trxsig_trxgroup_sync(self.h), "trxsig_trxgroup_sync")
+        self._call("sync")
 
     def energy_threshold(self, arfcn):
         v = C.c_double()
-        self._chk(self.L.trxsig_trxgroup_energy_threshold(self.h, arfcn, C.byref(v)), "trxsig_trxgroup_energy_threshold")
+        self._call("energy_threshold", arfcn, C.byref(v))
         return v.value
 
 
@@ -914,112 +844,45 @@ L1_TCH, L1_XCCH, L1_RACH = 0, 1, 2               # channel classes of trxsig_l1r
 L1_TCHF, L1_SACCH_TF, L1_SDCCH8, L1_SACCH_C8, L1_SDCCH4, L1_SACCH_C4, L1_RACH_C5 = range(7)   # mapping kinds (TRXSIG_L1_*)
 
 
-class L1RxOut(C.Structure):
-    """trxsig_l1rx_out"""
-    _fields_ = [(n, C.c_int) for n in ("n_tch", "n_xcch", "nb_tch", "nb_xcch", "rach_cap")] + \
-               [(n, C.c_void_p) for n in ("d_tch_status", "d_tch_frames", "d_facch", "d_tch_fer", "d_tch_fn", "d_xcch_status",
-                                          "d_xcch_frames", "d_xcch_fer", "d_xcch_fn", "d_rach_count", "d_rach_fn", "d_rach_arfcn",
-                                          "d_rach_rssi", "d_rach_timing", "d_rach_ok", "d_rach_ra", "d_tch_rssi", "d_tch_timing",
-                                          "d_xcch_rssi", "d_xcch_timing", "d_ms_power", "d_ms_ta")]
-
-
-class L1Rx:
+class L1Rx(_PlanObject):
     """ctypes view of include/trxsig_l1rx.h: a Transceiver group pull -> the logical channels' decoders, on the device.
-    comb: uint8 [n_arfcn, 8] in the CMD SETSLOT numbering (0 none, 1 = I, 5 = V on ARFCN 0 TN 0, 7 = VII)."""
+    open(cls, chan): L1Decoder::open of one TCH / XCCH channel (FER reset; SACCH: power 40, TA 0).
+    close(cls, chan): L1Decoder::close of one TCH / XCCH channel: its bursts are ignored until it is opened again.
+    destroy(): trxsig_l1rx_destroy (channels are closed with close(cls, chan))."""
+    _prefix = "trxsig_l1rx"
 
     def __init__(self, ctx, comb, bsic, band=900):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32 = C.c_void_p, C.c_int
-        L.trxsig_l1rx_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32]
-        L.trxsig_l1rx_destroy.argtypes = [vp]; L.trxsig_l1rx_destroy.restype = None
-        L.trxsig_l1rx_channels.argtypes = [vp, i32]
-        L.trxsig_l1rx_channel.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-        L.trxsig_l1rx_open.argtypes = [vp, i32, i32]
-        L.trxsig_l1rx_close.argtypes = [vp, i32, i32]
-        L.trxsig_l1rx_state.argtypes = [vp, i32, C.POINTER(vp)]
-        L.trxsig_l1rx_decode.argtypes = [vp, C.POINTER(TrxGroupResult), i32, i32, C.POINTER(L1RxOut)]
-        self.comb = np.ascontiguousarray(comb, np.uint8)
-        self.h = vp()
-        rc = L.trxsig_l1rx_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1rx_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        super().__init__(ctx, comb, int(bsic), int(band))
         self.out = None
-
-    def destroy(self):
-        """trxsig_l1rx_destroy (channels are closed with close(cls, chan))."""
-        if self.h:
-            self.L.trxsig_l1rx_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
-
-    def channels(self, cls):
-        return self._chk(self.L.trxsig_l1rx_channels(self.h, cls), "trxsig_l1rx_channels")
-
-    def channel(self, cls, chan):
-        """(arfcn, tn, kind, sub) of a channel"""
-        v = [C.c_int() for _ in range(4)]
-        self._chk(self.L.trxsig_l1rx_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1rx_channel")
-        return tuple(x.value for x in v)
-
-    def open(self, cls, chan):
-        """L1Decoder::open of one TCH / XCCH channel (FER reset; SACCH: power 40, TA 0)."""
-        self._chk(self.L.trxsig_l1rx_open(self.h, cls, chan), "trxsig_l1rx_open")
-
-    def close(self, cls, chan):
-        """L1Decoder::close of one TCH / XCCH channel: its bursts are ignored until it is opened again."""
-        self._chk(self.L.trxsig_l1rx_close(self.h, cls, chan), "trxsig_l1rx_close")
 
     def decode(self, res, fn, wire=True):
         """res: a TrxGroupResult (of trxsig_trxgroup_pull, or built from tensors); whole frames from (fn, TN 0)."""
         out = L1RxOut()
-        self._chk(self.L.trxsig_l1rx_decode(self.h, C.byref(res), int(fn), int(bool(wire)), C.byref(out)), "trxsig_l1rx_decode")
+        self._call("decode", C.byref(res), int(fn), int(bool(wire)), C.byref(out))
         self.out = out
         return out
 
-    def state(self, cls):
-        p = C.c_void_p()
-        self._chk(self.L.trxsig_l1rx_state(self.h, cls, C.byref(p)), "trxsig_l1rx_state")
-        return p.value
-
     def collect(self, state=True):
         """The last decode's outputs as host numpy arrays (synchronises the context's stream)."""
-        import torch
-        from .frontend import _DevView
-        np, o = self.np, self.out
+        o = self.out
         self.ctx.synchronize()
-
-        def get(p, shape, ts):
-            if p is None or int(np.prod(shape)) == 0:
-                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32, "<f4": np.float32}[ts])
-            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
         T, X, bt, bx, R = o.n_tch, o.n_xcch, o.nb_tch, o.nb_xcch, o.rach_cap
-        r = dict(tch_status=get(o.d_tch_status, (T, bt), "|u1"), tch=get(o.d_tch_frames, (T, bt, 33), "|u1"),
-                 facch=get(o.d_facch, (T, bt, 23), "|u1"), tch_fer=get(o.d_tch_fer, (T, bt), "<f4"),
-                 tch_fn=get(o.d_tch_fn, (T, bt), "<i4"),
-                 xcch_status=get(o.d_xcch_status, (X, bx), "|u1"), xcch=get(o.d_xcch_frames, (X, bx, 23), "|u1"),
-                 xcch_fer=get(o.d_xcch_fer, (X, bx), "<f4"), xcch_fn=get(o.d_xcch_fn, (X, bx), "<i4"),
-                 tch_rssi=get(o.d_tch_rssi, (T,), "<i4"), tch_timing=get(o.d_tch_timing, (T,), "<i4"),
-                 xcch_rssi=get(o.d_xcch_rssi, (X,), "<i4"), xcch_timing=get(o.d_xcch_timing, (X,), "<i4"),
-                 ms_power=get(o.d_ms_power, (X,), "<i4"), ms_ta=get(o.d_ms_ta, (X,), "<i4"))
-        n = int(get(o.d_rach_count, (1,), "<i4")[0]) if R else 0
-        r["rach"] = dict(fn=get(o.d_rach_fn, (R,), "<i4")[:n], arfcn=get(o.d_rach_arfcn, (R,), "<i4")[:n],
-                         rssi=get(o.d_rach_rssi, (R,), "<i4")[:n], timing=get(o.d_rach_timing, (R,), "<i4")[:n],
-                         ok=get(o.d_rach_ok, (R,), "|u1")[:n], ra=get(o.d_rach_ra, (R,), "|u1")[:n])
+        r = dict(tch_status=host(o.d_tch_status, (T, bt), "|u1"), tch=host(o.d_tch_frames, (T, bt, 33), "|u1"),
+                 facch=host(o.d_facch, (T, bt, 23), "|u1"), tch_fer=host(o.d_tch_fer, (T, bt), "<f4"),
+                 tch_fn=host(o.d_tch_fn, (T, bt), "<i4"),
+                 xcch_status=host(o.d_xcch_status, (X, bx), "|u1"), xcch=host(o.d_xcch_frames, (X, bx, 23), "|u1"),
+                 xcch_fer=host(o.d_xcch_fer, (X, bx), "<f4"), xcch_fn=host(o.d_xcch_fn, (X, bx), "<i4"),
+                 tch_rssi=host(o.d_tch_rssi, (T,), "<i4"), tch_timing=host(o.d_tch_timing, (T,), "<i4"),
+                 xcch_rssi=host(o.d_xcch_rssi, (X,), "<i4"), xcch_timing=host(o.d_xcch_timing, (X,), "<i4"),
+                 ms_power=host(o.d_ms_power, (X,), "<i4"), ms_ta=host(o.d_ms_ta, (X,), "<i4"))
+        n = int(host(o.d_rach_count, (1,), "<i4")[0]) if R else 0
+        r["rach"] = dict(fn=host(o.d_rach_fn, (R,), "<i4")[:n], arfcn=host(o.d_rach_arfcn, (R,), "<i4")[:n],
+                         rssi=host(o.d_rach_rssi, (R,), "<i4")[:n], timing=host(o.d_rach_timing, (R,), "<i4")[:n],
+                         ok=host(o.d_rach_ok, (R,), "|u1")[:n], ra=host(o.d_rach_ra, (R,), "|u1")[:n])
         if state:
-            r["tch_state"] = get(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
-            r["xcch_state"] = get(self.state(L1_XCCH), (X, XCCH_RX_STATE_BYTES), "|u1")
+            r["tch_state"] = host(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
+            r["xcch_state"] = host(self.state(L1_XCCH), (X, XCCH_RX_STATE_BYTES), "|u1")
         return r
 
 
@@ -1028,129 +891,50 @@ L1TX_STATE_BYTES = 160                           # TRXSIG_L1TX_STATE_BYTES
 L1TX_NONE, L1TX_FCCH, L1TX_SCH, L1TX_BCCH, L1TX_CCCH, L1TX_XCCH, L1TX_TCH, L1TX_IDLE = range(8)   # d_what codes
 
 
-class L1TxIn(C.Structure):
-    """trxsig_l1tx_in"""
-    _fields_ = [(n, C.c_void_p) for n in ("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_ccch_kind",
-                                          "d_ccch_payload")]
-
-
-class L1TxOut(C.Structure):
-    """trxsig_l1tx_out"""
-    _fields_ = [(n, C.c_int) for n in ("n_arfcn", "n_frames", "n_xcch")] + \
-               [(n, C.c_void_p) for n in ("d_bits", "d_what", "d_ms_power", "d_ms_ta")]
-
-
-class L1Tx:
+class L1Tx(_PlanObject):
     """ctypes view of include/trxsig_l1tx.h: per-channel payloads for whole frames -> timed bursts, on the device.
-    comb as for L1Rx; rssi_target is GSM.RSSITarget."""
+    comb as for L1Rx; rssi_target is GSM.RSSITarget.
+    open(cls, chan): L1Encoder::open of one TCH / XCCH / CCCH channel (SACCH: orders 40 dBm / TA 0; pending idle fill cancelled).
+    close(cls, chan): L1Encoder::close: nothing more is sent; the next numFrames positions carry the dummy burst."""
+    _prefix = "trxsig_l1tx"
 
     def __init__(self, ctx, comb, bsic, band=900, rssi_target=-15.0):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
-        L.trxsig_l1tx_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32, C.c_float]
-        L.trxsig_l1tx_destroy.argtypes = [vp]; L.trxsig_l1tx_destroy.restype = None
-        L.trxsig_l1tx_channels.argtypes = [vp, i32]
-        L.trxsig_l1tx_channel.argtypes = [vp, i32, i32, ip, ip, ip, ip]
-        L.trxsig_l1tx_open.argtypes = [vp, i32, i32]
-        L.trxsig_l1tx_close.argtypes = [vp, i32, i32]
-        L.trxsig_l1tx_set_si.argtypes = [vp, vp]
-        L.trxsig_l1tx_grid.argtypes = [vp, i32, i32, ip, ip, ip]
-        L.trxsig_l1tx_encode.argtypes = [vp, i32, i32, C.POINTER(L1TxIn), vp, C.POINTER(L1TxOut)]
-        L.trxsig_l1tx_datagrams.argtypes = [vp, vp, vp, i32, ip]
-        L.trxsig_l1tx_state.argtypes = [vp, i32, C.POINTER(vp)]
-        self.comb = np.ascontiguousarray(comb, np.uint8)
-        self.h = vp()
-        rc = L.trxsig_l1tx_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band),
-                                  float(rssi_target))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1tx_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        super().__init__(ctx, comb, int(bsic), int(band), float(rssi_target))
         self.out = None
         self._keep = None
-
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_l1tx_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
-
-    def channels(self, cls):
-        return self._chk(self.L.trxsig_l1tx_channels(self.h, cls), "trxsig_l1tx_channels")
-
-    def channel(self, cls, chan):
-        """(arfcn, tn, kind, sub) of a channel"""
-        v = [C.c_int() for _ in range(4)]
-        self._chk(self.L.trxsig_l1tx_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1tx_channel")
-        return tuple(x.value for x in v)
-
-    def open(self, cls, chan):
-        """L1Encoder::open of one TCH / XCCH / CCCH channel (SACCH: orders 40 dBm / TA 0; pending idle fill cancelled)."""
-        self._chk(self.L.trxsig_l1tx_open(self.h, cls, chan), "trxsig_l1tx_open")
-
-    def close(self, cls, chan):
-        """L1Encoder::close: nothing more is sent; the next numFrames positions carry the dummy burst."""
-        self._chk(self.L.trxsig_l1tx_close(self.h, cls, chan), "trxsig_l1tx_close")
 
     def set_si(self, si):
         """si: uint8 [4, 23], SI1..SI4."""
         si = self.np.ascontiguousarray(si, self.np.uint8).reshape(4, 23)
-        self._chk(self.L.trxsig_l1tx_set_si(self.h, si.ctypes.data), "trxsig_l1tx_set_si")
+        self._call("set_si", si.ctypes.data)
 
     def grid(self, fn, n_frames):
         """(nb_tch, nb_xcch, nb_ccch) of a call"""
         v = [C.c_int() for _ in range(3)]
-        self._chk(self.L.trxsig_l1tx_grid(self.h, int(fn), int(n_frames), *[C.byref(x) for x in v]), "trxsig_l1tx_grid")
+        self._call("grid", int(fn), int(n_frames), *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
     def encode(self, fn, n_frames, tch_kind=None, tch_payload=None, xcch_kind=None, xcch_payload=None, ccch_kind=None,
                ccch_payload=None, sibling=None):
         """Grids as torch uint8 tensors on the context's device (or None for a class without channels)."""
-        ins = L1TxIn()
-        keep = (tch_kind, tch_payload, xcch_kind, xcch_payload, ccch_kind, ccch_payload)
-        for name, t in zip(("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_ccch_kind", "d_ccch_payload"), keep):
-            if t is not None:
-                assert t.is_contiguous() and t.dtype.itemsize == 1
-                setattr(ins, name, t.data_ptr() if t.numel() else 1)
-        out = L1TxOut()
-        self._chk(self.L.trxsig_l1tx_encode(self.h, int(fn), int(n_frames), C.byref(ins), sibling.h if sibling is not None else None,
-                                            C.byref(out)), "trxsig_l1tx_encode")
+        ins, out = L1TxIn(), L1TxOut()
+        keep = _fill(ins, None, (tch_kind, tch_payload, xcch_kind, xcch_payload, ccch_kind, ccch_payload), itemsize=1, empty_as_one=True)
+        self._call("encode", int(fn), int(n_frames), C.byref(ins), sibling.h if sibling is not None else None, C.byref(out))
         self._keep = keep
         self.out = out
         return out
 
-    def state(self, cls):
-        p = C.c_void_p()
-        self._chk(self.L.trxsig_l1tx_state(self.h, cls, C.byref(p)), "trxsig_l1tx_state")
-        return p.value
-
     def collect(self, state=True):
         """The last encode's outputs as host numpy arrays (synchronises the context's stream)."""
-        import torch
-        from .frontend import _DevView
-        np, o = self.np, self.out
+        o = self.out
         self.ctx.synchronize()
-
-        def get(p, shape, ts):
-            if p is None or int(np.prod(shape)) == 0:
-                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32, "<f4": np.float32}[ts])
-            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
         A, F, X = o.n_arfcn, o.n_frames, o.n_xcch
-        r = dict(bits=get(o.d_bits, (A, 8 * F, 148), "|u1"), what=get(o.d_what, (A, 8 * F), "|u1"),
-                 ms_power=get(o.d_ms_power, (X,), "<i4"), ms_ta=get(o.d_ms_ta, (X,), "<f4"))
+        r = dict(bits=host(o.d_bits, (A, 8 * F, 148), "|u1"), what=host(o.d_what, (A, 8 * F), "|u1"),
+                 ms_power=host(o.d_ms_power, (X,), "<i4"), ms_ta=host(o.d_ms_ta, (X,), "<f4"))
         if state:
             for cls, key in ((L1_TCH, "tch_state"), (L1_XCCH, "xcch_state"), (L1_CCCH, "ccch_state")):
-                r[key] = get(self.state(cls), (self.channels(cls), L1TX_STATE_BYTES), "|u1")
+                r[key] = host(self.state(cls), (self.channels(cls), L1TX_STATE_BYTES), "|u1")
         return r
 
     def datagrams(self, cap=None):
@@ -1161,7 +945,7 @@ class L1Tx:
             o = self.out
             cap = o.n_arfcn * 8 * o.n_frames
         d = np.zeros((max(cap, 1), 154), np.uint8); a = np.zeros(max(cap, 1), np.int32)
-        self._chk(self.L.trxsig_l1tx_datagrams(self.h, d.ctypes.data, a.ctypes.data, int(cap), C.byref(n)), "trxsig_l1tx_datagrams")
+        self._call("datagrams", d.ctypes.data, a.ctypes.data, int(cap), C.byref(n))
         return d[:n.value], a[:n.value]
 
 
@@ -1169,109 +953,35 @@ L1MS_STATE_BYTES = 160                           # TRXSIG_L1MS_STATE_BYTES
 L1MS_NONE, L1MS_TCH, L1MS_XCCH, L1MS_ACCESS = range(4)   # d_what codes of trxsig_l1ms.h
 
 
-class L1MsIn(C.Structure):
-    """trxsig_l1ms_in"""
-    _fields_ = [(n, C.c_void_p) for n in ("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_rach_kind",
-                                          "d_rach_ra", "d_rach_bsic")]
-
-
-class L1MsOut(C.Structure):
-    """trxsig_l1ms_out"""
-    _fields_ = [(n, C.c_int) for n in ("n_arfcn", "n_frames", "n_xcch")] + \
-               [(n, C.c_void_p) for n in ("d_bits", "d_what", "d_ms_power", "d_ms_ta")]
-
-
-class L1MsAir(C.Structure):
-    """trxsig_l1ms_air"""
-    _fields_ = [(n, C.c_void_p) for n in ("d_tch_gain", "d_tch_delay", "d_xcch_gain", "d_xcch_delay", "d_rach_gain",
-                                          "d_rach_delay", "d_amp_of_power")]
-
-
-class L1Ms:
+class L1Ms(_PlanObject):
     """ctypes view of include/trxsig_l1ms.h: the handsets of a cell -- per-channel uplink payloads for whole frames -> timed
-    uplink bursts -> the samples TrxGroup.pull takes, on the device.  comb as for L1Rx."""
+    uplink bursts -> the samples TrxGroup.pull takes, on the device.  comb as for L1Rx.
+    open(cls, chan): open of one TCH / XCCH channel (SACCH: the handset back at the band's level nearest 40 dBm, TA 0).
+    close(cls, chan): no new block of the channel is sent until it is opened again."""
+    _prefix = "trxsig_l1ms"
 
     def __init__(self, ctx, comb, bsic, band=900):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, ip, i64 = C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int64
-        L.trxsig_l1ms_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32]
-        L.trxsig_l1ms_destroy.argtypes = [vp]; L.trxsig_l1ms_destroy.restype = None
-        L.trxsig_l1ms_channels.argtypes = [vp, i32]
-        L.trxsig_l1ms_channel.argtypes = [vp, i32, i32, ip, ip, ip, ip]
-        L.trxsig_l1ms_open.argtypes = [vp, i32, i32]
-        L.trxsig_l1ms_close.argtypes = [vp, i32, i32]
-        L.trxsig_l1ms_set_phy.argtypes = [vp, i32, i32, i32]
-        L.trxsig_l1ms_grid.argtypes = [vp, i32, i32, ip, ip, ip]
-        L.trxsig_l1ms_encode.argtypes = [vp, i32, i32, C.POINTER(L1MsIn), vp, C.POINTER(L1MsOut)]
-        L.trxsig_l1ms_radiate.argtypes = [vp, C.POINTER(L1MsAir), vp, i64, i64]
-        L.trxsig_l1ms_state.argtypes = [vp, i32, C.POINTER(vp)]
-        L.trxsig_l1ms_follow.argtypes = [vp, vp]
-        self.comb = np.ascontiguousarray(comb, np.uint8)
-        self.h = vp()
-        rc = L.trxsig_l1ms_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1ms_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        super().__init__(ctx, comb, int(bsic), int(band))
         self.out = None
         self._keep = None
 
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_l1ms_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
-
-    def channels(self, cls):
-        return self._chk(self.L.trxsig_l1ms_channels(self.h, cls), "trxsig_l1ms_channels")
-
-    def channel(self, cls, chan):
-        """(arfcn, tn, kind, sub) of a channel"""
-        v = [C.c_int() for _ in range(4)]
-        self._chk(self.L.trxsig_l1ms_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1ms_channel")
-        return tuple(x.value for x in v)
-
-    def open(self, cls, chan):
-        """open of one TCH / XCCH channel (SACCH: the handset back at the band's level nearest 40 dBm, TA 0)."""
-        self._chk(self.L.trxsig_l1ms_open(self.h, cls, chan), "trxsig_l1ms_open")
-
-    def close(self, cls, chan):
-        """close: no new block of the channel is sent until it is opened again."""
-        self._chk(self.L.trxsig_l1ms_close(self.h, cls, chan), "trxsig_l1ms_close")
-
     def set_phy(self, xcch_chan, power_dbm, ta):
         """The handset of a SACCH channel: power (0..40 dBm, taken to the band's nearest level) and TA (0..63)."""
-        self._chk(self.L.trxsig_l1ms_set_phy(self.h, int(xcch_chan), int(power_dbm), int(ta)), "trxsig_l1ms_set_phy")
+        self._call("set_phy", int(xcch_chan), int(power_dbm), int(ta))
 
     def grid(self, fn, n_frames):
         """(nb_tch, nb_xcch, n_rach) of a call"""
         v = [C.c_int() for _ in range(3)]
-        self._chk(self.L.trxsig_l1ms_grid(self.h, int(fn), int(n_frames), *[C.byref(x) for x in v]), "trxsig_l1ms_grid")
+        self._call("grid", int(fn), int(n_frames), *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
     def encode(self, fn, n_frames, tch_kind=None, tch_payload=None, xcch_kind=None, xcch_payload=None, rach_kind=None,
                rach_ra=None, rach_bsic=None, sibling=None):
         """Grids as torch uint8 tensors on the context's device (or None for a class without channels); sibling: an L1Tx."""
-        ins = L1MsIn()
-        keep = (tch_kind, tch_payload, xcch_kind, xcch_payload, rach_kind, rach_ra, rach_bsic)
-        for name, t in zip(("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_rach_kind", "d_rach_ra",
-                            "d_rach_bsic"), keep):
-            if t is not None:
-                assert t.is_contiguous() and t.dtype.itemsize == 1
-                setattr(ins, name, t.data_ptr() if t.numel() else 1)
-        out = L1MsOut()
-        self._chk(self.L.trxsig_l1ms_encode(self.h, int(fn), int(n_frames), C.byref(ins), sibling.h if sibling is not None else None,
-                                            C.byref(out)), "trxsig_l1ms_encode")
+        ins, out = L1MsIn(), L1MsOut()
+        keep = _fill(ins, None, (tch_kind, tch_payload, xcch_kind, xcch_payload, rach_kind, rach_ra, rach_bsic), itemsize=1,
+                     empty_as_one=True)
+        self._call("encode", int(fn), int(n_frames), C.byref(ins), sibling.h if sibling is not None else None, C.byref(out))
         self._keep = keep
         self.out = out
         return out
@@ -1281,43 +991,26 @@ class L1Ms:
         """The last encode as samples into `samples` (a complex64 / float32 tensor or a device address), strides in complex
         samples.  Gains: complex64 (or float32 [n, 2]) tensors, delays float32 (symbols), amp_of_power float32 [41]."""
         air = L1MsAir()
-        keep = (tch_gain, tch_delay, xcch_gain, xcch_delay, rach_gain, rach_delay, amp_of_power)
-        for name, t in zip(("d_tch_gain", "d_tch_delay", "d_xcch_gain", "d_xcch_delay", "d_rach_gain", "d_rach_delay",
-                            "d_amp_of_power"), keep):
-            if t is not None:
-                assert t.is_contiguous()
-                setattr(air, name, t.data_ptr() if t.numel() else 1)
-        self._chk(self.L.trxsig_l1ms_radiate(self.h, C.byref(air), _ptr(samples), int(slot_stride), int(arfcn_stride)),
-                  "trxsig_l1ms_radiate")
+        keep = _fill(air, None, (tch_gain, tch_delay, xcch_gain, xcch_delay, rach_gain, rach_delay, amp_of_power), empty_as_one=True)
+        self._call("radiate", C.byref(air), _ptr(samples), int(slot_stride), int(arfcn_stride))
         self._keep_air = keep
 
     def follow(self, rx):
         """Follow the SACCH orders an L1MsRx decodes (same context and plan); None stops following."""
-        self._chk(self.L.trxsig_l1ms_follow(self.h, rx.h if rx is not None else None), "trxsig_l1ms_follow")
+        self._call("follow", rx.h if rx is not None else None)
         self._follow = rx
-
-    def state(self, cls):
-        p = C.c_void_p()
-        self._chk(self.L.trxsig_l1ms_state(self.h, cls, C.byref(p)), "trxsig_l1ms_state")
-        return p.value
 
     def collect(self, state=True):
         """The last encode's outputs as host numpy arrays (synchronises the context's stream)."""
-        import torch
-        from .frontend import _DevView
-        np, o = self.np, self.out
+        o = self.out
         self.ctx.synchronize()
-
-        def get(p, shape, ts):
-            if p is None or int(np.prod(shape)) == 0:
-                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32}[ts])
-            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
         A, F, X = o.n_arfcn, o.n_frames, o.n_xcch
-        r = dict(bits=get(o.d_bits, (A, 8 * F, 148), "|u1"), what=get(o.d_what, (A, 8 * F), "|u1"),
-                 ms_power=get(o.d_ms_power, (X,), "<i4"), ms_ta=get(o.d_ms_ta, (X,), "<i4"))
+        r = dict(bits=host(o.d_bits, (A, 8 * F, 148), "|u1"), what=host(o.d_what, (A, 8 * F), "|u1"),
+                 ms_power=host(o.d_ms_power, (X,), "<i4"), ms_ta=host(o.d_ms_ta, (X,), "<i4"))
         if state:
             for cls, key in ((L1_TCH, "tch_state"), (L1_XCCH, "xcch_state")):
-                r[key] = get(self.state(cls), (self.channels(cls), L1MS_STATE_BYTES), "|u1")
+                r[key] = host(self.state(cls), (self.channels(cls), L1MS_STATE_BYTES), "|u1")
         return r
 
 
@@ -1325,121 +1018,51 @@ L1_BCCH, L1_SCH, L1_FCCH = 4, 5, 6               # the downlink-only classes of 
 L1_CCCH_C5, L1_BCCH_C5, L1_SCH_C5, L1_FCCH_C5 = 7, 8, 9, 10   # mapping kinds (TRXSIG_L1_*)
 
 
-class L1MsRxOut(C.Structure):
-    """trxsig_l1msrx_out"""
-    _fields_ = [(n, C.c_int) for n in ("n_tch", "n_xcch", "n_ccch", "n_bcch", "nb_tch", "nb_ctl", "sch_cap", "fcch_cap")] + \
-               [(n, C.c_void_p) for n in ("d_tch_status", "d_tch_frames", "d_facch", "d_tch_fer", "d_tch_fn",
-                                          "d_xcch_status", "d_xcch_frames", "d_xcch_fer", "d_xcch_fn",
-                                          "d_ccch_status", "d_ccch_frames", "d_ccch_fer", "d_ccch_fn",
-                                          "d_bcch_status", "d_bcch_frames", "d_bcch_fer", "d_bcch_fn", "d_bcch_tc",
-                                          "d_sch_fn", "d_sch_rfn", "d_sch_present", "d_sch_ok", "d_sch_bsic", "d_sch_sync",
-                                          "d_fcch_fn", "d_fcch_ones",
-                                          "d_tch_rssi", "d_tch_timing", "d_xcch_rssi", "d_xcch_timing", "d_ccch_rssi",
-                                          "d_ccch_timing", "d_bcch_rssi", "d_bcch_timing", "d_ord_power", "d_ord_ta")]
-
-
-class L1MsRx:
+class L1MsRx(_PlanObject):
     """ctypes view of include/trxsig_l1msrx.h: the handsets' receive side -- downlink bursts (a TrxGroupResult of whole frames)
     -> the logical channels' payloads, the SCH's frame number and BSIC, the FCCH, and the SACCH orders, on the device.  comb as
-    for L1Rx."""
+    for L1Rx.
+    open(cls, chan): open of one TCH / XCCH / CCCH / BCCH channel (FER reset; SACCH: orders 40 dBm / TA 0).
+    close(cls, chan): the channel's bursts are ignored until it is opened again.
+    destroy(): trxsig_l1msrx_destroy (an L1Ms that follows this object stops following first)."""
+    _prefix = "trxsig_l1msrx"
 
     def __init__(self, ctx, comb, bsic, band=900):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
-        L.trxsig_l1msrx_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, i32]
-        L.trxsig_l1msrx_destroy.argtypes = [vp]; L.trxsig_l1msrx_destroy.restype = None
-        L.trxsig_l1msrx_channels.argtypes = [vp, i32]
-        L.trxsig_l1msrx_channel.argtypes = [vp, i32, i32, ip, ip, ip, ip]
-        L.trxsig_l1msrx_open.argtypes = [vp, i32, i32]
-        L.trxsig_l1msrx_close.argtypes = [vp, i32, i32]
-        L.trxsig_l1msrx_state.argtypes = [vp, i32, C.POINTER(vp)]
-        L.trxsig_l1msrx_decode.argtypes = [vp, C.POINTER(TrxGroupResult), i32, i32, C.POINTER(L1MsRxOut)]
-        self.comb = np.ascontiguousarray(comb, np.uint8)
-        self.h = vp()
-        rc = L.trxsig_l1msrx_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(band))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1msrx_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        super().__init__(ctx, comb, int(bsic), int(band))
         self.out = None
-
-    def destroy(self):
-        """trxsig_l1msrx_destroy (an L1Ms that follows this object stops following first)."""
-        if self.h:
-            self.L.trxsig_l1msrx_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
-
-    def channels(self, cls):
-        return self._chk(self.L.trxsig_l1msrx_channels(self.h, cls), "trxsig_l1msrx_channels")
-
-    def channel(self, cls, chan):
-        """(arfcn, tn, kind, sub) of a channel"""
-        v = [C.c_int() for _ in range(4)]
-        self._chk(self.L.trxsig_l1msrx_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1msrx_channel")
-        return tuple(x.value for x in v)
-
-    def open(self, cls, chan):
-        """open of one TCH / XCCH / CCCH / BCCH channel (FER reset; SACCH: orders 40 dBm / TA 0)."""
-        self._chk(self.L.trxsig_l1msrx_open(self.h, cls, chan), "trxsig_l1msrx_open")
-
-    def close(self, cls, chan):
-        """close: the channel's bursts are ignored until it is opened again."""
-        self._chk(self.L.trxsig_l1msrx_close(self.h, cls, chan), "trxsig_l1msrx_close")
 
     def decode(self, res, fn, wire=True):
         """res: a TrxGroupResult (of a pull of downlink samples, or built from tensors); whole frames from (fn, TN 0)."""
         out = L1MsRxOut()
-        self._chk(self.L.trxsig_l1msrx_decode(self.h, C.byref(res), int(fn), int(bool(wire)), C.byref(out)), "trxsig_l1msrx_decode")
+        self._call("decode", C.byref(res), int(fn), int(bool(wire)), C.byref(out))
         self.out = out
         return out
 
-    def state(self, cls):
-        p = C.c_void_p()
-        self._chk(self.L.trxsig_l1msrx_state(self.h, cls, C.byref(p)), "trxsig_l1msrx_state")
-        return p.value
-
     def collect(self, state=True):
         """The last decode's outputs as host numpy arrays (synchronises the context's stream)."""
-        import torch
-        from .frontend import _DevView
-        np, o = self.np, self.out
+        o = self.out
         self.ctx.synchronize()
-
-        def get(p, shape, ts):
-            if p is None or int(np.prod(shape)) == 0:
-                return np.zeros(shape, {"|u1": np.uint8, "<i4": np.int32, "<f4": np.float32}[ts])
-            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
         T, bt, bx, S, Fc = o.n_tch, o.nb_tch, o.nb_ctl, o.sch_cap, o.fcch_cap
-        r = dict(tch_status=get(o.d_tch_status, (T, bt), "|u1"), tch=get(o.d_tch_frames, (T, bt, 33), "|u1"),
-                 facch=get(o.d_facch, (T, bt, 23), "|u1"), tch_fer=get(o.d_tch_fer, (T, bt), "<f4"),
-                 tch_fn=get(o.d_tch_fn, (T, bt), "<i4"), tch_rssi=get(o.d_tch_rssi, (T,), "<i4"),
-                 tch_timing=get(o.d_tch_timing, (T,), "<i4"))
+        r = dict(tch_status=host(o.d_tch_status, (T, bt), "|u1"), tch=host(o.d_tch_frames, (T, bt, 33), "|u1"),
+                 facch=host(o.d_facch, (T, bt, 23), "|u1"), tch_fer=host(o.d_tch_fer, (T, bt), "<f4"),
+                 tch_fn=host(o.d_tch_fn, (T, bt), "<i4"), tch_rssi=host(o.d_tch_rssi, (T,), "<i4"),
+                 tch_timing=host(o.d_tch_timing, (T,), "<i4"))
         for key, n in (("xcch", o.n_xcch), ("ccch", o.n_ccch), ("bcch", o.n_bcch)):
             f = lambda name: getattr(o, "d_%s_%s" % (key, name))
-            r.update({key + "_status": get(f("status"), (n, bx), "|u1"), key: get(f("frames"), (n, bx, 23), "|u1"),
-                      key + "_fer": get(f("fer"), (n, bx), "<f4"), key + "_fn": get(f("fn"), (n, bx), "<i4"),
-                      key + "_rssi": get(f("rssi"), (n,), "<i4"), key + "_timing": get(f("timing"), (n,), "<i4")})
-        r["bcch_tc"] = get(o.d_bcch_tc, (o.n_bcch, bx), "<i4")
-        r["ord_power"] = get(o.d_ord_power, (o.n_xcch,), "<i4")
-        r["ord_ta"] = get(o.d_ord_ta, (o.n_xcch,), "<i4")
-        r["sch"] = dict(fn=get(o.d_sch_fn, (S,), "<i4"), present=get(o.d_sch_present, (S,), "|u1"), ok=get(o.d_sch_ok, (S,), "|u1"),
-                        bsic=get(o.d_sch_bsic, (S,), "|u1"), rfn=get(o.d_sch_rfn, (S,), "<i4"), sync=get(o.d_sch_sync, (S,), "|u1"))
-        r["fcch"] = dict(fn=get(o.d_fcch_fn, (Fc,), "<i4"), ones=get(o.d_fcch_ones, (Fc,), "<i4"))
+            r.update({key + "_status": host(f("status"), (n, bx), "|u1"), key: host(f("frames"), (n, bx, 23), "|u1"),
+                      key + "_fer": host(f("fer"), (n, bx), "<f4"), key + "_fn": host(f("fn"), (n, bx), "<i4"),
+                      key + "_rssi": host(f("rssi"), (n,), "<i4"), key + "_timing": host(f("timing"), (n,), "<i4")})
+        r["bcch_tc"] = host(o.d_bcch_tc, (o.n_bcch, bx), "<i4")
+        r["ord_power"] = host(o.d_ord_power, (o.n_xcch,), "<i4")
+        r["ord_ta"] = host(o.d_ord_ta, (o.n_xcch,), "<i4")
+        r["sch"] = dict(fn=host(o.d_sch_fn, (S,), "<i4"), present=host(o.d_sch_present, (S,), "|u1"), ok=host(o.d_sch_ok, (S,), "|u1"),
+                        bsic=host(o.d_sch_bsic, (S,), "|u1"), rfn=host(o.d_sch_rfn, (S,), "<i4"), sync=host(o.d_sch_sync, (S,), "|u1"))
+        r["fcch"] = dict(fn=host(o.d_fcch_fn, (Fc,), "<i4"), ones=host(o.d_fcch_ones, (Fc,), "<i4"))
         if state:
-            r["tch_state"] = get(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
+            r["tch_state"] = host(self.state(L1_TCH), (T, TCH_RX_STATE_BYTES), "|u1")
             for cls, key, n in ((L1_XCCH, "xcch", o.n_xcch), (L1_CCCH, "ccch", o.n_ccch), (L1_BCCH, "bcch", o.n_bcch)):
-                r[key + "_state"] = get(self.state(cls), (n, XCCH_RX_STATE_BYTES), "|u1")
+                r[key + "_state"] = host(self.state(cls), (n, XCCH_RX_STATE_BYTES), "|u1")
         return r
 
 
@@ -1448,61 +1071,28 @@ ACQ_FCCH_THRESH, ACQ_SCH_THRESH = 0.5, 8.0                # TRXSIG_L1ACQ_FCCH_TH
 ACQ_MAX_WINDOW = 256                                      # TRXSIG_L1ACQ_MAX_WINDOW (symbols)
 
 
-class L1AcqOut(C.Structure):
-    """trxsig_l1acq_out"""
-    _fields_ = [("n_streams", C.c_int), ("soft_stride", C.c_int)] + \
-               [(n, C.c_void_p) for n in ("d_state", "d_fcch_k", "d_fcch_metric", "d_fcch_c", "d_fcch_e", "d_arg", "d_omega",
-                                          "d_sch_w0", "d_sch_ptm", "d_sch_amp", "d_sch_toa", "d_soft", "d_ok", "d_bsic", "d_rfn")]
-
-
-class L1Acq:
+class L1Acq(_Object):
     """ctypes view of include/trxsig_l1acq.h: mobile-side acquisition -- raw downlink samples of a C0 carrier -> the FCCH's
     position and frequency offset, the SCH burst's soft values, FN and BSIC, and where the frame grid lies, on the device."""
+    _prefix = "trxsig_l1acq"
 
     def __init__(self, ctx, max_streams, max_samples):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-        L.trxsig_l1acq_create.argtypes = [C.POINTER(vp), vp, i32, i32]
-        L.trxsig_l1acq_destroy.argtypes = [vp]; L.trxsig_l1acq_destroy.restype = None
-        L.trxsig_l1acq_search.argtypes = [vp, vp, C.c_int64, i32, i32, f32, f32, C.POINTER(L1AcqOut)]
-        L.trxsig_l1acq_detect_sch_batch.argtypes = [vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, i32]
-        L.trxsig_l1acq_sequence.argtypes = [vp, vp, vp, vp]
-        self.h = vp()
-        rc = L.trxsig_l1acq_create(C.byref(self.h), ctx.h, int(max_streams), int(max_samples))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1acq_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        super().__init__(ctx)
+        self._create(int(max_streams), int(max_samples))
         self.out = None
-
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_l1acq_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
 
     def sequence(self):
         """(seq[64 sps] complex64, gain complex64, toa float32): the SCH correlation sequence as built at create."""
         np = self.np
         seq = np.zeros(64 * self.ctx.sps, np.complex64); gain = np.zeros(1, np.complex64); toa = np.zeros(1, np.float32)
-        self._chk(self.L.trxsig_l1acq_sequence(self.h, seq.ctypes.data, gain.ctypes.data, toa.ctypes.data), "trxsig_l1acq_sequence")
+        self._call("sequence", seq.ctypes.data, gain.ctypes.data, toa.ctypes.data)
         return seq, gain[0], toa[0]
 
     def search(self, samples, stream_stride, n_samples, n_streams, fcch_thresh=ACQ_FCCH_THRESH, sch_thresh=ACQ_SCH_THRESH):
         """samples: device tensor (complex64, or float32 pairs) holding n_streams streams stream_stride samples apart."""
         out = L1AcqOut()
-        self._chk(self.L.trxsig_l1acq_search(self.h, _ptr(samples), int(stream_stride), int(n_samples), int(n_streams),
-                                             float(fcch_thresh), float(sch_thresh), C.byref(out)), "trxsig_l1acq_search")
+        self._call("search", _ptr(samples), int(stream_stride), int(n_samples), int(n_streams), float(fcch_thresh), float(sch_thresh),
+                   C.byref(out))
         self.out = out
         return out
 
@@ -1510,75 +1100,36 @@ class L1Acq:
                    detect_thresh=ACQ_SCH_THRESH, soft_stride=None):
         """Stage 2 on caller-chosen windows (all device tensors): offset / length int32 [B]; flags uint8 [B], amp [B, 2], toa [B],
         soft [B, >= 148] are written; omega float32 [B] (None: no frequency shift), ptm float32 [B], hard uint8 [B, stride]."""
-        self._chk(self.L.trxsig_l1acq_detect_sch_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), offset.numel(), _ptr(omega),
-                                                       float(detect_thresh), _ptr(flags), _ptr(amp), _ptr(toa), _ptr(ptm), _ptr(soft),
-                                                       _ptr(hard), soft_stride or soft.shape[-1]), "trxsig_l1acq_detect_sch_batch")
+        self._call("detect_sch_batch", _ptr(samples), _ptr(offset), _ptr(length), offset.numel(), _ptr(omega), float(detect_thresh),
+                   _ptr(flags), _ptr(amp), _ptr(toa), _ptr(ptm), _ptr(soft), _ptr(hard), soft_stride or soft.shape[-1])
 
     def collect(self):
         """The last search's outputs as host numpy arrays (synchronises the context's stream)."""
-        import torch
-        from .frontend import _DevView
         np, o = self.np, self.out
         self.ctx.synchronize()
         S = o.n_streams
-
-        def get(p, shape, ts):
-            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
-        r = dict(state=get(o.d_state, (S,), "|u1"), fcch_k=get(o.d_fcch_k, (S,), "<i4"), fcch_metric=get(o.d_fcch_metric, (S,), "<f4"),
-                 fcch_c=get(o.d_fcch_c, (S, 2), "<f4").view(np.complex64).ravel(), fcch_e=get(o.d_fcch_e, (S,), "<f4"),
-                 arg=get(o.d_arg, (S,), "<f4"), omega=get(o.d_omega, (S,), "<f4"), sch_w0=get(o.d_sch_w0, (S,), "<i4"),
-                 sch_ptm=get(o.d_sch_ptm, (S,), "<f4"), sch_amp=get(o.d_sch_amp, (S, 2), "<f4").view(np.complex64).ravel(),
-                 sch_toa=get(o.d_sch_toa, (S,), "<f4"), soft=get(o.d_soft, (S, o.soft_stride), "<f4"),
-                 ok=get(o.d_ok, (S,), "|u1"), bsic=get(o.d_bsic, (S,), "|u1"), rfn=get(o.d_rfn, (S,), "<i4"))
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
+        r = dict(state=host(o.d_state, (S,), "|u1"), fcch_k=host(o.d_fcch_k, (S,), "<i4"), fcch_metric=host(o.d_fcch_metric, (S,), "<f4"),
+                 fcch_c=host(o.d_fcch_c, (S, 2), "<f4").view(np.complex64).ravel(), fcch_e=host(o.d_fcch_e, (S,), "<f4"),
+                 arg=host(o.d_arg, (S,), "<f4"), omega=host(o.d_omega, (S,), "<f4"), sch_w0=host(o.d_sch_w0, (S,), "<i4"),
+                 sch_ptm=host(o.d_sch_ptm, (S,), "<f4"), sch_amp=host(o.d_sch_amp, (S, 2), "<f4").view(np.complex64).ravel(),
+                 sch_toa=host(o.d_sch_toa, (S,), "<f4"), soft=host(o.d_soft, (S, o.soft_stride), "<f4"),
+                 ok=host(o.d_ok, (S,), "|u1"), bsic=host(o.d_bsic, (S,), "|u1"), rfn=host(o.d_rfn, (S,), "<i4"))
         return r
 
 
 AIR_MAX_TAPS = 32                                         # TRXSIG_AIR_MAX_TAPS
 
 
-class AirCellParams(C.Structure):
-    """trxsig_air_cell_params"""
-    _fields_ = [("d_taps", C.c_void_p), ("n_taps", C.c_int), ("d_step", C.c_void_p), ("d_phase", C.c_void_p), ("d_sigma", C.c_void_p)]
-
-
-class AirStreamParams(C.Structure):
-    """trxsig_air_stream_params"""
-    _fields_ = [("n_arfcn", C.c_int)] + [(n, C.c_void_p) for n in ("d_arfcn", "d_cut", "d_delay", "d_step", "d_phase", "d_gain",
-                                                                   "d_sigma", "d_n0")]
-
-
-class Air:
+class Air(_Object):
     """ctypes view of include/trxsig_air.h: the radio channel on the device -- multipath, oscillator offset and counter-based
     Gaussian noise, slot cells -> slot cells (cells) or a carrier's cells -> one stream per handset (stream)."""
+    _prefix = "trxsig_air"
 
     def __init__(self, ctx, max_taps=AIR_MAX_TAPS):
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, i64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64
-        L.trxsig_air_create.argtypes = [C.POINTER(vp), vp, i32]
-        L.trxsig_air_destroy.argtypes = [vp]; L.trxsig_air_destroy.restype = None
-        L.trxsig_air_cells.argtypes = [vp, i32, i32, i32, u64, vp, i64, i64, C.POINTER(AirCellParams), vp, i64, i64, i32]
-        L.trxsig_air_stream.argtypes = [vp, i32, u64, vp, i64, i64, i32, C.POINTER(AirStreamParams), i32, vp, i64]
-        self.h = vp()
-        rc = L.trxsig_air_create(C.byref(self.h), ctx.h, int(max_taps))
-        if rc != 0:
-            raise TrxSigError("trxsig_air_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        super().__init__(ctx)
+        self._create(int(max_taps))
         self._keep = None
-
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_air_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
 
     def cells(self, fn, n_arfcn, n_frames, seed, x, slot_stride, arfcn_stride, out=None, out_slot_stride=None, out_arfcn_stride=None,
               taps=None, step=None, phase=None, sigma=None, accumulate=False):
@@ -1590,15 +1141,11 @@ class Air:
             assert taps.is_contiguous()
             p.d_taps = taps.data_ptr()
             p.n_taps = taps.shape[2]
-        for name, t in (("d_step", step), ("d_phase", phase), ("d_sigma", sigma)):
-            if t is not None:
-                assert t.is_contiguous() and t.element_size() == 4
-                setattr(p, name, t.data_ptr())
+        _fill(p, ("d_step", "d_phase", "d_sigma"), (step, phase, sigma), itemsize=4)
         if out is None:
             out, out_slot_stride, out_arfcn_stride = x, slot_stride, arfcn_stride
-        self._chk(self.L.trxsig_air_cells(self.h, int(fn), int(n_arfcn), int(n_frames), int(seed), _ptr(x), int(slot_stride),
-                                          int(arfcn_stride), C.byref(p), _ptr(out), int(out_slot_stride), int(out_arfcn_stride),
-                                          int(bool(accumulate))), "trxsig_air_cells")
+        self._call("cells", int(fn), int(n_arfcn), int(n_frames), int(seed), _ptr(x), int(slot_stride), int(arfcn_stride), C.byref(p),
+                   _ptr(out), int(out_slot_stride), int(out_arfcn_stride), int(bool(accumulate)))
         self._keep = (taps, step, phase, sigma)
 
     def stream(self, n_arfcn, n_cells, seed, x, slot_stride, arfcn_stride, out, out_stride, length, arfcn, cut, delay=None, step=None,
@@ -1608,13 +1155,9 @@ class Air:
         p = AirStreamParams()
         p.n_arfcn = int(n_arfcn)
         assert arfcn.element_size() == 4 and cut.element_size() == 8
-        keep = (arfcn, cut, delay, step, phase, gain, sigma, n0)
-        for name, t in zip(("d_arfcn", "d_cut", "d_delay", "d_step", "d_phase", "d_gain", "d_sigma", "d_n0"), keep):
-            if t is not None:
-                assert t.is_contiguous()
-                setattr(p, name, t.data_ptr())
-        self._chk(self.L.trxsig_air_stream(self.h, int(n_cells), int(seed), _ptr(x), int(slot_stride), int(arfcn_stride),
-                                           int(arfcn.numel()), C.byref(p), int(length), _ptr(out), int(out_stride)), "trxsig_air_stream")
+        keep = _fill(p, None, (arfcn, cut, delay, step, phase, gain, sigma, n0))
+        self._call("stream", int(n_cells), int(seed), _ptr(x), int(slot_stride), int(arfcn_stride), int(arfcn.numel()), C.byref(p),
+                   int(length), _ptr(out), int(out_stride))
         self._keep = keep
 
 
@@ -1622,110 +1165,65 @@ TRK_CLIPPED, TRK_UNLOCKED = 1, 2                          # trxsig_l1trk_meas.d_
 TRK_MAX_FRAMES, TRK_MAX_GATE = 65536, 1 << 24             # TRXSIG_L1TRK_MAX_FRAMES / _MAX_GATE
 
 
-class L1TrkView(C.Structure):
-    """trxsig_l1trk_view"""
-    _fields_ = [("n_phones", C.c_int), ("n_cols", C.c_int)] + \
-               [(n, C.c_void_p) for n in ("d_fn", "d_pos", "d_phase", "d_step", "d_locked", "d_quiet", "d_toa_sum", "d_toa_n", "d_adj",
-                                          "d_afc_n", "d_afc_delta")]
-
-
-class L1TrkMeas(C.Structure):
-    """trxsig_l1trk_meas"""
-    _fields_ = [("n_phones", C.c_int), ("n_cols", C.c_int), ("n_fcch", C.c_int), ("fcch_stride", C.c_int)] + \
-               [(n, C.c_void_p) for n in ("d_status", "d_fcch_fn", "d_fcch_c", "d_fcch_e", "d_fcch_ok")]
-
-
-class L1Trk:
+class L1Trk(_Object):
     """ctypes view of include/trxsig_l1trk.h: the handset's tracking receiver -- acquired streams -> the slot cells TrxGroup.pull
     reads, derotated by an exact NCO (slice), with the AFC measured on every frequency burst passed and the grid moved by the
     TOAs the pull reports (update)."""
+    _prefix = "trxsig_l1trk"
 
     def __init__(self, ctx, phone, c0, max_frames, afc_shift=1, toa_gate=512, fcch_thresh=ACQ_FCCH_THRESH):
         """phone: the phone of every column; c0: every phone's C0 column, -1: none"""
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, i64, u32, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_float
-        L.trxsig_l1trk_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp, vp, i32, i32, i32, f32]
-        L.trxsig_l1trk_destroy.argtypes = [vp]; L.trxsig_l1trk_destroy.restype = None
-        L.trxsig_l1trk_seed.argtypes = [vp, C.POINTER(L1AcqOut), vp]
-        L.trxsig_l1trk_set.argtypes = [vp, i32, i32, i32, i64, u32, u32]
-        L.trxsig_l1trk_state.argtypes = [vp, C.POINTER(L1TrkView)]
-        L.trxsig_l1trk_slice.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, i64, i64, C.POINTER(L1TrkMeas)]
-        L.trxsig_l1trk_update.argtypes = [vp, C.POINTER(TrxGroupResult), i32, vp]
+        super().__init__(ctx)
+        np = self.np
         phone, c0 = np.ascontiguousarray(phone, np.int32), np.ascontiguousarray(c0, np.int32)
         self.n_cols, self.n_phones = len(phone), len(c0)
-        self.h = vp()
-        rc = L.trxsig_l1trk_create(C.byref(self.h), ctx.h, self.n_phones, self.n_cols, phone.ctypes.data, c0.ctypes.data, int(max_frames),
-                                   int(afc_shift), int(toa_gate), float(fcch_thresh))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1trk_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
+        self._create(self.n_phones, self.n_cols, phone.ctypes.data, c0.ctypes.data, int(max_frames), int(afc_shift), int(toa_gate),
+                     float(fcch_thresh))
         self.meas = None
         self._keep = None
-
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_l1trk_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
 
     def seed(self, acq_out, src):
         """acq_out: the L1AcqOut of a search; src: device int32 [n_phones], the stream each phone was acquired on, -1: leave"""
         assert src.element_size() == 4 and src.numel() == self.n_phones
-        self._chk(self.L.trxsig_l1trk_seed(self.h, C.byref(acq_out), _ptr(src)), "trxsig_l1trk_seed")
+        self._call("seed", C.byref(acq_out), _ptr(src))
         self._keep = src
 
     def set(self, phone, locked, fn, pos, step, phase):
-        self._chk(self.L.trxsig_l1trk_set(self.h, int(phone), int(bool(locked)), int(fn), int(pos), int(step) & 0xffffffff,
-                                          int(phase) & 0xffffffff), "trxsig_l1trk_set")
+        self._call("set", int(phone), int(bool(locked)), int(fn), int(pos), int(step) & 0xffffffff, int(phase) & 0xffffffff)
 
     def slice(self, streams, stream_stride, n0, n_samples, fn, n_frames, cells, slot_stride, col_stride):
         """streams / cells: device tensors (complex64 or float32 pairs) or addresses; strides in complex samples"""
         out = L1TrkMeas()
-        self._chk(self.L.trxsig_l1trk_slice(self.h, _ptr(streams), int(stream_stride), int(n0), int(n_samples), int(fn), int(n_frames),
-                                            _ptr(cells), int(slot_stride), int(col_stride), C.byref(out)), "trxsig_l1trk_slice")
+        self._call("slice", _ptr(streams), int(stream_stride), int(n0), int(n_samples), int(fn), int(n_frames), _ptr(cells),
+                   int(slot_stride), int(col_stride), C.byref(out))
         self.meas = out
         return out
 
     def update(self, res, fn, use=None):
         """res: the TrxGroupResult of the pull of the cells just sliced; use: device uint8 [n_slots][n_cols] or None"""
-        self._chk(self.L.trxsig_l1trk_update(self.h, C.byref(res), int(fn), _ptr(use)), "trxsig_l1trk_update")
+        self._call("update", C.byref(res), int(fn), _ptr(use))
         self._keep = use
 
     def state(self):
         v = L1TrkView()
-        self._chk(self.L.trxsig_l1trk_state(self.h, C.byref(v)), "trxsig_l1trk_state")
+        self._call("state", C.byref(v))
         return v
 
     def collect(self):
         """The state, what the last update did and the last slice's records as host numpy arrays (synchronises the stream)."""
-        import torch
-        from .frontend import _DevView
         np, v, m = self.np, self.state(), self.meas
         self.ctx.synchronize()
         P = v.n_phones
-
-        def get(p, shape, ts):
-            return torch.as_tensor(_DevView(p, shape, ts), device="cuda:%d" % self.ctx.device).cpu().numpy()
-        r = dict(fn=get(v.d_fn, (P,), "<i4"), pos=get(v.d_pos, (P,), "<i8"), phase=get(v.d_phase, (P,), "<i4").view(np.uint32),
-                 step=get(v.d_step, (P,), "<i4").view(np.uint32), locked=get(v.d_locked, (P,), "|u1"), quiet=get(v.d_quiet, (P,), "<i4"),
-                 toa_sum=get(v.d_toa_sum, (P,), "<i8"), toa_n=get(v.d_toa_n, (P,), "<i4"), adj=get(v.d_adj, (P,), "<i8"),
-                 afc_n=get(v.d_afc_n, (P,), "<i4"), afc_delta=get(v.d_afc_delta, (P,), "<i8"))
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
+        r = dict(fn=host(v.d_fn, (P,), "<i4"), pos=host(v.d_pos, (P,), "<i8"), phase=host(v.d_phase, (P,), "<i4").view(np.uint32),
+                 step=host(v.d_step, (P,), "<i4").view(np.uint32), locked=host(v.d_locked, (P,), "|u1"), quiet=host(v.d_quiet, (P,), "<i4"),
+                 toa_sum=host(v.d_toa_sum, (P,), "<i8"), toa_n=host(v.d_toa_n, (P,), "<i4"), adj=host(v.d_adj, (P,), "<i8"),
+                 afc_n=host(v.d_afc_n, (P,), "<i4"), afc_delta=host(v.d_afc_delta, (P,), "<i8"))
         if m is not None:
             K, n = m.fcch_stride, m.n_fcch
-            r.update(status=get(m.d_status, (v.n_cols,), "|u1"), n_fcch=n, fcch_fn=get(m.d_fcch_fn, (P, K), "<i4")[:, :n],
-                     fcch_c=get(m.d_fcch_c, (P, K, 2), "<f8")[:, :n].copy().view(np.complex128)[..., 0],
-                     fcch_e=get(m.d_fcch_e, (P, K), "<f8")[:, :n], fcch_ok=get(m.d_fcch_ok, (P, K), "|u1")[:, :n])
+            r.update(status=host(m.d_status, (v.n_cols,), "|u1"), n_fcch=n, fcch_fn=host(m.d_fcch_fn, (P, K), "<i4")[:, :n],
+                     fcch_c=host(m.d_fcch_c, (P, K, 2), "<f8")[:, :n].copy().view(np.complex128)[..., 0],
+                     fcch_e=host(m.d_fcch_e, (P, K), "<f8")[:, :n], fcch_ok=host(m.d_fcch_ok, (P, K), "|u1")[:, :n])
         return r
 
 
@@ -1737,98 +1235,40 @@ def a5_1_blocks(ctx, kc, count, block1=None, block2=None):
     """trxsig_a5_1_blocks_batch: kc device uint8 [n][8], count device int32 / uint32 [n] -> BLOCK1 / BLOCK2 device uint8
     [n][114], one bit per byte (either may be None).  Enqueued on the context's stream."""
     L = ctx.L
-    vp = C.c_void_p
-    L.trxsig_a5_1_blocks_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     n = int(count.numel()) if hasattr(count, "numel") else 0
     rc = L.trxsig_a5_1_blocks_batch(ctx.h, n, _ptr(kc), _ptr(count), _ptr(block1), _ptr(block2))
     if rc < 0:
         raise TrxSigError("trxsig_a5_1_blocks_batch: %d (%s)" % (rc, L.trxsig_last_error(ctx.h).decode()))
 
 
-class L1Ciph:
+class L1Ciph(_PlanView):
     """ctypes view of include/trxsig_l1ciph.h: A5/1 ciphering of the dedicated channels' bursts -- bits() on an encoder's burst
     grid before it is sent, soft() on a pull's rows before they are decoded; a key per TCH / XCCH channel (set).
     comb: uint8 [n_arfcn, 8] as L1Rx takes it."""
+    _prefix = "trxsig_l1ciph"
 
     def __init__(self, ctx, comb):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, u32 = C.c_void_p, C.c_int, C.c_uint32
-        L.trxsig_l1ciph_create.argtypes = [C.POINTER(vp), vp, i32, vp]
-        L.trxsig_l1ciph_destroy.argtypes = [vp]; L.trxsig_l1ciph_destroy.restype = None
-        L.trxsig_l1ciph_channels.argtypes = [vp, i32]
-        L.trxsig_l1ciph_channel.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-        L.trxsig_l1ciph_set.argtypes = [vp, i32, i32, i32, vp]
-        L.trxsig_l1ciph_state.argtypes = [vp, i32, C.POINTER(vp)]
-        L.trxsig_l1ciph_bits.argtypes = [vp, i32, i32, i32, vp, vp, u32]
-        L.trxsig_l1ciph_soft.argtypes = [vp, i32, C.POINTER(TrxGroupResult), i32]
-        self.comb = np.ascontiguousarray(comb, np.uint8)
-        self.h = vp()
-        rc = L.trxsig_l1ciph_create(C.byref(self.h), ctx.h, self.comb.shape[0], self.comb.ctypes.data)
-        if rc != 0:
-            raise TrxSigError("trxsig_l1ciph_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
-
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_l1ciph_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
-
-    def channels(self, cls):
-        return self._chk(self.L.trxsig_l1ciph_channels(self.h, cls), "trxsig_l1ciph_channels")
-
-    def channel(self, cls, chan):
-        """(arfcn, tn, kind, sub) of a channel"""
-        v = [C.c_int() for _ in range(4)]
-        self._chk(self.L.trxsig_l1ciph_channel(self.h, cls, chan, *[C.byref(x) for x in v]), "trxsig_l1ciph_channel")
-        return tuple(x.value for x in v)
+        super().__init__(ctx, comb)
 
     def set(self, cls, chan, algo, kc=None):
         """algo: A5_OFF or A5_1; kc: 8 key bytes (host).  Takes effect in stream order."""
         key = None if kc is None else (C.c_uint8 * 8)(*[int(x) & 0xff for x in kc])
-        self._chk(self.L.trxsig_l1ciph_set(self.h, int(cls), int(chan), int(algo), key), "trxsig_l1ciph_set")
-
-    def state(self, cls):
-        p = C.c_void_p()
-        self._chk(self.L.trxsig_l1ciph_state(self.h, cls, C.byref(p)), "trxsig_l1ciph_state")
-        return p.value
+        self._call("set", int(cls), int(chan), int(algo), key)
 
     def bits(self, uplink, fn, n_frames, bits, what=None, what_mask=0):
         """bits: device uint8 [n_arfcn][8 n_frames][148] (a tensor or an address: an encoder's d_bits), ciphered in place; what:
         its [n_arfcn][8 n_frames] map or None"""
-        self._chk(self.L.trxsig_l1ciph_bits(self.h, int(bool(uplink)), int(fn), int(n_frames), _ptr(bits), _ptr(what),
-                                            int(what_mask) & 0xffffffff), "trxsig_l1ciph_bits")
+        self._call("bits", int(bool(uplink)), int(fn), int(n_frames), _ptr(bits), _ptr(what), int(what_mask) & 0xffffffff)
 
     def soft(self, uplink, res, fn):
         """res: a TrxGroupResult of whole frames from (fn, TN 0); its soft rows are deciphered in place, once"""
-        self._chk(self.L.trxsig_l1ciph_soft(self.h, int(bool(uplink)), C.byref(res), int(fn)), "trxsig_l1ciph_soft")
+        self._call("soft", int(bool(uplink)), C.byref(res), int(fn))
 
     def collect(self):
         """The channels' records as host numpy arrays uint32 [n_chan][4] per class (synchronises the context's stream)."""
-        import torch
-        from .frontend import _DevView
-        np = self.np
         self.ctx.synchronize()
-        r = {}
-        for name, cls in (("tch", L1_TCH), ("xcch", L1_XCCH)):
-            n = self.channels(cls)
-            if n == 0:
-                r[name] = np.zeros((0, 4), np.uint32)
-            else:
-                t = torch.as_tensor(_DevView(self.state(cls), (n, 4), "<i4"), device="cuda:%d" % self.ctx.device)
-                r[name] = t.cpu().numpy().view(np.uint32)
-        return r
+        return {name: _to_host(self.ctx, self.state(cls), (self.channels(cls), 4), "<i4").view(self.np.uint32)
+                for name, cls in (("tch", L1_TCH), ("xcch", L1_XCCH))}
 
 
 L1HOP_MAX_N = 64                                         # TRXSIG_L1HOP_MAX_N
@@ -1838,97 +1278,61 @@ def hop_mai(ctx, fn, hsn, maio, n, mai):
     """trxsig_hop_mai_batch: device int32 arrays of equal length, mai[i] = MAI(fn[i], hsn[i], maio[i], n[i]) (GSM 05.02 6.2.3).
     Entries out of range are undefined.  Enqueued on the context's stream."""
     L = ctx.L
-    vp = C.c_void_p
-    L.trxsig_hop_mai_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     cnt = int(fn.numel()) if hasattr(fn, "numel") else 0
     rc = L.trxsig_hop_mai_batch(ctx.h, cnt, _ptr(fn), _ptr(hsn), _ptr(maio), _ptr(n), _ptr(mai))
     if rc < 0:
         raise TrxSigError("trxsig_hop_mai_batch: %d (%s)" % (rc, L.trxsig_last_error(ctx.h).decode()))
 
 
-class L1Hop:
+class L1Hop(_Object):
     """ctypes view of include/trxsig_l1hop.h: slow frequency hopping of the dedicated channels -- bits() on an encoder's burst
     grid (in place), cells() on sample cells (out of place), result() on a pull (indices only), map() the radio row of every
     channel row.  comb: uint8 [n_arfcn, 8] as L1Rx takes it; group: int8 [n_arfcn, 8], -1 or a group id; hsn: one per group;
     max_frames: the longest map() / result() call."""
+    _prefix = "trxsig_l1hop"
 
     def __init__(self, ctx, comb, group, hsn, max_frames=104):
-        import numpy as np
-        self.np = np
-        self.ctx = ctx
-        self.L = L = ctx.L
-        vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-        L.trxsig_l1hop_create.argtypes = [C.POINTER(vp), vp, i32, vp, vp, i32, vp, i32]
-        L.trxsig_l1hop_destroy.argtypes = [vp]; L.trxsig_l1hop_destroy.restype = None
-        L.trxsig_l1hop_groups.argtypes = [vp]
-        L.trxsig_l1hop_members.argtypes = [vp, i32, i32, vp]
-        L.trxsig_l1hop_map.argtypes = [vp, i32, i32, C.POINTER(vp)]
-        L.trxsig_l1hop_bits.argtypes = [vp, i32, i32, i32, vp, vp]
-        L.trxsig_l1hop_cells.argtypes = [vp, i32, i32, i32, vp, i64, i64, vp, i64, i64]
-        L.trxsig_l1hop_result.argtypes = [vp, i32, C.POINTER(TrxGroupResult), C.POINTER(TrxGroupResult)]
+        super().__init__(ctx)
+        np = self.np
         self.comb = np.ascontiguousarray(comb, np.uint8)
         self.group = np.ascontiguousarray(group, np.int8)
         self.hsn = np.ascontiguousarray(hsn, np.uint8).reshape(-1)
         if self.group.shape != self.comb.shape:
             raise TrxSigError("L1Hop: comb and group differ in shape")
         self.n_arfcn = self.comb.shape[0]
-        self.h = vp()
-        rc = L.trxsig_l1hop_create(C.byref(self.h), ctx.h, self.n_arfcn, self.comb.ctypes.data, self.group.ctypes.data,
-                                   len(self.hsn), self.hsn.ctypes.data if len(self.hsn) else None, int(max_frames))
-        if rc != 0:
-            raise TrxSigError("trxsig_l1hop_create failed (%d): %s" % (rc, L.trxsig_last_error(ctx.h).decode()))
-
-    def destroy(self):
-        if self.h:
-            self.L.trxsig_l1hop_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc < 0:
-            raise TrxSigError("%s: %d (%s)" % (what, rc, self.L.trxsig_last_error(self.ctx.h).decode()))
-        return rc
+        self._create(self.n_arfcn, self.comb.ctypes.data, self.group.ctypes.data, len(self.hsn),
+                     self.hsn.ctypes.data if len(self.hsn) else None, int(max_frames))
 
     def groups(self):
-        return self._chk(self.L.trxsig_l1hop_groups(self.h), "trxsig_l1hop_groups")
+        return self._call("groups")
 
     def members(self, g, tn):
         """the rows of group g on timeslot tn, ascending: a row's place in the list is its MAIO"""
         rows = (C.c_int32 * L1HOP_MAX_N)()
-        n = self._chk(self.L.trxsig_l1hop_members(self.h, int(g), int(tn), rows), "trxsig_l1hop_members")
+        n = self._call("members", int(g), int(tn), rows)
         return list(rows[:n])
 
     def map(self, fn, n_frames):
         """device int32 [8 n_frames][n_arfcn] (a view of the object's array, valid until the next map): the radio row of channel
         row a in slot t"""
-        import torch
-        from .frontend import _DevView
         p = C.c_void_p()
-        self._chk(self.L.trxsig_l1hop_map(self.h, int(fn), int(n_frames), C.byref(p)), "trxsig_l1hop_map")
-        return torch.as_tensor(_DevView(p.value, (8 * int(n_frames), self.n_arfcn), "<i4"), device="cuda:%d" % self.ctx.device)
+        self._call("map", int(fn), int(n_frames), C.byref(p))
+        return _dev_tensor(self.ctx, p.value, (8 * int(n_frames), self.n_arfcn), "<i4")
 
     def bits(self, to_radio, fn, n_frames, bits, what=None):
         """bits: device uint8 [n_arfcn][8 n_frames][148] (a tensor or an address: an encoder's d_bits), hopped in place together
         with what, its [n_arfcn][8 n_frames] map (or None)"""
-        self._chk(self.L.trxsig_l1hop_bits(self.h, int(bool(to_radio)), int(fn), int(n_frames), _ptr(bits), _ptr(what)),
-                  "trxsig_l1hop_bits")
+        self._call("bits", int(bool(to_radio)), int(fn), int(n_frames), _ptr(bits), _ptr(what))
 
     def cells(self, to_radio, fn, n_frames, src, in_slot_stride, in_arfcn_stride, dst, out_slot_stride, out_arfcn_stride):
         """src, dst: device complex64 cells (tensors or addresses), strides in samples; out of place"""
-        self._chk(self.L.trxsig_l1hop_cells(self.h, int(bool(to_radio)), int(fn), int(n_frames), _ptr(src), int(in_slot_stride),
-                                            int(in_arfcn_stride), _ptr(dst), int(out_slot_stride), int(out_arfcn_stride)),
-                  "trxsig_l1hop_cells")
+        self._call("cells", int(bool(to_radio)), int(fn), int(n_frames), _ptr(src), int(in_slot_stride), int(in_arfcn_stride),
+                   _ptr(dst), int(out_slot_stride), int(out_arfcn_stride))
 
     def result(self, res, fn):
         """res: a TrxGroupResult of whole frames from (fn, TN 0) -> a copy whose d_row is in the channel domain (the object's
         array, valid until the next result; self.row is that array as a tensor)"""
-        import torch
-        from .frontend import _DevView
         out = TrxGroupResult()
-        self._chk(self.L.trxsig_l1hop_result(self.h, int(fn), C.byref(res), C.byref(out)), "trxsig_l1hop_result")
-        self.row = torch.as_tensor(_DevView(out.d_row, (out.n_slots, out.n_arfcn), "<i4"), device="cuda:%d" % self.ctx.device)
+        self._call("result", int(fn), C.byref(res), C.byref(out))
+        self.row = _dev_tensor(self.ctx, out.d_row, (out.n_slots, out.n_arfcn), "<i4")
         return out

@@ -7,73 +7,49 @@ import ctypes as C
 
 import numpy as np
 
+from . import _DevView, _Object   # (_DevView: tools and tests import it from here)
+
 OUTRATE = 96
 OUTCHUNK = 9 * OUTRATE          # 864
 OUTHISTORY = 2 * OUTRATE        # 192
 
 
-class _DevView:
-    """A device buffer owned by the library, presented to torch (zero copy) through __cuda_array_interface__."""
+class _FrontEnd(_Object):
+    """What the two ends share: made on a context, errors checked as the context checks its own (any rc != 0 raises), close()
+    releases."""
+    close = _Object.destroy
 
-    def __init__(self, ptr, shape, typestr):
-        self.__cuda_array_interface__ = dict(data=(int(ptr), False), shape=tuple(shape), typestr=typestr, version=2)
-
-
-def _bind(L):
-    vp, i32 = C.c_void_p, C.c_int
-    if getattr(L, "_frontend_bound", False):
-        return
-    L.trxsig_rxfe_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp, i32, i32, i32]
-    L.trxsig_rxfe_destroy.argtypes = [vp]; L.trxsig_rxfe_destroy.restype = None
-    L.trxsig_rxfe_push.argtypes = [vp, vp, i32]
-    L.trxsig_rxfe_pop.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, i32, C.POINTER(i32)]
-    L.trxsig_rxfe_pending.argtypes = [vp]
-    L.trxsig_rxfe_push_detect_demod_normal.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32,
-                                                       C.POINTER(i32)]
-    L.trxsig_rxfe_create_wideband.argtypes = [C.POINTER(vp), vp, i32, i32, vp, i32, i32, vp, i32, i32, i32]
-    L.trxsig_rxfe_push_wideband.argtypes = [vp, vp, i32]
-    L.trxsig_rxfe_set_shared_filter.argtypes = [vp, i32]
-    L.trxsig_txbe_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp, i32, C.c_float]
-    L.trxsig_txbe_destroy.argtypes = [vp]; L.trxsig_txbe_destroy.restype = None
-    L.trxsig_txbe_push_bursts.argtypes = [vp, vp, vp, vp, i32]
-    L.trxsig_txbe_pop.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(i32)]
-    L.trxsig_txbe_pending.argtypes = [vp]
-    L.trxsig_txbe_set_fused.argtypes = [vp, i32]
-    L.trxsig_txbe_create_wideband.argtypes = [C.POINTER(vp), vp, i32, i32, vp, i32, i32, vp, i32, C.c_float]
-    L.trxsig_txbe_streams.argtypes = [vp]
-    L._frontend_bound = True
+    def _chk(self, rc, what):
+        return self.ctx._chk(rc, what)
 
 
-class RxFrontEnd:
+class RxFrontEnd(_FrontEnd):
+    _prefix = "trxsig_rxfe"
+
     def __init__(self, ctx, n_streams, lpf_taps, device="cuda:0", swap_iq=True, max_chunks=1, start_tn=0, carrier_freq=None, rate_factor=0):
         """carrier_freq (radians per wideband sample, one per carrier) + rate_factor: the channeliser -- n_streams WIDEBAND
         streams at rate_factor x 400 kS/s, len(carrier_freq) ARFCNs each; bursts come out per (stream, carrier)."""
         import torch
+        super().__init__(ctx)
         self.torch = torch
-        self.ctx = ctx
-        self.L = ctx.L
-        _bind(self.L)
         self.sps = ctx.sps
         self.dev = torch.device(device)
         lpf = np.ascontiguousarray(lpf_taps, np.float32)
-        h = C.c_void_p()
         self.rate_factor = rate_factor
         if carrier_freq is not None:
             fr = np.ascontiguousarray(carrier_freq, np.float32)
-            ctx._chk(self.L.trxsig_rxfe_create_wideband(C.byref(h), ctx.h, n_streams, fr.size, fr.ctypes.data, rate_factor, max_chunks,
-                                                        lpf.ctypes.data, lpf.size, int(swap_iq), start_tn), "trxsig_rxfe_create_wideband")
+            self._create(n_streams, fr.size, fr.ctypes.data, rate_factor, max_chunks, lpf.ctypes.data, lpf.size, int(swap_iq), start_tn,
+                         name="create_wideband")
             self.S = n_streams * fr.size
             self.Sw = n_streams
         else:
-            ctx._chk(self.L.trxsig_rxfe_create(C.byref(h), ctx.h, n_streams, max_chunks, lpf.ctypes.data, lpf.size, int(swap_iq),
-                                               start_tn), "trxsig_rxfe_create")
+            self._create(n_streams, max_chunks, lpf.ctypes.data, lpf.size, int(swap_iq), start_tn)
             self.S = n_streams
-        self.h = h
 
     def set_shared_filter(self, on=True):
         """The channeliser's shared-filter form (carriers on the grid of sixteenths of the wideband rate): one pass over the raw
         samples for all carriers, ~1e-6 from the per-carrier form instead of bit-equal."""
-        self.ctx._chk(self.L.trxsig_rxfe_set_shared_filter(self.h, int(on)), "trxsig_rxfe_set_shared_filter")
+        self._call("set_shared_filter", int(on))
 
     def push_wideband(self, iq):
         """iq: int16 tensor [Sw, K*864*rate_factor, 2] (device), K whole chunks per wideband stream."""
@@ -81,26 +57,15 @@ class RxFrontEnd:
         n = OUTCHUNK * self.rate_factor
         assert iq.dtype == torch.int16 and iq.shape[0] == self.Sw and iq.shape[1] % n == 0 and iq.shape[2] == 2
         iq = iq.contiguous()
-        self.ctx._chk(self.L.trxsig_rxfe_push_wideband(self.h, iq.data_ptr(), iq.shape[1] // n), "trxsig_rxfe_push_wideband")
+        self._call("push_wideband", iq.data_ptr(), iq.shape[1] // n)
         self._keep = iq
-
-    def close(self):
-        if self.h:
-            self.L.trxsig_rxfe_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def push_chunk(self, iq):
         """iq: int16 tensor [S, K*864, 2] (device), K whole chunks per stream."""
         torch = self.torch
         assert iq.dtype == torch.int16 and iq.shape[0] == self.S and iq.shape[1] % OUTCHUNK == 0 and iq.shape[2] == 2
         iq = iq.contiguous()
-        self.ctx._chk(self.L.trxsig_rxfe_push(self.h, iq.data_ptr(), iq.shape[1] // OUTCHUNK), "trxsig_rxfe_push")
+        self._call("push", iq.data_ptr(), iq.shape[1] // OUTCHUNK)
         self._keep = iq                                       # the launch reads it asynchronously
 
     def pop_raw(self, max_bursts=4096):
@@ -108,8 +73,7 @@ class RxFrontEnd:
         ps, po, pl = C.c_void_p(), C.c_void_p(), C.c_void_p()
         nb = C.c_int()
         tn = np.zeros(max_bursts, np.int32)
-        self.ctx._chk(self.L.trxsig_rxfe_pop(self.h, C.byref(ps), C.byref(po), C.byref(pl), tn.ctypes.data, max_bursts, C.byref(nb)),
-                      "trxsig_rxfe_pop")
+        self._call("pop", C.byref(ps), C.byref(po), C.byref(pl), tn.ctypes.data, max_bursts, C.byref(nb))
         if nb.value == 0:
             return None
         return ps.value, po.value, pl.value, tn[:nb.value].copy(), nb.value
@@ -144,10 +108,8 @@ class RxFrontEnd:
         max_bursts = min(max_bursts, flags.numel() // self.S)    # cap_tn: what the output arrays hold, in bursts per stream
         tn = np.zeros(max(max_bursts, 1), np.int32)
         p = lambda t: None if t is None else t.data_ptr()
-        self.ctx._chk(self.L.trxsig_rxfe_push_detect_demod_normal(self.h, iq.data_ptr(), iq.shape[1] // OUTCHUNK, tsc, detect_thresh,
-                                                                  energy_thresh, p(flags), p(amp), p(toa), p(avgpwr), p(soft), p(hard),
-                                                                  nsoft, soft_stride, tn.ctypes.data, max_bursts, C.byref(nb)),
-                      "trxsig_rxfe_push_detect_demod_normal")
+        self._call("push_detect_demod_normal", iq.data_ptr(), iq.shape[1] // OUTCHUNK, tsc, detect_thresh, energy_thresh, p(flags), p(amp),
+                   p(toa), p(avgpwr), p(soft), p(hard), nsoft, soft_stride, tn.ctypes.data, max_bursts, C.byref(nb))
         self._keep = iq
         return nb.value, tn[:nb.value].copy()
 
@@ -155,45 +117,31 @@ class RxFrontEnd:
         return self.L.trxsig_rxfe_pending(self.h)
 
 
-class TxBackEnd:
+class TxBackEnd(_FrontEnd):
+    _prefix = "trxsig_txbe"
+
     def __init__(self, ctx, n_streams, lpf_taps, gain=13500.0, device="cuda:0", max_bursts=64, fused=True, carrier_freq=None, rate_factor=0):
         """carrier_freq (radians per wideband sample, one per carrier: the array RxFrontEnd takes) + rate_factor: the wideband
         synthesiser -- n_streams WIDEBAND int16 streams at rate_factor x 400 kS/s, each the sum of len(carrier_freq) ARFCNs;
         bursts go in per (stream, carrier), .S = n_streams * C of them, and pop_samples returns [n_streams, n, 2]."""
         import torch
+        super().__init__(ctx)
         self.torch = torch
-        self.ctx = ctx
-        self.L = ctx.L
-        _bind(self.L)
         self.sps = ctx.sps
         self.dev = torch.device(device)
         self.rate_factor = rate_factor
         lpf = np.ascontiguousarray(lpf_taps, np.float32)
-        h = C.c_void_p()
         if carrier_freq is not None:
             fr = np.ascontiguousarray(carrier_freq, np.float32)
-            ctx._chk(self.L.trxsig_txbe_create_wideband(C.byref(h), ctx.h, n_streams, fr.size, fr.ctypes.data, rate_factor, max_bursts,
-                                                        lpf.ctypes.data, lpf.size, float(gain)), "trxsig_txbe_create_wideband")
+            self._create(n_streams, fr.size, fr.ctypes.data, rate_factor, max_bursts, lpf.ctypes.data, lpf.size, float(gain),
+                         name="create_wideband")
             self.S = n_streams * fr.size
             self.Sw = n_streams
         else:
-            ctx._chk(self.L.trxsig_txbe_create(C.byref(h), ctx.h, n_streams, max_bursts, lpf.ctypes.data, lpf.size, float(gain)),
-                     "trxsig_txbe_create")
+            self._create(n_streams, max_bursts, lpf.ctypes.data, lpf.size, float(gain))
             self.S = self.Sw = n_streams
-        self.h = h
         if carrier_freq is None or not fused:                 # (the wideband form is fused only: asking for the other is refused)
-            ctx._chk(self.L.trxsig_txbe_set_fused(h, int(fused)), "trxsig_txbe_set_fused")
-
-    def close(self):
-        if self.h:
-            self.L.trxsig_txbe_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._call("set_fused", int(fused))
 
     def push_bursts(self, bits, guard, gain=None):
         """bits: uint8 [S, nb, 148] (numpy or device tensor); guard: int32 [nb] guard symbols per burst (same schedule on
@@ -205,16 +153,15 @@ class TxBackEnd:
         d_gain = None
         if gain is not None:
             d_gain = gain if torch.is_tensor(gain) else torch.as_tensor(np.ascontiguousarray(gain, np.float32)).to(self.dev)
-        self.ctx._chk(self.L.trxsig_txbe_push_bursts(self.h, d_bits.contiguous().data_ptr(), guard.ctypes.data,
-                                                     None if d_gain is None else d_gain.contiguous().data_ptr(), d_bits.shape[1]),
-                      "trxsig_txbe_push_bursts")
+        self._call("push_bursts", d_bits.contiguous().data_ptr(), guard.ctypes.data,
+                   None if d_gain is None else d_gain.contiguous().data_ptr(), d_bits.shape[1])
         self._keep = (d_bits, d_gain)
 
     def pop_samples(self):
         """int16 tensor [Sw, n, 2] for the radio (Sw = S for a narrowband back end) (a strided view of the library's output buffer, valid until the next pop),
         or None while less than one chunk is buffered."""
         p = C.c_void_p(); stride = C.c_int64(); n = C.c_int()
-        self.ctx._chk(self.L.trxsig_txbe_pop(self.h, C.byref(p), C.byref(stride), C.byref(n)), "trxsig_txbe_pop")
+        self._call("pop", C.byref(p), C.byref(stride), C.byref(n))
         if n.value == 0:
             return None
         # (the buffer is the back end's own, the same every pop: wrapped once -- torch.as_tensor on a __cuda_array_interface__

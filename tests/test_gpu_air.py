@@ -319,7 +319,6 @@ def test_stream_split_equals_whole(rig):
 def test_bad_arguments_and_lifetime(rig):
     import ctypes as C
     pkg, ctx, L, sps = rig.pkg, rig.ctx, rig.ctx.L, rig.sps
-    L.trxsig_live_children.argtypes = [C.c_void_p]
     before = L.trxsig_live_children(ctx.h)
     air = pkg.Air(ctx, 4)
     assert L.trxsig_live_children(ctx.h) == before + 1

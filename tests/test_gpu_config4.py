@@ -326,11 +326,9 @@ def test_refused_front_end_leaves_the_context_unreferenced():
     pkg = _pkg.load()
     ctx = pkg.TrxSig(4, 0)
     L = ctx.L
-    L.trxsig_live_children.argtypes = [C.c_void_p]
     assert L.trxsig_live_children(ctx.h) == 0
     lpf = np.ones(64, np.float32)
     h = C.c_void_p()
-    L.trxsig_rxfe_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
     # 65,535 streams x 65,535 chunks of 2,340 samples: beyond 2^31 samples (refused before anything is allocated)
     rc = L.trxsig_rxfe_create(C.byref(h), ctx.h, 65535, 65535, lpf.ctypes.data, lpf.size, 1, 0)
     assert rc == -1 and not h.value and b"2^31" in L.trxsig_last_error(ctx.h)
@@ -339,7 +337,6 @@ def test_refused_front_end_leaves_the_context_unreferenced():
     assert rc == -1 and L.trxsig_live_children(ctx.h) == 0
     rc = L.trxsig_rxfe_create(C.byref(h), ctx.h, 2, 4, lpf.ctypes.data, lpf.size, 1, 0)
     assert rc == 0 and L.trxsig_live_children(ctx.h) == 1
-    L.trxsig_rxfe_destroy.argtypes = [C.c_void_p]
     L.trxsig_rxfe_destroy(h)
     assert L.trxsig_live_children(ctx.h) == 0
     ctx.close()

@@ -330,7 +330,6 @@ def test_fec_sch_decode_batch(rig, tx):
 def test_bad_arguments_and_lifetime(rig):
     import ctypes as C
     pkg, ctx, L = rig.pkg, rig.ctx, rig.ctx.L
-    L.trxsig_live_children.argtypes = [C.c_void_p]
     before = L.trxsig_live_children(ctx.h)
     acq = pkg.L1Acq(ctx, 2, 1000)
     assert L.trxsig_live_children(ctx.h) == before + 1

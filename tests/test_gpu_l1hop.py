@@ -428,7 +428,6 @@ def test_bad_inputs(pkg, ctx):
             assert not h.value
         return rc
 
-    pkg.L1Hop(ctx, comb, group, hsn).destroy()               # binds the argtypes
     assert create(comb, group, hsn) == 0
     g = group.copy(); g[0, 0] = 0; assert create(comb, g, hsn) == EINVAL                 # the beacon slot
     g = group.copy(); g[6, 1] = 0; assert create(comb, g, hsn) == EINVAL                 # an OFF slot

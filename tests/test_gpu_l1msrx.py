@@ -532,7 +532,6 @@ def test_follow(pkg, ctx, prims):
     assert len(seen) > 1 and (ra["what"] != 0).sum() > 500
     # the bad-input rules
     L = ctx.L
-    L.trxsig_l1ms_follow.argtypes = [C.c_void_p, C.c_void_p]
     ins, out = pkg.L1MsIn(), pkg.L1MsOut()
     for name, t in zip(("d_tch_kind", "d_tch_payload", "d_xcch_kind", "d_xcch_payload", "d_rach_kind", "d_rach_ra"),
                        (g["tch_kind"], g["tch_payload"], g["xcch_kind"], g["xcch_payload"], g["rach_kind"], g["rach_ra"])):

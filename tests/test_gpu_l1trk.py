@@ -317,7 +317,6 @@ def test_update(rig):
 
 def test_bad_arguments_and_lifetime(rig):
     pkg, ctx, L, sps = rig.pkg, rig.ctx, rig.ctx.L, rig.sps
-    L.trxsig_live_children.argtypes = [C.c_void_p]
     before = L.trxsig_live_children(ctx.h)
     trk = pkg.L1Trk(ctx, PHONE, C0, 4)
     assert L.trxsig_live_children(ctx.h) == before + 1

@@ -279,7 +279,6 @@ def test_refusals(pkg, ctx):
     """Every TRXSIG_EINVAL of the contract leaves D's queues as they were; an all-empty encode is OK and changes nothing."""
     p = Pair(pkg, ctx, MIXED, seed=8)
     L = pkg.lib()
-    L.trxsig_trxgroup_add_l1tx.argtypes = [C.c_void_p, C.c_void_p]
     fn = 9000
     p.encode(fn, 8); n = p.hand()                            # something in the queues to stay unchanged
     before = p.same_queues()

@@ -266,9 +266,7 @@ def test_through_two_transceiver_groups(pkg):
 def test_refusals(pkg):
     ctx = pkg.TrxSig(4, 0)
     L = ctx.L
-    from openbts_ttsou_amd.frontend import TxBackEnd, _bind
-    _bind(L)
-    L.trxsig_live_children.argtypes = [C.c_void_p]
+    from openbts_ttsou_amd.frontend import TxBackEnd
     base = L.trxsig_live_children(ctx.h)
     lpf = tx_lpf(8)
     fr = spaced(8, 8)

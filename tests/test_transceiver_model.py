@@ -56,7 +56,6 @@ def test_tx_datagram_with_out_of_range_frame_number_is_rejected():
     import ctypes as C
     import _pkg
     L = _pkg.load().lib()
-    L.trxsig_trx_decode_tx_datagram.argtypes = [C.c_char_p, C.c_int] + [C.POINTER(C.c_int)] * 3 + [C.c_char_p]
     tn, fn, rssi = C.c_int(), C.c_int(), C.c_int()
     bits = C.create_string_buffer(148)
     ok = bytes([3]) + (tm.HYPERFRAME - 1).to_bytes(4, "big") + bytes([0xF6]) + bytes([1, 0] * 74)
