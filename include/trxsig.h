@@ -322,6 +322,15 @@ int trxsig_modulate_host(trxsig_ctx *ctx, const uint8_t *h_bits, const int32_t *
  * byte = (char)round(v*255.0) (Transceiver.cpp:669), v' = byte/256.0F (TRXManager.cpp:231) -- so the
  * result is what GSM::XCCHL1Decoder / RACHL1Decoder would have produced behind TRXManager.
  *
+ * Values the demodulator never produces.  With wire_quantise == 0 (and in trxsig_fec_viterbi_batch and
+ * trxsig_fec_sch_decode_batch, which have no such switch) any float32 word is accepted and decoded as
+ * SoftVector::decode is written: a value outside [0,1], +-Inf included, goes through the metric clamps of
+ * BitVector.cpp:481-485 and gives finite costs; a NaN makes every cost NaN from its trellis step on, and every
+ * later step takes the last survivor (16th of 16), as the scan of BitVector.cpp:382-393 does when no comparison
+ * holds.  Sliced values (TCH class 2, the stealing flag) are v > 0.5F, false for a NaN.  One block's output never
+ * depends on another block's input.  With wire_quantise != 0 the result is unspecified for a value outside [0,1]
+ * or a NaN: the reference's conversion (char)round(v*255.0) is undefined there.
+ *
  * XCCH (SACCH/SDCCH/BCCH..., GSML1FEC.cpp:584-653): block k = bursts 4k..4k+3 in arrival order (the "B"
  *   index of GSM 05.03 4.1.4); e-bits = burst[3..59] and [88..144]; deinterleave, decode 456 -> 228,
  *   invert the 40 parity bits, Fire-code syndrome.  d_frames: 23 octets per block = d[] after LSB8MSB,

@@ -137,6 +137,13 @@ __device__ __forceinline__ unsigned fec_trellis(float4 *tab, int n, int steps, b
       if (t >= kDeferral) {
         // minCost (bv:382-393): the FIRST survivor with the minimum cost.  The minimum itself by four DPP
         // exchanges; the lanes that hold it by ballot; the first of them = lowest set bit of the row's mask.
+        // NaN costs: a step's branch costs are shared by all 16 survivors, a NaN soft value makes both costs of
+        // its bit NaN (match and mismatch both derive from it) and every candidate adds one of the two; no other
+        // input gives a NaN (costs lie in [0, 25], at most 2 * 536 of them are summed).  So either all 16 costs
+        // of a row are NaN -- from the NaN's step on, NaN being absorbing -- or none is.  With all NaN the
+        // reference's scan skips no survivor (`thisCost >= minCost` is false, bv:388) and ends on survivor 15;
+        // here fminf gives NaN, no lane equals it and the row's mask is 0.  Bit 15 ORed in makes ctz answer 15
+        // then, changes nothing when a lower bit is set, and keeps mi inside the row.
         float mc = cost;
         mc = fminf(mc, dpp_f<0xB1>(mc));                   // quad_perm [1,0,3,2]
         mc = fminf(mc, dpp_f<0x4E>(mc));                   // quad_perm [2,3,0,1]
@@ -145,7 +152,7 @@ __device__ __forceinline__ unsigned fec_trellis(float4 *tab, int n, int steps, b
         const unsigned long long eq = __builtin_amdgcn_ballot_w64(cost == mc);
         const unsigned long long ob = __builtin_amdgcn_ballot_w64((ist >> kDeferral) & 1u);
         const unsigned rowmask = (unsigned)(eq >> (lane & 48)) & 0xFFFFu;
-        const int mi = __builtin_ctz(rowmask | 0x10000u);
+        const int mi = __builtin_ctz(rowmask | 0x8000u);
         const int op = t - kDeferral;
         const unsigned bit = (unsigned)(ob >> ((lane & 48) + mi)) & 1u;
         if ((op >> 5) == s) outw |= bit << (op & 31);      // lane s collects output bits 32s .. 32s+31

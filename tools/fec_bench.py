@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Side measurement for the L1 FEC row: k_fec_viterbi on the soft bits of 65,536 bursts
-resident in HBM -- 16,384 XCCH blocks, then 65,536 RACH bursts -- with the CPU oracle timed beside it.
+resident in HBM -- 16,384 XCCH blocks, 65,536 RACH bursts, then 16,383 TCH/FACCH blocks (both decodes of every block:
+two launches) -- with the CPU oracle timed beside it.
 Prints one JSON line per workload in the shape of bench.py's.  Run on the GPU box: python tools/fec_bench.py"""
 import json
 import os
@@ -20,6 +21,7 @@ g = torch.Generator(device="cuda"); g.manual_seed(1)
 soft = torch.rand(B, 148, device="cuda", generator=g)
 frames = torch.zeros(nb, 23, dtype=torch.uint8, device="cuda"); ok = torch.zeros(nb, dtype=torch.uint8, device="cuda")
 o3 = [torch.zeros(B, dtype=torch.uint8, device="cuda") for _ in range(3)]
+tch33 = torch.zeros(nb - 1, 33, dtype=torch.uint8, device="cuda")
 import fecbind
 o = fecbind.FecOracle()
 cores = min(os.cpu_count() or 1, 16)
@@ -28,6 +30,9 @@ work = {
              lambda s: o.xcch_decode_batch(s, wire=True, nthreads=cores)),
     "rach": (lambda: t.fec_rach_decode(soft, B, o3[0], o3[1], o3[2], wire=True), (36 * 4 + 3) * B,
              lambda s: o.rach_decode_batch(s, wire=True, nthreads=cores)),
+    "tch": (lambda: t.fec_tch_decode(soft, B, tch33, o3[0], o3[1], facch=frames, facch_ok=ok, wire=True),
+            4 * 114 * 4 * (nb - 1) + 30 * (nb - 1),                             # per launch: avg_kernel_ms is per launch too
+            lambda s: o.tch_decode_batch(s, wire=True, nthreads=cores)),
 }
 for name, (fn, alg_bytes, cpu) in work.items():
     for _ in range(400): fn()
