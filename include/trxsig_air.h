@@ -21,6 +21,9 @@
  * against a float64 model.  (The context's 1,024-step trig table is good to 4.7e-6, 2.7e-5 at the largest r: it does not meet
  * that bar and is not used here.)
  *
+ * The channel itself can come from the library too: trxsig_air_fade (below) writes the cell form's d_taps from a time-varying,
+ * frequency-selective multipath model.
+ *
  * Thread safety: one caller at a time per object.  Everything is enqueued on the context's stream; nothing synchronises.
  */
 #ifndef TRXSIG_AIR_H
@@ -94,6 +97,81 @@ typedef struct {
  * out overlapping in. */
 int trxsig_air_stream(trxsig_air *air, int n_cells, uint64_t seed, const trxsig_c32 *d_in, int64_t slot_stride, int64_t arfcn_stride,
                       int n_handsets, const trxsig_air_stream_params *params, int len, trxsig_c32 *d_out, int64_t out_stride);
+
+/* ---- Time-varying multipath: the fading-tap generator -------------------------------------------------------------------------
+ * Writes the [a][t][n_taps] array that trxsig_air_cell_params.d_taps reads: per cell the taps of a tapped-delay-line channel
+ * whose paths fade as sums of sinusoids (Clarke's model by Monte Carlo arrival angles, plus an optional line-of-sight term), with
+ * the noise generator's property: counter-based, a function of (seed, link, path, absolute slot, column) and of nothing else.  A
+ * run cut into calls gives the taps of one call; the launch geometry does not matter.  Every integer rule below is exact.
+ *
+ * Link.  One transmitter-receiver pair with its own fading process.  d_link[a][t] (int32, device) names the link of each cell;
+ *   NULL: link = 8 a + (t % 8).  A link outside [0, n_links) gives a cell whose taps are all +0.  With hopping the caller gives a
+ *   handset one link id on whichever radio row it lands on (trxsig_l1hop_map tells where).
+ * Time.  row = (8 fn + t) mod (8 * 2715648), the noise generator's row; slots are taken as equally long (the 157-symbol slots are
+ *   not told apart).  The process jumps at the hyperframe's wrap, as the noise row does: row 0 follows row 8 * 2715648 - 1.
+ * Profile (caller data; no GSM 05.05 table is in the library).  P paths, 1 <= P <= 12, each with a delay in integer nanoseconds
+ *   (0 .. 10^6), a power (finite, >= 0), optionally a line-of-sight share of that power in [0, 1] and the line-of-sight arrival
+ *   cosine in Q23 (|.| <= 2^23); S diffuse sinusoids per path, 1 <= S <= 32.
+ * Per (link l, path p, sinusoid s), s = 0 .. S: one Philox4x32-10 block, key = the call's seed, counter = (s, p, l, 2)  (form 2;
+ *   the cell form of the noise uses 0, the stream form 1).
+ *     phi  = w0, a phase in 2^-32 turn
+ *     k    = 2 (w1 >> 9) + 1;  c = cos(2 pi k 2^-24) by the separately rounded float32 steps of the noise's cosine
+ *     C    = (int) rintf(c * 2^23)  (ties to even; |C| <= 2^23).  The line-of-sight sinusoid is s = S: its phi is its own block's
+ *            w0, its C the profile's Q23 cosine.
+ *     step = (int32) (((int64) C * D_l) >> 23)  (an arithmetic shift: towards minus infinity), D_l = d_doppler[l] & 0x7fffffff:
+ *            the link's maximum Doppler shift in 2^-32 turn per slot, a uint32 below 2^31 (the top bit is not read).
+ * Path gain.  theta = phi + row * step in uint32 wrap-around arithmetic; e(theta) = (cos, sin) of the top 24 bits of theta by
+ *   the same float32 steps (a phase of 0 gives exactly (1, 0)); each component of e is within 1e-5 of the exact value.
+ *     g_p = a_p (e(theta_0) + e(theta_1) + ... + e(theta_{S-1})) + b_p e(theta_S)
+ *   the sum a chain of S - 1 rounded float32 additions per component in the order s = 0, 1, .., S - 1, then per component two
+ *   rounded products and a rounded sum.  a_p = sqrt(power_p (1 - los_p) / S), b_p = sqrt(power_p los_p), computed on the host in
+ *   double from the float32 arguments and rounded once to float32.
+ * Frequency selectivity.  trxsig_air_fade_columns gives column a its carrier offset f_a in kHz (|f_a| <= 10^7; before the first
+ *   call: 1,024 columns at 200 a).  With hopping these are the radio rows.  Per (column, path) the host forms the phase
+ *   -f_a tau_p 10^-6 turn exactly in integers: r = (-f_a tau_p) mod 10^6 in [0, 10^6), rot = (r 2^32 + 500000) div 10^6 mod 2^32
+ *   (rounded once, halves up).  The kernel multiplies g_p by e(rot): four rounded products, a rounded difference and a rounded sum.
+ * Projection onto taps.  The host computes w[p][j], j < n_taps, in double, rounded to float32: with
+ *   x = j - centre - tau_p sps 13 / 48000  (samples; 48000 x is an integer and is formed as one),
+ *     w = 1 where x = 0, 0 where x is another whole number or |x| >= 4, else sin(pi x) / (pi x) * (0.5 + 0.5 cos(pi x / 4))
+ *   (a Hann-windowed sinc of half-width 4 samples).  A path whose delay is a whole number of samples has exactly one non-zero
+ *   weight, 1.0f.  centre in 0..8 is the caller's bulk delay; centre = 0 truncates the precursors (the receiver's TOA absorbs the
+ *   rest).  tap[j] = sum over p, ascending, of (g_p rotated) * w[p][j]: per component a rounded product and a rounded sum, the
+ *   first term starting the sum.
+ * Error bound (what the tests hold the taps to against a float64 evaluation of the formulas above from the same integers).  With
+ *   d = 1e-5 (the promise for e), u = 2^-24, G_p = S a_p + b_p (no component of g_p exceeds it):
+ *     E_p = a_p (S d + S^2 u) + b_p d + 3 u G_p                 per component of g_p: the trig errors, the chain's and g_p's roundings
+ *     R_p = 2 E_p + 2 G_p d + 6 u G_p                           ... after the rotation (each component sums two products)
+ *     |tap[j] - exact| <= sum_p |w[p][j]| (R_p + 2 G_p (2 u + (P + 1) u))   per component
+ *   (2 u: w within one float32 spacing of its formula, whichever libm made it; (P + 1) u: the product and the P - 1 sums).
+ * Out of scope: the stream form (a fading downlink needs a per-handset copy of the carrier through trxsig_air_cells); variation
+ *   inside a burst (block fading: one set of taps per cell); correlated shadowing; antenna diversity. */
+
+#define TRXSIG_AIR_FADE_MAX_PATHS 12
+#define TRXSIG_AIR_FADE_MAX_SINUSOIDS 32
+#define TRXSIG_AIR_FADE_MAX_COLUMNS 1024
+
+/* Sets the profile, in stream order (as trxsig_l1ciph_set: launches enqueued before see the old one, launches after the new).
+ * h_* are host arrays [n_paths]; h_los_share and h_los_cos_q23 may be NULL (no line of sight / cosine 0).  n_taps in
+ * 1..the object's max_taps is the length of the taps trxsig_air_fade then writes.  The first call allocates the object's only
+ * device block.  TRXSIG_EINVAL: NULL object, delays or powers, a count or a path value outside the ranges above. */
+int trxsig_air_fade_profile(trxsig_air *air, int n_paths, const int32_t *h_delay_ns, const float *h_power, const float *h_los_share,
+                            const int32_t *h_los_cos_q23, int n_sinusoids, int n_taps, int centre);
+
+/* Sets the columns' carrier offsets (host int32 [n_arfcn], kHz), in stream order; n_arfcn in 1..1024 is from then on the most
+ * columns a trxsig_air_fade call may name.  TRXSIG_EINVAL: NULL object or array, n_arfcn or an offset out of range. */
+int trxsig_air_fade_columns(trxsig_air *air, int n_arfcn, const int32_t *h_col_khz);
+
+/* d_taps[a][t][n_taps] for a < n_arfcn, t < 8 n_frames, t = 0 at TN 0 of frame fn.  d_link: int32 [a][t] or NULL; d_doppler:
+ * uint32 [n_links].  One launch (k_air_fade); nothing synchronises.  Two taps leave in one 16-byte store where n_taps is even and
+ * d_taps is 16-byte aligned.  TRXSIG_EINVAL before any launch: NULL object, d_doppler or d_taps, no profile set, n_arfcn outside
+ * 1..the columns set, n_frames outside 1..2^24, fn outside [0, 2715648), n_links outside 1..2^30. */
+int trxsig_air_fade(trxsig_air *air, int fn, int n_arfcn, int n_frames, uint64_t seed, const int32_t *d_link, int n_links,
+                    const uint32_t *d_doppler, trxsig_c32 *d_taps);
+
+/* The integers behind the taps: d_phase (uint32) and d_step (int32), both [n_links][P][S + 1] -- phi and step of every
+ * (link, path, sinusoid), the line-of-sight one last.  One launch (k_air_fade_params).  TRXSIG_EINVAL: NULL object or arrays, no
+ * profile set, n_links outside 1..2^24. */
+int trxsig_air_fade_params(trxsig_air *air, uint64_t seed, int n_links, const uint32_t *d_doppler, uint32_t *d_phase, int32_t *d_step);
 
 #ifdef __cplusplus
 }

@@ -1123,7 +1123,8 @@ AIR_MAX_TAPS = 32                                         # TRXSIG_AIR_MAX_TAPS
 
 class Air(_Object):
     """ctypes view of include/trxsig_air.h: the radio channel on the device -- multipath, oscillator offset and counter-based
-    Gaussian noise, slot cells -> slot cells (cells) or a carrier's cells -> one stream per handset (stream)."""
+    Gaussian noise, slot cells -> slot cells (cells) or a carrier's cells -> one stream per handset (stream); and the taps of a
+    time-varying, frequency-selective multipath channel for the cell form (fade_profile, fade_columns, fade, fade_params)."""
     _prefix = "trxsig_air"
 
     def __init__(self, ctx, max_taps=AIR_MAX_TAPS):
@@ -1159,6 +1160,37 @@ class Air(_Object):
         self._call("stream", int(n_cells), int(seed), _ptr(x), int(slot_stride), int(arfcn_stride), int(arfcn.numel()), C.byref(p),
                    int(length), _ptr(out), int(out_stride))
         self._keep = keep
+
+
+    def fade_profile(self, delay_ns, power, n_sinusoids, n_taps, centre=0, los_share=None, los_cos_q23=None):
+        """The fading profile (host sequences, one entry per path): delays in ns, powers, optionally the line-of-sight share of
+        each power and its arrival cosine in Q23.  In stream order."""
+        np = self.np
+        d, w = np.ascontiguousarray(delay_ns, np.int32), np.ascontiguousarray(power, np.float32)
+        ls = None if los_share is None else np.ascontiguousarray(los_share, np.float32)
+        lc = None if los_cos_q23 is None else np.ascontiguousarray(los_cos_q23, np.int32)
+        assert len(w) == len(d) and all(v is None or len(v) == len(d) for v in (ls, lc))
+        self._call("fade_profile", len(d), d.ctypes.data, w.ctypes.data, None if ls is None else ls.ctypes.data,
+                   None if lc is None else lc.ctypes.data, int(n_sinusoids), int(n_taps), int(centre))
+        self.fade_shape = (len(d), int(n_sinusoids), int(n_taps))
+
+    def fade_columns(self, col_khz):
+        """The columns' carrier offsets in kHz (a host sequence); as many columns as it has entries.  In stream order."""
+        k = self.np.ascontiguousarray(col_khz, self.np.int32)
+        self._call("fade_columns", len(k), k.ctypes.data)
+
+    def fade(self, fn, n_arfcn, n_frames, seed, n_links, doppler, taps, link=None):
+        """taps: device complex64 [n_arfcn][8 n_frames][n_taps] (or float32 pairs), written; doppler: device uint32-sized words
+        [n_links]; link: device int32 [n_arfcn][8 n_frames] or None (link = 8 a + t % 8)."""
+        assert doppler.element_size() == 4 and (link is None or link.element_size() == 4)
+        self._call("fade", int(fn), int(n_arfcn), int(n_frames), int(seed), _ptr(link), int(n_links), _ptr(doppler), _ptr(taps))
+        self._keep = (link, doppler)
+
+    def fade_params(self, seed, n_links, doppler, phase, step):
+        """phase / step: device 32-bit words [n_links][P][S + 1], written: the integers behind the taps."""
+        assert doppler.element_size() == 4 and phase.element_size() == 4 and step.element_size() == 4
+        self._call("fade_params", int(seed), int(n_links), _ptr(doppler), _ptr(phase), _ptr(step))
+        self._keep = (doppler,)
 
 
 TRK_CLIPPED, TRK_UNLOCKED = 1, 2                          # trxsig_l1trk_meas.d_status bits (TRXSIG_TRK_*)

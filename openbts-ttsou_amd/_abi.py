@@ -320,6 +320,10 @@ SIGNATURES = {
     "trxsig_air_destroy": (None, [vp]),
     "trxsig_air_cells": (i32, [vp, i32, i32, i32, u64, vp, i64, i64, P(AirCellParams), vp, i64, i64, i32]),
     "trxsig_air_stream": (i32, [vp, i32, u64, vp, i64, i64, i32, P(AirStreamParams), i32, vp, i64]),
+    "trxsig_air_fade_profile": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32]),
+    "trxsig_air_fade_columns": (i32, [vp, i32, vp]),
+    "trxsig_air_fade": (i32, [vp, i32, i32, i32, u64, vp, i32, vp, vp]),
+    "trxsig_air_fade_params": (i32, [vp, u64, i32, vp, vp, vp]),
     # ---- include/trxsig_l1trk.h ----
     "trxsig_l1trk_create": (i32, [P(vp), vp, i32, i32, vp, vp, i32, i32, i32, f32]),
     "trxsig_l1trk_destroy": (None, [vp]),

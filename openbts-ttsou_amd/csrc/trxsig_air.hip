@@ -1,6 +1,7 @@
 // trxsig_air.hip -- the air (include/trxsig_air.h): multipath, oscillator offset and white Gaussian noise on the device.
 // k_air_cells: slot cells -> slot cells (the uplink: what trxsig_l1ms_radiate wrote -> what trxsig_trxgroup_pull reads).
 // k_air_stream: a carrier's cells -> one delayed, rotated, scaled, noisy stream per handset (what trxsig_l1acq_search reads).
+// k_air_fade: the taps k_air_cells reads, from a sum-of-sinusoids fading process per (link, path) (k_air_fade_params: its integers).
 // The signal path is the reference's arithmetic (convolve START_ONLY, expjLookup, delayVector, scaleVector) under the library's
 // numerical contract; the noise is counter-based (Philox4x32-10 -> Box-Muller) with ln / cos / sin in the kernel's own float32
 // arithmetic: the device library's logf / sincosf hold fused multiply-adds, which no kernel of this library may contain.
@@ -24,29 +25,11 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
   w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
 
-// Box-Muller on a pair of words: u = (2 (wa >> 9) + 1) 2^-24, v likewise; g = sqrt(-2 ln u) (cos 2 pi v, sin 2 pi v).
-// ln u: u = m 2^e with m in [sqrt(1/2), sqrt 2) by integer operations (u near 1 has e = 0: nothing cancels), ln m = 2 atanh(s),
-// s = (m - 1) / (m + 1), |s| < 0.1716: the series to s^9 leaves 2e-9 relative; e ln 2 with ln 2 split so that e * hi is exact.
-// cos, sin: the 24-bit phase is reduced to an octant in integers (exact), the angle theta in (0, pi/4] is one rounded product,
-// Taylor polynomials to theta^9 / theta^10 leave 2e-9.  Every step is a separately rounded float32 operation; the sum of the
-// rounding errors keeps each component of g within 3e-6 of the formulas' exact value (trxsig_air.h promises 1e-5).
-__device__ __forceinline__ cx air_gauss(unsigned wa, unsigned wb) {
-  const float u = (float)(2u * (wa >> 9) + 1u) * 5.9604644775390625e-8f;      // exact: 24 bits times 2^-24
-  const int bits = __float_as_int(u);
-  int e = (bits >> 23) - 127;
-  float m = __int_as_float((bits & 0x007fffff) | 0x3f800000);                 // [1, 2)
-  if (m > 1.41421354f) { m = m * 0.5f; e += 1; }
-  const float s = (m - 1.0f) / (m + 1.0f);
-  const float s2 = s * s;
-  float q = s2 * 0.111111111f + 0.142857143f;
-  q = q * s2 + 0.2f;
-  q = q * s2 + 0.333333333f;
-  q = q * s2;
-  const float lnm = (s + s * q) * 2.0f;
-  const float fe = (float)e;
-  const float lnu = fe * 0.693145751953125f + (lnm + fe * 1.42860682030941723212e-6f);
-  const float r = sqrtf(-2.0f * lnu);
-  const unsigned k = 2u * (wb >> 9) + 1u;                                    // the phase in 2^-24 turn, odd
+// (cos, sin) of a 24-bit phase k, in 2^-24 turn: the phase is reduced to an octant in integers (exact), the angle theta in
+// [0, pi/4] is one rounded product, Taylor polynomials to theta^9 / theta^10 leave 2e-9.  Every step is a separately rounded
+// float32 operation; each component is well inside the 1e-5 trxsig_air.h promises.  A phase on an axis has theta = 0: exactly (+-1, +-0) or
+// (+-0, +-1).  Shared by the noise (odd phases) and the fading generator (every phase).
+__device__ __forceinline__ void air_cossin(unsigned k, float &c, float &sgn) {
   const unsigned quad = k >> 22;
   unsigned f = k & 0x3fffffu;                                                // inside the quarter turn, in 2^-22 of it
   const bool mirror = f > 0x200000u;
@@ -64,13 +47,37 @@ __device__ __forceinline__ cx air_gauss(unsigned wa, unsigned wb) {
   pc = pc * t2 + -0.5f;
   float cs = 1.0f + pc * t2;
   if (mirror) { const float t = sn; sn = cs; cs = t; }
-  float c, sgn;
   switch (quad) {
     case 0: c = cs; sgn = sn; break;
     case 1: c = -sn; sgn = cs; break;
     case 2: c = -cs; sgn = -sn; break;
     default: c = sn; sgn = -cs; break;
   }
+}
+
+// Box-Muller on a pair of words: u = (2 (wa >> 9) + 1) 2^-24, v likewise; g = sqrt(-2 ln u) (cos 2 pi v, sin 2 pi v).
+// ln u: u = m 2^e with m in [sqrt(1/2), sqrt 2) by integer operations (u near 1 has e = 0: nothing cancels), ln m = 2 atanh(s),
+// s = (m - 1) / (m + 1), |s| < 0.1716: the series to s^9 leaves 2e-9 relative; e ln 2 with ln 2 split so that e * hi is exact.
+// cos, sin: air_cossin of the odd 24-bit phase.  Every step is a separately rounded float32 operation; the sum of the
+// rounding errors keeps each component of g within 3e-6 of the formulas' exact value (trxsig_air.h promises 1e-5).
+__device__ __forceinline__ cx air_gauss(unsigned wa, unsigned wb) {
+  const float u = (float)(2u * (wa >> 9) + 1u) * 5.9604644775390625e-8f;      // exact: 24 bits times 2^-24
+  const int bits = __float_as_int(u);
+  int e = (bits >> 23) - 127;
+  float m = __int_as_float((bits & 0x007fffff) | 0x3f800000);                 // [1, 2)
+  if (m > 1.41421354f) { m = m * 0.5f; e += 1; }
+  const float s = (m - 1.0f) / (m + 1.0f);
+  const float s2 = s * s;
+  float q = s2 * 0.111111111f + 0.142857143f;
+  q = q * s2 + 0.2f;
+  q = q * s2 + 0.333333333f;
+  q = q * s2;
+  const float lnm = (s + s * q) * 2.0f;
+  const float fe = (float)e;
+  const float lnu = fe * 0.693145751953125f + (lnm + fe * 1.42860682030941723212e-6f);
+  const float r = sqrtf(-2.0f * lnu);
+  float c, sgn;
+  air_cossin(2u * (wb >> 9) + 1u, c, sgn);                                    // the phase in 2^-24 turn, odd
   return mk(r * c, r * sgn);
 }
 
@@ -228,6 +235,116 @@ __global__ __launch_bounds__(256) void k_air_stream(const TrxTables *__restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The fading-tap generator (trxsig_air.h, "Time-varying multipath").  One (link, path, sinusoid) is one Philox block:
+// phase w0, Doppler cosine from w1 (the line-of-sight sinusoid s = S takes the profile's).  Integers only from there to the
+// phase theta of a slot, so the values are functions of (seed, link, path, row, column) alone.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void fade_pair(unsigned key0, unsigned key1, unsigned link, int path, int s, int S, unsigned D, int los_c,
+                                          unsigned &phi, int &step) {
+  unsigned w[4];
+  philox4x32_10((unsigned)s, (unsigned)path, link, 2u, key0, key1, w);
+  phi = w[0];
+  int C = los_c;
+  if (s != S) {
+    float c, sn;
+    air_cossin(2u * (w[1] >> 9) + 1u, c, sn);
+    C = (int)rintf(c * 8388608.0f);                          // Q23; the product is exact
+  }
+  step = (int)(((long long)C * (long long)D) >> 23);
+}
+
+__device__ __forceinline__ cx fade_e(unsigned theta) {
+  float c, s;
+  air_cossin(theta >> 8, c, s);
+  return mk(c, s);
+}
+
+// k_air_fade_params: thread i = (link, path, s) in that nesting writes phi and step (what the tests grade word for word)
+__global__ __launch_bounds__(256) void k_air_fade_params(TrxAirFade p) {
+  const int n_pairs = p.P * (p.S + 1);
+  const int i = blockIdx.x * 256 + threadIdx.x;              // the pair inside the link (blockIdx.y)
+  if (i >= n_pairs) return;
+  const unsigned link = blockIdx.y + 65535u * blockIdx.z;
+  if (link >= (unsigned)p.n_links) return;
+  const int path = (int)(((unsigned)i * p.inv) >> 16), s = i - path * (p.S + 1);
+  unsigned phi; int step;
+  fade_pair(p.key0, p.key1, link, path, s, p.S, p.doppler[link] & 0x7fffffffu, p.tab->los_c[path], phi, step);
+  const size_t o = (size_t)link * n_pairs + i;
+  p.phase[o] = phi; p.step[o] = step;
+}
+
+// k_air_fade: workgroup (x, y) takes column y's slots 4 x + wave, 4 (x + gridDim.x) + wave, ...: a wave per cell.  The weights,
+// amplitudes and the column's rotations go to LDS once.  Per cell: lane i, i + 64, ... of the wave forms e(theta) of pair i
+// into LDS; lane p < P sums its path's S diffuse terms in the order s = 0, 1, ..., S - 1 (a chain of S - 1 rounded sums from
+// e(theta_0): the same in every geometry), forms g_p = a_p sum + b_p e(theta_S) and rotates it by the column's e; lane l forms
+// taps 2 l and 2 l + 1, p ascending.  The barriers are the workgroup's: every wave takes every trip, with or without a cell.
+__global__ __launch_bounds__(256) void k_air_fade(TrxAirFade p) {
+  __shared__ float ws[TRX_FADE_MAX_PATHS * 32];
+  __shared__ float as[TRX_FADE_MAX_PATHS], bs[TRX_FADE_MAX_PATHS];
+  __shared__ int lc[TRX_FADE_MAX_PATHS];
+  __shared__ cx rs[TRX_FADE_MAX_PATHS];
+  __shared__ cx es[4][TRX_FADE_MAX_PATHS * (TRX_FADE_MAX_SIN + 1)];
+  __shared__ cx gs[4][TRX_FADE_MAX_PATHS];
+  const int a = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int P = p.P, S = p.S, n_pairs = P * (S + 1);
+  for (int i = threadIdx.x; i < TRX_FADE_MAX_PATHS * 32; i += 256) ws[i] = p.tab->w[i >> 5][i & 31];
+  if ((int)threadIdx.x < P) {
+    as[threadIdx.x] = p.tab->a[threadIdx.x]; bs[threadIdx.x] = p.tab->b[threadIdx.x]; lc[threadIdx.x] = p.tab->los_c[threadIdx.x];
+    rs[threadIdx.x] = fade_e(p.tab->rot[a][threadIdx.x]);
+  }
+  __syncthreads();
+  for (long long t0 = 4LL * blockIdx.x; t0 < p.rows; t0 += 4LL * gridDim.x) {
+    const long long t = t0 + wv;
+    const bool cell = t < p.rows;
+    int link = -1;
+    if (cell) link = p.link ? p.link[(size_t)a * p.rows + t] : 8 * a + (int)(t & 7);
+    const bool live = link >= 0 && link < p.n_links;
+    if (live) {
+      const unsigned D = p.doppler[link] & 0x7fffffffu;
+      const unsigned nrow = (p.row0 + (unsigned)t) % kAirRows;
+      for (int i = lane; i < n_pairs; i += 64) {
+        const int path = (int)(((unsigned)i * p.inv) >> 16), s = i - path * (S + 1);
+        unsigned phi; int step;
+        fade_pair(p.key0, p.key1, (unsigned)link, path, s, S, D, lc[path], phi, step);
+        es[wv][i] = fade_e(phi + nrow * (unsigned)step);
+      }
+    }
+    __syncthreads();
+    if (live && lane < P) {
+      const cx *e = &es[wv][lane * (S + 1)];
+      cx sum = e[0];
+      for (int s = 1; s < S; s++) sum = cadd(sum, e[s]);
+      const float av = as[lane], bv = bs[lane];
+      const cx g = mk(av * sum.r + bv * e[S].r, av * sum.i + bv * e[S].i);
+      const cx r = rs[lane];
+      gs[wv][lane] = mk(g.r * r.r - g.i * r.i, g.r * r.i + g.i * r.r);
+    }
+    __syncthreads();
+    if (cell && 2 * lane < p.n_taps) {
+      const int j = 2 * lane;
+      cx h0 = mk(0, 0), h1 = mk(0, 0);
+      if (live) {
+        cx g = gs[wv][0];
+        h0 = mk(g.r * ws[j], g.i * ws[j]); h1 = mk(g.r * ws[j + 1], g.i * ws[j + 1]);   // (j + 1 <= 31; a weight beyond n_taps is zero and its tap is not stored)
+        for (int q = 1; q < P; q++) {
+          g = gs[wv][q];
+          const float w0 = ws[32 * q + j], w1 = ws[32 * q + j + 1];
+          h0 = mk(h0.r + g.r * w0, h0.i + g.i * w0);
+          h1 = mk(h1.r + g.r * w1, h1.i + g.i * w1);
+        }
+      }
+      cx *o = p.taps + ((size_t)a * p.rows + t) * p.n_taps + j;
+      if (p.vec) {
+        *reinterpret_cast<float4 *>(o) = make_float4(h0.r, h0.i, h1.r, h1.i);
+      } else {
+        o[0] = h0;
+        if (j + 1 < p.n_taps) o[1] = h1;
+      }
+    }
+  }
+}
+
 constexpr long long kAirCellsWg = 16384;                     // as k_l1ms_radiate: the slots beyond go round the loop
 
 }  // namespace
@@ -255,5 +372,23 @@ hipError_t trx_launch_air_stream(hipStream_t st, int sps, const TrxTables *dT, c
     case 4: k_air_stream<4><<<grid, block, 0, st>>>(dT, p); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_air_fade(hipStream_t st, const TrxAirFade &p) {
+  if (p.rows <= 0 || p.n_arfcn <= 0 || p.n_arfcn > TRX_FADE_MAX_COLS || p.P < 1 || p.P > TRX_FADE_MAX_PATHS || p.S < 1 ||
+      p.S > TRX_FADE_MAX_SIN || p.n_taps < 1 || p.n_taps > 32)
+    return hipErrorInvalidValue;
+  const long long quads = (p.rows + 3) / 4;
+  long long gx = kAirCellsWg / p.n_arfcn > 0 ? kAirCellsWg / p.n_arfcn : 1;
+  if (gx > quads) gx = quads;
+  k_air_fade<<<dim3((unsigned)gx, (unsigned)p.n_arfcn), dim3(256), 0, st>>>(p);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_air_fade_params(hipStream_t st, const TrxAirFade &p) {
+  if (p.n_links <= 0 || p.P < 1 || p.P > TRX_FADE_MAX_PATHS || p.S < 1 || p.S > TRX_FADE_MAX_SIN) return hipErrorInvalidValue;
+  const unsigned gy = p.n_links < 65535 ? (unsigned)p.n_links : 65535u, gz = (unsigned)((p.n_links + 65534) / 65535);
+  k_air_fade_params<<<dim3((unsigned)((p.P * (p.S + 1) + 255) / 256), gy, gz), dim3(256), 0, st>>>(p);
   return hipGetLastError();
 }

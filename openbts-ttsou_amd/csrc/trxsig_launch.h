@@ -294,3 +294,26 @@ struct TrxAirStream {
 };
 #define TRX_AIR_TILE 512                                   // outputs per workgroup of k_air_stream
 hipError_t trx_launch_air_stream(hipStream_t st, int sps, const TrxTables *dT, const TrxAirStream &p);
+// the fading-tap generator (trxsig_air_fade; k_air_fade, k_air_fade_params).  The profile's image on the device, written by
+// trxsig_air_fade_profile / _columns in stream order: amplitudes, line-of-sight cosines, tap weights, column rotations.
+#define TRX_FADE_MAX_PATHS 12
+#define TRX_FADE_MAX_SIN 32
+#define TRX_FADE_MAX_COLS 1024
+struct TrxAirFadeTab {
+  float a[TRX_FADE_MAX_PATHS], b[TRX_FADE_MAX_PATHS];      // sqrt(power (1 - los) / S), sqrt(power los)
+  int32_t los_c[TRX_FADE_MAX_PATHS];                       // the line-of-sight arrival cosine, Q23
+  float w[TRX_FADE_MAX_PATHS][32];                         // w[p][j]: path p's weight on tap j (zero beyond n_taps)
+  uint32_t rot[TRX_FADE_MAX_COLS][TRX_FADE_MAX_PATHS];     // -f_kHz tau_ns 1e-6 turn, in 2^-32 turn
+};
+struct TrxAirFade {
+  const TrxAirFadeTab *tab;
+  int P, S, n_taps;
+  unsigned inv;                                            // ceil(2^16 / (S + 1)): pair i is path (i * inv) >> 16
+  const int32_t *link; const uint32_t *doppler; int n_links;
+  trx_c32 *taps; int vec;                                  // vec: two taps leave in one 16-byte store
+  uint32_t *phase; int32_t *step;                          // k_air_fade_params' outputs
+  long long rows; int n_arfcn;
+  unsigned row0, key0, key1;
+};
+hipError_t trx_launch_air_fade(hipStream_t st, const TrxAirFade &p);
+hipError_t trx_launch_air_fade_params(hipStream_t st, const TrxAirFade &p);
