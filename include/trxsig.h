@@ -201,7 +201,11 @@ int trxsig_modulate_batch(trxsig_ctx *ctx, const uint8_t *d_bits, const int32_t 
  *     after its "-= 1" update, :338-340), or snr_value > 0 = the SNR estimate itself for every burst (a caller
  *     that forms it in the reference's double arithmetic).  d_chan_off = chanRespOffset, d_w: B x 7, d_b: B x 5.
  *   trxsig_equalize_taps_batch: scaleVector(burst, 1/amp) + equalizeBurst(burst, toa_eq, w, b) with the taps of
- *     burst b at d_w + 7b, d_b + 5b; d_enable[b] & TRXSIG_F_DETECT selects the bursts to process (zeros otherwise). */
+ *     burst b at d_w + 7b, d_b + 5b; d_enable[b] & TRXSIG_F_DETECT selects the bursts to process (zeros otherwise).
+ *     The taps and the amplitude are the caller's and may be anything, Inf and NaN included: a feed-forward term that
+ *     reaches beyond the burst (sample k + 6 - j >= length) is SKIPPED, as the reference's convolve skips it
+ *     (sigProcLib.cpp:322-366), never formed as 0 * w[j] -- so with w[j] not finite the last 6 - j soft bits are the
+ *     finite values the reference gives, and a NaN soft bit (hard bit 0) stands exactly where the reference's does. */
 int trxsig_estimate_dfe_batch(trxsig_ctx *ctx, const trxsig_c32 *d_samples, const int32_t *d_offset,
                               const int32_t *d_length, int B, int tsc, float detect_thresh, float snr_thresh,
                               float snr_value, int variant52m, int max_toa, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa,
@@ -267,7 +271,10 @@ int trxsig_unpack_half(trxsig_ctx *ctx, const uint16_t *d_iq, int64_t n_samples,
  *   energy_thresh argument (the reference uses its adaptive mEnergyThreshold, whose sequential
  *   update stays with the caller: SURVEY 8a' item 14); energy_thresh < 0 disables the gate and
  *   uses thr = 0.  d_w: B x 7, d_b: B x 5 complex, written for detected bursts (may be NULL).
- *   max_toa (52M variant only): 0..17. */
+ *   max_toa (52M variant only): 0..17.  The 52M correlation window covers samples 66 - span .. 81 + span, span =
+ *   max(max_toa, 5); the reference reads it unchecked.  A burst that passes the energy gate but is too short for the
+ *   window (length < 82 + span: lengths 92..98 at the widest windows, max_toa 11..17) gets TRXSIG_F_BADLEN alone, amp = 0,
+ *   TOA = 0 and zero soft bits -- in this call, trxsig_estimate_dfe_batch and trxsig_channel_estimate_batch alike. */
 int trxsig_equalize_normal_batch(trxsig_ctx *ctx,
                                  const trxsig_c32 *d_samples, const int32_t *d_offset,
                                  const int32_t *d_length, int B,

@@ -159,8 +159,8 @@ __global__ __launch_bounds__(256) void k_eq_delay(const TrxTables *__restrict__ 
   for (int i = 0; i < OPL; i++) S[OPL * hl + i] = y[i];
   wave_lds_fence();
   // The whole row is written: the delayed burst's N samples, zeros from N to the row's end (and a row of zeros for a burst the
-  // gate refused).  The equaliser's feed-forward sums then meet a zero SAMPLE wherever the reference skips a term beyond the
-  // burst -- +0 + (+-0) = +0, the same value -- and carry no range check per tap (k_eq_dfe2's producer).
+  // gate refused), so the equaliser's tile loads need no mask.  Its feed-forward sums still SKIP the terms beyond the burst, as
+  // the reference does: a zero sample stands for a skipped term only while the tap is finite (k_eq_dfe2's producer).
   cx *out = xd + (size_t)(live ? b : 0) * xstride;
 #pragma unroll
   for (int i = 0; i < OPL; i++) {
@@ -1330,6 +1330,15 @@ __device__ __forceinline__ bool eq_enabled(uint8_t fl, int N, float toa_eq) {
   return (fl & TRXSIG_F_DETECT) && N >= 92 && N <= 157 && (fabsf(toa_eq) <= 4096.0f);
 }
 
+// Some burst of the wave is equalised with a feed-forward tap that is Inf or NaN (wave-uniform).  Only then does a zero sample stop
+// standing for a skipped term -- 0 * w is +-0 for every finite w -- and the feed-forward sums need their range check.
+__device__ __forceinline__ bool eq_taps_hostile(bool det, const v2f (&w)[7]) {
+  bool fin = true;
+#pragma unroll
+  for (int j = 0; j < 7; j++) fin = fin && __builtin_isfinite(w[j].x) && __builtin_isfinite(w[j].y);
+  return __any(det && !fin);
+}
+
 // equalizeBurst after its delayVector: xd = delayed, scaled burst (B x xstride complex)
 __global__ __launch_bounds__(64) void k_eq_dfe(const TrxTables *__restrict__ T, const cx *__restrict__ xd, int xstride,
                                                const int32_t *__restrict__ length, int B,
@@ -1467,6 +1476,8 @@ __global__ __launch_bounds__(128) void k_eq_dfe2(const TrxTables *__restrict__ T
     for (int j = 0; j < 7; j++) w[j] = pk(w_in[tb * 7 + j]);
 #pragma unroll
     for (int m = 0; m < 6; m++) win[m] = pk(x[5 - m]);       // win[m] = x[16 u + 5 - m] (the row holds zeros from N on: k_eq_delay)
+    const int Nff = det ? N : 160;                          // the burst's end for the feed-forward terms (a burst that is not equalised has none)
+    const bool hostile = eq_taps_hostile(det, w);           // (wave-uniform) some burst's taps are not finite
     // sample tile u: a = 16 u + 6 + c, c = 0..15 (output k = 16 u + i needs x[k + 6 - j]: FULL_SPAN keeps [6, 6+N), :1352-1356)
     auto load_tile = [&](int u, cx (&v)[16]) {
 #pragma unroll
@@ -1497,19 +1508,26 @@ __global__ __launch_bounds__(128) void k_eq_dfe2(const TrxTables *__restrict__ T
       v2f xa[16];
 #pragma unroll
       for (int i = 0; i < 16; i++) xa[i] = pk(xt[lane][i]);
+      // convolve general branch: sum += a[t-j]*b[j], t = k+6; k + 6 - j >= 0 always, and a term beyond the burst (k + 6 - j >= N) is
+      // SKIPPED in the reference (:322-366).  The row holds zero samples there (k_eq_delay), and with FINITE taps the product adds
+      // +-0 to a sum that starts at +0: the same value, with no branch and no range check.  But the taps may be the caller's
+      // (trxsig_equalize_taps_batch) or designDFE's answer to a hostile channel, and 0 * Inf and 0 * NaN are NaN: where a tap of
+      // the wave is not finite, the tiles in which some lane's burst ends select such terms away instead.
+      auto ff_tile = [&](auto checked_) {
+        constexpr bool CHK = decltype(checked_)::value;
 #pragma unroll
-      for (int i = 0; i < 16; i++) {
-        v2f d = pk(mk(0, 0));
+        for (int i = 0; i < 16; i++) {
+          v2f d = pk(mk(0, 0));
 #pragma unroll
-        for (int j = 0; j < 7; j++) {                       // convolve general branch: sum += a[t-j]*b[j], t = k+6
-          const v2f xv = (i - j >= 0) ? xa[(i - j >= 0) ? i - j : 0] : win[(j - i - 1 < 6) ? j - i - 1 : 5];
-          // (a term beyond the burst is skipped in the reference; here it is added as the product with a zero SAMPLE instead --
-          // k_eq_delay wrote zeros from N to the end of the row, the tile loader zeros beyond it --: the sum starts at +0 and
-          // +0 + (+-0) = +0, so the value is the same, with no branch and no range check; k + 6 - j >= 0 always)
-          d = pk_cadd(d, pk_cmul(xv, w[j]));
+          for (int j = 0; j < 7; j++) {
+            const v2f xv = (i - j >= 0) ? xa[(i - j >= 0) ? i - j : 0] : win[(j - i - 1 < 6) ? j - i - 1 : 5];
+            const v2f term = pk_cadd(d, pk_cmul(xv, w[j]));
+            d = (!CHK || EQ_TK * u + i + 6 - j < Nff) ? term : d;
+          }
+          fft[u & 1][lane][i] = mk(d.x, d.y);
         }
-        fft[u & 1][lane][i] = mk(d.x, d.y);
-      }
+      };
+      if (!hostile || __all(EQ_TK * u + 15 + 6 < Nff)) ff_tile(std::false_type()); else ff_tile(std::true_type());
 #pragma unroll
       for (int m = 0; m < 6; m++) win[m] = xa[15 - m];
       DFE_SYNC();                                           // barrier u
@@ -1938,6 +1956,8 @@ __global__ __launch_bounds__(256, 4) void k_eq_dfe4(const TrxTables *__restrict_
 #pragma unroll
     for (int m = 0; m < 6; m++) win[m] = pk(mk(0, 0));
     const int kc = lane & (TK - 1), r0 = lane / TK;          // tile traffic: this lane moves column kc of rows r0 + (64 / TK) i
+    const int Nff = det ? N : 160;                          // the burst's end for the feed-forward terms (a burst that is not equalised has none)
+    const bool hostile = eq_taps_hostile(det, wf);          // (wave-uniform) some burst's taps are not finite: zero samples no longer stand for skipped terms
     auto write_out = [&](int u) {                           // soft tile u, lanes along k
 #pragma unroll
       for (int i = 0; i < TK; i++) {
@@ -1956,16 +1976,23 @@ __global__ __launch_bounds__(256, 4) void k_eq_dfe4(const TrxTables *__restrict_
 #pragma unroll
         for (int i = 0; i < TK; i++) xa[i] = pk(xt[((u % 3) + 3) % 3][lane][i]);
         if (u >= 0) {
+          // convolve general branch: sum += a[t-j]*b[j], t = k+6, the terms beyond the burst SKIPPED -- by the range check where a tap of
+          // the wave is not finite and some lane's burst ends in the tile, by the zero samples everywhere else (see k_eq_dfe2's producer)
+          auto ff_tile = [&](auto checked_) {
+            constexpr bool CHK = decltype(checked_)::value;
 #pragma unroll
-          for (int i = 0; i < TK; i++) {
-            v2f dsum = pk(mk(0, 0));
+            for (int i = 0; i < TK; i++) {
+              v2f dsum = pk(mk(0, 0));
 #pragma unroll
-            for (int j = 0; j < (TRX_D4_EXP == 2 ? 1 : 7); j++) {   // convolve general branch: sum += a[t-j]*b[j], t = k+6 (zero samples beyond the burst: see k_eq_dfe2)
-              const v2f xv = (i - j >= 0) ? xa[(i - j >= 0) ? i - j : 0] : win[(j - i - 1 < 6) ? j - i - 1 : 5];
-              dsum = pk_cadd(dsum, pk_cmul(xv, wf[j]));
+              for (int j = 0; j < (TRX_D4_EXP == 2 ? 1 : 7); j++) {
+                const v2f xv = (i - j >= 0) ? xa[(i - j >= 0) ? i - j : 0] : win[(j - i - 1 < 6) ? j - i - 1 : 5];
+                const v2f term = pk_cadd(dsum, pk_cmul(xv, wf[j]));
+                dsum = (!CHK || TK * u + i + 6 - j < Nff) ? term : dsum;
+              }
+              fft[u & 1][lane][i] = unpk(dsum);
             }
-            fft[u & 1][lane][i] = unpk(dsum);
-          }
+          };
+          if (!hostile || __all(TK * u + TK - 1 + 6 < Nff)) ff_tile(std::false_type()); else ff_tile(std::true_type());
         }
 #pragma unroll
         for (int m = 0; m < 6; m++) win[m] = xa[TK - 1 - m];  // delayed samples 8 u + 13 - m: the next tile's x[k + 6 - j], j > i

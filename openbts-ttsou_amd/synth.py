@@ -84,6 +84,9 @@ def _delay(x, d):
     return out
 
 
+fractional_delay = _delay                                  # public: the tests' families build their own channels
+
+
 def _finish(rng, base, B, sps, delay, sigma_choices):
     guard, length, off = burst_lengths(B, sps)
     amp = (rng.uniform(300, 3000, B) * np.exp(2j * np.pi * rng.uniform(size=B))).astype(np.complex64)

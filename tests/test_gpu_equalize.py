@@ -369,14 +369,18 @@ def test_equalize_taps_rejected_burst_is_not_equalised_from_stale_scratch(pkg, t
     assert np.array_equal(second[ok], first[ok])
 
 
-def test_delay_and_equalize_with_arbitrary_toa_lengths_and_taps(pkg, t1):
-    """k_eq_delay + k_eq_dfe2 through trxsig_equalize_taps_batch on inputs analyzeTrafficBurst would never produce: every
-    length from 92 to 157 at ragged odd offsets, TOAs on the 1/512 grid, off it (table sinc computed in the kernel), within
+@pytest.mark.parametrize("eq_tail", [1, 2], ids=["fused", "two-kernels"])
+def test_delay_and_equalize_with_arbitrary_toa_lengths_and_taps(pkg, t1, eq_tail, request):
+    """trxsig_equalize_taps_batch -- the fused k_eq_dfe4 (eq_tail 1, the default) and k_eq_delay + k_eq_dfe2 through the
+    scratch rows (eq_tail 2: trxsig_set_tuning(TRXSIG_TUNE_EQ_TAIL), library-wide, restored when the test ends) -- on
+    inputs analyzeTrafficBurst would never produce: every length from 92 to 157 at ragged odd offsets, TOAs on the 1/512 grid, off it (table sinc computed in the kernel), within
     1e-2 of an integer (delayVector's copy branch), integer shifts of tens and hundreds of samples in both directions (the
     burst leaves the staging row partly or wholly), random amplitudes and random feed-forward / feedback taps; float32 and
     fp16 storage.  Every soft bit value-exact against scaleVector + equalizeBurst of the oracle."""
     import ctypes as C
     import torch
+    t1.set_tuning(eq_tail=eq_tail)
+    request.addfinalizer(lambda: t1.set_tuning(eq_tail=1))
     rng = np.random.default_rng(2024)
     o = oraclebind.Oracle(1)
     B = 528

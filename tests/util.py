@@ -38,6 +38,32 @@ def assert_veq(a, b, what=""):
             what, bad.size, a.size, bad[0], a.ravel()[bad[0]], b.ravel()[bad[0]]))
 
 
+def _parts(a, b):
+    """Both as real arrays: complex values become their (re, im) parts, so that (NaN, 1) is not (NaN, 2)."""
+    a = np.asarray(a); b = np.asarray(b)
+    if np.iscomplexobj(a) or np.iscomplexobj(b):
+        a = np.ascontiguousarray(a, np.complex64).view(np.float32); b = np.ascontiguousarray(b, np.complex64).view(np.float32)
+    return a, b
+
+
+def veq_nan(a, b):
+    """The equality rule where NaNs are expected, as a mask: both values NaN, or IEEE ==.  A NaN's sign and payload are not
+    compared (the CPU oracle and the compiled reference already differ there); complex values part by part."""
+    a, b = _parts(a, b)
+    return (np.isnan(a) & np.isnan(b)) | (a == b)
+
+
+def assert_veq_nan(a, b, what=""):
+    """assert_veq where NaNs are expected: veq_nan everywhere."""
+    assert np.shape(a) == np.shape(b), (what, np.shape(a), np.shape(b))
+    same = veq_nan(a, b)
+    if not same.all():
+        a, b = _parts(a, b)
+        bad = np.flatnonzero(~same.ravel())
+        raise AssertionError("%s: %d of %d values differ (%d NaN against %d), first at %d: %r vs %r" % (
+            what, bad.size, same.size, np.isnan(a).sum(), np.isnan(b).sum(), bad[0], a.ravel()[bad[0]], b.ravel()[bad[0]]))
+
+
 class GpuBatch:
     """A packed batch of bursts resident on cuda:0 plus output buffers (torch is plumbing only)."""
 
