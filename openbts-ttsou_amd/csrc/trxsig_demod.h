@@ -1,7 +1,7 @@
 // trxsig_demod.h -- demodulateBurst on the device: geometry of the LDS staging area, the two FIR forms
 // (demod_core: a lane owns soft bits m, m+64, m+128; fused_demod: a lane owns consecutive soft bits whose
 // windows share staged words) and the k_demod kernel template (instantiated by trxsig_normal.hip for the
-// burst path and by trxsig_eq.hip for the equaliser's delayVector step).
+// burst path and by trxsig_eq_dfe.hip for the equaliser's delayVector step).
 // Numerical contract: see trxsig_dev.h / DESIGN.md (every float32 operation is the reference's, in the
 // reference's order; built with -ffp-contract=off).
 #pragma once

@@ -1,4 +1,4 @@
-"""An adversarial family for the equaliser (csrc/trxsig_eq.hip: k_eq_detect in its three instantiations, k_eq_detect52,
+"""An adversarial family for the equaliser (csrc/trxsig_eq_est.hip, trxsig_eq_dfe.hip: k_eq_detect in its two instantiations, k_eq_detect52,
 k_eq_estimate_wave, k_design_dfe, k_eq_delay + k_eq_dfe2 and the fused k_eq_dfe4) and the one oracle chain every equaliser
 test compares with.  No GPU, no torch, no native product library here; seeded, the same members everywhere.
 

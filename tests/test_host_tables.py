@@ -116,6 +116,13 @@ def test_product_library_carries_the_defaults_only(pkg):
         assert k in tune, k
     for k in (b"10k_tsc_corrIL", b"11k_tsc_peak2IL", b"7k_demodIL", b"12k_rach_frontIL", b"12k_rach_peak2IL", b"11k_rach_fastIL", b"10k_resampleIL"):
         assert k in prod, k
+    # the equaliser: the lane-per-burst tail, the ring-buffer fusion and the fixed-geometry instantiation of the lane-per-burst
+    # detector are gone from both libraries; the product carries the two tails and the three estimators
+    for k in (b"8k_eq_dfeEPK", b"9k_eq_dfe3I", b"11k_eq_detectILi9E"):
+        assert k not in prod, k
+        assert k not in tune, k
+    for k in (b"9k_eq_dfe2EPK", b"9k_eq_dfe4I", b"13k_eq_detect52I", b"18k_eq_estimate_waveI"):
+        assert k in prod, k
     assert pkg.lib().trxsig_tuning_build() == 0 and pkg.tune_lib().trxsig_tuning_build() == 1
     assert pkg.lib().trxsig_abi_version() == pkg.tune_lib().trxsig_abi_version()
 
