@@ -184,6 +184,55 @@ enum { TRXSIG_SOFT_EXACT = 0, TRXSIG_SOFT_TOLERANCE = 1 };
 int trxsig_set_soft_mode(trxsig_ctx *ctx, int mode);
 int trxsig_get_soft_mode(const trxsig_ctx *ctx);
 
+/* ---- the sequence equaliser for normal bursts (csrc/trxsig_mlse.hip) -------------------------------------------------------
+ * trxsig_mlse_batch: the mirror of trxsig_demodulate_batch for a channel with delay spread -- a per-burst channel estimate from
+ *   the midamble and a 16-state max-log-MAP equaliser that hands up soft bits, at sps 1, 2 and 4, in one launch.  The reference
+ *   has no counterpart (Transceiver/README.Talgorithm is a design note); the stage is pinned by the float32 model
+ *   tests/mlse_model.py, which the kernel equals word for word: float add, subtract, multiply, minimum, compare and one correctly
+ *   rounded division per soft bit, nothing fused, no tolerance.  trxsig_set_soft_mode has no bearing on it.
+ *   With a[n] = 2 bit[n] - 1 and t[j] = a[61 + j] the training sequence `tsc`:
+ *   1. Symbols.  y[0..147] = demodulateBurst's vector just before vectorSlicer, both parts kept: scaleVector(1/amp),
+ *      delayVector(-TOA), GMSKReverseRotate (the complex product with rev[sps m]), decimateVector(sps); exact-mode arithmetic.
+ *   2. Channel.  c[d] = 0.0625f * sum_{i=0..15} t[5+i] * y[66+i+d] for d = -4..4 (complex float32, the sum starts from 0, i
+ *      ascending); p[d] = c.re*c.re + c.im*c.im; E_w = (((p[w] + p[w+1]) + p[w+2]) + p[w+3]) + p[w+4]; w = 0, -1, .., -4 is
+ *      scanned in that order and a later w is taken only on a strict >; h[k] = c[w+k], k = 0..4, E = E_w.
+ *      The model of the burst: y[n] = sum_k h[k] a[n-w-k].
+ *   3. Two independent half-burst trellises of 16 states and 61 steps.  Bit j of a state s is the j-th most recent symbol
+ *      (1 = +1); a step with symbol b leads to ((s << 1) & 15) | b and has the 5-bit index x = (s << 1) | b, the expected value
+ *      Z[x] = ((((+-g[0]) + +-g[1]) + +-g[2]) + +-g[3]) + +-g[4] (sign of term k: bit k of x) and the branch metric
+ *      dr*dr + di*di, (dr, di) = y - Z[x].  Right half: g = h, steps m = 87..147 on y[m+w], start state a[86], a[85], a[84],
+ *      a[83] (bit 0 first), a[145..147] = -1 known.  Left half: g[k] = h[4-k], steps m = 60..0 on y[m+4+w], start state a[61],
+ *      a[62], a[63], a[64], a[0..2] = -1 known.  alpha is 0 in the start state and +inf elsewhere; a branch against a known
+ *      symbol costs +inf.  alpha'[s'] = min(alpha[s'>>1] + gamma, alpha[(s'>>1)|8] + gamma); beta = 0 after the last step,
+ *      beta[s] = min_b(gamma[(s<<1)|b] + beta'[((s<<1)|b) & 15]).  Per step T[s] = alpha[s] + beta[s], both after the step,
+ *      and M_b = the minimum of T over the eight states whose bit 0 is b.
+ *   4. soft[m] = clamp(0.5f + (M_0 - M_1) / (8.0f * E), 0, 1); hard = soft > 0.5F.  A known symbol comes out as exactly 0.
+ *      Positions 61..86 carry the demodulator's formula clamp((y.re + 1) * 0.5).  (On a one-tap channel (M_0 - M_1) / (8 E) is
+ *      Re(y / h) / 2: the demodulator's soft bit.)
+ *   5. A burst gets the demodulator's formula on all of y instead -- demodulateBurst's exact-mode soft bits -- when
+ *      length/sps < 148 (y[m] = 0, soft bit 0.5, for m >= length/sps, where demodulateBurst has no symbol), or some component of y[0..147] fails fabsf(v) < 0x1p30f (a NaN or an infinity among them; what passes
+ *      keeps every metric finite), or E == 0.  No NaN can then arise in steps 2-4, and there is no survivor path to break ties on.
+ *   d_enable[b] == 0 skips burst b; NULL = all.  A burst k_demod would refuse (offset < 0, a length outside 92..157 symbols or
+ *   no multiple of sps, |TOA| > 4096 or NaN) counts as skipped.
+ *   d_chan   B x 5 taps h[0..4]; zeros for a burst that fell back or was skipped          (may be NULL)
+ *   d_win    w (-4..0) where the burst was equalised, 1 where it fell back, 2 where it was skipped (soft bits zeros)  (may be NULL)
+ *   d_soft / d_hard / nsoft (<= 148) / soft_stride: as trxsig_demodulate_batch
+ * trxsig_mlse_normal_batch: trxsig_detect_demod_normal_batch's detector (flags, amp, TOA and avgPwr are that call's, in either
+ *   soft mode) and then the equaliser on the bursts it flagged TRXSIG_F_DETECT. */
+int trxsig_mlse_batch(trxsig_ctx *ctx,
+                      const trxsig_c32 *d_samples, const int32_t *d_offset,
+                      const int32_t *d_length, int B, int tsc,
+                      const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable,
+                      trxsig_c32 *d_chan, int32_t *d_win,
+                      float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+int trxsig_mlse_normal_batch(trxsig_ctx *ctx,
+                             const trxsig_c32 *d_samples, const int32_t *d_offset,
+                             const int32_t *d_length, int B,
+                             int tsc, float detect_thresh, float energy_thresh,
+                             uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa,
+                             float *d_avgpwr, trxsig_c32 *d_chan, int32_t *d_win,
+                             float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+
 /* ---- TX path: modulateBurst (sigProcLib.h:171-174) as called by Transceiver::addRadioVector
  *   (Transceiver.cpp:100-113): bits -> GMSK-rotated impulses -> pulse shaping, then scaleVector by
  *   a real gain.  d_bits: B x 148 bytes (only bit 0 is used, BitVector.cpp:54-63); d_guard[b] =

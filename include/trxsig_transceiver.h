@@ -45,8 +45,10 @@ int trxsig_trx_create(trxsig_trx **out, int device, int sps, int start_fn, int s
  * TRXSIG_TSCLEG_DEMOD: analyzeTrafficBurst + demodulateBurst and no channel cache, which is what
  * Transceiver52M/Transceiver.cpp:272, 322, 382 does while its mMaxExpectedDelay <= 1 ("needDFE" false); any sps.  The
  * sigProcLib calls are Transceiver/sigProcLib.cpp's in both (full-window analyzeTrafficBurst, energyDetect over 20*sps
- * consecutive samples) and so is the slot schedule (expectedCorrType :207-269). */
-enum { TRXSIG_TSCLEG_EQUALIZE = 0, TRXSIG_TSCLEG_DEMOD = 1 };
+ * consecutive samples) and so is the slot schedule (expectedCorrType :207-269).
+ * TRXSIG_TSCLEG_MLSE (the Transceiver group only; this one-burst object refuses it): the demodulating leg with
+ * trxsig_mlse_batch's sequence equaliser in demodulateBurst's place on the training-sequence rows; any sps. */
+enum { TRXSIG_TSCLEG_EQUALIZE = 0, TRXSIG_TSCLEG_DEMOD = 1, TRXSIG_TSCLEG_MLSE = 2 };
 int trxsig_trx_set_tsc_leg(trxsig_trx *t, int leg);
 void trxsig_trx_destroy(trxsig_trx *t);
 const char *trxsig_trx_last_error(const trxsig_trx *t);

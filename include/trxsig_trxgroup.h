@@ -41,7 +41,10 @@ typedef struct trxsig_trxgroup trxsig_trxgroup;
 
 /* n_arfcn Transceivers on `ctx` (which the group borrows: destroy the group first).  tsc_leg: TRXSIG_TSCLEG_EQUALIZE
  * (Transceiver/Transceiver.cpp as written; needs a context with sps == 1) or TRXSIG_TSCLEG_DEMOD (see
- * trxsig_trx_set_tsc_leg; any sps).  Every ARFCN starts as Transceiver::Transceiver leaves it (:58-92): all slots
+ * trxsig_trx_set_tsc_leg; any sps) or TRXSIG_TSCLEG_MLSE (any sps): the demodulating leg's state machine -- no channel cache,
+ * set_beside_rows / set_pipelined as there -- with the training-sequence rows' soft bits from trxsig_mlse_batch (a launch per TSC
+ * class in use, on the rows demodulateBurst would have taken); access bursts go through demodulateBurst as before, and
+ * trxsig_trxgroup_pull_rxfe takes the push / pop route.  Every ARFCN starts as Transceiver::Transceiver leaves it (:58-92): all slots
  * NONE, TSC 0, threshold 250.0, prevFalseDetectionTime = channelEstimateTime[] = (start_fn, start_tn). */
 int trxsig_trxgroup_create(trxsig_trxgroup **out, trxsig_ctx *ctx, int n_arfcn, int tsc_leg, int start_fn, int start_tn);
 void trxsig_trxgroup_destroy(trxsig_trxgroup *g);

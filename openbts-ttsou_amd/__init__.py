@@ -321,6 +321,26 @@ class TrxSig:
                                                  _ptr(toa), _ptr(enable), _ptr(soft), _ptr(hard), nsoft,
                                                  soft_stride), "trxsig_demodulate_batch")
 
+    def mlse(self, samples, offset, length, tsc, amp, toa, soft, enable=None, chan=None, win=None, hard=None, nsoft=148,
+             soft_stride=None):
+        """The sequence equaliser with the caller's amp / TOA (trxsig_mlse_batch): chan [B, 5] complex, win [B] int32."""
+        B = offset.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, tsc, _ptr(amp), _ptr(toa),
+                                           _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride),
+                  "trxsig_mlse_batch")
+
+    def mlse_normal(self, samples, offset, length, tsc, flags, amp, toa, soft, avgpwr=None, chan=None, win=None, hard=None,
+                    detect_thresh=3.0, energy_thresh=0.0, nsoft=148, soft_stride=None):
+        """detect_demod_normal's detector, then the sequence equaliser on the detected bursts (trxsig_mlse_normal_batch)."""
+        B = offset.numel() if hasattr(offset, "numel") else len(offset)
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_normal_batch(
+            self.h, _ptr(samples), _ptr(offset), _ptr(length), B, tsc, detect_thresh, energy_thresh, _ptr(flags), _ptr(amp),
+            _ptr(toa), _ptr(avgpwr), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_normal_batch")
+
     def equalize_normal(self, samples, offset, length, tsc, flags, amp, toa, soft, w=None, b=None, hard=None,
                         detect_thresh=3.0, energy_thresh=0.0, variant52m=True, max_toa=4, nsoft=148,
                         soft_stride=None, fp16=False):
@@ -705,7 +725,7 @@ class TrxHost(_Object):
         return out
 
 
-TSCLEG_EQUALIZE, TSCLEG_DEMOD = 0, 1
+TSCLEG_EQUALIZE, TSCLEG_DEMOD, TSCLEG_MLSE = 0, 1, 2
 
 
 class TrxGroup(_Object):

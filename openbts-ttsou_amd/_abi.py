@@ -127,6 +127,8 @@ SIGNATURES = {
     "trxsig_demodulate_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_set_soft_mode": (i32, [vp, i32]),
     "trxsig_get_soft_mode": (i32, [vp]),
+    "trxsig_mlse_batch": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
+    "trxsig_mlse_normal_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_modulate_batch": (i32, [vp, vp, vp, vp, i32, vp, vp]),
     "trxsig_estimate_dfe_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "trxsig_equalize_taps_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]),

@@ -702,6 +702,21 @@ int trx_ctx_demod_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32
                              (const trx_c32 *)d_amp, d_toa, d_enable, need_mask, d_soft, nullptr, nsoft, soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
 }
+int trx_ctx_mlse_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
+                        const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
+                        int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples, d_offset, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 || nsoft > 148 || soft_stride < nsoft ||
+      (B > 0 && (!d_amp || !d_toa || !d_soft)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  unsigned bits = 0;
+  for (int k = 0; k < 26; k++) bits |= (unsigned)(trx_training_sequence(tsc)[k] == '1') << k;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_mlse(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, bits, (const trx_c32 *)d_amp,
+                            d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+  return TRXSIG_OK;
+}
 extern "C" {
 
 int trxsig_detect_demod_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset,
@@ -744,6 +759,28 @@ int trxsig_demodulate_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const in
   TRX_HIPCHK(c, trx_launch_demod(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B,
                              (const trx_c32 *)d_amp, d_toa, d_enable, 0, d_soft, d_hard, nsoft, soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
+}
+
+// ---- the sequence equaliser (trxsig_mlse.hip) ----
+int trxsig_mlse_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
+                      const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win,
+                      float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  return trx_ctx_mlse_masked(c, d_samples, d_offset, d_length, B, tsc, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft,
+                             soft_stride);
+}
+
+int trxsig_mlse_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
+                             float detect_thresh, float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
+                             trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && !d_soft))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_normal_batch: bad argument");
+  // the exact detector alone (nsoft = 0: no demodulator, whatever the soft mode), then the equaliser on the bursts it flagged
+  const int rc = trxsig_detect_demod_normal_batch(c, d_samples, d_offset, d_length, B, tsc, detect_thresh, energy_thresh, d_flags, d_amp, d_toa,
+                                                  d_avgpwr, nullptr, nullptr, 0, 0);
+  if (rc != TRXSIG_OK) return rc;
+  return trx_ctx_mlse_masked(c, d_samples, d_offset, d_length, B, tsc, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard,
+                             nsoft, soft_stride);
 }
 
 // ---- equaliser path (sps = 1) ------------------------------------------------------------------------

@@ -112,6 +112,11 @@ hipError_t trx_launch_demod(hipStream_t st, int sps, const TrxTables *dT, const 
                             const float *toa, const uint8_t *flags, int need_mask, float *soft,
                             uint8_t *hard, int nsoft, int stride, TrxProfiler *prof, int soft_tolerance = 0);
 // (soft_tolerance: TRXSIG_SOFT_TOLERANCE -- the rearranged demodulator of trxsig_demod.h; hard bits exact, soft bits within 3.7e-5)
+// the sequence equaliser (trxsig_mlse.hip; trxsig_mlse_batch): flags / need_mask as trx_launch_demod; tsc_bits: bit j = bit j of the
+// training sequence; chan (B x 5) and win (B) may be NULL; nsoft <= 148.  No profiler id.
+hipError_t trx_launch_mlse(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len, int B,
+                           unsigned tsc_bits, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan,
+                           int32_t *win, float *soft, uint8_t *hard, int nsoft, int stride);
 
 hipError_t trx_launch_modulate(hipStream_t st, int sps, const TrxTables *dT, const uint8_t *bits, const int32_t *guard,
                                const float *gain, int B, trx_c32 *out, const int32_t *out_off, TrxProfiler *prof);

@@ -193,7 +193,7 @@ int trxsig_trxgroup_create(trxsig_trxgroup **out, trxsig_ctx *c, int n_arfcn, in
   if (!out) return TRXSIG_EINVAL;
   *out = nullptr;
   if (!c) return TRXSIG_EINVAL;
-  if (n_arfcn <= 0 || n_arfcn > 65535 || (tsc_leg != TRXSIG_TSCLEG_EQUALIZE && tsc_leg != TRXSIG_TSCLEG_DEMOD) || start_fn < 0 ||
+  if (n_arfcn <= 0 || n_arfcn > 65535 || (tsc_leg != TRXSIG_TSCLEG_EQUALIZE && tsc_leg != TRXSIG_TSCLEG_DEMOD && tsc_leg != TRXSIG_TSCLEG_MLSE) || start_fn < 0 ||
       start_fn >= kHyperframe || start_tn < 0 || start_tn > 7)
     return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_create: bad argument", hipSuccess);
   if (tsc_leg == TRXSIG_TSCLEG_EQUALIZE && trxsig_sps(c) != 1)
@@ -493,6 +493,13 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
       TRX_HIPCHK(g->c, trx_launch_group_toa_eq(st, n_tsc, W.gate.p, W.toa.p, W.tap_ix.p, g->chan_off.p, W.toa_eq.p));
       G_LIB(trx_ctx_group_equalize(c, d_samples, W.off.p, W.len.p, n_tsc, (const trxsig_c32 *)W.amp.p, W.toa_eq.p, W.gate.p,
                                    (const trxsig_c32 *)g->w_tab.p, (const trxsig_c32 *)g->b_tab.p, W.tap_ix.p, W.soft.p, kSoft, kSoft));
+    } else if (g->leg == TRXSIG_TSCLEG_MLSE) {              // (never with src.gen: trxsig_trxgroup_pull_rxfe sends this leg through push / pop)
+      for (int k = 0; k < TRXG_CLASS_RACH; k++) {           // the sequence equaliser needs the class's training sequence: a launch per class
+        if (!count[k]) continue;
+        const int b0 = base[k];
+        G_LIB(trx_ctx_mlse_masked(c, d_samples, W.off.p + b0, W.len.p + b0, count[k], k, (const trxsig_c32 *)W.amp.p + b0, W.toa.p + b0,
+                                  demod_gate + b0, TRXSIG_F_DETECT, nullptr, nullptr, W.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
+      }
     } else if (!src.gen) {
       G_LIB(trx_ctx_demod_masked(c, d_samples, W.off.p, W.len.p, n_tsc, (const trxsig_c32 *)W.amp.p, W.toa.p, demod_gate, TRXSIG_F_DETECT,
                                  W.soft.p, kSoft, kSoft));
@@ -662,8 +669,8 @@ int trxsig_trxgroup_pull_host(trxsig_trxgroup *g, const trxsig_c32 *h_samples, i
 
 int trxsig_trxgroup_set_pipelined(trxsig_trxgroup *g, int on) {
   if (!g) return TRXSIG_EINVAL;
-  if (g->leg != TRXSIG_TSCLEG_DEMOD && on)
-    return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_set_pipelined: the demodulating TSC leg only (the equalising leg needs the machine's events inside the call)", hipSuccess);
+  if (g->leg == TRXSIG_TSCLEG_EQUALIZE && on)
+    return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_set_pipelined: the demodulating TSC legs only (the equalising leg needs the machine's events inside the call)", hipSuccess);
   TrxDeviceGuard gd(trxsig_device(g->c));
   G_LIB(join_side(g, (hipStream_t)trxsig_get_stream(g->c)));
   g->pipelined = on != 0;

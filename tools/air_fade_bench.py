@@ -5,12 +5,13 @@ tools/hbm_bench.hip reports on the same box (--hbm-bench: the compiled binary, r
 figure measured elsewhere).  Medians of repeated HIP-event windows, the taps going to a rotation of arrays larger than the
 Infinity Cache together.  Last, not timed: the uplink loop l1ms -> radiate -> [l1hop] -> fade + cells -> [l1hop back] ->
 trxsig_trxgroup_pull -> trxsig_l1rx_decode of tools/air_bench.py under a slow, frequency-selective profile at one noise level,
-once without and once with trxsig_l1hop, and how many XCCH blocks the stream decoder erases in each.  Side measurements: no
+once without and once with trxsig_l1hop, and how many XCCH blocks the stream decoder erases in each (--leg mlse: with the
+sequence equaliser on the group's TSC leg instead of demodulateBurst).  Side measurements: no
 threshold anywhere.  The profiles are tests/air_fade_model.py's (written from memory: inputs, not contract).  Results go to
 profiles/air_fade_bench.json (or --out) and to stdout.
 
     hipcc --offload-arch=gfx950 -O3 tools/hbm_bench.hip -o hbm_bench
-    python tools/air_fade_bench.py --hbm-bench ./hbm_bench [--arfcns 128] [--frames 104] [--reps 30] [--out profiles/air_fade_bench.json]"""
+    python tools/air_fade_bench.py --hbm-bench ./hbm_bench [--arfcns 128] [--frames 104] [--reps 30] [--leg demod|mlse] [--out profiles/air_fade_bench.json]"""
 import argparse
 import json
 import os
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--loop-taps", type=int, default=12)
     ap.add_argument("--doppler-hz", type=float, default=2.0, help="the loop's maximum Doppler shift")
     ap.add_argument("--snr-db", type=float, default=15.0, help="the loop's mean SNR")
+    ap.add_argument("--leg", choices=("demod", "mlse"), default="demod",
+                    help="the loop's TSC leg: demodulateBurst, or the sequence equaliser (TRXSIG_TSCLEG_MLSE)")
     ap.add_argument("--hbm-bench", default=None, help="compiled tools/hbm_bench.hip, run before anything else")
     ap.add_argument("--hbm-tbps", type=float, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "air_fade_bench.json"))
@@ -139,7 +142,7 @@ def main():
         else:
             air.fade(fn, A, F, 11, n_links, dop, ltaps)
             air.cells(fn, A, F, 100, clean, A * cell, cell, back, A * cell, cell, taps=ltaps, sigma=sg)
-        grp = m.TrxGroup(ctx, A, tsc_leg=m.TSCLEG_DEMOD, start=(fn, 0))
+        grp = m.TrxGroup(ctx, A, tsc_leg=m.TSCLEG_MLSE if a.leg == "mlse" else m.TSCLEG_DEMOD, start=(fn, 0))
         for ar in range(A):
             for cmd in ["CMD RXTUNE 890000", "CMD TXTUNE 935000", "CMD SETTSC %d" % (bsic & 7)] + \
                        ["CMD SETSLOT %d %d" % (tn, comb[ar, tn]) for tn in range(8)] + ["CMD POWERON"]:
@@ -152,11 +155,11 @@ def main():
         done = (xs & m.FEC_DECODED) != 0
         fer["with_l1hop" if hop else "without_l1hop"] = dict(xcch_blocks=int(done.sum()), xcch_erased=int((done & ((xs & m.FEC_TCH_GOOD) == 0)).sum()))
         rx.destroy(); grp.close()
-    out["uplink_loop"] = dict(profile=a.profile, doppler_hz=a.doppler_hz, snr_db=a.snr_db, n_taps=Lh, erasures=fer)
+    out["uplink_loop"] = dict(profile=a.profile, doppler_hz=a.doppler_hz, snr_db=a.snr_db, n_taps=Lh, leg=a.leg, erasures=fer)
     out["note"] = ("fade_bytes_at_hbm_rate_us: the taps written plus the Doppler words and the profile read, over hbm_read_tbps; "
                    "cells_with_those_taps_us: trxsig_air_cells, every stage on, out of place, reading the generated taps; the loop: "
-                   "one link per (ARFCN, TN), SNR = mean |h|^2 amplitude^2 / (2 sigma^2), the demodulating TSC leg (no equaliser at "
-                   "sps 4), the same encoded frames and the same links without and with hopping (groups of 64 rows per TN)")
+                   "one link per (ARFCN, TN), SNR = mean |h|^2 amplitude^2 / (2 sigma^2), the TSC leg of --leg (demod: demodulateBurst, "
+                   "no equaliser; mlse: trxsig_mlse_batch's sequence equaliser), the same encoded frames and the same links without and with hopping (groups of 64 rows per TN)")
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
