@@ -190,6 +190,11 @@ int trxsig_get_soft_mode(const trxsig_ctx *ctx);
  *   has no counterpart (Transceiver/README.Talgorithm is a design note); the stage is pinned by the float32 model
  *   tests/mlse_model.py, which the kernel equals word for word: float add, subtract, multiply, minimum, compare and one correctly
  *   rounded division per soft bit, nothing fused, no tolerance.  trxsig_set_soft_mode has no bearing on it.
+ *   The model, and the kernel directly, are in turn graded against tests/mlse_ref.py: step 3 below as a statement about symbol
+ *   sequences in float64 (exact min-marginals of a chain, proved against enumeration), with the a-priori bound
+ *   |soft - clamp(soft64)| <= 1.001 ((2 Q + 124 P) / (8 E) + 5) 2^-24 per burst and half -- P the sum over the 61 steps of the
+ *   step's largest finite branch metric, Q the same sum of the metrics' own rounding terms, 8 to 11 P; 2.4e-4 to 7.0e-4 on the
+ *   tests' bursts -- exact clamps beyond it and equal hard bits outside it (tests/test_mlse_ref.py, tests/test_gpu_mlse_ref.py).
  *   With a[n] = 2 bit[n] - 1 and t[j] = a[61 + j] the training sequence `tsc`:
  *   1. Symbols.  y[0..147] = demodulateBurst's vector just before vectorSlicer, both parts kept: scaleVector(1/amp),
  *      delayVector(-TOA), GMSKReverseRotate (the complex product with rev[sps m]), decimateVector(sps); exact-mode arithmetic.

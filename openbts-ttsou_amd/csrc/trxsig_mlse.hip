@@ -4,6 +4,10 @@
 // tests/mlse_model.py, which this kernel equals word for word.  The arithmetic is float add, subtract, multiply, minimum,
 // compare and one correctly rounded division per soft bit; nothing is fused (-ffp-contract=off), nothing is transcendental.
 // The algorithm is stated in include/trxsig.h (trxsig_mlse_batch) and again, operation by operation, in the model.
+// The model, and this kernel directly (tests/test_gpu_mlse_ref.py), are graded against a float64 statement of the same soft bits
+// as minima over symbol sequences, tests/mlse_ref.py: |soft - clamp(soft64)| <= 1.001 ((2 Q + 124 P) / (8 E) + 5) 2^-24 per burst
+// and half (P, Q: sums over the steps of the largest branch metric and of its rounding terms; derived there), exact clamps
+// beyond that bound and equal hard bits outside it.
 //
 // Layout.  One wave takes TWO bursts.
 //   * Symbols: the whole wave computes one burst at a time with k_demod's own code (demod_core, RAW form: scaleVector(1/amp),
