@@ -238,6 +238,56 @@ int trxsig_mlse_normal_batch(trxsig_ctx *ctx,
                              float *d_avgpwr, trxsig_c32 *d_chan, int32_t *d_win,
                              float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 
+/* ---- two-antenna receive diversity for the sequence equaliser (csrc/trxsig_mlse_div.hip) ------------------------------------
+ * trxsig_mlse_div_batch: trxsig_mlse_batch on two receive antennas -- one channel window for both, the branch metric summed over
+ *   both: maximal-ratio combining inside the trellis.  Both branches are assumed to have the same noise power (a common scale
+ *   1/amp keeps their noise on one footing; that is what makes the plain sum maximal-ratio).  Pinned by the float32 model
+ *   tests/mlse_div_model.py, which the kernel equals word for word, and graded against the float64 statement
+ *   tests/mlse_div_ref.py with the a-priori bound |soft - clamp(soft64)| <= 1.001 ((2 Q + 124 P) / (8 E) + 6) 2^-24 (P, Q: the sums
+ *   of trxsig_mlse_batch's bound over the summed metric, E = sum_a sum_k |h_a[k]|^2; derived there).
+ *   It is trxsig_mlse_batch's algorithm with these changes and no others; a = 0, 1 is the antenna:
+ *   1. Symbols.  y_a[0..147] = step 1 there on antenna a's samples (d_samples<a>, d_offset<a>; the length is shared), both with the
+ *      SAME amplitude and TOA: one d_amp[b], one d_toa[b] per burst.
+ *   2. Channel.  c_a[d] per antenna as there; p[d] = (c_0.re*c_0.re + c_0.im*c_0.im) + (c_1.re*c_1.re + c_1.im*c_1.im) (antenna
+ *      0's power first, one float32 addition); E_w, the scan order and the strict > as there, on this p: ONE window w for both
+ *      antennas; h_a[k] = c_a[w+k], E = E_w.
+ *   3. Trellis.  Z_a[x] per antenna from g_a (h_a for the right half, h_a reversed for the left); the branch metric is
+ *      gamma = (dr_0*dr_0 + di_0*di_0) + (dr_1*dr_1 + di_1*di_1), (dr_a, di_a) = y_a - Z_a[x]: each parenthesis the metric there,
+ *      joined by one float32 addition.  Start states, known tail symbols as +inf, alpha, beta, T, M_b: word for word as there.
+ *   4. soft[m] = clamp(0.5f + (M_0 - M_1) / (8.0f * E), 0, 1).  Positions 61..86 carry the demodulator's formula on y_p.re,
+ *      p = d_primary[b] the antenna that amp and TOA came from (0 or 1; NULL = 0 for every burst).
+ *   5. Fallback: the demodulator's formula on all of y_p when length/sps < 148, or a component of y_0 or y_1 fails
+ *      fabsf(v) < 0x1p30f, or E == 0.  The skip rule (d_enable, k_demod's geometry test) is as there and is applied once: the
+ *      antennas share the length and the TOA, and a negative offset on either antenna skips the burst.
+ *   Three identities hold exactly in IEEE arithmetic.  Antenna 1 all zeros: soft bits, hard bits and the window equal
+ *   trxsig_mlse_batch's on antenna 0, chan[b][0] its taps, chan[b][1] zeros.  The same samples on both antennas: p, gamma, E and
+ *   M_0 - M_1 all double exactly; soft bits, hard bits and the window equal trxsig_mlse_batch's.  Antennas swapped (d_primary
+ *   too): soft bits and the window are identical, chan[b][0] and chan[b][1] exchanged.
+ *   d_chan   B x 2 x 5 taps h_a[0..4]; zeros for a burst that fell back or was skipped     (may be NULL)
+ *   d_win    as trxsig_mlse_batch                                                            (may be NULL)
+ * trxsig_mlse_div_normal_batch: trxsig_detect_demod_normal_batch's detector on each antenna (d_flags, d_amp, d_toa, d_avgpwr:
+ *   2 x B, antenna a at [a * B + b]; that call's values bit for bit, in either soft mode), the selection, and the equaliser on the
+ *   bursts with d_sel[b] < 2 with the selected antenna's amp and TOA and d_primary = d_sel.
+ *   The selection rule: v_a = antenna a detected (TRXSIG_F_DETECT); n_a = amp_a.re*amp_a.re + amp_a.im*amp_a.im in float32, not
+ *   fused; sel = 1 if v_1 && (!v_0 || n_1 > n_0) (a NaN compares false); otherwise sel = 0 if v_0; otherwise sel = 2: neither
+ *   antenna detected, the soft bits are zeros and d_win is 2.
+ *   Refusals are trxsig_mlse_batch's: TRXSIG_EINVAL for a NULL context, nsoft > 148, tsc outside 0..7, NULL required arrays. */
+int trxsig_mlse_div_batch(trxsig_ctx *ctx,
+                          const trxsig_c32 *d_samples0, const int32_t *d_offset0,
+                          const trxsig_c32 *d_samples1, const int32_t *d_offset1,
+                          const int32_t *d_length, int B, int tsc,
+                          const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_primary, const uint8_t *d_enable,
+                          trxsig_c32 *d_chan, int32_t *d_win,
+                          float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+int trxsig_mlse_div_normal_batch(trxsig_ctx *ctx,
+                                 const trxsig_c32 *d_samples0, const int32_t *d_offset0,
+                                 const trxsig_c32 *d_samples1, const int32_t *d_offset1,
+                                 const int32_t *d_length, int B, int tsc,
+                                 float detect_thresh, float energy_thresh,
+                                 uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
+                                 uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win,
+                                 float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+
 /* ---- TX path: modulateBurst (sigProcLib.h:171-174) as called by Transceiver::addRadioVector
  *   (Transceiver.cpp:100-113): bits -> GMSK-rotated impulses -> pulse shaping, then scaleVector by
  *   a real gain.  d_bits: B x 148 bytes (only bit 0 is used, BitVector.cpp:54-63); d_guard[b] =

@@ -100,6 +100,33 @@ int trxsig_trxgroup_pull_rxfe(trxsig_trxgroup *g, trxsig_rxfe *fe, const int16_t
 int trxsig_trxgroup_pull_bursts(trxsig_trxgroup *g, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length,
                                 int n_per_arfcn, int fn, int tn, trxsig_trxgroup_result *res);
 
+/* Two-antenna receive diversity: ONE combined result from two groups' pulls (trxsig_mlse_div_batch, trxsig.h, on the
+ * training-sequence rows).  g0 and g1 are two ordinary groups on one context with the same configuration (ARFCN count, slot types,
+ * training sequences); each has pulled ITS antenna's samples -- d_samples0 / d_samples1, the pointers the pulls were given -- with
+ * trxsig_trxgroup_pull or trxsig_trxgroup_pull_bursts for the same (fn, tn) and the same slots (a group remembers its last pull's
+ * time for this check).  Each group keeps its own reference-exact state machine and thresholds; nothing in the groups' own paths
+ * changes, and the call changes no state of either group other than the buffers of the combined result: they live in g0,
+ * valid until g0's next pull or combine.  Stream-ordered on the context's stream; it waits for both groups' side streams the way
+ * a following pull would (with listed bursts it also copies the two length arrays down to compare them: the one place it
+ * synchronises).  The combined result:
+ *   d_row, d_threshold   g0's
+ *   d_valid[r]           TRXSIG_F_DETECT where either group's d_valid[r] is set
+ *   d_sel[r]             trxsig_mlse_div_normal_batch's selection rule with v_a = group a's d_valid[r]: 1 if v_1 && (!v_0 || n_1 > n_0),
+ *                        n_a = amp_a.re*amp_a.re + amp_a.im*amp_a.im (float32, not fused; a NaN compares false); else 0 if v_0; else 2
+ *   d_flags, d_amp, d_toa, d_avgpwr   the selected group's (g0's where neither group is valid)
+ *   d_soft   a valid training-sequence row: k_mlse_div on both antennas in the order (0, 1) with the selected amp and TOA and
+ *            d_primary = d_sel, one launch per TSC class in use; a valid access-burst row: the selected group's soft row, copied
+ *            (selection only); a row that is not valid: zeros
+ *   d_sel [n_rows], d_chan [n_rows][2][5], d_win [n_rows] (each may be NULL): as trxsig_mlse_div_batch; access-burst rows have
+ *            zero taps and window word 2.
+ * trxsig_l1hop_result, trxsig_l1ciph_soft and trxsig_l1rx_decode take the combined result as they take any result.
+ * Refused (TRXSIG_EINVAL): groups on different contexts; different ARFCN counts; different n_rows, n_tsc_rows, class bases or
+ * per-row lengths; different times or slot counts of the last pulls; a group that has had no pull, or whose last pull came through
+ * trxsig_trxgroup_pull_rxfe's fused source; a group on TRXSIG_TSCLEG_EQUALIZE.  Either of the other two legs is accepted -- the
+ * branches' own training-sequence soft bits are not used -- and TRXSIG_TSCLEG_DEMOD is the cheaper choice. */
+int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
+                                uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win, trxsig_trxgroup_result *res);
+
 /* What the caller of pullRadioVector sees, on the host, for the last pull (synchronises the stream): entry t*n_arfcn + a
  *   h_valid   1 where a SoftVector came back
  *   h_soft    [n_slots*n_arfcn][148] its soft bits (untouched where h_valid is 0); may be NULL

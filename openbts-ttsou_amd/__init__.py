@@ -341,6 +341,29 @@ class TrxSig:
             self.h, _ptr(samples), _ptr(offset), _ptr(length), B, tsc, detect_thresh, energy_thresh, _ptr(flags), _ptr(amp),
             _ptr(toa), _ptr(avgpwr), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_normal_batch")
 
+    def mlse_div(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, chan=None,
+                 win=None, hard=None, nsoft=148, soft_stride=None):
+        """The sequence equaliser over two receive antennas with the caller's amp / TOA (trxsig_mlse_div_batch): one amp / TOA per
+        burst, primary [B] uint8 the antenna they came from, chan [B, 2, 5] complex, win [B] int32."""
+        B = offset0.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_div_batch(
+            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, _ptr(amp), _ptr(toa),
+            _ptr(primary), _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_div_batch")
+
+    def mlse_div_normal(self, samples0, offset0, samples1, offset1, length, tsc, flags, amp, toa, sel, soft, avgpwr=None, chan=None,
+                        win=None, hard=None, detect_thresh=3.0, energy_thresh=0.0, nsoft=148, soft_stride=None):
+        """detect_demod_normal's detector on each antenna (flags, amp, toa, avgpwr: [2, B]), the selection (sel [B] uint8) and the
+        two-antenna sequence equaliser on the bursts either antenna detected (trxsig_mlse_div_normal_batch)."""
+        B = offset0.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_div_normal_batch(
+            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, detect_thresh, energy_thresh,
+            _ptr(flags), _ptr(amp), _ptr(toa), _ptr(avgpwr), _ptr(sel), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft,
+            soft_stride), "trxsig_mlse_div_normal_batch")
+
     def equalize_normal(self, samples, offset, length, tsc, flags, amp, toa, soft, w=None, b=None, hard=None,
                         detect_thresh=3.0, energy_thresh=0.0, variant52m=True, max_toa=4, nsoft=148,
                         soft_stride=None, fp16=False):
@@ -762,6 +785,16 @@ class TrxGroup(_Object):
         res = TrxGroupResult()
         self._call("pull_bursts", _ptr(samples), _ptr(offset), _ptr(length), n_per_arfcn, fn, tn, C.byref(res))
         self.n_slots = n_per_arfcn
+        return res
+
+    def combine_div(self, samples0, other, samples1, sel=None, chan=None, win=None):
+        """Two-antenna receive diversity (trxsig_trxgroup_combine_div): this group has pulled antenna 0's samples0, `other` (a group of
+        the same configuration on the same context) antenna 1's samples1, for the same time and slots.  Returns one combined result
+        like pull's, owned by this group: the selected group's flags / amp / TOA / avgPwr, the training-sequence rows' soft bits from
+        the two-antenna sequence equaliser.  sel [n_rows] uint8, chan [n_rows, 2, 5] complex, win [n_rows] int32: optional outputs."""
+        res = TrxGroupResult()
+        self._call("combine_div", _ptr(samples0), other.h if other is not None else None, _ptr(samples1), _ptr(sel), _ptr(chan), _ptr(win),
+                   C.byref(res))
         return res
 
     def pull_rxfe(self, fe, iq, fn):

@@ -73,6 +73,7 @@ struct trxsig_ctx {
   // equaliser scratch: toa_eq [B], w [B*7], b [B*5], xd [B*160]
   int eq_cap = 0;
   char *d_eq = nullptr;
+  TrxWork div;                       // trxsig_mlse_div_normal_batch: the selected amp [B], TOA [B] and enable byte [B]
   // staging for the *_host wrappers
   size_t stage_bytes = 0;
   void *d_stage = nullptr;
@@ -471,6 +472,7 @@ static void destroy_now(trxsig_ctx *c) {
     if (c->d_rec2) (void)hipFree(c->d_rec2);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->d_eq) (void)hipFree(c->d_eq);
+    if (c->div.p) (void)hipFree(c->div.p);
     if (c->d_det) (void)hipFree(c->d_det);
     if (c->h_chain_status) (void)hipHostFree(c->h_chain_status);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -717,6 +719,24 @@ int trx_ctx_mlse_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_
                             d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
   return TRXSIG_OK;
 }
+// trxsig_mlse_div_batch with the enable test spelt out (trxsig_trxgroup_combine_div: a launch per TSC class)
+int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
+                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan, int32_t *d_win,
+                            float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples0, d_offset0, d_length, B) || bad_batch(d_samples1, d_offset1, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 ||
+      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_div_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  unsigned bits = 0;
+  for (int k = 0; k < 26; k++) bits |= (unsigned)(trx_training_sequence(tsc)[k] == '1') << k;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_mlse_div(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples0, d_offset0, (const trx_c32 *)d_samples1,
+                                d_offset1, d_length, B, bits, (const trx_c32 *)d_amp, d_toa, d_primary, d_enable, need_mask,
+                                (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+  return TRXSIG_OK;
+}
 extern "C" {
 
 int trxsig_detect_demod_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset,
@@ -781,6 +801,48 @@ int trxsig_mlse_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const i
   if (rc != TRXSIG_OK) return rc;
   return trx_ctx_mlse_masked(c, d_samples, d_offset, d_length, B, tsc, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard,
                              nsoft, soft_stride);
+}
+
+// ---- two-antenna receive diversity for the sequence equaliser (trxsig_mlse_div.hip) ----
+int trxsig_mlse_div_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                          const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
+                          const uint8_t *d_primary, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft,
+                          uint8_t *d_hard, int nsoft, int soft_stride) {
+  return trx_ctx_mlse_div_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, d_amp, d_toa, d_primary, d_enable, 0,
+                                 d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+}
+
+int trxsig_mlse_div_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                                 const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, float detect_thresh,
+                                 float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr, uint8_t *d_sel,
+                                 trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples0, d_offset0, d_length, B) || bad_batch(d_samples1, d_offset1, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 ||
+      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_flags || !d_amp || !d_toa || !d_sel || !d_soft)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_div_normal_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  // the exact detector alone on each antenna (nsoft = 0: no demodulator, whatever the soft mode), the selection, then the
+  // equaliser on the bursts some antenna detected, with the selected antenna's amp and TOA
+  for (int a = 0; a < 2; a++) {
+    const int rc = trxsig_detect_demod_normal_batch(c, a ? d_samples1 : d_samples0, a ? d_offset1 : d_offset0, d_length, B, tsc, detect_thresh,
+                                                    energy_thresh, d_flags + (size_t)a * B, d_amp + (size_t)a * B, d_toa + (size_t)a * B,
+                                                    d_avgpwr ? d_avgpwr + (size_t)a * B : nullptr, nullptr, nullptr, 0, 0);
+    if (rc != TRXSIG_OK) return rc;
+  }
+  TrxDeviceGuard g(c->device);
+  const size_t o_toa = trx_align256(8 * (size_t)B), o_en = o_toa + trx_align256(4 * (size_t)B);
+  const int rc = trx_work_ensure(c, c->div, o_en + trx_align256((size_t)B), false, "trxsig_mlse_div_normal_batch: device allocation");
+  if (rc != TRXSIG_OK) return rc;
+  trx_c32 *amp_sel = (trx_c32 *)c->div.p;
+  float *toa_sel = (float *)((char *)c->div.p + o_toa);
+  uint8_t *en = (uint8_t *)c->div.p + o_en;
+  TrxDivSelect ds;
+  ds.valid0 = d_flags; ds.valid1 = d_flags + B; ds.amp0 = (const trx_c32 *)d_amp; ds.amp1 = (const trx_c32 *)d_amp + B;
+  ds.toa0 = d_toa; ds.toa1 = d_toa + B; ds.B = B; ds.need_mask = TRXSIG_F_DETECT;
+  ds.sel = d_sel; ds.amp = amp_sel; ds.toa = toa_sel; ds.valid = en;
+  TRX_HIPCHK(c, trx_launch_div_select(c->stream, ds));
+  return trx_ctx_mlse_div_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, (const trxsig_c32 *)amp_sel, toa_sel, d_sel,
+                                 en, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
 }
 
 // ---- equaliser path (sps = 1) ------------------------------------------------------------------------

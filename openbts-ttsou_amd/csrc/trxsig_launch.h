@@ -117,6 +117,29 @@ hipError_t trx_launch_demod(hipStream_t st, int sps, const TrxTables *dT, const 
 hipError_t trx_launch_mlse(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len, int B,
                            unsigned tsc_bits, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan,
                            int32_t *win, float *soft, uint8_t *hard, int nsoft, int stride);
+// the same over two antennas (trxsig_mlse_div.hip; trxsig_mlse_div_batch): a sample pointer and an offset array per antenna, one
+// amp / TOA per burst, primary (may be NULL = 0) the antenna they came from; chan is B x 2 x 5.  No profiler id.
+hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
+                               const trx_c32 *samples1, const int32_t *off1, const int32_t *len, int B, unsigned tsc_bits, const trx_c32 *amp,
+                               const float *toa, const uint8_t *primary, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
+                               float *soft, uint8_t *hard, int nsoft, int stride);
+// the selection rule of trxsig_mlse_div_normal_batch, v_a = (valid_a[b] & need_mask) != 0: sel (0, 1, 2 = neither); the selected
+// antenna's amp, TOA, flags byte and avgPwr (antenna 0's where neither); valid[b] = need_mask where sel < 2 else 0.  Every output,
+// and with flags / pwr their inputs, may be NULL.
+struct TrxDivSelect {
+  const uint8_t *valid0 = nullptr, *valid1 = nullptr, *flags0 = nullptr, *flags1 = nullptr;
+  const trx_c32 *amp0 = nullptr, *amp1 = nullptr;
+  const float *toa0 = nullptr, *toa1 = nullptr, *pwr0 = nullptr, *pwr1 = nullptr;
+  int B = 0, need_mask = 0;
+  uint8_t *sel = nullptr, *valid = nullptr, *flags = nullptr;
+  trx_c32 *amp = nullptr;
+  float *toa = nullptr, *pwr = nullptr;
+};
+hipError_t trx_launch_div_select(hipStream_t st, const TrxDivSelect &p);
+// trxsig_trxgroup_combine_div's access-burst rows: soft row r = the selected group's (sel[r] == 1: soft1) where valid[r], else zeros;
+// chan (rows x 2 x 5, may be NULL) zeros, win (may be NULL) 2
+hipError_t trx_launch_div_copy_rows(hipStream_t st, int rows, const uint8_t *valid, const uint8_t *sel, const float *soft0, const float *soft1,
+                                    int stride_in, float *soft, int stride, int nsoft, trx_c32 *chan, int32_t *win);
 
 hipError_t trx_launch_modulate(hipStream_t st, int sps, const TrxTables *dT, const uint8_t *bits, const int32_t *guard,
                                const float *gain, int B, trx_c32 *out, const int32_t *out_off, TrxProfiler *prof);

@@ -21,36 +21,9 @@
 //     = 40 bursts in flight per CU, where 2 x 2 x 3.9 KB of metrics in LDS would leave 7.  Listing (gfx950, sps 4): 82 VGPRs,
 //     90 SGPRs, no scratch, 29,824 B of LDS per workgroup: five waves per SIMD either way (DESIGN.md says what it took).
 //   * The difference M_0 - M_1 of step i is kept by lane i % 16 (four registers); the divisions and the stores come after the loop.
-#include "trxsig_demod.h"
+#include "trxsig_mlse_dev.h"                               // bperm, sgn, mlse_expected, mlse_gamma, mlse_slice: shared with k_mlse_div
 
 namespace {
-
-#define TRX_MLSE_WAVES 4                                    /* waves per workgroup: eight bursts */
-#define TRX_MLSE_NY 152                                     /* symbols kept per burst (148, padded to a multiple of 8) */
-#define TRX_MLSE_INF __builtin_inff()
-
-__device__ __forceinline__ float bperm(int byte_addr, float v) {
-  return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
-}
-__device__ __forceinline__ float sgn(float v, int plus) { return plus ? v : -v; }
-// Z[x] = sum_k g[k] * (+-1): starts from g[0] * (+-1), adds k = 1..4 in order; the sign is bit k of x (the flips are exact)
-__device__ __forceinline__ cx mlse_expected(const cx (&g)[5], int x) {
-  cx z = mk(sgn(g[0].r, x & 1), sgn(g[0].i, x & 1));
-#pragma unroll
-  for (int k = 1; k < 5; k++) z = cadd(z, mk(sgn(g[k].r, (x >> k) & 1), sgn(g[k].i, (x >> k) & 1)));
-  return z;
-}
-__device__ __forceinline__ float mlse_gamma(cx y, cx z) {
-  const float dr = y.r - z.r, di = y.i - z.i;
-  return dr * dr + di * di;
-}
-// the demodulator's slicer on a symbol (vectorSlicer, sigProcLib.cpp:513-515; see demod_core)
-__device__ __forceinline__ float mlse_slice(float re) {
-  float sv = (re + 1.0F) * 0.5F;
-  if (sv > 1.0f) sv = 1.0f;
-  if (sv < 0.0f) sv = 0.0f;
-  return sv;
-}
 
 // (amdgpu_waves_per_eu(4): a ceiling of 128 VGPRs for the register allocator -- occupancy decides for a dependent chain)
 template <int SPS>

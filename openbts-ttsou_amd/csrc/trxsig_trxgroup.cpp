@@ -95,6 +95,16 @@ struct trxsig_trxgroup {
   // the last pull
   int n_slots = 0, n_rows = 0, n_tsc_rows = 0;
   bool have = false;
+  // ... as trxsig_trxgroup_combine_div checks it against the other antenna's group: its time, where its bursts came from, its classes
+  int last_fn = 0, last_tn = 0, last_burst_len = 0, last_base[TRXG_NCLASS + 1] = {0};
+  bool last_fused = false, last_listed = false;
+  // trxsig_trxgroup_combine_div's result (kept by the FIRST group of a combine; valid until its next pull or combine)
+  struct Div {
+    DevBuf<uint8_t> valid, sel, flags;
+    DevBuf<trx_c32> amp;
+    DevBuf<float> toa, avgpwr, soft;
+    void release() { valid.release(); sel.release(); flags.release(); amp.release(); toa.release(); avgpwr.release(); soft.release(); }
+  } div;
   // ---- transmit half (created on first use): queue, filler table and payload pool on the device (trxsig_grouptx.hip) ----
   bool tx_ready = false;
   bool fmod_dirty = true;                                   // a SETSLOT changed some fillerModulus (setModulus, :183-204)
@@ -242,6 +252,7 @@ void trxsig_trxgroup_destroy(trxsig_trxgroup *g) {
     if (g->ev_join) (void)hipEventDestroy(g->ev_join);
     (void)hipFree(g->d_gid); (void)hipFree(g->d_pos); (void)hipFree(g->d_state); (void)hipFree(g->d_exp); (void)hipFree(g->d_err);
     for (int k = 0; k < 2; k++) { g->wk[k].release(); if (g->wk[k].done) (void)hipEventDestroy(g->wk[k].done); }
+    g->div.release();
     g->w_tab.release(); g->b_tab.release(); g->in.release(); g->chan_off.release(); g->seg_up.release();
     if (g->tx_ready) {
       (void)hipFree(g->tx.q_fn); (void)hipFree(g->tx.q_key); (void)hipFree(g->tx.q_n); (void)hipFree(g->tx.free_stack);
@@ -522,6 +533,8 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   if (equalize) TRX_HIPCHK(g->c, trx_launch_group_commit(st, S, g->d_state, g->w_tab.p, g->b_tab.p, g->chan_off.p));
 
   g->n_slots = n_slots; g->n_rows = n_rows; g->n_tsc_rows = n_tsc; g->have = true;
+  g->last_fn = fn; g->last_tn = tn; g->last_burst_len = burst_len; g->last_fused = src.gen != nullptr; g->last_listed = src.d_off != nullptr;
+  for (int k = 0; k <= TRXG_NCLASS; k++) g->last_base[k] = base[k];
   if (res) {
     res->n_slots = n_slots; res->n_arfcn = S; res->n_rows = n_rows;
     res->d_row = W.rowmap.p; res->d_valid = W.gate.p; res->d_flags = W.flags.p; res->d_amp = (const trxsig_c32 *)W.amp.p;
@@ -600,6 +613,67 @@ int trxsig_trxgroup_pull_rxfe(trxsig_trxgroup *g, trxsig_rxfe *fe, const int16_t
     if (res) std::memset(res, 0, sizeof *res);
   }
   return trx_rxfe_fused_end(fe, d_iq, n_chunks, p);
+}
+
+int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
+                                uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win, trxsig_trxgroup_result *res) {
+  if (!g0 || !g1) return TRXSIG_EINVAL;
+  trxsig_ctx *c = g0->c;
+  const char *why = nullptr;
+  if (g1->c != c) why = "trxsig_trxgroup_combine_div: the two groups live on different contexts";
+  else if (g0 == g1 || !d_samples0 || !d_samples1 || !res) why = "trxsig_trxgroup_combine_div: bad argument";
+  else if (g0->S != g1->S) why = "trxsig_trxgroup_combine_div: the groups have different ARFCN counts";
+  else if (g0->leg == TRXSIG_TSCLEG_EQUALIZE || g1->leg == TRXSIG_TSCLEG_EQUALIZE)
+    why = "trxsig_trxgroup_combine_div: a group on TRXSIG_TSCLEG_EQUALIZE (its taps are one antenna's)";
+  else if (!g0->have || !g1->have) why = "trxsig_trxgroup_combine_div: a group has had no pull";
+  else if (g0->last_fused || g1->last_fused) why = "trxsig_trxgroup_combine_div: a pull came through trxsig_trxgroup_pull_rxfe's fused source";
+  else if (g0->last_fn != g1->last_fn || g0->last_tn != g1->last_tn || g0->n_slots != g1->n_slots)
+    why = "trxsig_trxgroup_combine_div: the groups' last pulls are for different times or slots";
+  else if (g0->n_rows != g1->n_rows || g0->n_tsc_rows != g1->n_tsc_rows || std::memcmp(g0->last_base, g1->last_base, sizeof g0->last_base) != 0)
+    why = "trxsig_trxgroup_combine_div: the groups' rows differ (slot types or training sequences)";
+  else if (g0->last_listed != g1->last_listed || (!g0->last_listed && g0->last_burst_len != g1->last_burst_len))
+    why = "trxsig_trxgroup_combine_div: the groups' bursts have different lengths";
+  if (why) return trx_ctx_fail(c, TRXSIG_EINVAL, why, hipSuccess);
+  TrxDeviceGuard gd(trxsig_device(c));
+  hipStream_t st = (hipStream_t)trxsig_get_stream(c);
+  G_LIB(join_side(g0, st));
+  G_LIB(join_side(g1, st));
+  trxsig_trxgroup::Work &W0 = g0->wk[g0->cur], &W1 = g1->wk[g1->cur];
+  const int n_rows = g0->n_rows, n_tsc = g0->n_tsc_rows;
+  const size_t R = (size_t)(n_rows > 0 ? n_rows : 1);
+  if (g0->last_listed && n_rows > 0) {
+    // listed bursts: the lengths are the callers' device arrays, as the two pulls expanded them -- one small copy down, compared here
+    // (the only place this call waits for the stream)
+    std::vector<int32_t> l0((size_t)n_rows), l1((size_t)n_rows);
+    TRX_HIPCHK(c, hipMemcpyAsync(l0.data(), W0.len.p, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToHost, st));
+    TRX_HIPCHK(c, hipMemcpyAsync(l1.data(), W1.len.p, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToHost, st));
+    TRX_HIPCHK(c, hipStreamSynchronize(st));
+    if (l0 != l1) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_combine_div: the groups' bursts have different lengths", hipSuccess);
+  }
+  trxsig_trxgroup::Div &D = g0->div;
+  TRX_HIPCHK(c, D.valid.need(R, st)); TRX_HIPCHK(c, D.sel.need(R, st)); TRX_HIPCHK(c, D.flags.need(R, st)); TRX_HIPCHK(c, D.amp.need(R, st));
+  TRX_HIPCHK(c, D.toa.need(R, st)); TRX_HIPCHK(c, D.avgpwr.need(R, st)); TRX_HIPCHK(c, D.soft.need(R * kSoft, st));
+  uint8_t *sel = d_sel ? d_sel : D.sel.p;
+  TrxDivSelect ds;
+  ds.valid0 = W0.gate.p; ds.valid1 = W1.gate.p; ds.flags0 = W0.flags.p; ds.flags1 = W1.flags.p; ds.amp0 = W0.amp.p; ds.amp1 = W1.amp.p;
+  ds.toa0 = W0.toa.p; ds.toa1 = W1.toa.p; ds.pwr0 = W0.avgpwr.p; ds.pwr1 = W1.avgpwr.p; ds.B = n_rows; ds.need_mask = TRXSIG_F_DETECT;
+  ds.sel = sel; ds.valid = D.valid.p; ds.flags = D.flags.p; ds.amp = D.amp.p; ds.toa = D.toa.p; ds.pwr = D.avgpwr.p;
+  TRX_HIPCHK(c, trx_launch_div_select(st, ds));
+  for (int k = 0; k < TRXG_CLASS_RACH; k++) {               // the equaliser needs the class's training sequence: a launch per class in use
+    const int b0 = g0->last_base[k], n = g0->last_base[k + 1] - b0;
+    if (!n) continue;
+    G_LIB(trx_ctx_mlse_div_masked(c, d_samples0, W0.off.p + b0, d_samples1, W1.off.p + b0, W0.len.p + b0, n, k, (const trxsig_c32 *)D.amp.p + b0,
+                                  D.toa.p + b0, sel + b0, D.valid.p + b0, TRXSIG_F_DETECT, d_chan ? d_chan + (size_t)b0 * 10 : nullptr,
+                                  d_win ? d_win + b0 : nullptr, D.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
+  }
+  if (n_rows > n_tsc)                                       // access bursts: selection only
+    TRX_HIPCHK(c, trx_launch_div_copy_rows(st, n_rows - n_tsc, D.valid.p + n_tsc, sel + n_tsc, W0.soft.p + (size_t)n_tsc * kSoft,
+                                       W1.soft.p + (size_t)n_tsc * kSoft, kSoft, D.soft.p + (size_t)n_tsc * kSoft, kSoft, kSoft,
+                                       d_chan ? (trx_c32 *)d_chan + (size_t)n_tsc * 10 : nullptr, d_win ? d_win + n_tsc : nullptr));
+  res->n_slots = g0->n_slots; res->n_arfcn = g0->S; res->n_rows = n_rows;
+  res->d_row = W0.rowmap.p; res->d_valid = D.valid.p; res->d_flags = D.flags.p; res->d_amp = (const trxsig_c32 *)D.amp.p;
+  res->d_toa = D.toa.p; res->d_avgpwr = D.avgpwr.p; res->d_threshold = W0.thr_after.p; res->d_soft = D.soft.p; res->soft_stride = kSoft;
+  return TRXSIG_OK;
 }
 
 int trxsig_trxgroup_collect(trxsig_trxgroup *g, uint8_t *h_valid, float *h_soft, int *h_rssi, int *h_timing, double *h_threshold) {

@@ -1,0 +1,364 @@
+"""Two Transceiver groups, one per receive antenna, joined by trxsig_trxgroup_combine_div: 2 ARFCNs x 16 slots at sps 4, a training
+sequence per ARFCN, one access-burst slot, independent multipath per antenna, cells where antenna 0 is silent, where antenna 1 is,
+where both are, and where antenna 1 is the louder.  The combined result's d_valid is the OR of the two groups' verdicts, d_sel is
+the selection rule (tests/mlse_div_model.py's select) on the two pulls' values, flags / amp / TOA / avgPwr are the selected
+group's bytes, the training-sequence rows equal the two-antenna model with the selected amp and TOA, access-burst rows equal the
+selected pull's row, rows that are not valid are zeros, d_row and d_threshold are g0's; both groups' own results are those of
+groups that never combined; every refusal; and one closed loop through L1Rx.decode (tests/mlse_loop.py's SDCCH/8 slot) in which
+antenna 0 is silent in every second block."""
+import numpy as np
+import pytest
+
+import _pkg
+import mlse_div_model as dm
+import mlse_family
+import oraclebind
+import synth
+import transceiver_model as tm
+from util import assert_veq
+
+pytestmark = pytest.mark.gpu
+
+SPS, S, T, FN0 = 4, 2, 16, 101
+TSCS = (2, 5)
+CELL = 160 * SPS
+SILENT0, SILENT1, SILENT_BOTH, LOUD1 = [(3, 0), (6, 1), (12, 1)], [(4, 1), (10, 0)], [(5, 1)], [(2, 0), (7, 1), (13, 0)]
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    return _pkg.load()
+
+
+def combination(a, tn):
+    return tm.IV if (a == 0 and tn == 0) else tm.I           # ARFCN 0's slot 0 hears access bursts
+
+
+@pytest.fixture(scope="module")
+def cells():
+    """(x [2 antennas][T][S][CELL] complex64, ctype [T][S])."""
+    rng = np.random.default_rng(47)
+    o = oraclebind.Oracle(SPS)
+    x = np.zeros((2, T, S, CELL), np.complex64)
+    ctype = np.zeros((T, S), np.int8)
+    rx, roff, rlen, _ = synth.rach_batch(SPS, 8, seed=5, sigmas=(0.0, 0.1), max_delay_sym=10)
+    m = tm.TransceiverModel.__new__(tm.TransceiverModel)
+    profiles = ["five", "precursor", "flat"]
+    for t in range(T):
+        tn, fn = t % 8, FN0 + t // 8
+        n = (156 + (tn % 4 == 0)) * SPS
+        for a in range(S):
+            m.chan_type = np.array([combination(a, k) for k in range(8)])
+            ctype[t, a] = m.expected_corr_type(tn, fn)
+            if ctype[t, a] == tm.RACH:
+                i = 4 * (t // 8)                               # (bursts 0 and 4 of the pack are the 157-symbol ones)
+                r = rx[roff[i]:roff[i] + rlen[i]][:n]
+                x[0, t, a, :n] = r
+                x[1, t, a, :n] = r * np.complex64((1.5 if t == 0 else 0.5) * np.exp(0.7j))     # the louder antenna: 1 at t = 0, 0 at t = 8
+                continue
+            bits = synth.normal_bits(rng, 1, TSCS[a])[0]
+            s = o.modulate(bits.astype(np.int8), 9 if tn % 4 == 0 else 8)
+            for ant in (0, 1):
+                x[ant, t, a, :n] = mlse_family.channel(rng, s, SPS, mlse_family.PROFILES[profiles[(t + a + ant) % 3]], 18.0)[:n]
+            if (t, a) in LOUD1:
+                x[1, t, a] *= np.float32(2.5)
+            if (t, a) in SILENT0 + SILENT_BOTH:
+                x[0, t, a] = 0
+            if (t, a) in SILENT1 + SILENT_BOTH:
+                x[1, t, a] = 0
+    assert (ctype == tm.RACH).sum() == 2 and (ctype == tm.TSC).sum() == T * S - 2
+    return x, ctype
+
+
+def make_group(pkg, ctx, leg, tscs=TSCS, n_arfcn=S, comb=combination):
+    g = pkg.TrxGroup(ctx, n_arfcn, tsc_leg=leg, start=(FN0, 0))
+    for a in range(n_arfcn):
+        for cmd in ["CMD RXTUNE 890000", "CMD TXTUNE 935000", "CMD SETTSC %d" % tscs[a]] + \
+                   ["CMD SETSLOT %d %d" % (tn, comb(a, tn)) for tn in range(8)] + ["CMD POWERON"]:
+            g.control(a, cmd)
+    return g
+
+
+def fetch(pkg, ctx, res):
+    R = res.n_rows
+    return dict(row=pkg._to_host(ctx, res.d_row, (T, S), "<i4"), valid=pkg._to_host(ctx, res.d_valid, (R,), "|u1"),
+                flags=pkg._to_host(ctx, res.d_flags, (R,), "|u1"), amp=pkg._to_host(ctx, res.d_amp, (R, 2), "<f4").view(np.complex64).ravel(),
+                toa=pkg._to_host(ctx, res.d_toa, (R,), "<f4"), avgpwr=pkg._to_host(ctx, res.d_avgpwr, (R,), "<f4"),
+                threshold=pkg._to_host(ctx, res.d_threshold, (R,), "<f8"), soft=pkg._to_host(ctx, res.d_soft, (R, res.soft_stride), "<f4"))
+
+
+def to_dev(x):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x).view(np.float32).reshape(-1)).to("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def run(pkg, cells):
+    """The two pulls, the combine, and two groups that never combined: dict(comb, g0, g1, alone0, alone1, sel, chan, win)."""
+    import torch
+    x, _ = cells
+    ctx = pkg.TrxSig(SPS, 0)
+    ctx.use_torch_stream()
+    legs = (pkg.TSCLEG_MLSE, pkg.TSCLEG_DEMOD)                # either leg is accepted
+    dx = [to_dev(x[0]), to_dev(x[1])]
+    out = {}
+    for k in (0, 1):
+        g = make_group(pkg, ctx, legs[k])
+        res = g.pull(dx[k], S * CELL, CELL, FN0, 0, T)
+        g.sync(); torch.cuda.synchronize()
+        out["alone%d" % k] = dict(fetch(pkg, ctx, res), collect=g.collect())
+        g.close()
+    g0, g1 = make_group(pkg, ctx, legs[0]), make_group(pkg, ctx, legs[1])
+    r0 = g0.pull(dx[0], S * CELL, CELL, FN0, 0, T)
+    r1 = g1.pull(dx[1], S * CELL, CELL, FN0, 0, T)
+    R = r0.n_rows
+    sel = torch.full((R,), 9, dtype=torch.uint8, device="cuda:0")
+    chan = torch.full((R, 2, 5, 2), -7.0, dtype=torch.float32, device="cuda:0")
+    win = torch.full((R,), -99, dtype=torch.int32, device="cuda:0")
+    rc = g0.combine_div(dx[0], g1, dx[1], sel=sel, chan=chan, win=win)
+    torch.cuda.synchronize()
+    out["comb"] = fetch(pkg, ctx, rc)
+    out["g0"] = dict(fetch(pkg, ctx, r0), collect=g0.collect())
+    out["g1"] = dict(fetch(pkg, ctx, r1), collect=g1.collect())
+    out["sel"] = sel.cpu().numpy(); out["chan"] = chan.cpu().numpy().reshape(R, 2, 10).view(np.complex64); out["win"] = win.cpu().numpy()
+    bare = g0.combine_div(dx[0], g1, dx[1])                   # the optional outputs left out: the same result
+    torch.cuda.synchronize()
+    out["bare"] = fetch(pkg, ctx, bare)
+    g0.close(); g1.close(); ctx.close()
+    return out
+
+
+def test_groups_are_untouched_by_the_combine(run):
+    for k in (0, 1):
+        a, g = run["alone%d" % k], run["g%d" % k]
+        for key in ("row", "valid", "flags", "amp", "toa", "avgpwr", "threshold"):
+            assert a[key].tobytes() == g[key].tobytes(), (k, key)
+        v = a["valid"] != 0
+        assert a["soft"][v].tobytes() == g["soft"][v].tobytes(), k
+        for key in ("valid", "rssi", "timing", "threshold", "soft"):
+            assert a["collect"][key].tobytes() == g["collect"][key].tobytes(), (k, "collect " + key)
+
+
+def test_combined_selection(run, cells):
+    _, ctype = cells
+    c, g0, g1 = run["comb"], run["g0"], run["g1"]
+    assert g0["row"].tobytes() == g1["row"].tobytes()
+    assert c["row"].tobytes() == g0["row"].tobytes() and c["threshold"].tobytes() == g0["threshold"].tobytes()
+    v0, v1 = g0["valid"] != 0, g1["valid"] != 0
+    assert_veq(c["valid"], np.where(v0 | v1, 2, 0).astype(np.uint8), "d_valid")       # TRXSIG_F_DETECT
+    sel = dm.select(v0, g0["amp"], v1, g1["amp"])
+    assert_veq(run["sel"], sel, "d_sel")
+    row = g0["row"]
+    for t, a in SILENT0:
+        assert sel[row[t, a]] == 1 and not v0[row[t, a]]
+    for t, a in SILENT1:
+        assert sel[row[t, a]] == 0 and not v1[row[t, a]]
+    for t, a in SILENT_BOTH:
+        assert sel[row[t, a]] == 2
+    for t, a in LOUD1:
+        assert sel[row[t, a]] == 1 and v0[row[t, a]] and v1[row[t, a]]
+    assert sel[row[0, 0]] == 1 and sel[row[8, 0]] == 0 and ctype[0, 0] == tm.RACH     # the access bursts: the louder antenna
+    assert (sel == 0).sum() >= 4 and (sel == 1).sum() >= 8
+    one = sel == 1
+    for key in ("flags", "amp", "toa", "avgpwr"):
+        want = np.where(one, g1[key], g0[key]).astype(g0[key].dtype)
+        assert c[key].tobytes() == want.tobytes(), key
+    for key in c:
+        assert run["bare"][key].tobytes() == c[key].tobytes(), "without d_sel / d_chan / d_win: " + key
+
+
+def test_combined_soft_rows(run, cells):
+    x, ctype = cells
+    c, g0, g1, sel = run["comb"], run["g0"], run["g1"], run["sel"]
+    o = oraclebind.Oracle(SPS)
+    n_tsc = n_rach = n_zero = 0
+    for t in range(T):
+        n = (156 + (t % 8 % 4 == 0)) * SPS
+        for a in range(S):
+            r = c["row"][t, a]
+            assert r >= 0
+            if not c["valid"][r]:
+                assert not c["soft"][r].any()
+                n_zero += 1
+            elif ctype[t, a] == tm.RACH:
+                src = g1 if sel[r] == 1 else g0
+                assert c["soft"][r].tobytes() == src["soft"][r].tobytes()
+                assert run["win"][r] == 2 and not run["chan"][r].any()
+                n_rach += 1
+            else:
+                zero = np.array([0], np.int32)
+                want = dm.mlse_div_batch(SPS, x[0, t, a], zero, x[1, t, a], zero, np.array([n], np.int32), TSCS[a], c["amp"][r:r + 1],
+                                         c["toa"][r:r + 1], primary=sel[r:r + 1], oracle=o)
+                assert want["win"][0] <= 0
+                assert_veq(c["soft"][r, :148], want["soft"][0], "slot %d ARFCN %d" % (t, a))
+                assert run["win"][r] == want["win"][0]
+                assert_veq(run["chan"][r].ravel(), want["chan"][0].ravel(), "taps, slot %d ARFCN %d" % (t, a))
+                n_tsc += 1
+    assert n_tsc >= 26 and n_rach == 2 and n_zero >= 1
+
+
+def test_refusals(pkg, cells):
+    """Different contexts, ARFCN counts, rows (slot types), class bases (training sequences), burst lengths, times; no pull; the
+    equalising leg; the fused source: TRXSIG_EINVAL each."""
+    import torch
+    from openbts_ttsou_amd import synth as gsynth
+    from openbts_ttsou_amd.frontend import RxFrontEnd
+    x, _ = cells
+    ctx = pkg.TrxSig(SPS, 0); ctx.use_torch_stream()
+    other = pkg.TrxSig(SPS, 0); other.use_torch_stream()
+    dx = [to_dev(x[0]), to_dev(x[1])]
+
+    def pulled(g, k=1, fn=FN0, burst_len=0, n_arfcn=S):
+        g.pull(dx[k], n_arfcn * CELL, CELL, fn, 0, T, burst_len=burst_len)
+        return g
+    g0 = pulled(make_group(pkg, ctx, pkg.TSCLEG_DEMOD), k=0)
+    cases = [
+        ("different contexts", pulled(make_group(pkg, other, pkg.TSCLEG_DEMOD))),
+        ("ARFCN counts", pulled(make_group(pkg, ctx, pkg.TSCLEG_DEMOD, tscs=(2,), n_arfcn=1), n_arfcn=1)),
+        ("rows differ", pulled(make_group(pkg, ctx, pkg.TSCLEG_DEMOD, comb=lambda a, tn: 0 if (a, tn) == (1, 3) else combination(a, tn)))),
+        ("rows differ", pulled(make_group(pkg, ctx, pkg.TSCLEG_DEMOD, tscs=(2, 6)))),
+        ("different lengths", pulled(make_group(pkg, ctx, pkg.TSCLEG_DEMOD), burst_len=156 * SPS)),
+        ("different times", pulled(make_group(pkg, ctx, pkg.TSCLEG_DEMOD), fn=FN0 + 1)),
+        ("no pull", make_group(pkg, ctx, pkg.TSCLEG_DEMOD)),
+    ]
+    for what, g1 in cases:
+        with pytest.raises(pkg.TrxSigError, match=what):
+            g0.combine_div(dx[0], g1, dx[1])
+        with pytest.raises(pkg.TrxSigError):
+            g1.combine_div(dx[1], g0, dx[0])
+    with pytest.raises(pkg.TrxSigError):
+        g0.combine_div(dx[0], g0, dx[0])
+    with pytest.raises(pkg.TrxSigError):
+        g0.combine_div(None, cases[-1][1], dx[1])
+    good = pulled(make_group(pkg, ctx, pkg.TSCLEG_MLSE))
+    assert g0.combine_div(dx[0], good, dx[1]).n_rows == T * S  # ... and the accepted form goes through
+    torch.cuda.synchronize()
+    for g in [good] + [c[1] for c in cases]:
+        g.close()
+    g0.close(); ctx.close(); other.close()
+    # the equalising leg (sps 1) and the fused source (sps 4, the demodulating leg on a receive front end)
+    c1 = pkg.TrxSig(1, 0); c1.use_torch_stream()
+    z = torch.zeros(T * S * 160 * 2, dtype=torch.float32, device="cuda:0")
+    ge, gd = pkg.TrxGroup(c1, S, tsc_leg=pkg.TSCLEG_EQUALIZE), pkg.TrxGroup(c1, S, tsc_leg=pkg.TSCLEG_DEMOD)
+    for a, b in ((ge, gd), (gd, ge)):
+        with pytest.raises(pkg.TrxSigError, match="TRXSIG_TSCLEG_EQUALIZE"):
+            a.combine_div(z, b, z)
+    ge.close(); gd.close(); c1.close()
+    c4 = pkg.TrxSig(SPS, 0); c4.use_torch_stream()
+    lpf = gsynth.design_lpf(961, 65 * SPS)
+    iq = torch.zeros((S, 4 * 864, 2), dtype=torch.int16, device="cuda:0")
+    fused = []
+    for k in (0, 1):
+        g = make_group(pkg, c4, pkg.TSCLEG_DEMOD)
+        fe = RxFrontEnd(c4, S, lpf, max_chunks=4)
+        ns, _ = g.pull_rxfe(fe, iq, FN0)
+        assert ns > 0
+        fused.append((g, fe))
+    with pytest.raises(pkg.TrxSigError, match="fused source"):
+        fused[0][0].combine_div(z, fused[1][0], z)
+    torch.cuda.synchronize()
+    for g, fe in fused:
+        fe.close(); g.close()
+    c4.close()
+
+
+def test_listed_bursts(pkg, cells, run):
+    """The two pulls through trxsig_trxgroup_pull_bursts (listed offsets and lengths, the layout a front end's pop hands out): the
+    combined result is the strided pulls' byte for byte; one length changed on one antenna's list is refused."""
+    import torch
+    x, _ = cells
+    ctx = pkg.TrxSig(SPS, 0); ctx.use_torch_stream()
+    dx = [to_dev(x[0]), to_dev(x[1])]
+    t, a = np.meshgrid(np.arange(T), np.arange(S))            # entry a * T + t
+    off = (t * S * CELL + a * CELL).astype(np.int32).ravel()
+    length = ((156 + (t % 8 % 4 == 0)) * SPS).astype(np.int32).ravel()
+    d_off, d_len = torch.from_numpy(off).cuda(), torch.from_numpy(length).cuda()
+    g0, g1 = make_group(pkg, ctx, pkg.TSCLEG_DEMOD), make_group(pkg, ctx, pkg.TSCLEG_DEMOD)
+    g0.pull_bursts(dx[0], d_off, d_len, T, FN0, 0)
+    g1.pull_bursts(dx[1], d_off, d_len, T, FN0, 0)
+    got = fetch(pkg, ctx, g0.combine_div(dx[0], g1, dx[1]))
+    torch.cuda.synchronize()
+    for key in got:
+        assert got[key].tobytes() == run["comb"][key].tobytes(), key
+    other = length.copy(); other[5] = 152 * SPS
+    d_other = torch.from_numpy(other).cuda()
+    g1.pull_bursts(dx[1], d_off, d_other, T, FN0, 0)
+    with pytest.raises(pkg.TrxSigError, match="different lengths"):
+        g0.combine_div(dx[0], g1, dx[1])
+    g0.close(); g1.close(); ctx.close()
+
+
+# ---- the closed loop: antenna 0 silent in every second block's bursts ----
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def dev_c(a):
+    return dev(np.ascontiguousarray(a, np.complex64).view(np.float32).reshape(np.shape(a) + (2,)))
+
+
+def test_closed_loop_with_a_silent_antenna(pkg):
+    """L1Ms.encode -> radiate -> Air.cells per antenna with tests/mlse_loop.py's fixed taps -> two groups' pulls -> combine_div ->
+    L1Rx.decode on the SDCCH/8 slot (24 blocks, 96 bursts).  Antenna 1 carries the fixed tap set; antenna 0 carries it times a
+    constant and is silent (zero taps) in the four bursts of every second block.  Every block of the combined result decodes with
+    the payloads sent; a single group on antenna 0 loses exactly the silent blocks."""
+    import torch
+    import fectxbind
+    import fec_stream_model as fsm
+    import mlse_loop as ml
+    c = ml.case(fectxbind.FecTxOracle())
+    blk = ml.blocks(c)
+    assert len(blk) == 24
+    sps, A, F, fn0, comb, m = ml.SPS, ml.A, ml.F, ml.FN0, c["comb"], c["m"]
+    Tn, cell = 8 * F, 160 * sps
+    ctx = pkg.TrxSig(sps, 0)
+    ctx.use_torch_stream()
+    ms = pkg.L1Ms(ctx, comb, ml.BSIC, ml.BAND)
+    ms.encode(fn0, F, **{k: dev(v) for k, v in c["grids"].items()})
+    nx = len(c["model"].ch[ml.lms.XCCH])
+    clean = torch.zeros(Tn, A, cell, 2, dtype=torch.float32, device="cuda")
+    none_c, none_f = dev_c(np.zeros(0, np.complex64)), dev(np.zeros(0, np.float32))
+    ms.radiate(clean, A * cell, cell, tch_gain=none_c, tch_delay=none_f, xcch_gain=dev_c(np.full(nx, ml.GAIN, np.complex64)),
+               xcch_delay=dev(np.zeros(nx, np.float32)), rach_gain=none_c, rach_delay=none_f, amp_of_power=dev(np.ones(41, np.float32)))
+    h = ml.taps()
+    taps = np.zeros((2, A, Tn, len(h)), np.complex64)
+    taps[1] = h
+    taps[0] = h * np.complex64(0.6 + 0.5j)
+    silent = np.arange(len(blk)) % 2 == 1
+    for k in np.flatnonzero(silent):
+        for s in blk[k][3]:
+            taps[0, 0, s] = 0
+    air = pkg.Air(ctx, len(h))
+    rx = [torch.zeros_like(clean), torch.zeros_like(clean)]
+    for a in (0, 1):
+        air.cells(fn0, A, F, 1, clean, A * cell, cell, rx[a], A * cell, cell, taps=dev_c(taps[a]))
+    groups, pulls = [], []
+    for a in (0, 1):
+        g = pkg.TrxGroup(ctx, A, tsc_leg=pkg.TSCLEG_DEMOD, start=(fn0, 0))
+        for cmd in ["CMD RXTUNE 890000", "CMD TXTUNE 935000", "CMD SETTSC %d" % (ml.BSIC & 7)] + \
+                   ["CMD SETSLOT %d %d" % (tn, comb[0, tn]) for tn in range(8)] + ["CMD POWERON"]:
+            g.control(0, cmd)
+        pulls.append(g.pull(rx[a], A * cell, cell, fn0, 0, Tn))
+        groups.append(g)
+    both = groups[0].combine_div(rx[0], groups[1], rx[1])
+
+    def decoded(res):
+        l1 = pkg.L1Rx(ctx, comb, ml.BSIC, ml.BAND)
+        l1.decode(res, fn0)
+        got = l1.collect()
+        torch.cuda.synchronize()
+        ok = []
+        for i, b, want, slots in blk:
+            jb = list(got["xcch_fn"][i]).index((fn0 + slots[3] // 8) % tm.HYPERFRAME)
+            ok.append(got["xcch_status"][i, jb] == fsm.DECODED | fsm.TCH_GOOD and np.array_equal(got["xcch"][i, jb], want))
+        l1.destroy()
+        return np.array(ok)
+    ok_both, ok_one = decoded(both), decoded(pulls[0])
+    assert ok_both.all(), "the combined result lost blocks %s" % np.flatnonzero(~ok_both)
+    assert not ok_one[silent].any(), "antenna 0 alone decoded a block it never heard"
+    for g in groups:
+        g.close()
+    ms.destroy(); air.destroy(); ctx.close()
