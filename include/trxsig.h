@@ -288,6 +288,72 @@ int trxsig_mlse_div_normal_batch(trxsig_ctx *ctx,
                                  uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win,
                                  float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 
+/* ---- interference-rejection combining for the two-antenna sequence equaliser (csrc/trxsig_mlse_irc.hip) ---------------------
+ * trxsig_mlse_irc_batch: trxsig_mlse_div_batch for a disturbance that is NOT white, equally strong and uncorrelated between the
+ *   antennas -- a co-channel interferer reaches both antennas and its contributions there are correlated; unequal noise power per
+ *   branch is the diagonal special case.  The 2 x 2 covariance R of the disturbance is estimated from the midamble residuals (or
+ *   given by the caller) and the trellis runs on the whitened metric e^H R^-1 e, in a square-root-free LDL form: with
+ *   R ~ [[A, x], [conj(x), Bv]], det = A Bv - |x|^2,  A det e^H R^-1 e = det |e_0|^2 + |A e_1 - conj(x) e_0|^2.
+ *   Pinned by the float32 model tests/mlse_irc_model.py, which the kernel equals word for word, and graded against the float64
+ *   statement tests/mlse_irc_ref.py with the a-priori bounds derived there:
+ *     |soft - clamp(soft64)| <= 1.001 ((2 Q + 124 P) / (8 E_w) + e / 2 + 2) 2^-24   (P, Q: trxsig_mlse_div_batch's sums over the
+ *         whitened metric, Q with the whitening's and the det multiply's roundings; e: the relative rounding of E_w in units
+ *         of 2^-24, 7 there and at most 11 for the identity set),
+ *     |S - S64| <= 1.001 (sum_m tau_m + 21 sum_m |term_m|) 2^-24   for S = S00, S11, Xr, Xi (tau_m: the rounding a term inherits
+ *         from its residuals and its own operations).
+ *   It is trxsig_mlse_div_batch's algorithm with the changes below and no others; every step is one float32 operation in the order
+ *   written, nothing is fused.  Steps 1 and 2 are unchanged: the symbols, the correlations, the ONE window w chosen on the summed
+ *   tap powers, h_a, E, the skip rule and the fall-back rule.
+ *   2b. Residuals, on the 22 midamble positions whose five contributing symbols are all training symbols: for m = 65..86, x_m is
+ *      the 5-bit index whose bit k is training bit m - 61 - k (a[m - k]); r_a[m] = y_a[m + w] - Z_a[x_m], Z_a formed from h_a
+ *      exactly as step 3 forms the right half's expected values.  The sums start from 0, m ascending:
+ *      S00 += r0.re*r0.re + r0.im*r0.im, S11 likewise from r1; Xr += r0.re*r1.re + r0.im*r1.im, Xi += r0.im*r1.re - r0.re*r1.im
+ *      (X = sum r0 conj(r1)).
+ *   2c. The set (A, Bv, xr, xi).  Estimated (d_cov_in NULL): tt = S00 + S11, A = S00/tt + loading, Bv = S11/tt + loading,
+ *      xr = Xr/tt, xi = Xi/tt: four correctly rounded divisions per burst.  Given: the caller's four floats d_cov_in[b][0..3],
+ *      taken as they are (no loading).  Either way det = A*Bv - (xr*xr + xi*xi).  The set is replaced by the identity set
+ *      (1, 1, 0, 0) with det = 1 when !(tt > 0) (an estimated set only); when any of A, Bv, |xr|, |xi| fails v < 0x1p10f, or A or
+ *      Bv fails v >= 0 (negative or NaN); or when !(det > 0).  The magnitude bound, with |y| < 2^30, keeps every metric finite.
+ *   2d. Whitening, once per burst (the LDL form; no square root):
+ *      y1'[n].re = A*y1[n].re - (xr*y0[n].re + xi*y0[n].im),  y1'[n].im = A*y1[n].im - (xr*y0[n].im - xi*y0[n].re);
+ *      the same map takes (h0, h1) to h1'.  Antenna 0 is untouched.  pw[k] = det*(h0[k].re*h0[k].re + h0[k].im*h0[k].im) +
+ *      (h1'[k].re*h1'[k].re + h1'[k].im*h1'[k].im); E_w = (((pw[0] + pw[1]) + pw[2]) + pw[3]) + pw[4].  If !(E_w > 0) or E_w is
+ *      not finite the burst takes the identity set, and then E_w is E.
+ *   3. Trellis: trxsig_mlse_div_batch's on (y0, y1') with (h0, h1'), with one change:
+ *      gamma = det*(dr0*dr0 + di0*di0) + (dr1*dr1 + di1*di1).
+ *   4. soft = clamp(0.5f + (M_0 - M_1) / (8.0f * E_w)).  Positions 61..86, and every fall-back, use the UNWHITENED y_p of the
+ *      primary antenna, as there.
+ *   Identities.  (1) d_cov_in = (1, 1, 0, 0) on every burst: soft, hard, win and chan equal trxsig_mlse_div_batch's bit for bit
+ *   (1*v and v - 0 are exact).  (2) Antenna 1 all zeros and loading == 0: det is 0, the identity set is taken, and the outputs equal
+ *   trxsig_mlse_batch's on antenna 0 bit for bit.  (3) Antenna 1 all zeros and loading > 0: the soft bits equal trxsig_mlse_batch's
+ *   only up to the two roundings of det; the float64 reference grades that case.  The antenna-swap identity of
+ *   trxsig_mlse_div_batch does NOT carry over exactly: the LDL form is not symmetric in the antennas (antenna 1 is the one that is
+ *   whitened); it holds within the graded bound.
+ *   loading  0 <= loading <= 16, else TRXSIG_EINVAL (a NaN too); the tools and the Transceiver groups use 1/64: the estimate is
+ *            from 22 residuals, and a little loading keeps a near-singular estimate from nulling the wanted signal
+ *   d_cov_in B x 4 floats (A, Bv, xr, xi) per burst, or NULL = estimate; the hook for covariance smoothing across bursts
+ *   d_cov    B x 4: the set used -- (1, 1, 0, 0) where the identity set was taken, zeros for a burst that fell back or was
+ *            skipped                                                                        (may be NULL)
+ *   d_chan   B x 2 x 5: the UNWHITENED taps h_a[0..4]; d_win: as trxsig_mlse_div_batch        (may be NULL)
+ * trxsig_mlse_irc_normal_batch: the detector on each antenna and the selection exactly as trxsig_mlse_div_normal_batch, then this
+ *   equaliser with an estimated set.  Refusals are trxsig_mlse_div_batch's, and the loading's. */
+int trxsig_mlse_irc_batch(trxsig_ctx *ctx,
+                          const trxsig_c32 *d_samples0, const int32_t *d_offset0,
+                          const trxsig_c32 *d_samples1, const int32_t *d_offset1,
+                          const int32_t *d_length, int B, int tsc,
+                          const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_primary, const uint8_t *d_enable,
+                          float loading, const float *d_cov_in, float *d_cov,
+                          trxsig_c32 *d_chan, int32_t *d_win,
+                          float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+int trxsig_mlse_irc_normal_batch(trxsig_ctx *ctx,
+                                 const trxsig_c32 *d_samples0, const int32_t *d_offset0,
+                                 const trxsig_c32 *d_samples1, const int32_t *d_offset1,
+                                 const int32_t *d_length, int B, int tsc,
+                                 float detect_thresh, float energy_thresh, float loading,
+                                 uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
+                                 uint8_t *d_sel, float *d_cov, trxsig_c32 *d_chan, int32_t *d_win,
+                                 float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+
 /* ---- TX path: modulateBurst (sigProcLib.h:171-174) as called by Transceiver::addRadioVector
  *   (Transceiver.cpp:100-113): bits -> GMSK-rotated impulses -> pulse shaping, then scaleVector by
  *   a real gain.  d_bits: B x 148 bytes (only bit 0 is used, BitVector.cpp:54-63); d_guard[b] =

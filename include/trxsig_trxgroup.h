@@ -127,6 +127,16 @@ int trxsig_trxgroup_pull_bursts(trxsig_trxgroup *g, const trxsig_c32 *d_samples,
 int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
                                 uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win, trxsig_trxgroup_result *res);
 
+/* The same with interference-rejection combining (trxsig_mlse_irc_batch, trxsig.h): everything is trxsig_trxgroup_combine_div's --
+ * the checks and refusals, the selection, the access-burst rows (by selection), the result and its buffers in g0 -- except that a
+ * valid training-sequence row goes through k_mlse_irc with a set estimated from that burst's midamble residuals and `loading`
+ * (0 <= loading <= 16, else TRXSIG_EINVAL; 1/64 is what the tools use).  d_cov [n_rows][4] (may be NULL): the set used, as
+ * trxsig_mlse_irc_batch's d_cov; zeros on access-burst rows.  Where a co-channel interferer limits the uplink this is the call to
+ * use; with white noise of equal power on both antennas it costs nothing measurable against trxsig_trxgroup_combine_div. */
+int trxsig_trxgroup_combine_irc(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
+                                float loading, uint8_t *d_sel, float *d_cov, trxsig_c32 *d_chan, int32_t *d_win,
+                                trxsig_trxgroup_result *res);
+
 /* What the caller of pullRadioVector sees, on the host, for the last pull (synchronises the stream): entry t*n_arfcn + a
  *   h_valid   1 where a SoftVector came back
  *   h_soft    [n_slots*n_arfcn][148] its soft bits (untouched where h_valid is 0); may be NULL

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("TRXSIG_LIB", os.path.join(_HERE, "libtrxsig.so"))   #
 F_ENERGY, F_DETECT, F_BADLEN = 1, 2, 128
 SOFT_EXACT, SOFT_TOLERANCE = 0, 1                # trxsig_set_soft_mode
 ABI_VERSION = 2                                  # TRXSIG_ABI_VERSION of include/trxsig.h
+IRC_LOADING = 1.0 / 64.0                         # the diagonal loading the tools and the groups use (trxsig_mlse_irc_batch)
 TCH_FILLER, TCH_SPEECH, TCH_FACCH = 0, 1, 2      # block kinds of trxsig_fec_tch_encode_batch
 TCH_TX_STATE_BYTES = 32                          # TRXSIG_TCH_TX_STATE_BYTES
 FEC_DECODED, FEC_STOLEN, FEC_FACCH_OK, FEC_TCH_GOOD = 1, 2, 4, 8   # status bits of the stream decoders (TRXSIG_FEC_*)
@@ -363,6 +364,31 @@ class TrxSig:
             self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, detect_thresh, energy_thresh,
             _ptr(flags), _ptr(amp), _ptr(toa), _ptr(avgpwr), _ptr(sel), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft,
             soft_stride), "trxsig_mlse_div_normal_batch")
+
+    def mlse_irc(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, loading=IRC_LOADING,
+                 cov_in=None, cov=None, chan=None, win=None, hard=None, nsoft=148, soft_stride=None):
+        """mlse_div with interference-rejection combining (trxsig_mlse_irc_batch): the 2 x 2 covariance of the disturbance is
+        estimated per burst from the midamble residuals with `loading` on its diagonal, or given as cov_in [B, 4] float32
+        (A, Bv, xr, xi); cov [B, 4] returns the set used."""
+        B = offset0.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_irc_batch(
+            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, _ptr(amp), _ptr(toa),
+            _ptr(primary), _ptr(enable), loading, _ptr(cov_in), _ptr(cov), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft,
+            soft_stride), "trxsig_mlse_irc_batch")
+
+    def mlse_irc_normal(self, samples0, offset0, samples1, offset1, length, tsc, flags, amp, toa, sel, soft, loading=IRC_LOADING,
+                        avgpwr=None, cov=None, chan=None, win=None, hard=None, detect_thresh=3.0, energy_thresh=0.0, nsoft=148,
+                        soft_stride=None):
+        """mlse_div_normal's detector and selection, then mlse_irc with an estimated set (trxsig_mlse_irc_normal_batch)."""
+        B = offset0.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_irc_normal_batch(
+            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, detect_thresh, energy_thresh,
+            loading, _ptr(flags), _ptr(amp), _ptr(toa), _ptr(avgpwr), _ptr(sel), _ptr(cov), _ptr(chan), _ptr(win), _ptr(soft),
+            _ptr(hard), nsoft, soft_stride), "trxsig_mlse_irc_normal_batch")
 
     def equalize_normal(self, samples, offset, length, tsc, flags, amp, toa, soft, w=None, b=None, hard=None,
                         detect_thresh=3.0, energy_thresh=0.0, variant52m=True, max_toa=4, nsoft=148,
@@ -795,6 +821,14 @@ class TrxGroup(_Object):
         res = TrxGroupResult()
         self._call("combine_div", _ptr(samples0), other.h if other is not None else None, _ptr(samples1), _ptr(sel), _ptr(chan), _ptr(win),
                    C.byref(res))
+        return res
+
+    def combine_irc(self, samples0, other, samples1, loading=IRC_LOADING, sel=None, cov=None, chan=None, win=None):
+        """combine_div with interference-rejection combining on the training-sequence rows (trxsig_trxgroup_combine_irc): the
+        covariance of the disturbance is estimated per burst, `loading` on its diagonal.  cov [n_rows, 4] float32: the set used."""
+        res = TrxGroupResult()
+        self._call("combine_irc", _ptr(samples0), other.h if other is not None else None, _ptr(samples1), loading, _ptr(sel), _ptr(cov),
+                   _ptr(chan), _ptr(win), C.byref(res))
         return res
 
     def pull_rxfe(self, fe, iq, fn):

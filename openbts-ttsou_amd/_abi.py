@@ -131,6 +131,8 @@ SIGNATURES = {
     "trxsig_mlse_normal_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_div_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_div_normal_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
+    "trxsig_mlse_irc_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32]),
+    "trxsig_mlse_irc_normal_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_modulate_batch": (i32, [vp, vp, vp, vp, i32, vp, vp]),
     "trxsig_estimate_dfe_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "trxsig_equalize_taps_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
@@ -238,6 +240,7 @@ SIGNATURES = {
     "trxsig_trxgroup_pull_rxfe": (i32, [vp, vp, vp, i32, i32, P(i32), P(TrxGroupResult)]),
     "trxsig_trxgroup_pull_bursts": (i32, [vp, vp, vp, vp, i32, i32, i32, P(TrxGroupResult)]),
     "trxsig_trxgroup_combine_div": (i32, [vp, vp, vp, vp, vp, vp, vp, P(TrxGroupResult)]),
+    "trxsig_trxgroup_combine_irc": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, vp, P(TrxGroupResult)]),
     "trxsig_trxgroup_collect": (i32, [vp, vp, vp, vp, vp, vp]),
     "trxsig_trxgroup_pull_host": (i32, [vp, vp, i64, i64, i32, i32, i32, i32]),
     "trxsig_trxgroup_set_pipelined": (i32, [vp, i32]),

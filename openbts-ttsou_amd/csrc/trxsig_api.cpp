@@ -737,6 +737,26 @@ int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const i
                                 (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
   return TRXSIG_OK;
 }
+// trxsig_mlse_irc_batch with the enable test spelt out (trxsig_trxgroup_combine_irc: a launch per TSC class)
+int trx_ctx_mlse_irc_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
+                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, float loading, const float *d_cov_in,
+                            float *d_cov, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples0, d_offset0, d_length, B) || bad_batch(d_samples1, d_offset1, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 ||
+      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_irc_batch: bad argument");
+  if (!(loading >= 0.0f && loading <= 16.0f))               // (a NaN too)
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_irc_batch: loading outside 0..16");
+  if (B == 0) return TRXSIG_OK;
+  unsigned bits = 0;
+  for (int k = 0; k < 26; k++) bits |= (unsigned)(trx_training_sequence(tsc)[k] == '1') << k;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_mlse_irc(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples0, d_offset0, (const trx_c32 *)d_samples1,
+                                d_offset1, d_length, B, bits, (const trx_c32 *)d_amp, d_toa, d_primary, d_enable, need_mask, loading,
+                                d_cov_in, d_cov, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+  return TRXSIG_OK;
+}
 extern "C" {
 
 int trxsig_detect_demod_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset,
@@ -812,14 +832,18 @@ int trxsig_mlse_div_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int
                                  d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
 }
 
-int trxsig_mlse_div_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
-                                 const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, float detect_thresh,
-                                 float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr, uint8_t *d_sel,
-                                 trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+// the body of trxsig_mlse_div_normal_batch and trxsig_mlse_irc_normal_batch: irc == nullptr is the first
+struct TrxIrcArgs { float loading; float *d_cov; };
+static int mlse_two_normal(trxsig_ctx *c, const char *bad_argument, const char *bad_alloc, const TrxIrcArgs *irc, const trxsig_c32 *d_samples0,
+                           const int32_t *d_offset0, const trxsig_c32 *d_samples1, const int32_t *d_offset1, const int32_t *d_length, int B,
+                           int tsc, float detect_thresh, float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa,
+                           float *d_avgpwr, uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft,
+                           int soft_stride) {
   if (!c) return TRXSIG_EINVAL;
   if (bad_batch(d_samples0, d_offset0, d_length, B) || bad_batch(d_samples1, d_offset1, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 ||
-      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_flags || !d_amp || !d_toa || !d_sel || !d_soft)))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_div_normal_batch: bad argument");
+      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_flags || !d_amp || !d_toa || !d_sel || !d_soft)) ||
+      (irc && !(irc->loading >= 0.0f && irc->loading <= 16.0f)))
+    return fail(c, TRXSIG_EINVAL, bad_argument);
   if (B == 0) return TRXSIG_OK;
   // the exact detector alone on each antenna (nsoft = 0: no demodulator, whatever the soft mode), the selection, then the
   // equaliser on the bursts some antenna detected, with the selected antenna's amp and TOA
@@ -831,7 +855,7 @@ int trxsig_mlse_div_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, co
   }
   TrxDeviceGuard g(c->device);
   const size_t o_toa = trx_align256(8 * (size_t)B), o_en = o_toa + trx_align256(4 * (size_t)B);
-  const int rc = trx_work_ensure(c, c->div, o_en + trx_align256((size_t)B), false, "trxsig_mlse_div_normal_batch: device allocation");
+  const int rc = trx_work_ensure(c, c->div, o_en + trx_align256((size_t)B), false, bad_alloc);
   if (rc != TRXSIG_OK) return rc;
   trx_c32 *amp_sel = (trx_c32 *)c->div.p;
   float *toa_sel = (float *)((char *)c->div.p + o_toa);
@@ -841,8 +865,41 @@ int trxsig_mlse_div_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, co
   ds.toa0 = d_toa; ds.toa1 = d_toa + B; ds.B = B; ds.need_mask = TRXSIG_F_DETECT;
   ds.sel = d_sel; ds.amp = amp_sel; ds.toa = toa_sel; ds.valid = en;
   TRX_HIPCHK(c, trx_launch_div_select(c->stream, ds));
+  if (irc)
+    return trx_ctx_mlse_irc_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, (const trxsig_c32 *)amp_sel, toa_sel,
+                                   d_sel, en, TRXSIG_F_DETECT, irc->loading, nullptr, irc->d_cov, d_chan, d_win, d_soft, d_hard, nsoft,
+                                   soft_stride);
   return trx_ctx_mlse_div_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, (const trxsig_c32 *)amp_sel, toa_sel, d_sel,
                                  en, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+}
+
+int trxsig_mlse_div_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                                 const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, float detect_thresh,
+                                 float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr, uint8_t *d_sel,
+                                 trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  return mlse_two_normal(c, "trxsig_mlse_div_normal_batch: bad argument", "trxsig_mlse_div_normal_batch: device allocation", nullptr,
+                         d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, detect_thresh, energy_thresh, d_flags, d_amp, d_toa,
+                         d_avgpwr, d_sel, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+}
+
+// ---- interference-rejection combining for the two-antenna sequence equaliser (trxsig_mlse_irc.hip) ----
+int trxsig_mlse_irc_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                          const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
+                          const uint8_t *d_primary, const uint8_t *d_enable, float loading, const float *d_cov_in, float *d_cov,
+                          trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  return trx_ctx_mlse_irc_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, d_amp, d_toa, d_primary, d_enable, 0,
+                                 loading, d_cov_in, d_cov, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+}
+
+int trxsig_mlse_irc_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                                 const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, float detect_thresh,
+                                 float energy_thresh, float loading, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
+                                 uint8_t *d_sel, float *d_cov, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft,
+                                 int soft_stride) {
+  const TrxIrcArgs irc = { loading, d_cov };
+  return mlse_two_normal(c, "trxsig_mlse_irc_normal_batch: bad argument", "trxsig_mlse_irc_normal_batch: device allocation", &irc,
+                         d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, detect_thresh, energy_thresh, d_flags, d_amp, d_toa,
+                         d_avgpwr, d_sel, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
 }
 
 // ---- equaliser path (sps = 1) ------------------------------------------------------------------------

@@ -164,6 +164,11 @@ int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const i
                             const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
                             const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan, int32_t *d_win,
                             float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+// trxsig_mlse_irc_batch likewise (trxsig_trxgroup_combine_irc)
+int trx_ctx_mlse_irc_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
+                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
+                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, float loading, const float *d_cov_in,
+                            float *d_cov, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 // the receive front end's side of a fused push (trxsig_frontend.cpp): which bursts this push completes and how the kernels
 // find their samples (begin), and the window / clock bookkeeping once the kernels are enqueued (end)
 struct trxsig_rxfe;

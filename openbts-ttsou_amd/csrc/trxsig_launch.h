@@ -123,6 +123,14 @@ hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, con
                                const trx_c32 *samples1, const int32_t *off1, const int32_t *len, int B, unsigned tsc_bits, const trx_c32 *amp,
                                const float *toa, const uint8_t *primary, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
                                float *soft, uint8_t *hard, int nsoft, int stride);
+// the same with interference-rejection combining (trxsig_mlse_irc.hip; trxsig_mlse_irc_batch): loading (0..16) is added to the
+// diagonal of the estimated set; cov_in (B x 4, may be NULL = estimate) is the caller's set (A, Bv, xr, xi), cov (B x 4, may be
+// NULL) the set used.  No profiler id.
+hipError_t trx_launch_mlse_irc(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
+                               const trx_c32 *samples1, const int32_t *off1, const int32_t *len, int B, unsigned tsc_bits, const trx_c32 *amp,
+                               const float *toa, const uint8_t *primary, const uint8_t *flags, int need_mask, float loading,
+                               const float *cov_in, float *cov, trx_c32 *chan, int32_t *win, float *soft, uint8_t *hard, int nsoft,
+                               int stride);
 // the selection rule of trxsig_mlse_div_normal_batch, v_a = (valid_a[b] & need_mask) != 0: sel (0, 1, 2 = neither); the selected
 // antenna's amp, TOA, flags byte and avgPwr (antenna 0's where neither); valid[b] = need_mask where sel < 2 else 0.  Every output,
 // and with flags / pwr their inputs, may be NULL.

@@ -1,5 +1,6 @@
-// trxsig_mlse_dev.h -- device code the two sequence-equaliser kernels share (k_mlse, trxsig_mlse.hip; k_mlse_div,
-// trxsig_mlse_div.hip): the row permute, the expected values of a branch, its metric and the demodulator's slicer.
+// trxsig_mlse_dev.h -- device code the sequence-equaliser kernels share (k_mlse, trxsig_mlse.hip; k_mlse_div,
+// trxsig_mlse_div.hip; k_mlse_irc, trxsig_mlse_irc.hip): the row permute, the expected values of a branch, its metric, the
+// whitening of the second antenna and the demodulator's slicer.
 // Numerical contract as everywhere: one float32 operation at a time, nothing fused (-ffp-contract=off).
 #pragma once
 #include "trxsig_demod.h"
@@ -24,6 +25,11 @@ __device__ __forceinline__ cx mlse_expected(const cx (&g)[5], int x) {
 __device__ __forceinline__ float mlse_gamma(cx y, cx z) {
   const float dr = y.r - z.r, di = y.i - z.i;
   return dr * dr + di * di;
+}
+// k_mlse_irc's whitening of antenna 1 (trxsig_mlse_irc.hip; the LDL form, no square root): A v1 - conj(x) v0, x = xr + i xi, as
+// A*v1.re - (xr*v0.re + xi*v0.im) and A*v1.im - (xr*v0.im - xi*v0.re), one float32 operation at a time
+__device__ __forceinline__ cx mlse_whiten(float A, float xr, float xi, cx v0, cx v1) {
+  return mk(A * v1.r - (xr * v0.r + xi * v0.i), A * v1.i - (xr * v0.i - xi * v0.r));
 }
 // the demodulator's slicer on a symbol (vectorSlicer, sigProcLib.cpp:513-515; see demod_core)
 __device__ __forceinline__ float mlse_slice(float re) {

@@ -615,25 +615,29 @@ int trxsig_trxgroup_pull_rxfe(trxsig_trxgroup *g, trxsig_rxfe *fe, const int16_t
   return trx_rxfe_fused_end(fe, d_iq, n_chunks, p);
 }
 
-int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
-                                uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win, trxsig_trxgroup_result *res) {
+// trxsig_trxgroup_combine_div (irc == false) and trxsig_trxgroup_combine_irc: the checks, the selection, the access-burst rows and
+// the result are one; the training-sequence rows go through k_mlse_div or through k_mlse_irc with an estimated set
+static int combine_two(const char *name, bool irc, float loading, trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1,
+                       const trxsig_c32 *d_samples1, uint8_t *d_sel, float *d_cov, trxsig_c32 *d_chan, int32_t *d_win,
+                       trxsig_trxgroup_result *res) {
   if (!g0 || !g1) return TRXSIG_EINVAL;
   trxsig_ctx *c = g0->c;
   const char *why = nullptr;
-  if (g1->c != c) why = "trxsig_trxgroup_combine_div: the two groups live on different contexts";
-  else if (g0 == g1 || !d_samples0 || !d_samples1 || !res) why = "trxsig_trxgroup_combine_div: bad argument";
-  else if (g0->S != g1->S) why = "trxsig_trxgroup_combine_div: the groups have different ARFCN counts";
+  if (g1->c != c) why = ": the two groups live on different contexts";
+  else if (g0 == g1 || !d_samples0 || !d_samples1 || !res) why = ": bad argument";
+  else if (g0->S != g1->S) why = ": the groups have different ARFCN counts";
   else if (g0->leg == TRXSIG_TSCLEG_EQUALIZE || g1->leg == TRXSIG_TSCLEG_EQUALIZE)
-    why = "trxsig_trxgroup_combine_div: a group on TRXSIG_TSCLEG_EQUALIZE (its taps are one antenna's)";
-  else if (!g0->have || !g1->have) why = "trxsig_trxgroup_combine_div: a group has had no pull";
-  else if (g0->last_fused || g1->last_fused) why = "trxsig_trxgroup_combine_div: a pull came through trxsig_trxgroup_pull_rxfe's fused source";
+    why = ": a group on TRXSIG_TSCLEG_EQUALIZE (its taps are one antenna's)";
+  else if (!g0->have || !g1->have) why = ": a group has had no pull";
+  else if (g0->last_fused || g1->last_fused) why = ": a pull came through trxsig_trxgroup_pull_rxfe's fused source";
   else if (g0->last_fn != g1->last_fn || g0->last_tn != g1->last_tn || g0->n_slots != g1->n_slots)
-    why = "trxsig_trxgroup_combine_div: the groups' last pulls are for different times or slots";
+    why = ": the groups' last pulls are for different times or slots";
   else if (g0->n_rows != g1->n_rows || g0->n_tsc_rows != g1->n_tsc_rows || std::memcmp(g0->last_base, g1->last_base, sizeof g0->last_base) != 0)
-    why = "trxsig_trxgroup_combine_div: the groups' rows differ (slot types or training sequences)";
+    why = ": the groups' rows differ (slot types or training sequences)";
   else if (g0->last_listed != g1->last_listed || (!g0->last_listed && g0->last_burst_len != g1->last_burst_len))
-    why = "trxsig_trxgroup_combine_div: the groups' bursts have different lengths";
-  if (why) return trx_ctx_fail(c, TRXSIG_EINVAL, why, hipSuccess);
+    why = ": the groups' bursts have different lengths";
+  if (!why && irc && !(loading >= 0.0f && loading <= 16.0f)) why = ": loading outside 0..16";
+  if (why) return trx_ctx_fail(c, TRXSIG_EINVAL, (std::string(name) + why).c_str(), hipSuccess);
   TrxDeviceGuard gd(trxsig_device(c));
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   G_LIB(join_side(g0, st));
@@ -648,7 +652,7 @@ int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples
     TRX_HIPCHK(c, hipMemcpyAsync(l0.data(), W0.len.p, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToHost, st));
     TRX_HIPCHK(c, hipMemcpyAsync(l1.data(), W1.len.p, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToHost, st));
     TRX_HIPCHK(c, hipStreamSynchronize(st));
-    if (l0 != l1) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_combine_div: the groups' bursts have different lengths", hipSuccess);
+    if (l0 != l1) return trx_ctx_fail(c, TRXSIG_EINVAL, (std::string(name) + ": the groups' bursts have different lengths").c_str(), hipSuccess);
   }
   trxsig_trxgroup::Div &D = g0->div;
   TRX_HIPCHK(c, D.valid.need(R, st)); TRX_HIPCHK(c, D.sel.need(R, st)); TRX_HIPCHK(c, D.flags.need(R, st)); TRX_HIPCHK(c, D.amp.need(R, st));
@@ -662,18 +666,37 @@ int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples
   for (int k = 0; k < TRXG_CLASS_RACH; k++) {               // the equaliser needs the class's training sequence: a launch per class in use
     const int b0 = g0->last_base[k], n = g0->last_base[k + 1] - b0;
     if (!n) continue;
-    G_LIB(trx_ctx_mlse_div_masked(c, d_samples0, W0.off.p + b0, d_samples1, W1.off.p + b0, W0.len.p + b0, n, k, (const trxsig_c32 *)D.amp.p + b0,
-                                  D.toa.p + b0, sel + b0, D.valid.p + b0, TRXSIG_F_DETECT, d_chan ? d_chan + (size_t)b0 * 10 : nullptr,
-                                  d_win ? d_win + b0 : nullptr, D.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
+    if (irc)
+      G_LIB(trx_ctx_mlse_irc_masked(c, d_samples0, W0.off.p + b0, d_samples1, W1.off.p + b0, W0.len.p + b0, n, k, (const trxsig_c32 *)D.amp.p + b0,
+                                    D.toa.p + b0, sel + b0, D.valid.p + b0, TRXSIG_F_DETECT, loading, nullptr,
+                                    d_cov ? d_cov + (size_t)b0 * 4 : nullptr, d_chan ? d_chan + (size_t)b0 * 10 : nullptr,
+                                    d_win ? d_win + b0 : nullptr, D.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
+    else
+      G_LIB(trx_ctx_mlse_div_masked(c, d_samples0, W0.off.p + b0, d_samples1, W1.off.p + b0, W0.len.p + b0, n, k, (const trxsig_c32 *)D.amp.p + b0,
+                                    D.toa.p + b0, sel + b0, D.valid.p + b0, TRXSIG_F_DETECT, d_chan ? d_chan + (size_t)b0 * 10 : nullptr,
+                                    d_win ? d_win + b0 : nullptr, D.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
   }
   if (n_rows > n_tsc)                                       // access bursts: selection only
     TRX_HIPCHK(c, trx_launch_div_copy_rows(st, n_rows - n_tsc, D.valid.p + n_tsc, sel + n_tsc, W0.soft.p + (size_t)n_tsc * kSoft,
                                        W1.soft.p + (size_t)n_tsc * kSoft, kSoft, D.soft.p + (size_t)n_tsc * kSoft, kSoft, kSoft,
                                        d_chan ? (trx_c32 *)d_chan + (size_t)n_tsc * 10 : nullptr, d_win ? d_win + n_tsc : nullptr));
+  if (d_cov && n_rows > n_tsc)                              // ... and no set
+    TRX_HIPCHK(c, hipMemsetAsync(d_cov + (size_t)n_tsc * 4, 0, sizeof(float) * 4 * (size_t)(n_rows - n_tsc), st));
   res->n_slots = g0->n_slots; res->n_arfcn = g0->S; res->n_rows = n_rows;
   res->d_row = W0.rowmap.p; res->d_valid = D.valid.p; res->d_flags = D.flags.p; res->d_amp = (const trxsig_c32 *)D.amp.p;
   res->d_toa = D.toa.p; res->d_avgpwr = D.avgpwr.p; res->d_threshold = W0.thr_after.p; res->d_soft = D.soft.p; res->soft_stride = kSoft;
   return TRXSIG_OK;
+}
+
+int trxsig_trxgroup_combine_div(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
+                                uint8_t *d_sel, trxsig_c32 *d_chan, int32_t *d_win, trxsig_trxgroup_result *res) {
+  return combine_two("trxsig_trxgroup_combine_div", false, 0.0f, g0, d_samples0, g1, d_samples1, d_sel, nullptr, d_chan, d_win, res);
+}
+
+int trxsig_trxgroup_combine_irc(trxsig_trxgroup *g0, const trxsig_c32 *d_samples0, trxsig_trxgroup *g1, const trxsig_c32 *d_samples1,
+                                float loading, uint8_t *d_sel, float *d_cov, trxsig_c32 *d_chan, int32_t *d_win,
+                                trxsig_trxgroup_result *res) {
+  return combine_two("trxsig_trxgroup_combine_irc", true, loading, g0, d_samples0, g1, d_samples1, d_sel, d_cov, d_chan, d_win, res);
 }
 
 int trxsig_trxgroup_collect(trxsig_trxgroup *g, uint8_t *h_valid, float *h_soft, int *h_rssi, int *h_timing, double *h_threshold) {
