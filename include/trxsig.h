@@ -238,6 +238,52 @@ int trxsig_mlse_normal_batch(trxsig_ctx *ctx,
                              float *d_avgpwr, trxsig_c32 *d_chan, int32_t *d_win,
                              float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 
+/* ---- the sequence equaliser for access bursts (csrc/trxsig_mlse_access.hip) ------------------------------------------------
+ * trxsig_mlse_access_batch: trxsig_mlse_batch's counterpart for the access burst (GSM 05.02 5.2.7): a least-squares channel
+ *   estimate of nine taps from the burst's 49 known leading symbols and ONE trellis of 39 steps over the 36 coded bits and the
+ *   three tail bits, at sps 1, 2 and 4, in one launch.  Pinned by the float32 model tests/mlse_access_model.py, which the kernel
+ *   equals word for word; the arithmetic rules are trxsig_mlse_batch's: every step is one float32 operation in the order written,
+ *   nothing fused, one correctly rounded division per soft bit.  Graded against the float64 statement tests/mlse_access_ref.py
+ *   with the a-priori bound |soft - clamp(soft64)| <= 1.001 ((2 Q + 80 P) / (8 E) + 5) 2^-24 per burst (P, Q as in
+ *   trxsig_mlse_batch, over the 39 steps; derived there).
+ *   With a[n] = 2 bit[n] - 1: bits 0..48 are the extended tail and the synchronisation sequence, 49..84 the coded bits, 85..87 are 0.
+ *   1. Symbols.  y[0..147] is step 1 of trxsig_mlse_batch with the amplitude and TOA detectRACHBurst reports; that TOA is relative
+ *      to the start of the burst, so a[n] sits at y[n].
+ *   2. Channel.  The model of the burst is y[n] = sum_{d=-4..4} c[d] a[n-d]; for the 41 positions n = 4..44 all nine symbols are
+ *      known.  With A[n-4][d+4] = a[n-d] (41 x 9), G = A^T A (integer: diagonal 41, off-diagonals of magnitude <= 5, condition
+ *      number 1.8), N = adj(G) A^T and det = det(G) exact integers below 2^53:
+ *          P32[d+4][j] = (float)((double)N[d+4][j] / (double)det)       (csrc/trxsig_mlse_access_tab.h; |P32| < 0.04)
+ *          c[d].re = sum_{j=0..40} P32[d+4][j] * y[4+j].re, the sum starts from 0, j ascending, one multiply and one add per
+ *      term; c[d].im likewise.  p[d], E_w, the scan w = 0, -1, .., -4 with a strict >, h[k] = c[w+k] and E = E_w are
+ *      trxsig_mlse_batch's step 2.  The estimator's noise gain is 0.0248 to 0.0258 per tap (1/16 = 0.0625 for the normal burst's).
+ *   3. One trellis of 16 states and 39 steps: state, branch index, Z[x] and the metric as in trxsig_mlse_batch, g = h.  Step
+ *      i = 0..38 is symbol m = 49 + i on y[m+w]; the start state is a[48], a[47], a[46], a[45] (bit 0 first); for i >= 36 a
+ *      branch with b = 1 costs +inf.  alpha, beta, T and M_b word for word as there.
+ *   4. soft[m] = clamp(0.5f + (M_0 - M_1) / (8.0f * E), 0, 1) for m = 49..87; the three tail bits come out as exactly 0.
+ *      Positions 0..48 and 88..147 carry the demodulator's formula clamp((y.re + 1) * 0.5).  hard = soft > 0.5F.
+ *   5. Fall back and skip exactly as trxsig_mlse_batch: the demodulator's formula on all of y when length/sps < 148, when a
+ *      component of y fails fabsf(v) < 0x1p30f, or when E == 0; a burst k_demod's geometry test refuses, or d_enable[b] == 0,
+ *      is skipped.  Every metric stays finite under that guard: |c| components <= 41 * 0.04 * 2^30 < 2^31, so |Z| components
+ *      < 5 * 2^31 < 2^34, a branch metric < 2 * (2^34 + 2^30)^2 < 2^70, 39 of them and one more sum < 2^77, and E < 10 * 2^62 < 2^66.
+ *   d_chan / d_win / d_soft / d_hard / nsoft (<= 148) / soft_stride: as trxsig_mlse_batch.  Refusals are trxsig_mlse_batch's.
+ * trxsig_mlse_rach_batch: trxsig_detect_demod_rach_batch's detector (flags, amp, TOA and avgPwr are that call's, bit for bit, in
+ *   either soft mode), then the equaliser on the bursts flagged TRXSIG_F_DETECT; the others get zeros and d_win = 2.
+ * trxsig_mlse_access_pinv_host: P32, row d + 4 first, to the caller's 9 * 41 floats. */
+int trxsig_mlse_access_batch(trxsig_ctx *ctx,
+                             const trxsig_c32 *d_samples, const int32_t *d_offset,
+                             const int32_t *d_length, int B,
+                             const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable,
+                             trxsig_c32 *d_chan, int32_t *d_win,
+                             float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+int trxsig_mlse_rach_batch(trxsig_ctx *ctx,
+                           const trxsig_c32 *d_samples, const int32_t *d_offset,
+                           const int32_t *d_length, int B,
+                           float detect_thresh, float energy_thresh,
+                           uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa,
+                           float *d_avgpwr, trxsig_c32 *d_chan, int32_t *d_win,
+                           float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+int trxsig_mlse_access_pinv_host(float out[9 * 41]);
+
 /* ---- two-antenna receive diversity for the sequence equaliser (csrc/trxsig_mlse_div.hip) ------------------------------------
  * trxsig_mlse_div_batch: trxsig_mlse_batch on two receive antennas -- one channel window for both, the branch metric summed over
  *   both: maximal-ratio combining inside the trellis.  Both branches are assumed to have the same noise power (a common scale

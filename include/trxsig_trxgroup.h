@@ -43,7 +43,8 @@ typedef struct trxsig_trxgroup trxsig_trxgroup;
  * (Transceiver/Transceiver.cpp as written; needs a context with sps == 1) or TRXSIG_TSCLEG_DEMOD (see
  * trxsig_trx_set_tsc_leg; any sps) or TRXSIG_TSCLEG_MLSE (any sps): the demodulating leg's state machine -- no channel cache,
  * set_beside_rows / set_pipelined as there -- with the training-sequence rows' soft bits from trxsig_mlse_batch (a launch per TSC
- * class in use, on the rows demodulateBurst would have taken); access bursts go through demodulateBurst as before, and
+ * class in use, on the rows demodulateBurst would have taken); access bursts go through demodulateBurst as before (or through
+ * their own sequence equaliser: trxsig_trxgroup_set_rach_leg), and
  * trxsig_trxgroup_pull_rxfe takes the push / pop route.  Every ARFCN starts as Transceiver::Transceiver leaves it (:58-92): all slots
  * NONE, TSC 0, threshold 250.0, prevFalseDetectionTime = channelEstimateTime[] = (start_fn, start_tn). */
 int trxsig_trxgroup_create(trxsig_trxgroup **out, trxsig_ctx *ctx, int n_arfcn, int tsc_leg, int start_fn, int start_tn);
@@ -161,6 +162,14 @@ int trxsig_trxgroup_set_pipelined(trxsig_trxgroup *g, int on);
  * least `rows` (slot, ARFCN) rows; 0 = never (the default since round 4: a long call's replay is parallel in time and one stream
  * is faster).  An implementation choice for A/B measurements and for pipelined mode; same values either way. */
 int trxsig_trxgroup_set_beside_rows(trxsig_trxgroup *g, int rows);
+/* What turns an access-burst row (rows n_tsc..n_rows of a pull) into soft bits.  TRXSIG_RACHLEG_DEMOD, the default: demodulateBurst,
+ * as the reference does; with it nothing changes by a byte.  TRXSIG_RACHLEG_MLSE: trxsig_mlse_access_batch (trxsig.h) on the same
+ * rows, with the same gate and the group's own amplitude and TOA -- the access burst's counterpart of TRXSIG_TSCLEG_MLSE, on any of
+ * the three tsc legs and with set_beside_rows / set_pipelined; everything but the soft bits of access-burst rows is unchanged.
+ * trxsig_trxgroup_pull_rxfe then takes the push / pop route, as for every leg but the fused demodulating one; the combine calls
+ * take their access rows from the selected group as before.  Holds from the next pull on.  TRXSIG_EINVAL for any other value. */
+enum { TRXSIG_RACHLEG_DEMOD = 0, TRXSIG_RACHLEG_MLSE = 1 };
+int trxsig_trxgroup_set_rach_leg(trxsig_trxgroup *g, int rach_leg);
 /* Which pulls on a fused front end (trxsig_trxgroup_pull_fused) detect their access bursts BESIDE their normal bursts: those with at
  * least `rows` rows that hold both kinds (the access-burst class goes first on the context's stream, the normal-burst classes
  * follow on the group's side stream and are joined before the state machine; two cross-stream hops of ~10 us are what it costs).

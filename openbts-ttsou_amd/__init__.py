@@ -342,6 +342,34 @@ class TrxSig:
             self.h, _ptr(samples), _ptr(offset), _ptr(length), B, tsc, detect_thresh, energy_thresh, _ptr(flags), _ptr(amp),
             _ptr(toa), _ptr(avgpwr), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_normal_batch")
 
+    def mlse_access(self, samples, offset, length, amp, toa, soft, enable=None, chan=None, win=None, hard=None, nsoft=148,
+                    soft_stride=None):
+        """The sequence equaliser for access bursts with the caller's amp / TOA (trxsig_mlse_access_batch): chan [B, 5] complex,
+        win [B] int32."""
+        B = offset.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_access_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, _ptr(amp), _ptr(toa),
+                                                  _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride),
+                  "trxsig_mlse_access_batch")
+
+    def mlse_rach(self, samples, offset, length, flags, amp, toa, soft, avgpwr=None, chan=None, win=None, hard=None,
+                  detect_thresh=5.0, energy_thresh=0.0, nsoft=148, soft_stride=None):
+        """detect_demod_rach's detector, then the access-burst sequence equaliser on the detected bursts (trxsig_mlse_rach_batch)."""
+        B = offset.numel() if hasattr(offset, "numel") else len(offset)
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_rach_batch(
+            self.h, _ptr(samples), _ptr(offset), _ptr(length), B, detect_thresh, energy_thresh, _ptr(flags), _ptr(amp),
+            _ptr(toa), _ptr(avgpwr), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_rach_batch")
+
+    def mlse_access_pinv(self):
+        """The access-burst equaliser's least-squares table P32 [9, 41] float32, from the library (trxsig_mlse_access_pinv_host)."""
+        import numpy as np
+        out = np.zeros((9, 41), np.float32)
+        self._chk(self.L.trxsig_mlse_access_pinv_host(out.ctypes.data), "trxsig_mlse_access_pinv_host")
+        return out
+
     def mlse_div(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, chan=None,
                  win=None, hard=None, nsoft=148, soft_stride=None):
         """The sequence equaliser over two receive antennas with the caller's amp / TOA (trxsig_mlse_div_batch): one amp / TOA per
@@ -775,6 +803,7 @@ class TrxHost(_Object):
 
 
 TSCLEG_EQUALIZE, TSCLEG_DEMOD, TSCLEG_MLSE = 0, 1, 2
+RACHLEG_DEMOD, RACHLEG_MLSE = 0, 1
 
 
 class TrxGroup(_Object):
@@ -913,6 +942,10 @@ class TrxGroup(_Object):
     def set_beside_rows(self, rows):
         """Pulls with at least `rows` rows replay the state machine on the group's side stream (0 = never, the default)."""
         self._call("set_beside_rows", int(rows))
+
+    def set_rach_leg(self, rach_leg):
+        """RACHLEG_DEMOD (the default: demodulateBurst) or RACHLEG_MLSE (trxsig_mlse_access_batch) for the access-burst rows."""
+        self._call("set_rach_leg", int(rach_leg))
 
     def set_split_rows(self, rows):
         """Fused pulls with at least `rows` rows and both kinds of burst detect the access bursts beside the normal ones (0 = never)."""

@@ -129,6 +129,9 @@ SIGNATURES = {
     "trxsig_get_soft_mode": (i32, [vp]),
     "trxsig_mlse_batch": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_normal_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
+    "trxsig_mlse_access_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
+    "trxsig_mlse_rach_batch": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
+    "trxsig_mlse_access_pinv_host": (i32, [vp]),
     "trxsig_mlse_div_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_div_normal_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_irc_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32]),
@@ -245,6 +248,7 @@ SIGNATURES = {
     "trxsig_trxgroup_pull_host": (i32, [vp, vp, i64, i64, i32, i32, i32, i32]),
     "trxsig_trxgroup_set_pipelined": (i32, [vp, i32]),
     "trxsig_trxgroup_set_beside_rows": (i32, [vp, i32]),
+    "trxsig_trxgroup_set_rach_leg": (i32, [vp, i32]),
     "trxsig_trxgroup_set_split_rows": (i32, [vp, i32]),
     "trxsig_trxgroup_sync": (i32, [vp]),
     "trxsig_trxgroup_energy_threshold": (i32, [vp, i32, P(f64)]),

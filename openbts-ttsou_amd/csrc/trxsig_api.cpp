@@ -18,6 +18,7 @@
 #include "trxsig_ctx.h"
 #include "trxsig_launch.h"
 #include "trxsig_tablegen.h"
+#include "trxsig_mlse_access_tab.h"   // the host's copy of the access-burst equaliser's table (trxsig_mlse_access_pinv_host)
 
 // kernel ids the profiler knows: the TRXSIG_K_COUNT of ABI 2, then the ones appended since (trxsig.h)
 constexpr int kKernels = TRXSIG_K_GROUP_TX_GRID + 1;
@@ -719,6 +720,19 @@ int trx_ctx_mlse_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_
                             d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
   return TRXSIG_OK;
 }
+// trxsig_mlse_access_batch with the enable test spelt out (the group's TRXSIG_RACHLEG_MLSE)
+int trx_ctx_mlse_access_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                               const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
+                               int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples, d_offset, d_length, B) || nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_access_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_mlse_access(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, (const trx_c32 *)d_amp,
+                                   d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+  return TRXSIG_OK;
+}
 // trxsig_mlse_div_batch with the enable test spelt out (trxsig_trxgroup_combine_div: a launch per TSC class)
 int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
                             const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
@@ -821,6 +835,34 @@ int trxsig_mlse_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const i
   if (rc != TRXSIG_OK) return rc;
   return trx_ctx_mlse_masked(c, d_samples, d_offset, d_length, B, tsc, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard,
                              nsoft, soft_stride);
+}
+
+// ---- the sequence equaliser for access bursts (trxsig_mlse_access.hip) ----
+int trxsig_mlse_access_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                             const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win,
+                             float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  return trx_ctx_mlse_access_masked(c, d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft,
+                                    soft_stride);
+}
+
+int trxsig_mlse_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                           float detect_thresh, float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
+                           trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && !d_soft))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_rach_batch: bad argument");
+  // the detector alone (nsoft = 0: no demodulator, whatever the soft mode), then the equaliser on the bursts it flagged
+  const int rc = trxsig_detect_demod_rach_batch(c, d_samples, d_offset, d_length, B, detect_thresh, energy_thresh, d_flags, d_amp, d_toa, d_avgpwr,
+                                                nullptr, nullptr, 0, 0);
+  if (rc != TRXSIG_OK) return rc;
+  return trx_ctx_mlse_access_masked(c, d_samples, d_offset, d_length, B, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard,
+                                    nsoft, soft_stride);
+}
+
+int trxsig_mlse_access_pinv_host(float out[9 * 41]) {
+  if (!out) return TRXSIG_EINVAL;
+  std::memcpy(out, trx_mlse_access_p32, sizeof trx_mlse_access_p32);
+  return TRXSIG_OK;
 }
 
 // ---- two-antenna receive diversity for the sequence equaliser (trxsig_mlse_div.hip) ----

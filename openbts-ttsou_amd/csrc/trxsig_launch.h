@@ -117,6 +117,11 @@ hipError_t trx_launch_demod(hipStream_t st, int sps, const TrxTables *dT, const 
 hipError_t trx_launch_mlse(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len, int B,
                            unsigned tsc_bits, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan,
                            int32_t *win, float *soft, uint8_t *hard, int nsoft, int stride);
+// the sequence equaliser for access bursts (trxsig_mlse_access.hip; trxsig_mlse_access_batch): trx_launch_mlse's arguments without
+// the training sequence (the burst's 49 leading symbols are fixed).  No profiler id.
+hipError_t trx_launch_mlse_access(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
+                                  int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
+                                  float *soft, uint8_t *hard, int nsoft, int stride);
 // the same over two antennas (trxsig_mlse_div.hip; trxsig_mlse_div_batch): a sample pointer and an offset array per antenna, one
 // amp / TOA per burst, primary (may be NULL = 0) the antenna they came from; chan is B x 2 x 5.  No profiler id.
 hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,

@@ -52,6 +52,7 @@ struct DevBuf {                                             // grow-only device 
 struct trxsig_trxgroup {
   trxsig_ctx *c = nullptr;
   int S = 0, sps = 1, leg = TRXSIG_TSCLEG_EQUALIZE;
+  int rach_leg = TRXSIG_RACHLEG_DEMOD;   // trxsig_trxgroup_set_rach_leg: what turns a gated access-burst row into soft bits
   std::vector<TrxControl> ctl;
   // segment tables, re-derived when a SETSLOT / SETTSC changed something
   bool dirty = true;
@@ -520,7 +521,11 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
     TrxRxGen gen = *src.gen;
     gen.sel = W.off.p;
     G_LIB(trx_ctx_rx_demod(c, gen, n_rows, (const trxsig_c32 *)W.amp.p, W.toa.p, demod_gate, TRXSIG_F_DETECT, W.soft.p, kSoft, kSoft));
-  } else if (n_rows > n_tsc)                                // :385-388
+  } else if (n_rows > n_tsc && g->rach_leg == TRXSIG_RACHLEG_MLSE)   // the same rows, gate and stride through the access-burst sequence equaliser
+    G_LIB(trx_ctx_mlse_access_masked(c, d_samples, W.off.p + n_tsc, W.len.p + n_tsc, n_rows - n_tsc, (const trxsig_c32 *)W.amp.p + n_tsc,
+                                     W.toa.p + n_tsc, demod_gate + n_tsc, TRXSIG_F_DETECT, nullptr, nullptr, W.soft.p + (size_t)n_tsc * kSoft,
+                                     nullptr, kSoft, kSoft));
+  else if (n_rows > n_tsc)                                  // :385-388
     G_LIB(trx_ctx_demod_masked(c, d_samples, W.off.p + n_tsc, W.len.p + n_tsc, n_rows - n_tsc, (const trxsig_c32 *)W.amp.p + n_tsc,
                                W.toa.p + n_tsc, demod_gate + n_tsc, TRXSIG_F_DETECT, W.soft.p + (size_t)n_tsc * kSoft, kSoft, kSoft));
   if (piped) {
@@ -580,9 +585,9 @@ int trxsig_trxgroup_pull_rxfe(trxsig_trxgroup *g, trxsig_rxfe *fe, const int16_t
   if (!fe || !n_slots || fn < 0 || fn >= kHyperframe) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_rxfe: bad argument", hipSuccess);
   if (trx_rxfe_ctx(fe) != c) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_rxfe: the front end lives on another context", hipSuccess);
   const bool wide = trx_rxfe_rate_factor(fe) > 0;
-  if (g->leg != TRXSIG_TSCLEG_DEMOD || g->sps != 4 || wide) {
+  if (g->leg != TRXSIG_TSCLEG_DEMOD || g->rach_leg != TRXSIG_RACHLEG_DEMOD || g->sps != 4 || wide) {
     // The fused front end is the 260 : 96 resampler feeding the demodulating leg.  Everything else -- the equalising leg at one
-    // sample per symbol, the reference's own configuration, and the wideband channeliser -- goes through the resampled stream:
+    // sample per symbol, the reference's own configuration, the sequence equalisers and the wideband channeliser -- goes through the resampled stream:
     // push, pop, and the group on the bursts the pop lists (same results as the fused form where both exist:
     // tests/test_gpu_trxgroup.py).
     if (trx_rxfe_streams(fe) != g->S) return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_trxgroup_pull_rxfe: one stream per ARFCN, please", hipSuccess);
@@ -771,6 +776,14 @@ int trxsig_trxgroup_set_pipelined(trxsig_trxgroup *g, int on) {
   TrxDeviceGuard gd(trxsig_device(g->c));
   G_LIB(join_side(g, (hipStream_t)trxsig_get_stream(g->c)));
   g->pipelined = on != 0;
+  return TRXSIG_OK;
+}
+
+int trxsig_trxgroup_set_rach_leg(trxsig_trxgroup *g, int rach_leg) {
+  if (!g) return TRXSIG_EINVAL;
+  if (rach_leg != TRXSIG_RACHLEG_DEMOD && rach_leg != TRXSIG_RACHLEG_MLSE)
+    return trx_ctx_fail(g->c, TRXSIG_EINVAL, "trxsig_trxgroup_set_rach_leg: TRXSIG_RACHLEG_DEMOD or TRXSIG_RACHLEG_MLSE", hipSuccess);
+  g->rach_leg = rach_leg;                                   // (host-side switch: it holds from the next pull on)
   return TRXSIG_OK;
 }
 
