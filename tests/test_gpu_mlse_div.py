@@ -14,6 +14,7 @@ import mlse_div_ref as dref
 import mlse_family
 import mlse_ref
 import oraclebind
+from mlse_run import dev, run_div
 from util import GpuBatch, assert_veq, assert_veq_nan
 
 pytestmark = pytest.mark.gpu
@@ -32,35 +33,6 @@ def ctx(pkg):
     for v in c.values():
         v.use_torch_stream()
     return c
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.float32).copy() if a.dtype == np.complex64 else a.copy()).cuda()
-
-
-def run_div(t, f, sel=None, enable=None, primary="own", nsoft=148, stride=160, with_aux=True):
-    """trxsig_mlse_div_batch on bursts `sel` of two-antenna family f: dict(soft [B, stride], hard, chan [B, 2, 5], win [B])."""
-    import torch
-    sel = np.arange(len(f["off0"])) if sel is None else np.asarray(sel)
-    B = len(sel)
-    gb = GpuBatch(f["x0"], f["off0"][sel], f["length"][sel], nsoft=nsoft, stride=stride)
-    x1, off1 = dev(np.ascontiguousarray(f["x1"], np.complex64)), dev(f["off1"][sel].astype(np.int32))
-    d_amp, d_toa = dev(f["amp"][sel]), dev(f["toa"][sel])
-    prim = f["primary"] if isinstance(primary, str) else primary
-    d_prim = None if prim is None else dev(np.asarray(prim, np.uint8)[sel])
-    d_en = None if enable is None else dev(np.asarray(enable, np.uint8)[sel])
-    chan = torch.full((B, 2, 5, 2), -7.0, dtype=torch.float32, device="cuda:0") if with_aux else None
-    win = torch.full((B,), -99, dtype=torch.int32, device="cuda:0") if with_aux else None
-    t.mlse_div(gb.x, gb.off, x1, off1, gb.len, f["tsc"], d_amp, d_toa, gb.soft, primary=d_prim, enable=d_en, chan=chan, win=win,
-               hard=gb.hard, nsoft=nsoft, soft_stride=stride)
-    r = gb.results()
-    out = dict(soft=r["soft"], hard=r["hard"])
-    if with_aux:
-        out["chan"] = chan.cpu().numpy().reshape(B, 2, 10).view(np.complex64)
-        out["win"] = win.cpu().numpy()
-    return out
 
 
 def run_one(t, x, off, length, tsc, amp, toa, enable=None):
