@@ -284,6 +284,48 @@ int trxsig_mlse_rach_batch(trxsig_ctx *ctx,
                            float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 int trxsig_mlse_access_pinv_host(float out[9 * 41]);
 
+/* ---- the sequence equaliser for synchronisation bursts (csrc/trxsig_mlse_sch.hip) ------------------------------------------
+ * trxsig_mlse_sch_batch: trxsig_mlse_batch's counterpart for the synchronisation burst (SCH, GSM 05.02 5.2.5): a least-squares
+ *   channel estimate of nine taps from the burst's 64-symbol extended training sequence and TWO half-burst trellises of 42 steps
+ *   each over the 39 coded bits and the three tail bits of a side, at sps 1, 2 and 4, in one launch.  Pinned by the float32 model
+ *   tests/mlse_sch_model.py, which the kernel equals word for word; the arithmetic rules are trxsig_mlse_batch's: every step is
+ *   one float32 operation in the order written, nothing fused, one correctly rounded division per soft bit.  trxsig_set_soft_mode
+ *   has no bearing on it.  Graded against the float64 statement tests/mlse_sch_ref.py with the a-priori bound
+ *   |soft - clamp(soft64)| <= 1.001 ((2 Q + 86 P) / (8 E) + 5) 2^-24 per burst and half (P, Q as in trxsig_mlse_batch, over the
+ *   42 steps; derived there).
+ *   With a[n] = 2 bit[n] - 1: bits 0..2 are tail (0), 3..41 coded, 42..105 the extended training sequence XTS
+ *   (a[42 + i] = 2 XTS[i] - 1), 106..144 coded, 145..147 tail.
+ *   1. Symbols.  y[0..147] is step 1 of trxsig_mlse_batch; the TOA is relative to the start of the burst, so a[n] sits at y[n].
+ *   2. Channel.  The model of the burst is y[n] = sum_{d=-4..4} c[d] a[n-d]; for the 56 positions n = 46..101 all nine symbols are
+ *      known.  With A[n-46][d+4] = a[n-d] (56 x 9), G = A^T A (integer: diagonal 56, off-diagonals of magnitude <= 6, condition
+ *      number 1.64), N = adj(G) A^T and det = det(G) exact integers below 2^53:
+ *          P32[d+4][j] = (float)((double)N[d+4][j] / (double)det)       (csrc/trxsig_mlse_sch_tab.h; |P32| < 0.0253)
+ *          c[d].re = sum_{j=0..55} P32[d+4][j] * y[46+j].re, the sum starts from 0, j ascending, one multiply and one add per
+ *      term; c[d].im likewise.  p[d], E_w, the scan w = 0, -1, .., -4 with a strict >, h[k] = c[w+k] and E = E_w are
+ *      trxsig_mlse_batch's step 2.  The estimator's noise gain is 0.01824 to 0.01850 per tap (0.0248 for the access burst's,
+ *      1/16 = 0.0625 for the normal burst's).
+ *   3. Two independent half-burst trellises of 16 states and 42 steps: state, branch index, Z[x], the metric, alpha, beta, T and
+ *      M_b as in trxsig_mlse_batch.  Right half: g = h, steps m = 106..147 on y[m+w], start state a[105], a[104], a[103], a[102]
+ *      (bit 0 first: 11), a[145..147] = -1 known.  Left half: g[k] = h[4-k], steps m = 41..0 on y[m+4+w], start state a[42],
+ *      a[43], a[44], a[45] (13), a[0..2] = -1 known.
+ *   4. soft[m] = clamp(0.5f + (M_0 - M_1) / (8.0f * E), 0, 1) for m = 0..41 and 106..147; the six tail bits come out as exactly 0.
+ *      Positions 42..105 carry the demodulator's formula clamp((y.re + 1) * 0.5).  hard = soft > 0.5F.
+ *   5. Fall back and skip exactly as trxsig_mlse_batch: the demodulator's formula on all of y when length/sps < 148, when a
+ *      component of y fails fabsf(v) < 0x1p30f, or when E == 0; a burst k_demod's geometry test refuses, or d_enable[b] == 0,
+ *      is skipped.  Every metric stays finite under that guard: the rows of P32 sum to S1 <= 1.0001 in magnitude, so |c|
+ *      components stay below 1.0001 * 2^30 < 2^31, and from there on the access burst's chain holds with 42 steps for 39:
+ *      |Z| components < 2^34, a branch metric < 2^70, 42 of them and one more sum < 2^77, E < 2^66.
+ *   d_chan / d_win / d_soft / d_hard / nsoft (<= 148) / soft_stride: as trxsig_mlse_batch.  Refusals are trxsig_mlse_batch's.
+ *   trxsig_l1acq_set_sch_leg (trxsig_l1acq.h) puts it behind acquisition's SCH detector.
+ * trxsig_mlse_sch_pinv_host: P32, row d + 4 first, to the caller's 9 * 56 floats. */
+int trxsig_mlse_sch_batch(trxsig_ctx *ctx,
+                          const trxsig_c32 *d_samples, const int32_t *d_offset,
+                          const int32_t *d_length, int B,
+                          const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable,
+                          trxsig_c32 *d_chan, int32_t *d_win,
+                          float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+int trxsig_mlse_sch_pinv_host(float out[9 * 56]);
+
 /* ---- two-antenna receive diversity for the sequence equaliser (csrc/trxsig_mlse_div.hip) ------------------------------------
  * trxsig_mlse_div_batch: trxsig_mlse_batch on two receive antennas -- one channel window for both, the branch metric summed over
  *   both: maximal-ratio combining inside the trellis.  Both branches are assumed to have the same noise power (a common scale

@@ -125,6 +125,22 @@ int  trxsig_l1acq_detect_sch_batch(trxsig_l1acq *acq, const trxsig_c32 *d_sample
 /* the correlation sequence as built at create (host copies): seq[64 sps], its gain and TOA; any pointer may be NULL */
 int  trxsig_l1acq_sequence(const trxsig_l1acq *acq, trxsig_c32 *h_seq, trxsig_c32 *h_gain, float *h_toa);
 
+/* The SCH leg: what step 7 of stage 2 makes of a detected window.  TRXSIG_SCHLEG_DEMOD (the default): demodulateBurst, as stated
+ * above; with it every output of trxsig_l1acq_search and trxsig_l1acq_detect_sch_batch is what it was before the switch existed,
+ * byte for byte.  TRXSIG_SCHLEG_MLSE: trxsig_mlse_sch_batch (trxsig.h) in the demodulator's place, for a channel with delay
+ * spread -- on the same shifted window y[i0 : i0 + len), with the same amp and toa_b - i0 and on the same windows (the detected
+ * ones; zeros elsewhere).  Flags, amp, TOA, ptm and state bits 1, 2 and 4 do not depend on the leg; d_soft, d_hard and what the
+ * SCH decoder makes of them (d_ok, d_bsic, d_rfn, state bit 8) do.  Host-side switch, takes effect from the next call on; anything
+ * but the two values returns TRXSIG_EINVAL. */
+enum { TRXSIG_SCHLEG_DEMOD = 0, TRXSIG_SCHLEG_MLSE = 1 };
+int  trxsig_l1acq_set_sch_leg(trxsig_l1acq *acq, int leg);
+/* The channel the equalising leg estimated in the last trxsig_l1acq_search: device arrays owned by the object, d_chan
+ * [n_streams][5] taps h[0..4] and d_win [n_streams] window words (w = -4..0 equalised, 1 fell back, 2 skipped), as
+ * trxsig_mlse_sch_batch reports them.  Zeros and 2 where the last search ran on TRXSIG_SCHLEG_DEMOD, where there was none yet, or
+ * where nothing was detected (those are filled, on the context's stream, by this call).  trxsig_l1acq_detect_sch_batch leaves them
+ * alone: a caller who wants the taps of caller-chosen windows calls trxsig_mlse_sch_batch. */
+int  trxsig_l1acq_sch_channel(trxsig_l1acq *acq, const trxsig_c32 **d_chan, const int32_t **d_win);
+
 #ifdef __cplusplus
 }
 #endif

@@ -370,6 +370,24 @@ class TrxSig:
         self._chk(self.L.trxsig_mlse_access_pinv_host(out.ctypes.data), "trxsig_mlse_access_pinv_host")
         return out
 
+    def mlse_sch(self, samples, offset, length, amp, toa, soft, enable=None, chan=None, win=None, hard=None, nsoft=148,
+                 soft_stride=None):
+        """The sequence equaliser for synchronisation bursts with the caller's amp / TOA (trxsig_mlse_sch_batch): chan [B, 5]
+        complex, win [B] int32."""
+        B = offset.numel()
+        if soft_stride is None:
+            soft_stride = soft.shape[-1]
+        self._chk(self.L.trxsig_mlse_sch_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, _ptr(amp), _ptr(toa),
+                                               _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride),
+                  "trxsig_mlse_sch_batch")
+
+    def mlse_sch_pinv(self):
+        """The synchronisation-burst equaliser's least-squares table P32 [9, 56] float32, from the library (trxsig_mlse_sch_pinv_host)."""
+        import numpy as np
+        out = np.zeros((9, 56), np.float32)
+        self._chk(self.L.trxsig_mlse_sch_pinv_host(out.ctypes.data), "trxsig_mlse_sch_pinv_host")
+        return out
+
     def mlse_div(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, chan=None,
                  win=None, hard=None, nsoft=148, soft_stride=None):
         """The sequence equaliser over two receive antennas with the caller's amp / TOA (trxsig_mlse_div_batch): one amp / TOA per
@@ -1189,6 +1207,7 @@ class L1MsRx(_PlanObject):
 ACQ_FCCH, ACQ_WINDOW, ACQ_SCH, ACQ_DECODED = 1, 2, 4, 8   # trxsig_l1acq_out.d_state bits (TRXSIG_ACQ_*)
 ACQ_FCCH_THRESH, ACQ_SCH_THRESH = 0.5, 8.0                # TRXSIG_L1ACQ_FCCH_THRESH / _SCH_THRESH
 ACQ_MAX_WINDOW = 256                                      # TRXSIG_L1ACQ_MAX_WINDOW (symbols)
+SCHLEG_DEMOD, SCHLEG_MLSE = 0, 1                          # TRXSIG_SCHLEG_*
 
 
 class L1Acq(_Object):
@@ -1222,6 +1241,21 @@ class L1Acq(_Object):
         soft [B, >= 148] are written; omega float32 [B] (None: no frequency shift), ptm float32 [B], hard uint8 [B, stride]."""
         self._call("detect_sch_batch", _ptr(samples), _ptr(offset), _ptr(length), offset.numel(), _ptr(omega), float(detect_thresh),
                    _ptr(flags), _ptr(amp), _ptr(toa), _ptr(ptm), _ptr(soft), _ptr(hard), soft_stride or soft.shape[-1])
+
+    def set_sch_leg(self, sch_leg):
+        """SCHLEG_DEMOD (the default: demodulateBurst) or SCHLEG_MLSE (trxsig_mlse_sch_batch) behind the SCH detector."""
+        self._call("set_sch_leg", int(sch_leg))
+
+    def sch_channel(self):
+        """(chan [n_streams, 5] complex64, win [n_streams] int32) of the last search as host numpy arrays: the equalising leg's
+        taps and window words; zeros and 2 on SCHLEG_DEMOD or where nothing was detected (synchronises the context's stream)."""
+        np = self.np
+        d_chan, d_win = C.c_void_p(), C.c_void_p()
+        self._call("sch_channel", C.byref(d_chan), C.byref(d_win))
+        self.ctx.synchronize()
+        S = self.out.n_streams if self.out is not None else 0
+        chan = _to_host(self.ctx, d_chan.value, (S, 10), "<f4").view(np.complex64).reshape(S, 5)
+        return chan, _to_host(self.ctx, d_win.value, (S,), "<i4")
 
     def collect(self):
         """The last search's outputs as host numpy arrays (synchronises the context's stream)."""

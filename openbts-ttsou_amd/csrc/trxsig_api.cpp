@@ -19,6 +19,7 @@
 #include "trxsig_launch.h"
 #include "trxsig_tablegen.h"
 #include "trxsig_mlse_access_tab.h"   // the host's copy of the access-burst equaliser's table (trxsig_mlse_access_pinv_host)
+#include "trxsig_mlse_sch_tab.h"      // ... and of the synchronisation-burst equaliser's (trxsig_mlse_sch_pinv_host)
 
 // kernel ids the profiler knows: the TRXSIG_K_COUNT of ABI 2, then the ones appended since (trxsig.h)
 constexpr int kKernels = TRXSIG_K_GROUP_TX_GRID + 1;
@@ -733,6 +734,19 @@ int trx_ctx_mlse_access_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const
                                    d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
   return TRXSIG_OK;
 }
+// trxsig_mlse_sch_batch with the enable test spelt out (trxsig_l1acq's TRXSIG_SCHLEG_MLSE)
+int trx_ctx_mlse_sch_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                            const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
+                            int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples, d_offset, d_length, B) || nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_sch_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_mlse_sch(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, (const trx_c32 *)d_amp,
+                                d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+  return TRXSIG_OK;
+}
 // trxsig_mlse_div_batch with the enable test spelt out (trxsig_trxgroup_combine_div: a launch per TSC class)
 int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
                             const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
@@ -862,6 +876,20 @@ int trxsig_mlse_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int
 int trxsig_mlse_access_pinv_host(float out[9 * 41]) {
   if (!out) return TRXSIG_EINVAL;
   std::memcpy(out, trx_mlse_access_p32, sizeof trx_mlse_access_p32);
+  return TRXSIG_OK;
+}
+
+// ---- the sequence equaliser for synchronisation bursts (trxsig_mlse_sch.hip) ----
+int trxsig_mlse_sch_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                          const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win,
+                          float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
+  return trx_ctx_mlse_sch_masked(c, d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft,
+                                 soft_stride);
+}
+
+int trxsig_mlse_sch_pinv_host(float out[9 * 56]) {
+  if (!out) return TRXSIG_EINVAL;
+  std::memcpy(out, trx_mlse_sch_p32, sizeof trx_mlse_sch_p32);
   return TRXSIG_OK;
 }
 

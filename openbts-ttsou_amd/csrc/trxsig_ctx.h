@@ -163,6 +163,10 @@ int trx_ctx_mlse_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_
 int trx_ctx_mlse_access_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                                const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
                                int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+// trxsig_mlse_sch_batch likewise (trxsig_l1acq's TRXSIG_SCHLEG_MLSE: the windows of stage 2)
+int trx_ctx_mlse_sch_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                            const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
+                            int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 // trxsig_mlse_div_batch likewise (trxsig_trxgroup_combine_div)
 int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
                             const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,

@@ -1,7 +1,8 @@
 // trxsig_l1acq.cpp -- the acquisition object's host side (include/trxsig_l1acq.h): the SCH correlation sequence built once with
 // the table generator's restatements, the per-stream arrays and the stage-2 workspace on the device, and per call the launches
 // on the context's stream: k_l1acq_fcch, k_l1acq_pick, k_l1acq_shift, the correlation over every lag and peakDetect
-// (trxsig_prim.hip), k_l1acq_verdict, the exact demodulator, the SCH decode (k_fec_viterbi's SCH mode), k_l1acq_finish.
+// (trxsig_prim.hip), k_l1acq_verdict, the exact demodulator -- or, on TRXSIG_SCHLEG_MLSE, the synchronisation burst's sequence
+// equaliser (trxsig_mlse_sch.hip) in its place --, the SCH decode (k_fec_viterbi's SCH mode), k_l1acq_finish.
 #include <hip/hip_runtime_api.h>
 
 #include <cstring>
@@ -40,6 +41,11 @@ struct trxsig_l1acq {
   trx_c32 *y = nullptr, *corr = nullptr, *peak = nullptr;
   float *pidx = nullptr, *dtoa = nullptr;
   int32_t *woff = nullptr, *wlen = nullptr, *doff = nullptr, *dlen = nullptr;
+  // the SCH leg (trxsig_l1acq_set_sch_leg) and what the equalising leg's last search left: taps [max_streams][5], window words
+  int sch_leg = TRXSIG_SCHLEG_DEMOD;
+  trx_c32 *chan = nullptr;
+  int32_t *win = nullptr;
+  bool chan_valid = false;             // false: the arrays are filled (zeros, 2) when trxsig_l1acq_sch_channel next asks for them
 };
 
 namespace {
@@ -65,7 +71,7 @@ int ensure_work(trxsig_l1acq *a, int B) {
 // stage 2 on B windows already described by (base64 | off32, len): everything after the window set-up
 int stage2(trxsig_l1acq *a, const trxsig_c32 *d_samples, const long long *base64, const int32_t *off32, const int32_t *len,
            const float *omega, int B, float thresh, int search, uint8_t *flags, trxsig_c32 *amp, float *toa, float *ptm, float *soft,
-           uint8_t *hard, int soft_stride, uint8_t *state) {
+           uint8_t *hard, int soft_stride, uint8_t *state, trx_c32 *chan, int32_t *win) {
   trxsig_ctx *c = a->c;
   hipStream_t st = (hipStream_t)trxsig_get_stream(c);
   const TrxTables *dT = (const TrxTables *)trxsig_tables_device(c);
@@ -77,6 +83,12 @@ int stage2(trxsig_l1acq *a, const trxsig_c32 *d_samples, const long long *base64
   TRX_HIPCHK(c, trx_launch_peak_detect(st, dT, a->corr, a->woff, a->wlen, B, a->peak, a->pidx, nullptr));
   TRX_HIPCHK(c, trx_launch_l1acq_verdict(st, sps, a->corr, a->wlen, a->peak, a->pidx, B, a->gain, a->seq_toa, thresh, search, flags,
                                          (trx_c32 *)amp, toa, ptm, a->doff, a->dlen, a->dtoa, state));
+  // TRXSIG_SCHLEG_MLSE: the equaliser on the same shifted windows, amplitudes, TOAs and mask, in the demodulator's place
+  if (a->sch_leg == TRXSIG_SCHLEG_MLSE) {
+    TRX_HIPCHK(c, trx_launch_mlse_sch(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, chan, win,
+                                      soft, hard, kSoft, soft_stride));
+    return TRXSIG_OK;
+  }
   // acquisition always demodulates with the exact arithmetic, whatever trxsig_set_soft_mode says
   TRX_HIPCHK(c, trx_launch_demod(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, soft,
                                  hard, kSoft, soft_stride, prof, TRXSIG_SOFT_EXACT));
@@ -105,7 +117,8 @@ int trxsig_l1acq_create(trxsig_l1acq **out, trxsig_ctx *c, int max_streams, int 
   const TrxCarve cv = { a->h_seq.size() * sizeof(trx_c32),
                         S, S * 4, S * 4, S * 8, S * 4, S * 4, S * 4, S * 4, S * 8, S * 4,        // state, k, m, c, e, arg, omega, w0, base, wlen
                         S * 4, S * 4, S * 8, S * kSoft * 4, S, S, S, S * 4,                       // ptm, toa, amp, soft, ok, bsic, flags, rfn
-                        NT * 4, NT * 4, NT * 8, NT * 4 };                                         // tiles: m, k, c, e
+                        NT * 4, NT * 4, NT * 8, NT * 4,                                           // tiles: m, k, c, e
+                        S * 5 * 8, S * 4 };                                                       // the equalising leg's taps and window words
   TrxDeviceGuard g(trxsig_device(c));
   int rc = trx_device_block(c, "trxsig_l1acq_create", cv.total, { { cv.off[0], a->h_seq.data(), a->h_seq.size() * sizeof(trx_c32) } }, &a->d_persist);
   if (rc != TRXSIG_OK) { delete a; return rc; }
@@ -118,6 +131,7 @@ int trxsig_l1acq_create(trxsig_l1acq **out, trxsig_ctx *c, int max_streams, int 
   a->ptm = cv.at<float>(b, 11); a->toa = cv.at<float>(b, 12); a->amp = cv.at<trx_c32>(b, 13); a->soft = cv.at<float>(b, 14);
   a->ok = cv.at<uint8_t>(b, 15); a->bsic = cv.at<uint8_t>(b, 16); a->flags = cv.at<uint8_t>(b, 17); a->rfn = cv.at<int32_t>(b, 18);
   a->tile_m = cv.at<float>(b, 19); a->tile_k = cv.at<int32_t>(b, 20); a->tile_c = cv.at<trx_c32>(b, 21); a->tile_e = cv.at<float>(b, 22);
+  a->chan = cv.at<trx_c32>(b, 23); a->win = cv.at<int32_t>(b, 24);
   rc = ensure_work(a, max_streams);
   if (rc != TRXSIG_OK) {
     if (a->work.p) (void)hipFree(a->work.p);
@@ -160,8 +174,9 @@ int trxsig_l1acq_search(trxsig_l1acq *a, const trxsig_c32 *d_samples, int64_t st
   TRX_HIPCHK(c, trx_launch_l1acq_pick(st, a->sps, stream_stride, n_samples, n_streams, n_tiles, a->tile_m, a->tile_k, a->tile_c,
                                       a->tile_e, fcch_thresh, s));
   const int rc = stage2(a, d_samples, s.base, nullptr, s.wlen, s.omega, n_streams, sch_thresh, 1, a->flags, (trxsig_c32 *)a->amp, a->toa,
-                        a->ptm, a->soft, nullptr, kSoft, s.state);
+                        a->ptm, a->soft, nullptr, kSoft, s.state, a->chan, a->win);
   if (rc != TRXSIG_OK) return rc;
+  a->chan_valid = a->sch_leg == TRXSIG_SCHLEG_MLSE;
   TRX_HIPCHK(c, trx_launch_fec(st, TRX_FEC_MODE_SCH, a->soft, kSoft, 78, 39, n_streams, 0, a->ok, a->bsic, reinterpret_cast<uint8_t *>(a->rfn), 0,
                                trx_ctx_profiler(c)));
   TRX_HIPCHK(c, trx_launch_l1acq_finish(st, n_streams, a->ok, s.state));
@@ -184,5 +199,28 @@ int trxsig_l1acq_detect_sch_batch(trxsig_l1acq *a, const trxsig_c32 *d_samples, 
   const int rc = ensure_work(a, B);
   if (rc != TRXSIG_OK) return rc;
   return stage2(a, d_samples, nullptr, d_offset, d_length, d_omega, B, detect_thresh, 0, d_flags, d_amp, d_toa, d_ptm, d_soft, d_hard,
-                soft_stride, nullptr);
+                soft_stride, nullptr, nullptr, nullptr);
+}
+
+int trxsig_l1acq_set_sch_leg(trxsig_l1acq *a, int leg) {
+  if (!a) return TRXSIG_EINVAL;
+  if (leg != TRXSIG_SCHLEG_DEMOD && leg != TRXSIG_SCHLEG_MLSE) return fail(a, "trxsig_l1acq_set_sch_leg: not a leg");
+  a->sch_leg = leg;
+  return TRXSIG_OK;
+}
+
+int trxsig_l1acq_sch_channel(trxsig_l1acq *a, const trxsig_c32 **d_chan, const int32_t **d_win) {
+  if (!a) return TRXSIG_EINVAL;
+  if (!d_chan || !d_win) return fail(a, "trxsig_l1acq_sch_channel: bad argument");
+  if (!a->chan_valid) {                                     // no search on the equalising leg since: zeros and "skipped", filled on demand
+    trxsig_ctx *c = a->c;
+    TrxDeviceGuard g(trxsig_device(c));
+    hipStream_t st = (hipStream_t)trxsig_get_stream(c);
+    TRX_HIPCHK(c, hipMemsetAsync(a->chan, 0, (size_t)a->max_streams * 5 * sizeof(trx_c32), st));
+    TRX_HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)a->win, 2, (size_t)a->max_streams, st));
+    a->chan_valid = true;
+  }
+  *d_chan = (const trxsig_c32 *)a->chan;
+  *d_win = a->win;
+  return TRXSIG_OK;
 }

@@ -122,6 +122,11 @@ hipError_t trx_launch_mlse(hipStream_t st, int sps, const TrxTables *dT, const t
 hipError_t trx_launch_mlse_access(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
                                   int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
                                   float *soft, uint8_t *hard, int nsoft, int stride);
+// the sequence equaliser for synchronisation bursts (trxsig_mlse_sch.hip; trxsig_mlse_sch_batch; trxsig_l1acq's TRXSIG_SCHLEG_MLSE):
+// trx_launch_mlse_access's arguments (the burst's 64-symbol extended training sequence is fixed).  No profiler id.
+hipError_t trx_launch_mlse_sch(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
+                               int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
+                               float *soft, uint8_t *hard, int nsoft, int stride);
 // the same over two antennas (trxsig_mlse_div.hip; trxsig_mlse_div_batch): a sample pointer and an offset array per antenna, one
 // amp / TOA per burst, primary (may be NULL = 0) the antenna they came from; chan is B x 2 x 5.  No profiler id.
 hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
