@@ -326,6 +326,41 @@ int trxsig_mlse_sch_batch(trxsig_ctx *ctx,
                           float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
 int trxsig_mlse_sch_pinv_host(float out[9 * 56]);
 
+/* ---- the fit detector's statistic for synchronisation bursts (csrc/trxsig_sch_fit.hip) --------------------------------------
+ * trxsig_sch_fit_batch: how well the burst's 56 fully known rows fit the five-tap channel trxsig_mlse_sch_batch estimates from
+ *   them: q = sqrt(51 E / R), tap energy over residual power.  51 is 56 rows less 5 taps, so q^2 estimates the linear SNR, and it
+ *   does not care where the echoes of the channel lie (the valley rule of trxsig_l1acq.h takes its noise 2 to 5 symbols beside the
+ *   correlation peak, where they are).  Pinned by the float32 model tests/sch_fit_model.py, which the kernel equals word for word;
+ *   every step is one float32 operation in the order written, nothing fused, one correctly rounded division and one correctly
+ *   rounded square root per burst.  Graded against the float64 statement tests/sch_fit_ref.py with the a-priori bounds
+ *   (u = 2^-24, g_k = k u / (1 - k u), H.re = sum_k |h[k].re|, r, e and R below the float64 values; derived there)
+ *       d.re[n] = u |r[n].re| + (1 + u) g_4 H.re, d.im[n] likewise            (four additions in Z, one subtraction)
+ *       b[n] = (1 + g_2) (2 (|r.re| d.re + |r.im| d.im) + d.re^2 + d.im^2) + g_2 e[n]          (two squares, one addition)
+ *       |R32 - R| <= bR = sum b[n] + g_6 (R + sum b[n])                                        (six levels of the tree)
+ *       |q32 - q| <= q (sqrt((1 + g_8) / (1 - bR / R)) (1 + u) - 1)   where bR < R     (E: six roundings, 51 E, the quotient; the root)
+ *   1. Symbols y[0..147]: step 1 of trxsig_mlse_sch_batch, word for word.
+ *   2. c[-4..4] = P32 y[46..101], the window w, h[k] = c[w + k] and E: step 2 of trxsig_mlse_sch_batch, word for word.
+ *   3. The residual on the rows n = 46..101 (every a[n - w - k] lies in the extended training sequence, 42..105):
+ *          Z[n] = h[0] a[n - w], then + h[1] a[n - w - 1], .., + h[4] a[n - w - 4], in this order (the products with +-1 are sign
+ *          flips; real and imaginary parts apart): trxsig_mlse_batch's Z[x] with bit k of x the bit of a[n - w - k];
+ *          r[n] = y[n] - Z[n];  e[n - 46] = r.re * r.re + r.im * r.im.
+ *   4. R = the pairwise tree over e[0..63] with e[56..63] = 0: s1[i] = e[2 i] + e[2 i + 1], s2[i] = s1[2 i] + s1[2 i + 1], .. six
+ *      levels down to one number (the kernel's reduction over the 64 lanes of a wave).
+ *   5. q = sqrtf((51.0f * E) / R): the product first, then the division, then the root.  R == 0 with E > 0 gives +inf and stays
+ *      +inf.  q = 0 where the result is a NaN.
+ *   6. Where trxsig_mlse_sch_batch falls back (length/sps < 148, a component of y that fails fabsf(v) < 0x1p30f, E == 0) or skips
+ *      (k_demod's geometry test refuses the burst, d_enable[b] == 0): q = 0, E = 0, R = 0, the nine taps zero, d_win = 1 or 2.
+ *      Under the guard everything is finite: |Z| components < 2^34, |r| components < 2^35, R < 2^78, 51 E < 2^72.
+ *   d_chan9 [B][9] receives c[-4..4], d_win [B] the window word as trxsig_mlse_sch_batch reports it, d_E, d_R, d_q [B]; any of
+ *   the five may be NULL.  Inputs and refusals are trxsig_mlse_sch_batch's.  trxsig_l1acq_set_sch_detector (trxsig_l1acq.h) makes
+ *   q acquisition's SCH verdict. */
+int trxsig_sch_fit_batch(trxsig_ctx *ctx,
+                         const trxsig_c32 *d_samples, const int32_t *d_offset,
+                         const int32_t *d_length, int B,
+                         const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable,
+                         trxsig_c32 *d_chan9, int32_t *d_win,
+                         float *d_E, float *d_R, float *d_q);
+
 /* ---- two-antenna receive diversity for the sequence equaliser (csrc/trxsig_mlse_div.hip) ------------------------------------
  * trxsig_mlse_div_batch: trxsig_mlse_batch on two receive antennas -- one channel window for both, the branch metric summed over
  *   both: maximal-ratio combining inside the trellis.  Both branches are assumed to have the same noise power (a common scale

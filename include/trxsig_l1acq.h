@@ -57,6 +57,8 @@
  *   lies inside d_samples; the kernels cannot check it.  (A search checks its own windows against n_samples.)
  *   A window with a negative offset or a length outside (0, TRXSIG_L1ACQ_MAX_WINDOW sps] gets TRXSIG_F_BADLEN and zeros.
  *   On SCH bursts ptm was at least 14 at 10 dB SNR on the CPU model; on windows without one at most 4.7.
+ *   Steps 4 to 6 as written are TRXSIG_SCHDET_VALLEY, the default; under delay spread the valley fills with echoes and ptm
+ *   falls to 1.5 .. 9.  trxsig_l1acq_set_sch_detector (below) puts the fit detector in their place.
  *
  * In a search: w0 = k - 3 sps + 1250 sps - 12 sps (the FCCH window starts three tail symbols into its burst, the SCH burst
  *   starts one frame later; a margin of 12 symbols, more than three times the largest FCCH position error seen on the model,
@@ -82,7 +84,16 @@ typedef struct trxsig_l1acq trxsig_l1acq;
 
 #define TRXSIG_L1ACQ_FCCH_THRESH 0.5f
 #define TRXSIG_L1ACQ_SCH_THRESH 8.0f
-#define TRXSIG_L1ACQ_MAX_WINDOW 256            /* symbols: the longest window trxsig_l1acq_detect_sch_batch takes */
+/* The suggested threshold of TRXSIG_SCHDET_FIT (below), measured on the float32 model (tests/sch_fit_model.py;
+ * tests/test_sch_fit_model.py repeats the measurement), sps 1 and 4:
+ *   (a) the largest q on candidate windows that hold no SCH -- white noise; random, dummy, frequency and alternating-bit bursts
+ *       through the flat, five-tap and precursor channels at 15 dB, cut as a search cuts them; the SCH windows of the negative
+ *       streams -- 28,601 windows a rate, of which 2,803 (sps 1) and 2,720 (sps 4) pass the geometry gate: 0.923 (sps 4: 0.874);
+ *   (b) the smallest q on 60 SCH windows a profile at 10 dB: 2.06 (sps 1, precursor; flat 2.69, five 2.18; sps 4: 2.82, 2.09, 2.49).
+ *   (b) / (a) = 2.23; the constant is their geometric mean, 1.379, to two digits.  At 6 dB the smallest q is 1.37 (sps 1, five):
+ *   there the detector begins to miss.  At 15 dB the smallest is 2.88. */
+#define TRXSIG_L1ACQ_SCH_FIT_THRESH 1.4f
+#define TRXSIG_L1ACQ_MAX_WINDOW 256           /* symbols: the longest window trxsig_l1acq_detect_sch_batch takes */
 
 /* d_state bits */
 enum { TRXSIG_ACQ_FCCH = 1,      /* FCCH found: m > fcch_thresh */
@@ -140,6 +151,29 @@ int  trxsig_l1acq_set_sch_leg(trxsig_l1acq *acq, int leg);
  * where nothing was detected (those are filled, on the context's stream, by this call).  trxsig_l1acq_detect_sch_batch leaves them
  * alone: a caller who wants the taps of caller-chosen windows calls trxsig_mlse_sch_batch. */
 int  trxsig_l1acq_sch_channel(trxsig_l1acq *acq, const trxsig_c32 **d_chan, const int32_t **d_win);
+
+/* The SCH detector: how steps 4 to 6 of stage 2 decide that a window holds a synchronisation burst.  TRXSIG_SCHDET_VALLEY (the
+ * default): the valley rule, as stated above; with it every output of trxsig_l1acq_search and trxsig_l1acq_detect_sch_batch is
+ * what it was before the switch existed, byte for byte -- also after the switch has been used and set back -- and nothing more
+ * is enqueued.  TRXSIG_SCHDET_FIT: the fit detector, for a channel with delay spread (the valley rule takes its noise 2 to 5
+ * symbols beside the peak, which is where the echoes lie: peak-to-valley falls from 18..37 to 1.5..9 there).
+ *   Steps 1 to 3 are unchanged.  A window is a CANDIDATE iff 0 <= toa <= n, amp = peak / gain is finite and nonzero,
+ *   i0 = floor(toa_b) >= 0 and i0 + 148 sps <= n; the valley is not evaluated (no numRms rule).  trxsig_sch_fit_batch's kernel
+ *   (trxsig.h) then runs on the candidates, on the segment, amp and toa_b - i0 that step 7 takes, and a candidate is detected iff
+ *   its q > detect_thresh.  Step 7, on either leg, runs on the detected windows as before.
+ *   d_amp = peak / gain wherever 0 <= toa <= n (0 elsewhere) and d_toa = toa_b: the bytes VALLEY reports for every window the
+ *   valley rule does not call bogus.  d_ptm and d_sch_ptm CARRY q, THE METRIC OF THE ACTIVE DETECTOR (0 for a window that is no
+ *   candidate).  Flags, state bit 4 and everything behind them follow the fit verdict.
+ *   The threshold is the caller's, as ever (sch_thresh, detect_thresh); the suggested one is TRXSIG_L1ACQ_SCH_FIT_THRESH below.
+ * Host-side switch, independent of trxsig_l1acq_set_sch_leg (all four combinations work), takes effect from the next call on;
+ * anything but the two values returns TRXSIG_EINVAL. */
+enum { TRXSIG_SCHDET_VALLEY = 0, TRXSIG_SCHDET_FIT = 1 };
+int  trxsig_l1acq_set_sch_detector(trxsig_l1acq *acq, int detector);
+/* What the fit detector left in the last trxsig_l1acq_search: device arrays owned by the object, d_q and d_R [n_streams], as
+ * trxsig_sch_fit_batch reports them (zeros for a stream that was no candidate).  Zeros where the last search ran on
+ * TRXSIG_SCHDET_VALLEY or where there was none yet (filled, on the context's stream, by this call).
+ * trxsig_l1acq_detect_sch_batch leaves them alone. */
+int  trxsig_l1acq_sch_fit(trxsig_l1acq *acq, const float **d_q, const float **d_R);
 
 #ifdef __cplusplus
 }

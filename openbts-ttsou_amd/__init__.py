@@ -388,6 +388,13 @@ class TrxSig:
         self._chk(self.L.trxsig_mlse_sch_pinv_host(out.ctypes.data), "trxsig_mlse_sch_pinv_host")
         return out
 
+    def sch_fit(self, samples, offset, length, amp, toa, enable=None, chan9=None, win=None, E=None, R=None, q=None):
+        """The fit detector's statistic for synchronisation bursts with the caller's amp / TOA (trxsig_sch_fit_batch): chan9 [B, 9]
+        complex, win [B] int32, E, R, q [B] float32; each may be None."""
+        B = offset.numel()
+        self._chk(self.L.trxsig_sch_fit_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, _ptr(amp), _ptr(toa), _ptr(enable),
+                                              _ptr(chan9), _ptr(win), _ptr(E), _ptr(R), _ptr(q)), "trxsig_sch_fit_batch")
+
     def mlse_div(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, chan=None,
                  win=None, hard=None, nsoft=148, soft_stride=None):
         """The sequence equaliser over two receive antennas with the caller's amp / TOA (trxsig_mlse_div_batch): one amp / TOA per
@@ -1208,6 +1215,8 @@ ACQ_FCCH, ACQ_WINDOW, ACQ_SCH, ACQ_DECODED = 1, 2, 4, 8   # trxsig_l1acq_out.d_s
 ACQ_FCCH_THRESH, ACQ_SCH_THRESH = 0.5, 8.0                # TRXSIG_L1ACQ_FCCH_THRESH / _SCH_THRESH
 ACQ_MAX_WINDOW = 256                                      # TRXSIG_L1ACQ_MAX_WINDOW (symbols)
 SCHLEG_DEMOD, SCHLEG_MLSE = 0, 1                          # TRXSIG_SCHLEG_*
+SCHDET_VALLEY, SCHDET_FIT = 0, 1                          # TRXSIG_SCHDET_*
+ACQ_SCH_FIT_THRESH = 1.4                                  # TRXSIG_L1ACQ_SCH_FIT_THRESH: the threshold to pass with SCHDET_FIT
 
 
 class L1Acq(_Object):
@@ -1256,6 +1265,19 @@ class L1Acq(_Object):
         S = self.out.n_streams if self.out is not None else 0
         chan = _to_host(self.ctx, d_chan.value, (S, 10), "<f4").view(np.complex64).reshape(S, 5)
         return chan, _to_host(self.ctx, d_win.value, (S,), "<i4")
+
+    def set_sch_detector(self, detector):
+        """SCHDET_VALLEY (the default: analyzeTrafficBurst's valley rule) or SCHDET_FIT (trxsig_sch_fit_batch's q) as the SCH verdict."""
+        self._call("set_sch_detector", int(detector))
+
+    def sch_fit(self):
+        """(q [n_streams], R [n_streams]) float32 of the last search as host numpy arrays: the fit detector's statistic and
+        residual; zeros on SCHDET_VALLEY or for a stream that was no candidate (synchronises the context's stream)."""
+        d_q, d_R = C.c_void_p(), C.c_void_p()
+        self._call("sch_fit", C.byref(d_q), C.byref(d_R))
+        self.ctx.synchronize()
+        S = self.out.n_streams if self.out is not None else 0
+        return _to_host(self.ctx, d_q.value, (S,), "<f4"), _to_host(self.ctx, d_R.value, (S,), "<f4")
 
     def collect(self):
         """The last search's outputs as host numpy arrays (synchronises the context's stream)."""

@@ -134,6 +134,7 @@ SIGNATURES = {
     "trxsig_mlse_access_pinv_host": (i32, [vp]),
     "trxsig_mlse_sch_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_sch_pinv_host": (i32, [vp]),
+    "trxsig_sch_fit_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "trxsig_mlse_div_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_div_normal_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
     "trxsig_mlse_irc_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32]),
@@ -331,6 +332,8 @@ SIGNATURES = {
     "trxsig_l1acq_sequence": (i32, [vp, vp, vp, vp]),
     "trxsig_l1acq_set_sch_leg": (i32, [vp, i32]),
     "trxsig_l1acq_sch_channel": (i32, [vp, P(vp), P(vp)]),
+    "trxsig_l1acq_set_sch_detector": (i32, [vp, i32]),
+    "trxsig_l1acq_sch_fit": (i32, [vp, P(vp), P(vp)]),
     # ---- include/trxsig_air.h ----
     "trxsig_air_create": (i32, [P(vp), vp, i32]),
     "trxsig_air_destroy": (None, [vp]),

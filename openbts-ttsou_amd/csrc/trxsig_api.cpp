@@ -893,6 +893,20 @@ int trxsig_mlse_sch_pinv_host(float out[9 * 56]) {
   return TRXSIG_OK;
 }
 
+// ---- the fit detector's statistic for synchronisation bursts (trxsig_sch_fit.hip) ----
+int trxsig_sch_fit_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
+                         const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan9, int32_t *d_win,
+                         float *d_E, float *d_R, float *d_q) {
+  if (!c) return TRXSIG_EINVAL;
+  if (bad_batch(d_samples, d_offset, d_length, B) || (B > 0 && (!d_amp || !d_toa)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_sch_fit_batch: bad argument");
+  if (B == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_sch_fit(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, (const trx_c32 *)d_amp,
+                                   d_toa, d_enable, 0, (trx_c32 *)d_chan9, d_win, d_E, d_R, d_q));
+  return TRXSIG_OK;
+}
+
 // ---- two-antenna receive diversity for the sequence equaliser (trxsig_mlse_div.hip) ----
 int trxsig_mlse_div_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
                           const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,

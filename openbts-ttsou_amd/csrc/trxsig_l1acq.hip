@@ -17,6 +17,8 @@
 //   object's workspace row.  The correlation over every lag and peakDetect are trxsig_prim.hip's kernels on those rows.
 // k_l1acq_verdict: the tail of analyzeTrafficBurst (:961-1000) for the extended training sequence, a thread per window, and the
 //   demodulator's segment.  demodulateBurst is k_demod (trxsig_demod.h), exact arithmetic.
+// k_l1acq_candidates, k_l1acq_fit_verdict: TRXSIG_SCHDET_FIT's two halves of the verdict, round k_sch_fit (trxsig_sch_fit.hip):
+//   the geometry gate with amp, TOA and the segment before it, q > thresh behind it.  k_l1acq_verdict is untouched by them.
 // Built with -ffp-contract=off like every kernel file.
 #include "trxsig_dev.h"
 #include "trxsig_l1acq_dev.h"
@@ -286,6 +288,59 @@ __global__ __launch_bounds__(64) void k_l1acq_verdict(int sps, const cx *__restr
   if (state && (fl & TRXSIG_F_DETECT)) state[b] |= TRXSIG_ACQ_SCH;
 }
 
+// TRXSIG_SCHDET_FIT: the geometry gate in the valley rule's place (a thread per window); the verdict waits for k_sch_fit
+__global__ __launch_bounds__(64) void k_l1acq_candidates(int sps, const int32_t *__restrict__ wlen, const cx *__restrict__ peak,
+                                                         const float *__restrict__ pidx, int B, cx gain, float seq_toa, int search,
+                                                         uint8_t *__restrict__ flags, cx *__restrict__ amp_out,
+                                                         float *__restrict__ toa_out, int32_t *__restrict__ doff,
+                                                         int32_t *__restrict__ dlen, float *__restrict__ dtoa) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const int n = wlen[b];
+  uint8_t fl = 0;
+  cx amp = mk(0, 0);
+  float toa_b = 0.0f, rest = 0.0f;
+  int i0 = 0, nd = 0;
+  if (n <= 0) {
+    fl = search ? 0 : TRXSIG_F_BADLEN;
+  } else {
+    const float toa = pidx[b];
+    const bool inside = toa >= 0.0f && toa <= (float)n;    // :964 (a NaN index is outside too)
+    if (inside) amp = cdiv(peak[b], gain);                 // :997
+    toa_b = toa - seq_toa;                                 // :998
+    toa_b = toa_b - (float)(42 * sps);                     // the sequence starts at bit 42
+    if (inside && acq_finite(amp.r) && acq_finite(amp.i) && (amp.r != 0.0f || amp.i != 0.0f)) {
+      const float fl0 = floorf(toa_b);
+      if (fl0 >= 0.0f && fl0 <= (float)(n - 148 * sps)) {
+        i0 = (int)fl0;
+        const int sh = sps >> 1;                           // log2(sps) for 1, 2, 4
+        nd = ((n - i0) >> sh) << sh;                       // whole symbols
+        if (nd > 156 * sps) nd = 156 * sps;
+        rest = toa_b - fl0;
+        fl = TRXSIG_F_DETECT;                              // a candidate; k_l1acq_fit_verdict decides
+      }
+    }
+  }
+  flags[b] = fl;
+  amp_out[b] = amp;
+  toa_out[b] = toa_b;
+  doff[b] = b * TRX_ACQ_WMAX + i0;
+  dlen[b] = nd;
+  dtoa[b] = rest;
+}
+
+__global__ __launch_bounds__(64) void k_l1acq_fit_verdict(int B, const float *__restrict__ q, float thresh, uint8_t *__restrict__ flags,
+                                                          float *__restrict__ ptm_out, uint8_t *__restrict__ state) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  uint8_t fl = flags[b];
+  const float qb = (fl & TRXSIG_F_DETECT) ? q[b] : 0.0f;   // (k_sch_fit wrote 0 for the others already)
+  if ((fl & TRXSIG_F_DETECT) && !(qb > thresh)) fl = 0;
+  flags[b] = fl;
+  if (ptm_out) ptm_out[b] = qb;
+  if (state && (fl & TRXSIG_F_DETECT)) state[b] |= TRXSIG_ACQ_SCH;
+}
+
 __global__ __launch_bounds__(256) void k_l1acq_finish(int n, const uint8_t *__restrict__ ok, uint8_t *__restrict__ state) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n && ok[i] && (state[i] & TRXSIG_ACQ_SCH)) state[i] |= TRXSIG_ACQ_DECODED;
@@ -336,6 +391,21 @@ hipError_t trx_launch_l1acq_verdict(hipStream_t st, int sps, const trx_c32 *c, c
   if (B <= 0) return hipSuccess;
   k_l1acq_verdict<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(sps, c, wlen, peak, pidx, B, gain, seq_toa, thresh, search, flags, amp,
                                                            toa, ptm, doff, dlen, dtoa, state);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_l1acq_candidates(hipStream_t st, int sps, const int32_t *wlen, const trx_c32 *peak, const float *pidx, int B,
+                                       trx_c32 gain, float seq_toa, int search, uint8_t *flags, trx_c32 *amp, float *toa, int32_t *doff,
+                                       int32_t *dlen, float *dtoa) {
+  if (B <= 0) return hipSuccess;
+  k_l1acq_candidates<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(sps, wlen, peak, pidx, B, gain, seq_toa, search, flags, amp, toa, doff,
+                                                              dlen, dtoa);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_l1acq_fit_verdict(hipStream_t st, int B, const float *q, float thresh, uint8_t *flags, float *ptm, uint8_t *state) {
+  if (B <= 0) return hipSuccess;
+  k_l1acq_fit_verdict<<<dim3((B + 63) / 64), dim3(64), 0, st>>>(B, q, thresh, flags, ptm, state);
   return hipGetLastError();
 }
 

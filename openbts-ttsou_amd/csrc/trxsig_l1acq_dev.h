@@ -43,6 +43,15 @@ hipError_t trx_launch_l1acq_shift(hipStream_t st, int sps, const TrxTables *dT, 
 hipError_t trx_launch_l1acq_verdict(hipStream_t st, int sps, const trx_c32 *c, const int32_t *wlen, const trx_c32 *peak,
                                     const float *pidx, int B, trx_c32 gain, float seq_toa, float thresh, int search, uint8_t *flags,
                                     trx_c32 *amp, float *toa, float *ptm, int32_t *doff, int32_t *dlen, float *dtoa, uint8_t *state);
+// TRXSIG_SCHDET_FIT, in k_l1acq_verdict's place.  First the candidates, before the fit: no valley; amp = peak / gain where the TOA
+// lies inside the window (0 elsewhere), toa as the verdict kernel reports it, the demodulator's segment and flags = TRXSIG_F_DETECT
+// for a window that passes the geometry gate (0 <= toa <= n, amp finite and nonzero, floor(toa_b) >= 0, the burst inside).
+hipError_t trx_launch_l1acq_candidates(hipStream_t st, int sps, const int32_t *wlen, const trx_c32 *peak, const float *pidx, int B,
+                                       trx_c32 gain, float seq_toa, int search, uint8_t *flags, trx_c32 *amp, float *toa, int32_t *doff,
+                                       int32_t *dlen, float *dtoa);
+// ... then, behind k_sch_fit on the candidates: a candidate keeps TRXSIG_F_DETECT iff q > thresh; ptm (may be null) reports q;
+// state[b] (search) gains TRXSIG_ACQ_SCH on detection
+hipError_t trx_launch_l1acq_fit_verdict(hipStream_t st, int B, const float *q, float thresh, uint8_t *flags, float *ptm, uint8_t *state);
 // state[s] |= TRXSIG_ACQ_DECODED where ok[s]
 hipError_t trx_launch_l1acq_finish(hipStream_t st, int n_streams, const uint8_t *ok, uint8_t *state);
 

@@ -127,6 +127,11 @@ hipError_t trx_launch_mlse_access(hipStream_t st, int sps, const TrxTables *dT, 
 hipError_t trx_launch_mlse_sch(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
                                int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
                                float *soft, uint8_t *hard, int nsoft, int stride);
+// the fit detector's statistic for synchronisation bursts (trxsig_sch_fit.hip; trxsig_sch_fit_batch; trxsig_l1acq's
+// TRXSIG_SCHDET_FIT): trx_launch_mlse_sch's inputs; chan9 (B x 9), win, E, R and q (B each) may each be NULL.  No profiler id.
+hipError_t trx_launch_sch_fit(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
+                              int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan9, int32_t *win,
+                              float *E, float *R, float *q);
 // the same over two antennas (trxsig_mlse_div.hip; trxsig_mlse_div_batch): a sample pointer and an offset array per antenna, one
 // amp / TOA per burst, primary (may be NULL = 0) the antenna they came from; chan is B x 2 x 5.  No profiler id.
 hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
