@@ -5,7 +5,8 @@
 // this kernel equals word for word, and graded against the float64 statement tests/mlse_div_ref.py.  The algorithm is stated in
 // include/trxsig.h (trxsig_mlse_div_batch).  Nothing is fused, nothing is transcendental, one division per soft bit.
 //
-// Layout: k_mlse's (trxsig_mlse.hip) -- a wave takes two bursts, each of its four 16-lane rows is one half-burst trellis, the 61
+// Layout: k_mlse's (trxsig_mlse.hip), every shared step from trxsig_mlse_dev.h (mlse_symbols, mlse_corr_tap, mlse_window2,
+// mlse_trellis2, mlse_soft_out) -- a wave takes two bursts, each of its four 16-lane rows is one half-burst trellis, the 61
 // forward metrics of a lane stay in VGPRs, predecessors and successors come by ds_bpermute, the minimum by DPP.  What doubles:
 //   * the symbol vectors in LDS, ysh[wave][burst][antenna][152]; demod_core runs four times per wave through the one staging area
 //     (a rolled loop: one copy of its code), each antenna with its own sample pointer, offset and 16-byte load decision;
@@ -53,41 +54,14 @@ void k_mlse_div(const TrxTables *__restrict__ T, const void *__restrict__ sample
       const int o0 = offset0[b], o1 = offset1[b];
       off = a ? o1 : o0; N = length[b]; amp = amp_in[b]; toa = toa_in[b];
       // k_demod's test, once for the burst: the antennas share the length, and both offsets have to pass
-      enabled = (o0 >= 0) && (o1 >= 0) && (N >= 92 * SPS) && (N <= 157 * SPS) && (N % SPS == 0) && (fabsf(toa) <= 4096.0f);
-      if (flags) enabled = enabled && (need_mask ? ((flags[b] & need_mask) == need_mask) : (flags[b] != 0));
+      enabled = (o1 >= 0) && mlse_enabled<SPS>(o0, N, toa, flags, need_mask, b);
     }
     if (!__builtin_amdgcn_readfirstlane(enabled)) {
-      for (int m = lane; m < TRX_MLSE_NY; m += 64) Y[m] = mk(0, 0);      // (the trellis rows of this burst run on zeros; nothing of theirs is stored)
+      mlse_zero(Y, lane);
       states |= 2 << (4 * j);
       continue;
     }
-    constexpr int NLD = (157 * SPS / 2 + 63) / 64;
-    const bool wide = (off & 1) == 0;                       // per antenna: the two offsets of a burst may differ in parity
-    float4 v[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; i++) v[i] = make_float4(0, 0, 0, 0);
-    if (wide) {
-#pragma unroll
-      for (int i = 0; i < NLD; i++) {
-        const int p = lane + 64 * i;
-        if (p < N / 2) v[i] = SmpC32::ld2(samples, off, p);
-      }
-    }
-    wave_lds_fence();                                       // the staging area's readers of the run before are done
-    demod_core<SPS, true, 148>(T, ph[wave], samples, off, N, wide, v, amp, toa, lane, nullptr, nullptr, Y, 148);
-    wave_lds_fence();
-    // GMSKReverseRotate at the decimated instants, both parts kept: the reference's complex product with rev[sps m]
-    bool bad = false;
-    const cx *rev = T->rev;
-    for (int m = lane; m < TRX_MLSE_NY; m += 64) {
-      cx y = mk(0, 0);
-      if (m < 148 && m < N / SPS) {                        // (a short burst's symbols past its end are zeros: demodulateBurst has none there)
-        y = cmul(Y[m], rev[SPS * m]);
-        bad = bad || !(fabsf(y.r) < 0x1p30f) || !(fabsf(y.i) < 0x1p30f);
-      }
-      Y[m] = y;
-    }
-    if (__builtin_amdgcn_ballot_w64(bad) != 0 || N / SPS < 148) states |= 1 << (4 * j);     // (either antenna's)
+    if (mlse_symbols<SPS>(T, ph[wave], samples, off, N, amp, toa, lane, Y)) states |= 1 << (4 * j);     // (either antenna's)
   }
   wave_lds_fence();
 
@@ -101,38 +75,13 @@ void k_mlse_div(const TrxTables *__restrict__ T, const void *__restrict__ sample
   cx *scr = ph[wave] + TRX_MLSE_DIV_SCR * (lane >> 4);
   {
     const int d = (s < 9 ? s : 8) - 4;
-    cx acc0 = mk(0, 0), acc1 = mk(0, 0);
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const cx y0 = Y0[66 + i + d], y1 = Y1[66 + i + d];
-      const int plus = (tsc_bits >> (5 + i)) & 1;
-      acc0 = cadd(acc0, mk(sgn(y0.r, plus), sgn(y0.i, plus)));
-      acc1 = cadd(acc1, mk(sgn(y1.r, plus), sgn(y1.i, plus)));
-    }
-    if (s < 9) { scr[s] = cmulr(acc0, 0.0625f); scr[9 + s] = cmulr(acc1, 0.0625f); }
+    const cx cd0 = mlse_corr_tap(tsc_bits, d, Y0), cd1 = mlse_corr_tap(tsc_bits, d, Y1);
+    if (s < 9) { scr[s] = cd0; scr[9 + s] = cd1; }
   }
   wave_lds_fence();
-  cx c0[9], c1[9];
-  float p[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    c0[i] = scr[i]; c1[i] = scr[9 + i];
-    p[i] = (c0[i].r * c0[i].r + c0[i].i * c0[i].i) + (c1[i].r * c1[i].r + c1[i].i * c1[i].i);      // antenna 0's power first
-  }
-  int w = 0;
-  float E = (((p[4] + p[5]) + p[6]) + p[7]) + p[8];
-#pragma unroll
-  for (int q = 1; q <= 4; q++) {                            // w = -q; a later window only on a strict >
-    const float Ew = (((p[4 - q] + p[5 - q]) + p[6 - q]) + p[7 - q]) + p[8 - q];
-    if (Ew > E) { E = Ew; w = -q; }
-  }
   cx h0[5], h1[5];                                          // one window for both antennas
-#pragma unroll
-  for (int k = 0; k < 5; k++) {
-    h0[k] = c0[4 + k]; h1[k] = c1[4 + k];
-#pragma unroll
-    for (int q = 1; q <= 4; q++) if (w == -q) { h0[k] = c0[4 - q + k]; h1[k] = c1[4 - q + k]; }
-  }
+  int w;
+  const float E = mlse_window2(scr, h0, h1, w);
   int st = (states >> (4 * j)) & 15;
   if (st == 0 && E == 0.0f) st = 1;
 
@@ -152,80 +101,22 @@ void k_mlse_div(const TrxTables *__restrict__ T, const void *__restrict__ sample
 
   // ---- 3. the half-burst trellis of this row ----
   wave_lds_fence();                                         // (c_0, c_1 have been read by the whole row)
-  cx zf00, zf10, zf01, zf11;                                // zf<b><antenna>: into state s from s >> 1 (b = 0), (s >> 1) | 8 (b = 1)
-  {
-    cx g0[5], g1[5];
+  cx g0[5], g1[5];
 #pragma unroll
-    for (int k = 0; k < 5; k++) { g0[k] = left ? h0[4 - k] : h0[k]; g1[k] = left ? h1[4 - k] : h1[k]; }
-    zf00 = mlse_expected(g0, s); zf10 = mlse_expected(g0, s | 16);
-    zf01 = mlse_expected(g1, s); zf11 = mlse_expected(g1, s | 16);
-    // (E, w, the burst's state and the row's taps are wanted after the way up: parked in LDS meanwhile, the 61 forward metrics want
-    //  the registers)
-    if (s == 0) {
-      scr[18] = mk(E, __int_as_float(w)); scr[19] = mk(__int_as_float(st), 0.0f);
+  for (int k = 0; k < 5; k++) { g0[k] = left ? h0[4 - k] : h0[k]; g1[k] = left ? h1[4 - k] : h1[k]; }
+  // (E, w, the burst's state and the row's taps are wanted after the way up: parked in LDS meanwhile, the 61 forward metrics want
+  //  the registers)
+  if (s == 0) {
+    scr[18] = mk(E, __int_as_float(w)); scr[19] = mk(__int_as_float(st), 0.0f);
 #pragma unroll
-      for (int k = 0; k < 5; k++) { scr[20 + k] = g0[k]; scr[25 + k] = g1[k]; }
-    }
+    for (int k = 0; k < 5; k++) { scr[20 + k] = g0[k]; scr[25 + k] = g1[k]; }
   }
-  const int rowbase = lane & 48;
-  const int pf0 = 4 * (rowbase | (s >> 1)), pf1 = pf0 + 32;
-  const int pb0 = 4 * (rowbase | ((2 * s) & 15)), pb1 = pb0 + 4;
   // start state: bit 0 first a[86], a[85], a[84], a[83] (right) or a[61], a[62], a[63], a[64] (left); a[61 + t] = training bit t
   const int start = left ? (int)(tsc_bits & 15u)
                          : (int)(((tsc_bits >> 25) & 1u) | (((tsc_bits >> 24) & 1u) << 1) | (((tsc_bits >> 23) & 1u) << 2) | (((tsc_bits >> 22) & 1u) << 3));
   // step i = 0..60 is symbol m = 87 + i with sample y[m + w] (right), m = 60 - i with y[m + 4 + w] (left)
-  int yi = left ? 64 + w : 87 + w;
-  const int dir = left ? -1 : 1;
-  // (a scheduling fence per step, the next step's symbols fetched ahead of it: as in k_mlse)
-  float A[61];
-  float al = (s == start) ? 0.0f : TRX_MLSE_INF;
-  cx y0 = Y0[yi], y1 = Y1[yi];
-#pragma unroll
-  for (int i = 0; i < 61; i++) {
-    if (i < 60) yi += dir;
-    const cx yn0 = Y0[yi], yn1 = Y1[yi];
-    float g0 = mlse_gamma(y0, zf00) + mlse_gamma(y1, zf01);  // antenna 0's metric first
-    float g1 = mlse_gamma(y0, zf10) + mlse_gamma(y1, zf11);
-    if (i >= 58 && (s & 1)) { g0 = TRX_MLSE_INF; g1 = TRX_MLSE_INF; }            // the tail symbols are -1
-    const float a0 = bperm(pf0, al) + g0, a1 = bperm(pf1, al) + g1;
-    al = fminf(a0, a1);
-    A[i] = al;
-    y0 = yn0; y1 = yn1;                                     // (after step 60 the symbols are that step's again: the backward pass starts there)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  wave_lds_fence();
-  cx zb00, zb10, zb01, zb11;                                // zb<b><antenna>: out of state s with b = 0, 1 -- Z[2 s], Z[2 s + 1]
-  {
-    cx g0[5], g1[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) { g0[k] = scr[20 + k]; g1[k] = scr[25 + k]; }
-    zb00 = mlse_expected(g0, 2 * s); zb10 = mlse_expected(g0, 2 * s + 1);
-    zb01 = mlse_expected(g1, 2 * s); zb11 = mlse_expected(g1, 2 * s + 1);
-  }
-  asm volatile("" : "+v"(yi));                              // (or the 61 addresses of the way up are kept in registers for the way back)
-  float be = 0.0f;
   float D[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int i = 60; i >= 0; i--) {
-    if (i > 0) yi -= dir;
-    const cx yn0 = Y0[yi], yn1 = Y1[yi];
-    float t = A[i] + be;                                    // alpha and beta, both after step i
-    t = fminf(t, dpp_f<0x4E>(t));                           // lane ^ 2
-    t = fminf(t, dpp_f<0x124>(t));                          // the row rotated by 4
-    t = fminf(t, dpp_f<0x128>(t));                          // ... by 8: the minimum over the eight states of this lane's parity
-    const float o = dpp_f<0xB1>(t);                         // lane ^ 1: the other parity's
-    const float diff = (s & 1) ? o - t : t - o;             // M_0 - M_1
-    if ((i & 15) == s) D[i >> 4] = diff;
-    asm volatile("" : "+v"(D[i >> 4]));                     // (the select happens here: not 61 differences kept for a chain of selects after the loop)
-    if (i > 0) {
-      const float g0 = mlse_gamma(y0, zb00) + mlse_gamma(y1, zb01);
-      const float g1 = (i >= 58) ? TRX_MLSE_INF : mlse_gamma(y0, zb10) + mlse_gamma(y1, zb11);
-      const float b0 = g0 + bperm(pb0, be), b1 = g1 + bperm(pb1, be);
-      be = fminf(b0, b1);
-    }
-    y0 = yn0; y1 = yn1;
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  mlse_trellis2<61, false>(Y0, Y1, left ? 64 + w : 87 + w, left ? -1 : 1, g0, g1, 1.0f, scr, lane, start, D);
 
   // ---- 4 / 5. soft bits out ----
   if (b >= B) return;
@@ -240,26 +131,12 @@ void k_mlse_div(const TrxTables *__restrict__ T, const void *__restrict__ sample
     for (int q = 0; q < 4; q++) {
       const int i = 16 * q + s;
       const int m = left ? 60 - i : 87 + i;
-      if (i < 61 && m < nsoft) {
-        float sv = 0.5f + D[q] / den;
-        if (sv > 1.0f) sv = 1.0f;
-        if (sv < 0.0f) sv = 0.0f;
-        sb[m] = sv;
-        if (hb) hb[m] = sv > 0.5F;
-      }
+      if (i < 61 && m < nsoft) mlse_soft_out(sb, hb, m, D[q], den);
     }
     const int m = 61 + hl;                                  // the midamble: the demodulator's formula on the primary antenna
-    if (hl < 26 && m < nsoft) {
-      const float sv = mlse_slice(Yp[m].r);
-      sb[m] = sv;
-      if (hb) hb[m] = sv > 0.5F;
-    }
+    if (hl < 26 && m < nsoft) mlse_put(sb, hb, m, mlse_slice(Yp[m].r));
   } else {
-    for (int m = hl; m < nsoft; m += 32) {
-      const float sv = st_ == 1 ? mlse_slice(Yp[m].r) : 0.0f;
-      sb[m] = sv;
-      if (hb) hb[m] = sv > 0.5F;
-    }
+    mlse_fall_back(sb, hb, Yp, st_, hl, 32, nsoft);
   }
 }
 
@@ -317,14 +194,8 @@ hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, con
   const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
 #define TRX_MLSE_DIV_GO(S) k_mlse_div<S><<<grid, block, 0, st>>>(dT, samples0, off0, samples1, off1, len, B, tsc_bits, amp, toa, primary, flags, \
                                                                  need_mask, chan, win, soft, hard, nsoft, stride)
-  switch (sps) {
-    case 1: TRX_MLSE_DIV_GO(1); break;
-    case 2: TRX_MLSE_DIV_GO(2); break;
-    case 4: TRX_MLSE_DIV_GO(4); break;
-    default: return hipErrorInvalidValue;
-  }
+  TRX_MLSE_DISPATCH(sps, TRX_MLSE_DIV_GO);
 #undef TRX_MLSE_DIV_GO
-  return hipGetLastError();
 }
 
 hipError_t trx_launch_div_select(hipStream_t st, const TrxDivSelect &p) {

@@ -7,7 +7,7 @@
 // and graded against the float64 statement tests/mlse_irc_ref.py.  The algorithm is stated in include/trxsig.h
 // (trxsig_mlse_irc_batch).  Nothing is fused, nothing is transcendental; four more divisions per burst than k_mlse_div.
 //
-// Layout: k_mlse_div's (trxsig_mlse_div.hip), steps 1 and 2 word for word.  What is added:
+// Layout: k_mlse_div's (trxsig_mlse_div.hip); steps 1, 2 and the trellis are the shared code of trxsig_mlse_dev.h.  What is added:
 //   * the residual sums: lane s of a row forms the terms of midamble positions 65 + s and (s < 6) 81 + s, and the row adds them up in
 //     the stated order through 22 x 4 ds_bpermute -- no LDS words, no fence;
 //   * the set (A, Bv, xr, xi), det, the whitened taps and E_w: every lane of a row, redundantly, as the estimate is;
@@ -39,7 +39,7 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
   const int bw = 2 * (blockIdx.x * TRX_MLSE_WAVES + wave);   // the wave's first burst (wave-uniform)
   if (bw >= B) return;
 
-  // ---- 1. symbols: k_mlse_div's step, word for word.  States, four bits per burst: 0 = equalise, 1 = fall back, 2 = not enabled ----
+  // ---- 1. symbols, as in k_mlse_div.  States, four bits per burst: 0 = equalise, 1 = fall back, 2 = not enabled ----
   int states = 0;
 #pragma unroll 1
   for (int q = 0; q < 4; q++) {
@@ -54,44 +54,19 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
     if (b < B) {
       const int o0 = offset0[b], o1 = offset1[b];
       off = a ? o1 : o0; N = length[b]; amp = amp_in[b]; toa = toa_in[b];
-      enabled = (o0 >= 0) && (o1 >= 0) && (N >= 92 * SPS) && (N <= 157 * SPS) && (N % SPS == 0) && (fabsf(toa) <= 4096.0f);
-      if (flags) enabled = enabled && (need_mask ? ((flags[b] & need_mask) == need_mask) : (flags[b] != 0));
+      // k_demod's test, once for the burst: the antennas share the length, and both offsets have to pass
+      enabled = (o1 >= 0) && mlse_enabled<SPS>(o0, N, toa, flags, need_mask, b);
     }
     if (!__builtin_amdgcn_readfirstlane(enabled)) {
-      for (int m = lane; m < TRX_MLSE_NY; m += 64) Y[m] = mk(0, 0);
+      mlse_zero(Y, lane);
       states |= 2 << (4 * j);
       continue;
     }
-    constexpr int NLD = (157 * SPS / 2 + 63) / 64;
-    const bool wide = (off & 1) == 0;
-    float4 v[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; i++) v[i] = make_float4(0, 0, 0, 0);
-    if (wide) {
-#pragma unroll
-      for (int i = 0; i < NLD; i++) {
-        const int p = lane + 64 * i;
-        if (p < N / 2) v[i] = SmpC32::ld2(samples, off, p);
-      }
-    }
-    wave_lds_fence();                                       // the staging area's readers of the run before are done
-    demod_core<SPS, true, 148>(T, ph[wave], samples, off, N, wide, v, amp, toa, lane, nullptr, nullptr, Y, 148);
-    wave_lds_fence();
-    bool bad = false;
-    const cx *rev = T->rev;
-    for (int m = lane; m < TRX_MLSE_NY; m += 64) {
-      cx y = mk(0, 0);
-      if (m < 148 && m < N / SPS) {
-        y = cmul(Y[m], rev[SPS * m]);
-        bad = bad || !(fabsf(y.r) < 0x1p30f) || !(fabsf(y.i) < 0x1p30f);
-      }
-      Y[m] = y;
-    }
-    if (__builtin_amdgcn_ballot_w64(bad) != 0 || N / SPS < 148) states |= 1 << (4 * j);     // (either antenna's)
+    if (mlse_symbols<SPS>(T, ph[wave], samples, off, N, amp, toa, lane, Y)) states |= 1 << (4 * j);     // (either antenna's)
   }
   wave_lds_fence();
 
-  // ---- 2. channel estimate: k_mlse_div's step, word for word ----
+  // ---- 2. channel estimate, as in k_mlse_div: one window for both antennas ----
   const int s = lane & 15;                                  // the state this lane carries
   const int j = lane >> 5;                                  // which of the wave's two bursts
   const bool left = (lane >> 4) & 1;                        // which half of it
@@ -102,41 +77,13 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
   cx *scr = ph[wave] + TRX_MLSE_IRC_SCR * (lane >> 4);
   {
     const int d = (s < 9 ? s : 8) - 4;
-    cx acc0 = mk(0, 0), acc1 = mk(0, 0);
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const cx y0 = Y0[66 + i + d], y1 = Y1[66 + i + d];
-      const int plus = (tsc_bits >> (5 + i)) & 1;
-      acc0 = cadd(acc0, mk(sgn(y0.r, plus), sgn(y0.i, plus)));
-      acc1 = cadd(acc1, mk(sgn(y1.r, plus), sgn(y1.i, plus)));
-    }
-    if (s < 9) { scr[s] = cmulr(acc0, 0.0625f); scr[9 + s] = cmulr(acc1, 0.0625f); }
+    const cx cd0 = mlse_corr_tap(tsc_bits, d, Y0), cd1 = mlse_corr_tap(tsc_bits, d, Y1);
+    if (s < 9) { scr[s] = cd0; scr[9 + s] = cd1; }
   }
   wave_lds_fence();
-  int w = 0;
-  float E;
   cx h0[5], h1[5];                                          // one window for both antennas
-  {
-    cx c0[9], c1[9];
-    float p[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      c0[i] = scr[i]; c1[i] = scr[9 + i];
-      p[i] = (c0[i].r * c0[i].r + c0[i].i * c0[i].i) + (c1[i].r * c1[i].r + c1[i].i * c1[i].i);      // antenna 0's power first
-    }
-    E = (((p[4] + p[5]) + p[6]) + p[7]) + p[8];
-#pragma unroll
-    for (int q = 1; q <= 4; q++) {                          // w = -q; a later window only on a strict >
-      const float Ew = (((p[4 - q] + p[5 - q]) + p[6 - q]) + p[7 - q]) + p[8 - q];
-      if (Ew > E) { E = Ew; w = -q; }
-    }
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-      h0[k] = c0[4 + k]; h1[k] = c1[4 + k];
-#pragma unroll
-      for (int q = 1; q <= 4; q++) if (w == -q) { h0[k] = c0[4 - q + k]; h1[k] = c1[4 - q + k]; }
-    }
-  }
+  int w;
+  const float E = mlse_window2(scr, h0, h1, w);
   int st = (states >> (4 * j)) & 15;
   if (st == 0 && E == 0.0f) st = 1;
   const int rowbase = lane & 48;
@@ -226,11 +173,7 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
     }
     // the midamble's soft bits: the demodulator's formula on the primary antenna as it is now, before y_1 is whitened
     const int m = 61 + hl;
-    if (st == 0 && hl < 26 && m < nsoft) {
-      const float sv = mlse_slice(Yp[m].r);
-      sb[m] = sv;
-      if (hb) hb[m] = sv > 0.5F;
-    }
+    if (st == 0 && hl < 26 && m < nsoft) mlse_put(sb, hb, m, mlse_slice(Yp[m].r));
   }
   wave_lds_fence();                                         // (c_0, c_1, the residuals' and the midamble's symbols have been read)
   if (st == 0) {                                            // y_1 in place; a burst that falls back keeps its symbols for step 5
@@ -238,75 +181,20 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
   }
   wave_lds_fence();
 
-  // ---- 3. the half-burst trellis of this row: k_mlse_div's on (y_0, y_1') with (h_0, h_1') and det on antenna 0's metric ----
-  cx zf00, zf10, zf01, zf11;                                // zf<b><antenna>: into state s from s >> 1 (b = 0), (s >> 1) | 8 (b = 1)
-  {
-    cx g0[5], g1[5];
+  // ---- 3. the half-burst trellis of this row: mlse_trellis2 on (y_0, y_1') with (h_0, h_1') and det on antenna 0's metric ----
+  cx g0[5], g1[5];
 #pragma unroll
-    for (int k = 0; k < 5; k++) { g0[k] = left ? h0[4 - k] : h0[k]; g1[k] = left ? h1w[4 - k] : h1w[k]; }
-    zf00 = mlse_expected(g0, s); zf10 = mlse_expected(g0, s | 16);
-    zf01 = mlse_expected(g1, s); zf11 = mlse_expected(g1, s | 16);
-    if (s == 0) {
-      scr[18] = mk(Ew_, __int_as_float(w)); scr[19] = mk(__int_as_float(st), det);
+  for (int k = 0; k < 5; k++) { g0[k] = left ? h0[4 - k] : h0[k]; g1[k] = left ? h1w[4 - k] : h1w[k]; }
+  if (s == 0) {
+    scr[18] = mk(Ew_, __int_as_float(w)); scr[19] = mk(__int_as_float(st), det);
 #pragma unroll
-      for (int k = 0; k < 5; k++) { scr[20 + k] = g0[k]; scr[25 + k] = g1[k]; }
-    }
+    for (int k = 0; k < 5; k++) { scr[20 + k] = g0[k]; scr[25 + k] = g1[k]; }
   }
-  const int pf0 = 4 * (rowbase | (s >> 1)), pf1 = pf0 + 32;
-  const int pb0 = 4 * (rowbase | ((2 * s) & 15)), pb1 = pb0 + 4;
+  // start state and steps: k_mlse_div's
   const int start = left ? (int)(tsc_bits & 15u)
                          : (int)(((tsc_bits >> 25) & 1u) | (((tsc_bits >> 24) & 1u) << 1) | (((tsc_bits >> 23) & 1u) << 2) | (((tsc_bits >> 22) & 1u) << 3));
-  int yi = left ? 64 + w : 87 + w;
-  const int dir = left ? -1 : 1;
-  float A[61];
-  float al = (s == start) ? 0.0f : TRX_MLSE_INF;
-  cx y0 = Y0[yi], y1 = Y1[yi];
-#pragma unroll
-  for (int i = 0; i < 61; i++) {
-    if (i < 60) yi += dir;
-    const cx yn0 = Y0[yi], yn1 = Y1[yi];
-    float g0 = det * mlse_gamma(y0, zf00) + mlse_gamma(y1, zf01);  // antenna 0's metric first
-    float g1 = det * mlse_gamma(y0, zf10) + mlse_gamma(y1, zf11);
-    if (i >= 58 && (s & 1)) { g0 = TRX_MLSE_INF; g1 = TRX_MLSE_INF; }            // the tail symbols are -1
-    const float a0 = bperm(pf0, al) + g0, a1 = bperm(pf1, al) + g1;
-    al = fminf(a0, a1);
-    A[i] = al;
-    y0 = yn0; y1 = yn1;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  wave_lds_fence();
-  cx zb00, zb10, zb01, zb11;                                // zb<b><antenna>: out of state s with b = 0, 1 -- Z[2 s], Z[2 s + 1]
-  {
-    cx g0[5], g1[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) { g0[k] = scr[20 + k]; g1[k] = scr[25 + k]; }
-    zb00 = mlse_expected(g0, 2 * s); zb10 = mlse_expected(g0, 2 * s + 1);
-    zb01 = mlse_expected(g1, 2 * s); zb11 = mlse_expected(g1, 2 * s + 1);
-  }
-  asm volatile("" : "+v"(yi));                              // (or the 61 addresses of the way up are kept in registers for the way back)
-  float be = 0.0f;
   float D[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int i = 60; i >= 0; i--) {
-    if (i > 0) yi -= dir;
-    const cx yn0 = Y0[yi], yn1 = Y1[yi];
-    float t = A[i] + be;                                    // alpha and beta, both after step i
-    t = fminf(t, dpp_f<0x4E>(t));                           // lane ^ 2
-    t = fminf(t, dpp_f<0x124>(t));                          // the row rotated by 4
-    t = fminf(t, dpp_f<0x128>(t));                          // ... by 8: the minimum over the eight states of this lane's parity
-    const float o = dpp_f<0xB1>(t);                         // lane ^ 1: the other parity's
-    const float diff = (s & 1) ? o - t : t - o;             // M_0 - M_1
-    if ((i & 15) == s) D[i >> 4] = diff;
-    asm volatile("" : "+v"(D[i >> 4]));
-    if (i > 0) {
-      const float g0 = det * mlse_gamma(y0, zb00) + mlse_gamma(y1, zb01);
-      const float g1 = (i >= 58) ? TRX_MLSE_INF : det * mlse_gamma(y0, zb10) + mlse_gamma(y1, zb11);
-      const float b0 = g0 + bperm(pb0, be), b1 = g1 + bperm(pb1, be);
-      be = fminf(b0, b1);
-    }
-    y0 = yn0; y1 = yn1;
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  mlse_trellis2<61, true>(Y0, Y1, left ? 64 + w : 87 + w, left ? -1 : 1, g0, g1, det, scr, lane, start, D);
 
   // ---- 4 / 5. soft bits out (the midamble of an equalised burst is out already) ----
   if (b >= B) return;
@@ -318,20 +206,10 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
     for (int q = 0; q < 4; q++) {
       const int i = 16 * q + s;
       const int m = left ? 60 - i : 87 + i;
-      if (i < 61 && m < nsoft) {
-        float sv = 0.5f + D[q] / den;
-        if (sv > 1.0f) sv = 1.0f;
-        if (sv < 0.0f) sv = 0.0f;
-        sb[m] = sv;
-        if (hb) hb[m] = sv > 0.5F;
-      }
+      if (i < 61 && m < nsoft) mlse_soft_out(sb, hb, m, D[q], den);
     }
   } else {
-    for (int m = hl; m < nsoft; m += 32) {
-      const float sv = st_ == 1 ? mlse_slice(Yp[m].r) : 0.0f;
-      sb[m] = sv;
-      if (hb) hb[m] = sv > 0.5F;
-    }
+    mlse_fall_back(sb, hb, Yp, st_, hl, 32, nsoft);
   }
 }
 
@@ -348,12 +226,6 @@ hipError_t trx_launch_mlse_irc(hipStream_t st, int sps, const TrxTables *dT, con
   const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
 #define TRX_MLSE_IRC_GO(S) k_mlse_irc<S><<<grid, block, 0, st>>>(dT, samples0, off0, samples1, off1, len, B, tsc_bits, amp, toa, primary, flags, \
                                                                  need_mask, loading, cov_in, cov, chan, win, soft, hard, nsoft, stride)
-  switch (sps) {
-    case 1: TRX_MLSE_IRC_GO(1); break;
-    case 2: TRX_MLSE_IRC_GO(2); break;
-    case 4: TRX_MLSE_IRC_GO(4); break;
-    default: return hipErrorInvalidValue;
-  }
+  TRX_MLSE_DISPATCH(sps, TRX_MLSE_IRC_GO);
 #undef TRX_MLSE_IRC_GO
-  return hipGetLastError();
 }

@@ -6,7 +6,7 @@
 // subtract, multiply, minimum, compare and one correctly rounded division per soft bit; nothing is fused.  The algorithm is stated
 // in include/trxsig.h (trxsig_mlse_sch_batch) and again, operation by operation, in the model.
 //
-// Layout.  One wave takes TWO bursts: k_mlse's rows with k_mlse_access's estimator.
+// Layout.  One wave takes TWO bursts: k_mlse's rows with k_mlse_access's estimator, every step from trxsig_mlse_dev.h.
 //   * Symbols: the whole wave computes one burst at a time with k_demod's own code (demod_core, RAW form) and keeps the 148 rotated
 //     outputs, complex, in LDS.  The loop over the two bursts is NOT unrolled (the bursts' states travel in one packed register):
 //     one copy of demod_core in the listing, as in k_mlse_access.
@@ -16,13 +16,12 @@
 //     k_mlse_access: read once per wave, L2- and L1-resident for the whole launch, no LDS for it.
 //   * Trellis: each of the wave's four 16-lane rows is one half-burst trellis (rows 0, 1: the first burst's right and left half;
 //     rows 2, 3: the second burst's); lane s of a row is state s.  Predecessors and successors come across the row by ds_bpermute,
-//     the parity minima by the three DPP steps, the received symbol of a step is one LDS broadcast read per row -- all k_mlse's.
-//     The 42 forward metrics of a lane stay in 42 VGPRs (both loops fully unrolled, the per-step scheduling fence that k_mlse
-//     needs); M_0 - M_1 of step i is kept by lane i % 16 (three registers).
+//     the parity minima by the three DPP steps, the received symbol of a step is one LDS broadcast read per row -- mlse_trellis<42>.
+//     The 42 forward metrics of a lane stay in 42 VGPRs (both loops fully unrolled, a scheduling fence per step); M_0 - M_1 of step i is kept by lane i % 16 (three registers).
 //   * LDS: the staging area and two symbol vectors a wave: k_mlse's.  Listing (gfx950): DESIGN.md 5.4.v and the README.
 #define TRX_MLSE_SCH_TAB_QUAL static __device__ __constant__ const
 #include "trxsig_mlse_sch_tab.h"
-#include "trxsig_mlse_dev.h"                                // bperm, sgn, mlse_expected, mlse_gamma, mlse_slice: shared with k_mlse
+#include "trxsig_mlse_dev.h"                                // mlse_symbols, mlse_ls_tap, mlse_window, mlse_trellis, mlse_soft_out, ...
 
 namespace {
 
@@ -59,41 +58,14 @@ void k_mlse_sch(const TrxTables *__restrict__ T, const void *__restrict__ sample
     float toa = 0.0f;
     if (b < B) {
       off = offset[b]; N = length[b]; amp = amp_in[b]; toa = toa_in[b];
-      enabled = (off >= 0) && (N >= 92 * SPS) && (N <= 157 * SPS) && (N % SPS == 0) && (fabsf(toa) <= 4096.0f);   // k_demod's test
-      if (flags) enabled = enabled && (need_mask ? ((flags[b] & need_mask) == need_mask) : (flags[b] != 0));
+      enabled = mlse_enabled<SPS>(off, N, toa, flags, need_mask, b);
     }
     if (!__builtin_amdgcn_readfirstlane(enabled)) {
-      for (int m = lane; m < TRX_MLSE_NY; m += 64) Y[m] = mk(0, 0);      // (the trellis rows of this burst run on zeros; nothing of theirs is stored)
+      mlse_zero(Y, lane);
       states |= 2 << (2 * j);
       continue;
     }
-    constexpr int NLD = (157 * SPS / 2 + 63) / 64;
-    const bool wide = (off & 1) == 0;
-    float4 v[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; i++) v[i] = make_float4(0, 0, 0, 0);
-    if (wide) {
-#pragma unroll
-      for (int i = 0; i < NLD; i++) {
-        const int q = lane + 64 * i;
-        if (q < N / 2) v[i] = SmpC32::ld2(samples, off, q);
-      }
-    }
-    wave_lds_fence();                                       // the staging area's readers of the burst before are done
-    demod_core<SPS, true, 148>(T, ph[wave], samples, off, N, wide, v, amp, toa, lane, nullptr, nullptr, Y, 148);
-    wave_lds_fence();
-    // GMSKReverseRotate at the decimated instants, both parts kept: the reference's complex product with rev[sps m]
-    bool bad = false;
-    const cx *rev = T->rev;
-    for (int m = lane; m < TRX_MLSE_NY; m += 64) {
-      cx y = mk(0, 0);
-      if (m < 148 && m < N / SPS) {                        // (a short burst's symbols past its end are zeros: demodulateBurst has none there)
-        y = cmul(Y[m], rev[SPS * m]);
-        bad = bad || !(fabsf(y.r) < 0x1p30f) || !(fabsf(y.i) < 0x1p30f);
-      }
-      Y[m] = y;
-    }
-    if (__builtin_amdgcn_ballot_w64(bad) != 0 || N / SPS < 148) states |= 1 << (2 * j);
+    if (mlse_symbols<SPS>(T, ph[wave], samples, off, N, amp, toa, lane, Y)) states |= 1 << (2 * j);
   }
   wave_lds_fence();
 
@@ -105,36 +77,13 @@ void k_mlse_sch(const TrxTables *__restrict__ T, const void *__restrict__ sample
   const cx *Y = ysh[wave][j];
   cx *scr = ph[wave] + 44 * (lane >> 4);                    // this row's 44 words of the (dead) staging area: c[9], (E, w), state, Z[32] from word 12
   {
-    const float *P = trx_mlse_sch_p32 + TRX_MLSE_SCH_NROW * (s < 9 ? s : 8);
-    float ar = 0.0f, ai = 0.0f;
-#pragma unroll
-    for (int i = 0; i < TRX_MLSE_SCH_NROW; i++) {
-      const cx y = Y[TRX_MLSE_SCH_ROW0 + i];
-      const float pk = P[i];
-      ar = ar + pk * y.r;
-      ai = ai + pk * y.i;
-    }
-    if (s < 9) scr[s] = mk(ar, ai);
+    const cx cd = mlse_ls_tap<TRX_MLSE_SCH_NROW>(trx_mlse_sch_p32 + TRX_MLSE_SCH_NROW * (s < 9 ? s : 8), Y, TRX_MLSE_SCH_ROW0);
+    if (s < 9) scr[s] = cd;
   }
   wave_lds_fence();
-  cx c[9];
-  float p[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) { c[i] = scr[i]; p[i] = c[i].r * c[i].r + c[i].i * c[i].i; }
-  int w = 0;
-  float E = (((p[4] + p[5]) + p[6]) + p[7]) + p[8];
-#pragma unroll
-  for (int q = 1; q <= 4; q++) {                            // w = -q; a later window only on a strict >
-    const float Ew = (((p[4 - q] + p[5 - q]) + p[6 - q]) + p[7 - q]) + p[8 - q];
-    if (Ew > E) { E = Ew; w = -q; }
-  }
   cx h[5];
-#pragma unroll
-  for (int k = 0; k < 5; k++) {
-    h[k] = c[4 + k];
-#pragma unroll
-    for (int q = 1; q <= 4; q++) if (w == -q) h[k] = c[4 - q + k];
-  }
+  int w;
+  const float E = mlse_window(scr, h, w);
   int st = (states >> (2 * j)) & 3;
   if (st == 0 && E == 0.0f) st = 1;
 
@@ -157,56 +106,11 @@ void k_mlse_sch(const TrxTables *__restrict__ T, const void *__restrict__ sample
   // (the way back needs Z[2 s], Z[2 s + 1] -- out of state s with b = 0, 1 -- and E and the burst's state are wanted after it: parked in LDS)
   scr[12 + s] = zf0; scr[28 + s] = zf1;
   if (s == 0) { scr[9] = mk(E, __int_as_float(w)); scr[10] = mk(__int_as_float(st), 0.0f); }
-  const int rowbase = lane & 48;
-  const int pf0 = 4 * (rowbase | (s >> 1)), pf1 = pf0 + 32;
-  const int pb0 = 4 * (rowbase | ((2 * s) & 15)), pb1 = pb0 + 4;
   // start state, bit 0 first: a[105], a[104], a[103], a[102] (right) or a[42], a[43], a[44], a[45] (left), from the extended training sequence
   const int start = left ? TRX_MLSE_SCH_START_LEFT : TRX_MLSE_SCH_START_RIGHT;
   // step i = 0..41 is symbol m = 106 + i with sample y[m + w] (right), m = 41 - i with y[m + 4 + w] (left)
-  int yi = left ? TRX_MLSE_SCH_LEFT0 + 4 + w : TRX_MLSE_SCH_RIGHT0 + w;
-  const int dir = left ? -1 : 1;
-  // (a scheduling fence per step, the next step's symbol fetched ahead of it: see k_mlse)
-  float A[TRX_MLSE_SCH_STEPS];
-  float al = (s == start) ? 0.0f : TRX_MLSE_INF;
-  cx y = Y[yi];
-#pragma unroll
-  for (int i = 0; i < TRX_MLSE_SCH_STEPS; i++) {
-    if (i < TRX_MLSE_SCH_STEPS - 1) yi += dir;
-    const cx yn = Y[yi];
-    float g0 = mlse_gamma(y, zf0), g1 = mlse_gamma(y, zf1);
-    if (i >= TRX_MLSE_SCH_STEPS - 3 && (s & 1)) { g0 = TRX_MLSE_INF; g1 = TRX_MLSE_INF; }   // the tail symbols are -1
-    const float a0 = bperm(pf0, al) + g0, a1 = bperm(pf1, al) + g1;
-    al = fminf(a0, a1);
-    A[i] = al;
-    y = yn;                                                 // (after the last step the symbol is that step's again: the backward pass starts there)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  wave_lds_fence();
-  const cx zb0 = scr[12 + 2 * s], zb1 = scr[13 + 2 * s];
-  asm volatile("" : "+v"(yi));                              // (or the addresses of the way up are kept in registers for the way back)
-  float be = 0.0f;
   float D[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int i = TRX_MLSE_SCH_STEPS - 1; i >= 0; i--) {
-    if (i > 0) yi -= dir;
-    const cx yn = Y[yi];
-    float t = A[i] + be;                                    // alpha and beta, both after step i
-    t = fminf(t, dpp_f<0x4E>(t));                           // lane ^ 2
-    t = fminf(t, dpp_f<0x124>(t));                          // the row rotated by 4
-    t = fminf(t, dpp_f<0x128>(t));                          // ... by 8: the minimum over the eight states of this lane's parity
-    const float o = dpp_f<0xB1>(t);                         // lane ^ 1: the other parity's
-    const float diff = (s & 1) ? o - t : t - o;             // M_0 - M_1
-    if ((i & 15) == s) D[i >> 4] = diff;
-    asm volatile("" : "+v"(D[i >> 4]));                     // (the select happens here: not 42 differences kept for a chain of selects after the loop)
-    if (i > 0) {
-      const float g0 = mlse_gamma(y, zb0);
-      const float g1 = (i >= TRX_MLSE_SCH_STEPS - 3) ? TRX_MLSE_INF : mlse_gamma(y, zb1);
-      const float b0 = g0 + bperm(pb0, be), b1 = g1 + bperm(pb1, be);
-      be = fminf(b0, b1);
-    }
-    y = yn;
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  mlse_trellis<TRX_MLSE_SCH_STEPS>(Y, left ? TRX_MLSE_SCH_LEFT0 + 4 + w : TRX_MLSE_SCH_RIGHT0 + w, left ? -1 : 1, zf0, zf1, scr, lane, start, D);
 
   // ---- 4 / 5. soft bits out ----
   if (b >= B) return;
@@ -220,29 +124,15 @@ void k_mlse_sch(const TrxTables *__restrict__ T, const void *__restrict__ sample
     for (int q = 0; q < 3; q++) {
       const int i = 16 * q + s;
       const int m = left ? TRX_MLSE_SCH_LEFT0 - i : TRX_MLSE_SCH_RIGHT0 + i;
-      if (i < TRX_MLSE_SCH_STEPS && m < nsoft) {
-        float sv = 0.5f + D[q] / den;
-        if (sv > 1.0f) sv = 1.0f;
-        if (sv < 0.0f) sv = 0.0f;
-        sb[m] = sv;
-        if (hb) hb[m] = sv > 0.5F;
-      }
+      if (i < TRX_MLSE_SCH_STEPS && m < nsoft) mlse_soft_out(sb, hb, m, D[q], den);
     }
 #pragma unroll
     for (int q = 0; q < 2; q++) {                           // the extended training sequence, 42..105: the demodulator's formula
       const int m = TRX_MLSE_SCH_LEFT0 + 1 + 32 * q + hl;
-      if (m < nsoft) {
-        const float sv = mlse_slice(Y[m].r);
-        sb[m] = sv;
-        if (hb) hb[m] = sv > 0.5F;
-      }
+      if (m < nsoft) mlse_put(sb, hb, m, mlse_slice(Y[m].r));
     }
   } else {
-    for (int m = hl; m < nsoft; m += 32) {
-      const float sv = st_ == 1 ? mlse_slice(Y[m].r) : 0.0f;
-      sb[m] = sv;
-      if (hb) hb[m] = sv > 0.5F;
-    }
+    mlse_fall_back(sb, hb, Y, st_, hl, 32, nsoft);
   }
 }
 
@@ -255,11 +145,7 @@ hipError_t trx_launch_mlse_sch(hipStream_t st, int sps, const TrxTables *dT, con
   if (nsoft < 0 || nsoft > 148) return hipErrorInvalidValue;
   const int per = 2 * TRX_MLSE_WAVES;
   const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
-  switch (sps) {
-    case 1: k_mlse_sch<1><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan, win, soft, hard, nsoft, stride); break;
-    case 2: k_mlse_sch<2><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan, win, soft, hard, nsoft, stride); break;
-    case 4: k_mlse_sch<4><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan, win, soft, hard, nsoft, stride); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+#define TRX_MLSE_SCH_GO(S) k_mlse_sch<S><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan, win, soft, hard, nsoft, stride)
+  TRX_MLSE_DISPATCH(sps, TRX_MLSE_SCH_GO);
+#undef TRX_MLSE_SCH_GO
 }

@@ -1,6 +1,6 @@
 // trxsig_sch_fit.hip -- the fit detector's statistic for synchronisation bursts (trxsig_sch_fit_batch; trxsig_l1acq's
-// TRXSIG_SCHDET_FIT): the burst's symbols, the nine-tap least-squares estimate and the best five-tap window exactly as
-// k_mlse_sch (trxsig_mlse_sch.hip) forms them, then the residual of that fit on the 56 rows whose symbols are all known and
+// TRXSIG_SCHDET_FIT): the burst's symbols, the nine-tap least-squares estimate and the best five-tap window by the code
+// k_mlse_sch (trxsig_mlse_sch.hip) forms them with (trxsig_mlse_dev.h), then the residual of that fit on the 56 rows whose symbols are all known and
 // q = sqrtf(51 E / R): tap energy over residual power, an SNR estimate that does not care where the echoes of the channel lie.
 // The reference has no counterpart; the stage is pinned by the float32 model tests/sch_fit_model.py, which this kernel equals
 // word for word, and graded against the float64 statement tests/sch_fit_ref.py.  The arithmetic rules are k_mlse's: float add,
@@ -21,7 +21,7 @@
 //   * LDS: the staging area and ONE symbol vector a wave (k_mlse_sch keeps two).  Listing (gfx950): DESIGN.md 5.4.vi.
 #define TRX_MLSE_SCH_TAB_QUAL static __device__ __constant__ const
 #include "trxsig_mlse_sch_tab.h"
-#include "trxsig_mlse_dev.h"                                // sgn, mlse_expected, mlse_gamma: shared with k_mlse
+#include "trxsig_mlse_dev.h"                                // mlse_symbols, mlse_ls_tap, mlse_window, mlse_expected, mlse_gamma
 
 namespace {
 
@@ -57,42 +57,13 @@ void k_sch_fit(const TrxTables *__restrict__ T, const void *__restrict__ samples
   for (int jb = 0; jb < 2; jb++) {
     const int b = bw + jb;                                  // wave-uniform
     if (b >= B) break;
-    // ---- 1. symbols: k_mlse_sch's.  st: 0 = fit, 1 = fell back, 2 = not enabled ----
+    // ---- 1. symbols (mlse_symbols).  st: 0 = fit, 1 = fell back, 2 = not enabled ----
     const int off = offset[b], N = length[b];
     const cx amp = amp_in[b];
     const float toa = toa_in[b];
-    bool enabled = (off >= 0) && (N >= 92 * SPS) && (N <= 157 * SPS) && (N % SPS == 0) && (fabsf(toa) <= 4096.0f);   // k_demod's test
-    if (flags) enabled = enabled && (need_mask ? ((flags[b] & need_mask) == need_mask) : (flags[b] != 0));
+    const bool enabled = mlse_enabled<SPS>(off, N, toa, flags, need_mask, b);
     int st = 2;
-    if (__builtin_amdgcn_readfirstlane(enabled)) {
-      constexpr int NLD = (157 * SPS / 2 + 63) / 64;
-      const bool wide = (off & 1) == 0;
-      float4 v[NLD];
-#pragma unroll
-      for (int i = 0; i < NLD; i++) v[i] = make_float4(0, 0, 0, 0);
-      if (wide) {
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-          const int q = lane + 64 * i;
-          if (q < N / 2) v[i] = SmpC32::ld2(samples, off, q);
-        }
-      }
-      wave_lds_fence();                                     // the staging area's readers of the burst before are done
-      demod_core<SPS, true, 148>(T, ph[wave], samples, off, N, wide, v, amp, toa, lane, nullptr, nullptr, Y, 148);
-      wave_lds_fence();
-      // GMSKReverseRotate at the decimated instants, both parts kept: the reference's complex product with rev[sps m]
-      bool bad = false;
-      const cx *rev = T->rev;
-      for (int m = lane; m < TRX_MLSE_NY; m += 64) {
-        cx y = mk(0, 0);
-        if (m < 148 && m < N / SPS) {
-          y = cmul(Y[m], rev[SPS * m]);
-          bad = bad || !(fabsf(y.r) < 0x1p30f) || !(fabsf(y.i) < 0x1p30f);
-        }
-        Y[m] = y;
-      }
-      st = (__builtin_amdgcn_ballot_w64(bad) != 0 || N / SPS < 148) ? 1 : 0;
-    }
+    if (__builtin_amdgcn_readfirstlane(enabled)) st = mlse_symbols<SPS>(T, ph[wave], samples, off, N, amp, toa, lane, Y) ? 1 : 0;
 
     cx cm = mk(0, 0);                                       // lane d < 9: c[d - 4]
     int w = 0;
@@ -100,37 +71,11 @@ void k_sch_fit(const TrxTables *__restrict__ T, const void *__restrict__ samples
     if (st == 0) {                                          // wave-uniform
       wave_lds_fence();
       // ---- 2. channel estimate: lanes 0..8 form c[-4..4] = P32 y[46..101]; every lane then reads all nine ----
-      {
-        const float *P = trx_mlse_sch_p32 + TRX_MLSE_SCH_NROW * (lane < 9 ? lane : 8);
-        float ar = 0.0f, ai = 0.0f;
-#pragma unroll
-        for (int i = 0; i < TRX_MLSE_SCH_NROW; i++) {
-          const cx y = Y[TRX_MLSE_SCH_ROW0 + i];
-          const float pk = P[i];
-          ar = ar + pk * y.r;
-          ai = ai + pk * y.i;
-        }
-        cm = mk(ar, ai);
-        if (lane < 9) scr[lane] = cm;
-      }
+      cm = mlse_ls_tap<TRX_MLSE_SCH_NROW>(trx_mlse_sch_p32 + TRX_MLSE_SCH_NROW * (lane < 9 ? lane : 8), Y, TRX_MLSE_SCH_ROW0);
+      if (lane < 9) scr[lane] = cm;
       wave_lds_fence();
-      cx c[9];
-      float p[9];
-#pragma unroll
-      for (int i = 0; i < 9; i++) { c[i] = scr[i]; p[i] = c[i].r * c[i].r + c[i].i * c[i].i; }
-      E = (((p[4] + p[5]) + p[6]) + p[7]) + p[8];
-#pragma unroll
-      for (int k = 1; k <= 4; k++) {                        // w = -k; a later window only on a strict >
-        const float Ew = (((p[4 - k] + p[5 - k]) + p[6 - k]) + p[7 - k]) + p[8 - k];
-        if (Ew > E) { E = Ew; w = -k; }
-      }
       cx h[5];
-#pragma unroll
-      for (int k = 0; k < 5; k++) {
-        h[k] = c[4 + k];
-#pragma unroll
-        for (int u = 1; u <= 4; u++) if (w == -u) h[k] = c[4 - u + k];
-      }
+      E = mlse_window(scr, h, w);
       if (E == 0.0f) {
         st = 1;
       } else {
@@ -176,11 +121,7 @@ hipError_t trx_launch_sch_fit(hipStream_t st, int sps, const TrxTables *dT, cons
   if (B <= 0) return hipSuccess;
   const int per = 2 * TRX_MLSE_WAVES;
   const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
-  switch (sps) {
-    case 1: k_sch_fit<1><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan9, win, E, R, q); break;
-    case 2: k_sch_fit<2><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan9, win, E, R, q); break;
-    case 4: k_sch_fit<4><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan9, win, E, R, q); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+#define TRX_SCH_FIT_GO(S) k_sch_fit<S><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan9, win, E, R, q)
+  TRX_MLSE_DISPATCH(sps, TRX_SCH_FIT_GO);
+#undef TRX_SCH_FIT_GO
 }

@@ -95,6 +95,8 @@ def test_kernel_file_is_built():
     assert re.search(r"^KERNELS\s*:=.*\btrxsig_mlse_access\b", mk, re.M)
     src = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_access.hip")).read()
     assert "k_mlse_access" in src and "amdgpu_waves_per_eu(4)" in src and "trxsig_mlse_dev.h" in src and "trxsig_mlse_access_tab.h" in src
+    for call in ("mlse_symbols<SPS>(", "mlse_ls_tap<TRX_MLSE_ACCESS_NROW>(", "mlse_window(", "mlse_trellis<TRX_MLSE_ACC_STEPS>(", "#pragma unroll 1"):
+        assert call in src, call
 
 
 def test_documents_name_the_stage():

@@ -70,6 +70,10 @@ def test_kernel_file_is_built():
     assert re.search(r"^KERNELS\s*:=.*\btrxsig_mlse_irc\b", mk, re.M)
     src = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_irc.hip")).read()
     assert "k_mlse_irc" in src and "amdgpu_waves_per_eu(4)" in src
+    for call in ("mlse_symbols<SPS>(", "mlse_window2(", "mlse_trellis2<61, true>(", "#pragma unroll 1"):
+        assert call in src, call
+    dev = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_dev.h")).read()
+    assert "if (WEIGHTED) return det * mlse_gamma(y0, z0) + mlse_gamma(y1, z1);" in dev       # det on antenna 0's metric, and only here
 
 
 def test_documents_name_the_stage():

@@ -103,6 +103,8 @@ def test_kernel_file_is_built():
     assert re.search(r"^KERNELS\s*:=.*\btrxsig_mlse_sch\b", mk, re.M)
     src = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_sch.hip")).read()
     assert "k_mlse_sch" in src and "amdgpu_waves_per_eu(4)" in src and "trxsig_mlse_dev.h" in src and "trxsig_mlse_sch_tab.h" in src
+    for call in ("mlse_symbols<SPS>(", "mlse_ls_tap<TRX_MLSE_SCH_NROW>(", "mlse_window(", "mlse_trellis<TRX_MLSE_SCH_STEPS>(", "#pragma unroll 1"):
+        assert call in src, call
     acq = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_l1acq.cpp")).read()
     assert "trx_launch_mlse_sch" in acq and "trx_launch_demod" in acq
 

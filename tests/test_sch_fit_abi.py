@@ -80,7 +80,9 @@ def test_kernel_file_is_built():
     assert re.search(r"^KERNELS\s*:=.*\btrxsig_sch_fit\b", mk, re.M)
     src = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_sch_fit.hip")).read()
     assert "k_sch_fit" in src and "amdgpu_waves_per_eu(4)" in src and "trxsig_mlse_dev.h" in src and "trxsig_mlse_sch_tab.h" in src
-    assert "demod_core<SPS, true, 148>" in src and "#pragma unroll 1" in src
+    dev = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_dev.h")).read()
+    assert "demod_core<SPS, true, 148>" in dev and "mlse_symbols<SPS>(" in src and "#pragma unroll 1" in src      # the symbols step is the shared one
+    assert "mlse_ls_tap<TRX_MLSE_SCH_NROW>(" in src and "mlse_window(" in src
     acq = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_l1acq.cpp")).read()
     assert "trx_launch_sch_fit" in acq and "trx_launch_l1acq_verdict" in acq and "trx_launch_l1acq_fit_verdict" in acq
 
