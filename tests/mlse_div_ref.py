@@ -68,17 +68,9 @@ def equalise64(y, w, h, tsc):
 def grade(soft, hard, y, w, h, tsc):
     """mlse_ref.grade's three conditions (bad_soft, bad_clamp, bad_hard), `excluded` and `ratio` on soft [B, 148] float32 and hard
     [B, 148] against this reference on (y [B, 2, 148], w, h [B, 2, 5]).  The reference alone decides `excluded`."""
-    return mlse_ref.grade(soft, hard, None, None, None, tsc, ref=equalise64(y, w, h, tsc))
+    return mlse_ref.graded(soft, hard, equalise64(y, w, h, tsc), TRELLIS)
 
 
 def check(soft, hard, y, w, h, tsc, what):
     """Assert the three conditions; returns grade's dict."""
-    g = grade(soft, hard, y, w, h, tsc)
-    r = g["ref"]
-    for key, text in (("bad_soft", "|soft - clamp(soft64)| > bound"), ("bad_clamp", "soft64 beyond the clamp by more than the bound, soft not clamped"),
-                      ("bad_hard", "hard bit differs outside the margin")):
-        if g[key].any():
-            b, m = np.argwhere(g[key])[0]
-            raise AssertionError("%s: %s at %d positions; first: burst %d symbol %d: soft %.9g hard %d, soft64 %.12g, bound %.3g"
-                                 % (what, text, g[key].sum(), b, m, np.asarray(soft)[b, m], np.asarray(hard)[b, m], r["soft"][b, m], r["bound"][b, m]))
-    return g
+    return mlse_ref.checked(grade(soft, hard, y, w, h, tsc), soft, hard, what)

@@ -1,18 +1,17 @@
 """The float32 model of the two-antenna sequence equaliser with interference-rejection combining (trxsig_mlse_irc_batch,
 csrc/trxsig_mlse_irc.hip): the algorithm of include/trxsig.h restated in numpy float32, operation by operation, vectorised over
 bursts.  The kernel must equal it word for word.  It is tests/mlse_div_model.py with steps 2b-2d added and det in the branch
-metric: the symbols, the estimator, the expected values, the selection and the geometry test are that module's, by import; the
-residual sums, the set, the whitening and the two half-burst trellises (their metric differs) are stated here.
+metric: the estimator and the selection are that module's, by import, the expected values, the trellis and the batch wrapper
+tests/mlse_core.py's; the residual sums, the set, the whitening and the branch metric are stated here.
 
 Every arithmetic step below is ONE float32 operation on float32 arrays, in the order the header states."""
 import numpy as np
 
-import oraclebind
-from mlse_div_model import WIN_FELL_BACK, WIN_SKIPPED, _expected, estimate, select  # noqa: F401  (select: the callers' rule)
-from mlse_model import burst_enabled, slicer, symbols, tsc_symbols
+import mlse_core as core
+from mlse_core import F, INF, WIN_FELL_BACK, WIN_SKIPPED  # noqa: F401  (the importers' names)
+from mlse_div_model import estimate, select  # noqa: F401  (select: the callers' rule)
+from mlse_model import LEFT0, RIGHT0, STEPS, slicer, start_states, tsc_symbols
 
-F = np.float32
-INF = F(np.inf)
 LOADING = F(1.0 / 64.0)                                       # what the tools and the Transceiver groups use
 IDENTITY = np.array([1.0, 1.0, 0.0, 0.0], F)
 
@@ -22,8 +21,8 @@ def residual_sums(y, w, h, t):
     B = y.shape[0]
     rows = np.arange(B)
     yr, yi = y.real.astype(F), y.imag.astype(F)
-    Z0r, Z0i = _expected(h[:, 0].real.astype(F), h[:, 0].imag.astype(F))
-    Z1r, Z1i = _expected(h[:, 1].real.astype(F), h[:, 1].imag.astype(F))
+    Z0r, Z0i = core.expected(h[:, 0].real.astype(F), h[:, 0].imag.astype(F))
+    Z1r, Z1i = core.expected(h[:, 1].real.astype(F), h[:, 1].imag.astype(F))
     bit = (t > 0).astype(np.int64)
     S00 = np.zeros(B, F); S11 = np.zeros(B, F); Xr = np.zeros(B, F); Xi = np.zeros(B, F)
     for m in range(65, 87):
@@ -63,37 +62,19 @@ def whiten(A, xr, xi, v0r, v0i, v1r, v1i):
     return wr, wi
 
 
-def _half(yr, yi, w, gr, gi, det, start, left):
-    """One half-burst trellis for every burst: M_0 - M_1 per step, [B, 61].  yr, yi [B, 2, 148] (antenna 1 whitened); gr, gi
-    [B, 2, 5] (antenna 1's whitened); det [B]; start [B].  mlse_div_model._half with det on antenna 0's metric."""
-    B = yr.shape[0]
-    Z0r, Z0i = _expected(gr[:, 0], gi[:, 0])
-    Z1r, Z1i = _expected(gr[:, 1], gi[:, 1])
-    rows = np.arange(B)
-    gam = np.zeros((61, B, 32), F)
-    for i in range(61):
-        n = (60 - i + 4 + w) if left else (87 + i + w)
+def metric(yr, yi, gr, gi, det):
+    """The branch metrics as core.half takes them: mlse_div_model.metric with det [B] on antenna 0's term.  yr, yi [B, 2, 148]
+    (antenna 1 whitened); gr, gi [B, 2, 5] (antenna 1's whitened)."""
+    Z0r, Z0i = core.expected(gr[:, 0], gi[:, 0])
+    Z1r, Z1i = core.expected(gr[:, 1], gi[:, 1])
+    rows = np.arange(yr.shape[0])
+
+    def at(n):
         dr0 = yr[rows, 0, n][:, None] - Z0r; di0 = yi[rows, 0, n][:, None] - Z0i
         dr1 = yr[rows, 1, n][:, None] - Z1r; di1 = yi[rows, 1, n][:, None] - Z1i
         g = det[:, None] * (dr0 * dr0 + di0 * di0) + (dr1 * dr1 + di1 * di1)
-        if i >= 58:
-            g[:, 1::2] = INF                                   # the tail symbols are -1: b = 1 contradicts
-        gam[i] = g
-    s = np.arange(16)
-    alpha = np.where(s[None, :] == start[:, None], F(0.0), INF).astype(F)
-    A = np.zeros((61, B, 16), F)
-    p0, p1 = s >> 1, (s >> 1) | 8
-    for i in range(61):
-        alpha = np.minimum(alpha[:, p0] + gam[i][:, s], alpha[:, p1] + gam[i][:, s | 16])     # x = (pred << 1) | b
-        A[i] = alpha
-    beta = np.zeros((B, 16), F)
-    D = np.zeros((B, 61), F)
-    for i in range(60, -1, -1):
-        T = A[i] + beta
-        D[:, i] = T[:, 0::2].min(axis=1) - T[:, 1::2].min(axis=1)
-        x0, x1 = 2 * s, 2 * s + 1
-        beta = np.minimum(gam[i][:, x0] + beta[:, x0 & 15], gam[i][:, x1] + beta[:, x1 & 15])
-    return D
+        return g
+    return at
 
 
 def trellis(y, tsc, w, h0, h1w, cov, det, E, Ew, primary=None):
@@ -103,27 +84,22 @@ def trellis(y, tsc, w, h0, h1w, cov, det, E, Ew, primary=None):
     y = np.ascontiguousarray(y, np.complex64)
     B = y.shape[0]
     primary = np.zeros(B, np.int64) if primary is None else np.asarray(primary, np.int64)
-    t = tsc_symbols(tsc)
     yr, yi = y.real.astype(F), y.imag.astype(F)
     A, xr, xi = cov[:, 0], cov[:, 2], cov[:, 3]
-    bit = (t > 0).astype(np.int64)
-    start_r = np.full(B, bit[25] | (bit[24] << 1) | (bit[23] << 2) | (bit[22] << 3))
-    start_l = np.full(B, bit[0] | (bit[1] << 1) | (bit[2] << 2) | (bit[3] << 3))
+    start_r, start_l = start_states(tsc_symbols(tsc), B)
     with np.errstate(all="ignore"):
         y1r, y1i = whiten(A[:, None], xr[:, None], xi[:, None], yr[:, 0], yi[:, 0], yr[:, 1], yi[:, 1])
         ywr = np.stack([yr[:, 0], y1r], axis=1); ywi = np.stack([yi[:, 0], y1i], axis=1)
         hr = np.stack([h0.real.astype(F), h1w.real.astype(F)], axis=1); hi = np.stack([h0.imag.astype(F), h1w.imag.astype(F)], axis=1)
-        Dr = _half(ywr, ywi, w, hr, hi, det, start_r, False)
-        Dl = _half(ywr, ywi, w, hr[:, :, ::-1], hi[:, :, ::-1], det, start_l, True)
+        Dr = core.half(metric(ywr, ywi, hr, hi, det), w, start_r, STEPS, RIGHT0, False)
+        Dl = core.half(metric(ywr, ywi, hr[:, :, ::-1], hi[:, :, ::-1], det), w, start_l, STEPS, LEFT0, True)
         den_E = Ew.astype(F)
         den = (F(8.0) * den_E)[:, None]
-        sr = F(0.5) + Dr / den
-        sl = F(0.5) + Dl / den
-        sr = np.where(sr > F(1.0), F(1.0), sr); sr = np.where(sr < F(0.0), F(0.0), sr)
-        sl = np.where(sl > F(1.0), F(1.0), sl); sl = np.where(sl < F(0.0), F(0.0), sl)
+        sr = core.soft_out(Dr, den)
+        sl = core.soft_out(Dl, den)
     soft = slicer(yr[np.arange(B), primary])
-    soft[:, 87:148] = sr
-    soft[:, 60::-1] = sl                                      # step i is symbol 60 - i
+    soft[:, RIGHT0:148] = sr
+    soft[:, LEFT0::-1] = sl                                   # step i is symbol 60 - i
     return soft.astype(F)
 
 
@@ -135,9 +111,8 @@ def equalise(y, tsc, primary=None, loading=LOADING, cov_in=None):
     B = y.shape[0]
     primary = np.zeros(B, np.int64) if primary is None else np.asarray(primary, np.int64)
     t = tsc_symbols(tsc)
+    fine, ys = core.usable(y)                                 # either antenna's
     with np.errstate(all="ignore"):
-        fine = (np.abs(y.real) < F(2.0 ** 30)).all(axis=(1, 2)) & (np.abs(y.imag) < F(2.0 ** 30)).all(axis=(1, 2))   # either antenna's
-        ys = np.where(fine[:, None, None], y, 0).astype(np.complex64)     # (a burst that falls back runs through below on zeros, unused)
         _, w, h, E = estimate(ys, t)
         ok = fine & (E != 0)
         S00, S11, Xr, Xi = residual_sums(ys, w, h, t)
@@ -156,10 +131,7 @@ def equalise(y, tsc, primary=None, loading=LOADING, cov_in=None):
         h1w = (wr + 1j * wi).astype(np.complex64)
         cov = np.stack([A, Bv, xr, xi], axis=1).astype(F)
         eq = trellis(ys, tsc, w, h[:, 0], h1w, cov, det, E, Ew, primary)
-    yp = y[np.arange(B), primary]
-    soft = np.where(ok[:, None], eq, slicer(yp.real.astype(F))).astype(F)
-    win = np.where(ok, w, WIN_FELL_BACK).astype(np.int32)
-    h = np.where(ok[:, None, None], h, 0).astype(np.complex64)
+    soft, win, h = core.fall_back(ok, eq, y[np.arange(B), primary], w, h)
     cov = np.where(ok[:, None], cov, 0).astype(F)
     return dict(soft=soft, win=win, chan=h, cov=cov, sums=np.stack([S00, S11, Xr, Xi], axis=1), det=det, Ew=Ew, h1w=h1w)
 
@@ -169,32 +141,7 @@ def mlse_irc_batch(sps, x0, off0, x1, off1, length, tsc, amp, toa, primary=None,
     """trxsig_mlse_irc_batch on packed bursts: dict(soft [B, nsoft], hard, win [B], chan [B, 2, 5], cov [B, 4], y [B, 2, 148], ...).
     y: the symbols of an earlier run of this or of mlse_div_model.mlse_div_batch on the same bursts, amp and TOA (step 1 is the same;
     it is the slow part), or None."""
-    B = len(off0)
-    amp = np.broadcast_to(np.asarray(amp, np.complex64), (B,)); toa = np.broadcast_to(np.asarray(toa, np.float32), (B,))
-    primary = np.zeros(B, np.int64) if primary is None else (np.asarray(primary) != 0).astype(np.int64)
-    have = y is not None
-    y = np.array(y, np.complex64) if have else np.zeros((B, 2, 148), np.complex64)
-    o = None if have else (oracle or oraclebind.Oracle(sps))
-    state = np.zeros(B, np.int32)
-    for b in range(B):
-        if (enable is not None and not enable[b]) or not burst_enabled(sps, int(off0[b]), int(length[b]), toa[b]) or int(off1[b]) < 0:
-            state[b] = WIN_SKIPPED
-            y[b] = 0
-            continue
-        if not have:
-            y[b, 0] = symbols(o, x0[off0[b]:off0[b] + length[b]], amp[b], toa[b])
-            y[b, 1] = symbols(o, x1[off1[b]:off1[b] + length[b]], amp[b], toa[b])
-        if length[b] // sps < 148:
-            state[b] = WIN_FELL_BACK
-    r = equalise(y, tsc, primary, loading, cov_in)
-    soft, win, h, cov = r["soft"], r["win"], r["chan"], r["cov"]
-    short = state == WIN_FELL_BACK
-    if short.any():
-        soft[short] = slicer(y[short, primary[short]].real)
-        win[short] = WIN_FELL_BACK; h[short] = 0; cov[short] = 0
-    skip = state == WIN_SKIPPED
-    soft[skip] = 0; win[skip] = WIN_SKIPPED; h[skip] = 0; cov[skip] = 0
-    soft = np.ascontiguousarray(soft[:, :nsoft])
-    with np.errstate(all="ignore"):
-        hard = (soft > F(0.5)).astype(np.uint8)
-    return dict(r, soft=soft, hard=hard, win=win, chan=h, cov=cov, y=y)
+    return core.batch(lambda y, primary: equalise(y, tsc, primary, loading, cov_in), sps, [x0, x1], [off0, off1], length, amp, toa,
+                      primary=primary, enable=enable, nsoft=nsoft, oracle=oracle, y=y, zeroed=("chan", "cov"))
+
+

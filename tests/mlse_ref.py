@@ -93,25 +93,31 @@ def training_bits(tsc):
     return np.array([int(ch) for ch in synth.TRAINING_SEQUENCE[tsc]], np.int64)
 
 
-def half_tables(y, w, h, tsc, left):
-    """The factor tables of one half, [B, 61, 32], with the known symbols pinned, and (dr, di) [B, 61, 32] for the bound.
-    Chain variable v is a[first + v]; factor l covers a[first + l .. first + l + 4], the newest of them against tap h[0]."""
+def chain_tables(y, w, h, n, first, known):
+    """The factor tables of one chain, [B, L, 32], with the known symbols pinned, and (dr, di) [B, L, 32] for the bound: (tab, dr,
+    di).  Chain variable v is a[first + v]; factor l covers a[first + l .. first + l + 4], the newest of them against tap h[0], and
+    reads y[n[l] + w]; known {m: bit} pins a[m].  Every equaliser's reference builds its tables here."""
     y = np.asarray(y, np.complex128); h = np.asarray(h, np.complex128); w = np.asarray(w, np.int64)
     B = y.shape[0]
     a = 2.0 * ((_X[:, None] >> np.arange(5)[None, :]) & 1) - 1.0            # a[x, j]: the value of the factor's j-th symbol
     Z = (a[None, :, :] * h[:, None, ::-1]).sum(axis=2)                      # sum_k h[k] a[newest - k], newest = j = 4
-    if left:
-        first, n = 0, np.arange(0, 61)[None, :] + 4 + w[:, None]            # m = 0..60 reads y[m + 4 + w]; factor m covers a[m..m+4]
-    else:
-        first, n = 83, np.arange(87, 148)[None, :] + w[:, None]             # m = 87..147 reads y[m + w]; factor m - 87 covers a[m-4..m]
-    d = y[np.arange(B)[:, None], n][:, :, None] - Z[:, None, :]
+    d = y[np.arange(B)[:, None], np.asarray(n)[None, :] + w[:, None]][:, :, None] - Z[:, None, :]
     tab = d.real ** 2 + d.imag ** 2
-    t = training_bits(tsc)
-    known = {61 + j: int(t[j]) for j in range(4)} if left else {61 + j: int(t[j]) for j in range(22, 26)}
-    known.update({m: 0 for m in ((0, 1, 2) if left else (145, 146, 147))})
     for m, v in known.items():
         pin(tab, m - first, v)
-    return tab, d.real, d.imag, first
+    return tab, d.real, d.imag
+
+
+def half_tables(y, w, h, tsc, left):
+    """chain_tables of one half of a normal burst, [B, 61, 32], and the chain's first symbol: (tab, dr, di, first)."""
+    t = training_bits(tsc)
+    if left:                                                  # m = 0..60 reads y[m + 4 + w]; factor m covers a[m..m+4]
+        first, n, known = 0, np.arange(0, 61) + 4, {61 + j: int(t[j]) for j in range(4)}
+        known.update({0: 0, 1: 0, 2: 0})
+    else:                                                     # m = 87..147 reads y[m + w]; factor m - 87 covers a[m-4..m]
+        first, n, known = 83, np.arange(87, 148), {61 + j: int(t[j]) for j in range(22, 26)}
+        known.update({145: 0, 146: 0, 147: 0})
+    return chain_tables(y, w, h, n, first, known) + (first,)
 
 
 def bound_terms(tab, dr, di, h):
@@ -162,17 +168,17 @@ def estimate64(y, tsc):
     return dict(c=c, E=E, tol_c=e, tol_E=SLACK * 2.0 * tau.max(axis=1))
 
 
-def grade(soft, hard, y, w, h, tsc, ref=None):
-    """The three conditions on soft [B, 148] float32 and hard [B, 148] (0/1) against the reference on (y, w, h):
+def graded(soft, hard, r, positions):
+    """The three conditions on soft [B, 148] float32 and hard [B, 148] (0/1) against a reference r (an equalise64's dict) on the
+    trellis positions it decides:
       bad_soft  [B, 148]  |soft - clamp(soft64)| > bound                                  (trellis positions)
       bad_clamp [B, 148]  soft64 outside [0, 1] by more than the bound and soft not exactly 0 / 1
       bad_hard  [B, 148]  |soft64 - 0.5| > bound and the hard bit is not soft64 > 0.5
       excluded  [B, 148]  trellis positions the reference keeps out of the hard-bit comparison (|soft64 - 0.5| <= bound)
       ratio     [B, 148]  |soft - clamp(soft64)| / bound (0 off the trellis)
-    The reference alone decides `excluded`."""
-    r = ref or equalise64(y, w, h, tsc)
+    The reference alone decides `excluded`.  Every equaliser's grade() is this on its own reference and positions."""
     s64, bd = r["soft"], r["bound"]
-    on = np.zeros(148, bool); on[TRELLIS] = True
+    on = np.zeros(148, bool); on[positions] = True
     s32 = np.asarray(soft, np.float32)[:, :148].astype(np.float64)
     hb = np.asarray(hard)[:, :148] != 0
     with np.errstate(invalid="ignore"):
@@ -186,10 +192,13 @@ def grade(soft, hard, y, w, h, tsc, ref=None):
     return dict(bad_soft=bad_soft, bad_clamp=bad_clamp, bad_hard=bad_hard, excluded=on[None, :] & ~decided, ratio=ratio, ref=r)
 
 
-def check(soft, hard, y, w, h, tsc, what, named=None):
-    """Assert the three conditions (grade) and, on the named barely-observed positions the reference keeps out of the hard-bit
-    comparison, |soft - 0.5| <= bound.  Returns grade's dict."""
-    g = grade(soft, hard, y, w, h, tsc)
+def grade(soft, hard, y, w, h, tsc, ref=None):
+    """graded() against the reference on (y, w, h), or against a given one."""
+    return graded(soft, hard, ref or equalise64(y, w, h, tsc), TRELLIS)
+
+
+def checked(g, soft, hard, what):
+    """Assert the three conditions of a grade()'s dict g; returns g."""
     r = g["ref"]
     for key, text in (("bad_soft", "|soft - clamp(soft64)| > bound"), ("bad_clamp", "soft64 beyond the clamp by more than the bound, soft not clamped"),
                       ("bad_hard", "hard bit differs outside the margin")):
@@ -197,6 +206,14 @@ def check(soft, hard, y, w, h, tsc, what, named=None):
             b, m = np.argwhere(g[key])[0]
             raise AssertionError("%s: %s at %d positions; first: burst %d symbol %d: soft %.9g hard %d, soft64 %.12g, bound %.3g"
                                  % (what, text, g[key].sum(), b, m, np.asarray(soft)[b, m], np.asarray(hard)[b, m], r["soft"][b, m], r["bound"][b, m]))
+    return g
+
+
+def check(soft, hard, y, w, h, tsc, what, named=None):
+    """Assert the three conditions (grade) and, on the named barely-observed positions the reference keeps out of the hard-bit
+    comparison, |soft - 0.5| <= bound.  Returns grade's dict."""
+    g = checked(grade(soft, hard, y, w, h, tsc), soft, hard, what)
+    r = g["ref"]
     if named is not None:
         at = named & g["excluded"]
         dev = np.abs(np.asarray(soft, np.float32)[:, :148].astype(np.float64) - 0.5)

@@ -1,8 +1,8 @@
 """The float64 reference of the synchronisation-burst sequence equaliser (trxsig_mlse_sch_batch): step 3 of the header's comment read
 as a statement about SEQUENCES -- no states, no predecessors, no alpha or beta -- and step 2 as a plain least-squares solve.
 tests/mlse_sch_model.py and the kernel are graded against it (tests/test_mlse_sch_model.py, tests/test_gpu_mlse_sch_ref.py).  What
-is general in tests/mlse_ref.py is used from there (the exact min-marginals of a chain, the pinning of known symbols, the sums P
-and Q of a factor table); nothing is shared with the model or the kernel.
+is general in tests/mlse_ref.py is used from there (the factor tables of a chain with its known symbols pinned, its exact
+min-marginals, the sums P and Q, the three conditions); nothing is shared with the model or the kernel.
 
 The operation.  With the burst model y[n] = sum_k h[k] a[n - w - k], a[n] = +-1, the soft bit of symbol m is
     soft64[m] = 0.5 + (M_0 - M_1) / (8 E64),       E64 = sum_k |h[k]|^2,
@@ -53,24 +53,15 @@ XTS = np.array([int(v) for v in XTS_BITS], np.int64)          # x[i] = bit 42 + 
 def half_tables(y, w, h, left):
     """The factor tables of one half, [B, 42, 32], with the known symbols pinned, and (dr, di) for the bound.  Chain variable v is
     a[first + v]; factor l covers a[first + l .. first + l + 4], the newest of them against tap h[0]."""
-    y = np.asarray(y, np.complex128); h = np.asarray(h, np.complex128); w = np.asarray(w, np.int64)
-    B = y.shape[0]
-    x = np.arange(32)
-    a = 2.0 * ((x[:, None] >> np.arange(5)[None, :]) & 1) - 1.0             # a[x, j]: the value of the factor's j-th symbol
-    Z = (a[None, :, :] * h[:, None, ::-1]).sum(axis=2)                      # sum_k h[k] a[newest - k], newest = j = 4
     if left:
-        first, n = 0, LEFT[None, :] + 4 + w[:, None]                        # m = 0..41 reads y[m + 4 + w]; factor m covers a[m..m+4]
+        first, n = 0, LEFT + 4                                              # m = 0..41 reads y[m + 4 + w]; factor m covers a[m..m+4]
         known = {42 + i: int(XTS[i]) for i in range(4)}
         known.update({0: 0, 1: 0, 2: 0})
     else:
-        first, n = 102, RIGHT[None, :] + w[:, None]                         # m = 106..147 reads y[m + w]; factor m - 106 covers a[m-4..m]
+        first, n = 102, RIGHT                                               # m = 106..147 reads y[m + w]; factor m - 106 covers a[m-4..m]
         known = {42 + i: int(XTS[i]) for i in range(60, 64)}
         known.update({145: 0, 146: 0, 147: 0})
-    d = y[np.arange(B)[:, None], n][:, :, None] - Z[:, None, :]
-    tab = d.real ** 2 + d.imag ** 2
-    for m, v in known.items():
-        mlse_ref.pin(tab, m - first, v)
-    return tab, d.real, d.imag, first
+    return mlse_ref.chain_tables(y, w, h, n, first, known) + (first,)
 
 
 def equalise64(y, w, h):
@@ -117,30 +108,9 @@ def grade(soft, hard, y, w, h, ref=None):
     """tests/mlse_ref.py's three conditions on soft [B, 148] float32 and hard [B, 148] against the reference on (y, w, h), on the
     positions 0..41 and 106..147: bad_soft, bad_clamp, bad_hard, excluded, ratio (see there).  The reference alone decides
     `excluded`."""
-    r = ref or equalise64(y, w, h)
-    s64, bd = r["soft"], r["bound"]
-    on = np.zeros(148, bool); on[TRELLIS] = True
-    s32 = np.asarray(soft, np.float32)[:, :148].astype(np.float64)
-    hb = np.asarray(hard)[:, :148] != 0
-    with np.errstate(invalid="ignore"):
-        err = np.abs(s32 - np.clip(s64, 0.0, 1.0))
-        bad_soft = on[None, :] & ~(err <= bd)                 # (a NaN soft bit is bad)
-        low, high = s64 < -bd, s64 > 1.0 + bd
-        bad_clamp = on[None, :] & ((low & (s32 != 0.0)) | (high & (s32 != 1.0)))
-        decided = on[None, :] & (np.abs(s64 - 0.5) > bd)
-        bad_hard = decided & (hb != (s64 > 0.5))
-        ratio = np.where(on[None, :], err / bd, 0.0)
-    return dict(bad_soft=bad_soft, bad_clamp=bad_clamp, bad_hard=bad_hard, excluded=on[None, :] & ~decided, ratio=ratio, ref=r)
+    return mlse_ref.graded(soft, hard, ref or equalise64(y, w, h), TRELLIS)
 
 
 def check(soft, hard, y, w, h, what):
     """Assert the three conditions (grade).  Returns grade's dict."""
-    g = grade(soft, hard, y, w, h)
-    r = g["ref"]
-    for key, text in (("bad_soft", "|soft - clamp(soft64)| > bound"), ("bad_clamp", "soft64 beyond the clamp by more than the bound, soft not clamped"),
-                      ("bad_hard", "hard bit differs outside the margin")):
-        if g[key].any():
-            b, m = np.argwhere(g[key])[0]
-            raise AssertionError("%s: %s at %d positions; first: burst %d symbol %d: soft %.9g hard %d, soft64 %.12g, bound %.3g"
-                                 % (what, text, g[key].sum(), b, m, np.asarray(soft)[b, m], np.asarray(hard)[b, m], r["soft"][b, m], r["bound"][b, m]))
-    return g
+    return mlse_ref.checked(grade(soft, hard, y, w, h), soft, hard, what)

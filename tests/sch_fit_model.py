@@ -2,7 +2,7 @@
 TRXSIG_SCHDET_FIT): the algorithm of include/trxsig.h restated in numpy float32, operation by operation, vectorised over bursts.
 The kernel must equal it word for word.
 
-The symbols, the nine taps, the window and E are tests/mlse_sch_model.py's and tests/mlse_model.py's, called, not copied.  What is
+The symbols, the nine taps, the window and E are tests/mlse_sch_model.py's and tests/mlse_core.py's, called, not copied.  What is
 new here is the residual of that fit on the 56 rows whose symbols are all known, its sum R in the kernel's reduction order, and
 q = sqrtf((51 E) / R).  Every arithmetic step below is ONE float32 operation on float32 arrays, in the order the header states.
 
@@ -11,12 +11,9 @@ l1_acq_model.search_model unchanged."""
 import numpy as np
 
 import l1_acq_model as am
-import mlse_model
+import mlse_core as core
 import mlse_sch_model as sm
-import oraclebind
-
-F = np.float32
-WIN_FELL_BACK, WIN_SKIPPED = sm.WIN_FELL_BACK, sm.WIN_SKIPPED
+from mlse_core import F, WIN_FELL_BACK, WIN_SKIPPED
 NDOF = 51                                                     # 56 rows less 5 taps
 A_SIGN = np.zeros(148, np.int64)                              # a[n] = 2 bit - 1 on the extended training sequence, 0 elsewhere
 A_SIGN[sm.XTS0:sm.XTS0 + sm.NXTS] = 2 * sm.XTS - 1
@@ -64,9 +61,8 @@ def fit(y, **mutant):
     """Steps 2-6 on symbols y [B, 148]: dict(chan9 [B, 9], win [B] (w, or 1 = fell back), E, R, q [B])."""
     y = np.ascontiguousarray(y, np.complex64)
     drop_last = mutant.pop("drop_last", False)
+    fine, ys = core.usable(y)
     with np.errstate(all="ignore"):
-        fine = (np.abs(y.real) < F(2.0 ** 30)).all(axis=1) & (np.abs(y.imag) < F(2.0 ** 30)).all(axis=1)
-        ys = np.where(fine[:, None], y, 0).astype(np.complex64)
         c, w, h, E = sm.estimate(ys)
         ok = fine & (E != 0)
         R = tree(row_energies(ys, w, h, **mutant), drop_last)
@@ -78,18 +74,8 @@ def fit(y, **mutant):
 
 def fit_batch(sps, x, off, length, amp, toa, enable=None, oracle=None, **mutant):
     """trxsig_sch_fit_batch on packed bursts: dict(chan9 [B, 9], win, E, R, q [B], y [B, 148])."""
-    o = oracle or oraclebind.Oracle(sps)
-    B = len(off)
-    amp = np.broadcast_to(np.asarray(amp, np.complex64), (B,)); toa = np.broadcast_to(np.asarray(toa, np.float32), (B,))
-    y = np.zeros((B, 148), np.complex64)
-    state = np.zeros(B, np.int32)
-    for b in range(B):
-        if (enable is not None and not enable[b]) or not mlse_model.burst_enabled(sps, int(off[b]), int(length[b]), toa[b]):
-            state[b] = WIN_SKIPPED
-            continue
-        y[b] = mlse_model.symbols(o, x[off[b]:off[b] + length[b]], amp[b], toa[b])
-        if length[b] // sps < 148:
-            state[b] = WIN_FELL_BACK
+    y, state = core.burst_symbols(sps, [x], [off], length, amp, toa, enable, oracle)
+    y = y[:, 0]
     r = fit(y, **mutant)
     out_ = state != 0
     r["chan9"][out_] = 0; r["E"][out_] = 0; r["R"][out_] = 0; r["q"][out_] = 0

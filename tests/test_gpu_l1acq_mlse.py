@@ -12,25 +12,13 @@
 import numpy as np
 import pytest
 
-import _pkg
 import l1_acq_model as am
 import mlse_sch_family as family
+from mlse_run import dev, pkg  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
 EINVAL = -1
 KEYS = ("state", "fcch_k", "fcch_metric", "fcch_c", "fcch_e", "arg", "omega", "sch_w0", "sch_ptm", "sch_amp", "sch_toa", "soft", "ok", "bsic", "rfn")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 class Rig:

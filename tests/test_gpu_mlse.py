@@ -5,38 +5,13 @@ TOAs across +-3 symbols on and off the 1/512 grid, and on the hostile bursts tha
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_family
 import mlse_model
 import oraclebind
-from mlse_run import run_mlse
+from mlse_run import check, ctx, pkg, run_mlse  # noqa: F401  (the fixtures)
 from util import GpuBatch, assert_veq, assert_veq_nan
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    c = {s: pkg.TrxSig(s, 0) for s in (1, 2, 4)}
-    for v in c.values():
-        v.use_torch_stream()
-    return c
-
-
-def check(got, want, sel=None, nsoft=148, what=""):
-    sel = slice(None) if sel is None else sel
-    assert_veq(got["win"], want["win"][sel], what + " window word")
-    assert_veq_nan(got["soft"][:, :nsoft], want["soft"][sel][:, :nsoft], what + " soft bits")
-    assert_veq(got["hard"][:, :nsoft], want["hard"][sel][:, :nsoft], what + " hard bits")
-    assert_veq(got["chan"], want["chan"][sel], what + " taps")
-    assert np.all(got["soft"][:, nsoft:] == -1.0) and np.all(got["hard"][:, nsoft:] == 255), what + ": written past nsoft"
 
 
 @pytest.mark.parametrize("sps", [1, 2, 4])

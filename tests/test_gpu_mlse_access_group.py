@@ -9,13 +9,13 @@ spread -> pull -> l1rx on one combination-V slot (tests/mlse_access_loop.py)."""
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_access_family as family
 import mlse_access_model as model
 import mlse_family
 import oraclebind
 import synth
 import transceiver_model as tm
+from mlse_run import dev, dev_c, pkg  # noqa: F401  (the fixtures)
 from util import assert_veq
 
 pytestmark = pytest.mark.gpu
@@ -24,13 +24,6 @@ S, T, FN0 = 3, 16, 101
 TSCS = (2, 5, 7)
 ACCESS_SLOTS = {(0, 0), (0, 3), (1, 4)}                       # (ARFCN, TN) on combination IV: every frame's burst is an access burst
 KEYS = ("row", "valid", "flags", "amp", "toa", "avgpwr", "threshold")
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
 
 
 def combination(a, tn):
@@ -252,15 +245,6 @@ def test_setter_refusals(pkg):
 
 
 # ---- the closed loop: l1ms -> radiate -> trxsig_air_cells with a fixed tap set -> pull -> l1rx, one combination-V slot ----
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_c(a):
-    return dev(np.ascontiguousarray(a, np.complex64).view(np.float32).reshape(np.shape(a) + (2,)))
-
-
 def test_closed_loop_through_three_symbols_of_spread(pkg):
     """L1Ms.encode -> radiate -> Air.cells with tests/mlse_access_loop.py's fixed taps (three symbols of spread at sps 4, no noise) ->
     TrxGroup.pull -> L1Rx.decode on the RACH of one combination-V slot: 27 access bursts in 51 frames, each with a random RA and the

@@ -5,27 +5,14 @@ bound of the float64 least-squares solution (which uses no table) and its window
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_access_family as family
 import mlse_access_model as model
 import mlse_access_ref as ref
+from mlse_run import dev, pkg  # noqa: F401  (the fixtures)
 from util import GpuBatch
 
 pytestmark = pytest.mark.gpu
 B_ALL = 37
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.float32).copy() if a.dtype == np.complex64 else a.copy()).cuda()
 
 
 @pytest.mark.parametrize("sps", [1, 2, 4])

@@ -7,32 +7,16 @@ bursts on either antenna; and the kernel's output graded directly by the float64
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_div_family as dfam
 import mlse_div_model as dm
 import mlse_div_ref as dref
 import mlse_family
 import mlse_ref
 import oraclebind
-from mlse_run import dev, run_div
-from util import GpuBatch, assert_veq, assert_veq_nan
+from mlse_run import check, ctx, dev, pkg, run_div  # noqa: F401  (the fixtures)
+from util import GpuBatch, assert_veq
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    c = {s: pkg.TrxSig(s, 0) for s in (1, 2, 4)}
-    for v in c.values():
-        v.use_torch_stream()
-    return c
 
 
 def run_one(t, x, off, length, tsc, amp, toa, enable=None):
@@ -45,15 +29,6 @@ def run_one(t, x, off, length, tsc, amp, toa, enable=None):
            hard=gb.hard, nsoft=148, soft_stride=148)
     r = gb.results()
     return dict(soft=r["soft"], hard=r["hard"], chan=chan.cpu().numpy().reshape(B, 10).view(np.complex64), win=win.cpu().numpy())
-
-
-def check(got, want, sel=None, nsoft=148, what=""):
-    sel = slice(None) if sel is None else sel
-    assert_veq(got["win"], want["win"][sel], what + " window word")
-    assert_veq_nan(got["soft"][:, :nsoft], want["soft"][sel][:, :nsoft], what + " soft bits")
-    assert_veq(got["hard"][:, :nsoft], want["hard"][sel][:, :nsoft], what + " hard bits")
-    assert_veq(got["chan"].reshape(-1, 10), want["chan"][sel].reshape(-1, 10), what + " taps")
-    assert np.all(got["soft"][:, nsoft:] == -1.0) and np.all(got["hard"][:, nsoft:] == 255), what + ": written past nsoft"
 
 
 @pytest.mark.parametrize("sps", [1, 2, 4])

@@ -9,89 +9,25 @@ antenna 0 is silent in every second block."""
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_div_model as dm
 import mlse_family
 import oraclebind
-import synth
 import transceiver_model as tm
+from mlse_combine import CELL, FN0, PROFILES, S, SPS, T, TSCS, aux, aux_host, combination, fetch, make_cells, make_group, to_dev
+from mlse_run import dev, dev_c, pkg  # noqa: F401  (pkg: the fixture)
 from util import assert_veq
 
 pytestmark = pytest.mark.gpu
 
-SPS, S, T, FN0 = 4, 2, 16, 101
-TSCS = (2, 5)
-CELL = 160 * SPS
 SILENT0, SILENT1, SILENT_BOTH, LOUD1 = [(3, 0), (6, 1), (12, 1)], [(4, 1), (10, 0)], [(5, 1)], [(2, 0), (7, 1), (13, 0)]
 
 
 @pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-def combination(a, tn):
-    return tm.IV if (a == 0 and tn == 0) else tm.I           # ARFCN 0's slot 0 hears access bursts
-
-
-@pytest.fixture(scope="module")
 def cells():
-    """(x [2 antennas][T][S][CELL] complex64, ctype [T][S])."""
-    rng = np.random.default_rng(47)
-    o = oraclebind.Oracle(SPS)
-    x = np.zeros((2, T, S, CELL), np.complex64)
-    ctype = np.zeros((T, S), np.int8)
-    rx, roff, rlen, _ = synth.rach_batch(SPS, 8, seed=5, sigmas=(0.0, 0.1), max_delay_sym=10)
-    m = tm.TransceiverModel.__new__(tm.TransceiverModel)
-    profiles = ["five", "precursor", "flat"]
-    for t in range(T):
-        tn, fn = t % 8, FN0 + t // 8
-        n = (156 + (tn % 4 == 0)) * SPS
-        for a in range(S):
-            m.chan_type = np.array([combination(a, k) for k in range(8)])
-            ctype[t, a] = m.expected_corr_type(tn, fn)
-            if ctype[t, a] == tm.RACH:
-                i = 4 * (t // 8)                               # (bursts 0 and 4 of the pack are the 157-symbol ones)
-                r = rx[roff[i]:roff[i] + rlen[i]][:n]
-                x[0, t, a, :n] = r
-                x[1, t, a, :n] = r * np.complex64((1.5 if t == 0 else 0.5) * np.exp(0.7j))     # the louder antenna: 1 at t = 0, 0 at t = 8
-                continue
-            bits = synth.normal_bits(rng, 1, TSCS[a])[0]
-            s = o.modulate(bits.astype(np.int8), 9 if tn % 4 == 0 else 8)
-            for ant in (0, 1):
-                x[ant, t, a, :n] = mlse_family.channel(rng, s, SPS, mlse_family.PROFILES[profiles[(t + a + ant) % 3]], 18.0)[:n]
-            if (t, a) in LOUD1:
-                x[1, t, a] *= np.float32(2.5)
-            if (t, a) in SILENT0 + SILENT_BOTH:
-                x[0, t, a] = 0
-            if (t, a) in SILENT1 + SILENT_BOTH:
-                x[1, t, a] = 0
-    assert (ctype == tm.RACH).sum() == 2 and (ctype == tm.TSC).sum() == T * S - 2
-    return x, ctype
-
-
-def make_group(pkg, ctx, leg, tscs=TSCS, n_arfcn=S, comb=combination):
-    g = pkg.TrxGroup(ctx, n_arfcn, tsc_leg=leg, start=(FN0, 0))
-    for a in range(n_arfcn):
-        for cmd in ["CMD RXTUNE 890000", "CMD TXTUNE 935000", "CMD SETTSC %d" % tscs[a]] + \
-                   ["CMD SETSLOT %d %d" % (tn, comb(a, tn)) for tn in range(8)] + ["CMD POWERON"]:
-            g.control(a, cmd)
-    return g
-
-
-def fetch(pkg, ctx, res):
-    R = res.n_rows
-    return dict(row=pkg._to_host(ctx, res.d_row, (T, S), "<i4"), valid=pkg._to_host(ctx, res.d_valid, (R,), "|u1"),
-                flags=pkg._to_host(ctx, res.d_flags, (R,), "|u1"), amp=pkg._to_host(ctx, res.d_amp, (R, 2), "<f4").view(np.complex64).ravel(),
-                toa=pkg._to_host(ctx, res.d_toa, (R,), "<f4"), avgpwr=pkg._to_host(ctx, res.d_avgpwr, (R,), "<f4"),
-                threshold=pkg._to_host(ctx, res.d_threshold, (R,), "<f8"), soft=pkg._to_host(ctx, res.d_soft, (R, res.soft_stride), "<f4"))
-
-
-def to_dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.float32).reshape(-1)).to("cuda:0")
+    """(x [2 antennas][T][S][CELL] complex64, ctype [T][S]): independent multipath per antenna."""
+    def received(rng, o, s, t, a, n):
+        return [mlse_family.channel(rng, s, SPS, PROFILES[(t + a + ant) % 3], 18.0)[:n] for ant in (0, 1)]
+    return make_cells(47, received, SILENT0 + SILENT_BOTH, SILENT1 + SILENT_BOTH, LOUD1)
 
 
 @pytest.fixture(scope="module")
@@ -114,15 +50,13 @@ def run(pkg, cells):
     r0 = g0.pull(dx[0], S * CELL, CELL, FN0, 0, T)
     r1 = g1.pull(dx[1], S * CELL, CELL, FN0, 0, T)
     R = r0.n_rows
-    sel = torch.full((R,), 9, dtype=torch.uint8, device="cuda:0")
-    chan = torch.full((R, 2, 5, 2), -7.0, dtype=torch.float32, device="cuda:0")
-    win = torch.full((R,), -99, dtype=torch.int32, device="cuda:0")
-    rc = g0.combine_div(dx[0], g1, dx[1], sel=sel, chan=chan, win=win)
+    a = aux(R)
+    rc = g0.combine_div(dx[0], g1, dx[1], **a)
     torch.cuda.synchronize()
     out["comb"] = fetch(pkg, ctx, rc)
     out["g0"] = dict(fetch(pkg, ctx, r0), collect=g0.collect())
     out["g1"] = dict(fetch(pkg, ctx, r1), collect=g1.collect())
-    out["sel"] = sel.cpu().numpy(); out["chan"] = chan.cpu().numpy().reshape(R, 2, 10).view(np.complex64); out["win"] = win.cpu().numpy()
+    out.update(aux_host(a, R))
     bare = g0.combine_div(dx[0], g1, dx[1])                   # the optional outputs left out: the same result
     torch.cuda.synchronize()
     out["bare"] = fetch(pkg, ctx, bare)
@@ -291,15 +225,6 @@ def test_listed_bursts(pkg, cells, run):
 
 
 # ---- the closed loop: antenna 0 silent in every second block's bursts ----
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_c(a):
-    return dev(np.ascontiguousarray(a, np.complex64).view(np.float32).reshape(np.shape(a) + (2,)))
-
-
 def test_closed_loop_with_a_silent_antenna(pkg):
     """L1Ms.encode -> radiate -> Air.cells per antenna with tests/mlse_loop.py's fixed taps -> two groups' pulls -> combine_div ->
     L1Rx.decode on the SDCCH/8 slot (24 blocks, 96 bursts).  Antenna 1 carries the fixed tap set; antenna 0 carries it times a

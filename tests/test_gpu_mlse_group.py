@@ -7,12 +7,12 @@ trxsig_air_cells with a fixed tap set of three symbols' spread -> pull -> l1rx o
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_family
 import mlse_model
 import oraclebind
 import synth
 import transceiver_model as tm
+from mlse_run import dev, dev_c, pkg  # noqa: F401  (the fixtures)
 from util import assert_veq
 
 pytestmark = pytest.mark.gpu
@@ -20,13 +20,6 @@ pytestmark = pytest.mark.gpu
 SPS, S, T, FN0 = 4, 3, 16, 101
 TSCS = (2, 5, 7)
 CELL = 160 * SPS
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
 
 
 def combination(a, tn):
@@ -168,15 +161,6 @@ def test_group_leg_rules(pkg):
 
 
 # ---- the closed loop: l1ms -> radiate -> trxsig_air_cells with a fixed tap set -> pull -> l1rx, one SDCCH/8 slot ----
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def dev_c(a):
-    return dev(np.ascontiguousarray(a, np.complex64).view(np.float32).reshape(np.shape(a) + (2,)))
-
-
 def test_closed_loop_through_three_symbols_of_spread(pkg):
     """L1Ms.encode -> radiate -> Air.cells with tests/mlse_loop.py's fixed taps (three symbols of spread at sps 4, no noise) ->
     TrxGroup.pull -> L1Rx.decode on one SDCCH/8 slot: 16 channels, 24 blocks, 96 bursts.  The tap set was chosen on the CPU through

@@ -8,102 +8,34 @@ after, gives identical bytes; combine_irc's refusals are combine_div's, and the 
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_family
 import mlse_irc_model as im
 import oraclebind
 import synth
 import transceiver_model as tm
+from mlse_combine import CELL, FN0, PROFILES, S, SPS, T, TSCS, aux, aux_host, combination, fetch, make_cells, make_group, to_dev
+from mlse_run import canaries, pkg  # noqa: F401  (pkg: the fixture)
 from util import assert_veq
 
 pytestmark = pytest.mark.gpu
 
-SPS, S, T, FN0 = 4, 2, 16, 101
-TSCS = (2, 5)
 ITSC = 7
-CELL = 160 * SPS
 SILENT0, SILENT1, SILENT_BOTH = [(3, 0), (6, 1)], [(4, 1), (10, 0)], [(5, 1)]
 
 
 @pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-def combination(a, tn):
-    return tm.IV if (a == 0 and tn == 0) else tm.I           # ARFCN 0's slot 0 hears access bursts
-
-
-@pytest.fixture(scope="module")
 def cells():
-    """(x [2 antennas][T][S][CELL] complex64, ctype [T][S])."""
-    rng = np.random.default_rng(53)
-    o = oraclebind.Oracle(SPS)
-    x = np.zeros((2, T, S, CELL), np.complex64)
-    ctype = np.zeros((T, S), np.int8)
-    rx, roff, rlen, _ = synth.rach_batch(SPS, 8, seed=5, sigmas=(0.0, 0.1), max_delay_sym=10)
-    m = tm.TransceiverModel.__new__(tm.TransceiverModel)
-    profiles = ["five", "precursor", "flat"]
-    for t in range(T):
-        tn, fn = t % 8, FN0 + t // 8
-        n = (156 + (tn % 4 == 0)) * SPS
-        for a in range(S):
-            m.chan_type = np.array([combination(a, k) for k in range(8)])
-            ctype[t, a] = m.expected_corr_type(tn, fn)
-            if ctype[t, a] == tm.RACH:
-                i = 4 * (t // 8)                               # (bursts 0 and 4 of the pack are the 157-symbol ones)
-                r = rx[roff[i]:roff[i] + rlen[i]][:n]
-                x[0, t, a, :n] = r
-                x[1, t, a, :n] = r * np.complex64((1.5 if t == 0 else 0.5) * np.exp(0.7j))
-                continue
-            bits = synth.normal_bits(rng, 1, TSCS[a])[0]
-            s = o.modulate(bits.astype(np.int8), 9 if tn % 4 == 0 else 8)
-            si = o.modulate(synth.normal_bits(rng, 1, ITSC)[0].astype(np.int8), 9)
-            for ant in (0, 1):
-                own = mlse_family.channel(rng, s, SPS, mlse_family.PROFILES[profiles[(t + a + ant) % 3]], 22.0)[:n]
-                other = mlse_family.channel(rng, si, SPS, mlse_family.PROFILES[profiles[(t + ant) % 2 * 2]], None)[:n]
-                ci_db = (6.0, 3.0, 10.0)[(t + a) % 3]
-                x[ant, t, a, :n] = own + (0.0 if (t + a) % 5 == 0 else 10.0 ** (-ci_db / 20.0)) * other
-            if (t, a) in SILENT0 + SILENT_BOTH:
-                x[0, t, a] = 0
-            if (t, a) in SILENT1 + SILENT_BOTH:
-                x[1, t, a] = 0
-    assert (ctype == tm.RACH).sum() == 2 and (ctype == tm.TSC).sum() == T * S - 2
-    return x, ctype
-
-
-def make_group(pkg, ctx, leg, tscs=TSCS, n_arfcn=S, comb=combination):
-    g = pkg.TrxGroup(ctx, n_arfcn, tsc_leg=leg, start=(FN0, 0))
-    for a in range(n_arfcn):
-        for cmd in ["CMD RXTUNE 890000", "CMD TXTUNE 935000", "CMD SETTSC %d" % tscs[a]] + \
-                   ["CMD SETSLOT %d %d" % (tn, comb(a, tn)) for tn in range(8)] + ["CMD POWERON"]:
-            g.control(a, cmd)
-    return g
-
-
-def fetch(pkg, ctx, res):
-    R = res.n_rows
-    return dict(row=pkg._to_host(ctx, res.d_row, (T, S), "<i4"), valid=pkg._to_host(ctx, res.d_valid, (R,), "|u1"),
-                flags=pkg._to_host(ctx, res.d_flags, (R,), "|u1"), amp=pkg._to_host(ctx, res.d_amp, (R, 2), "<f4").view(np.complex64).ravel(),
-                toa=pkg._to_host(ctx, res.d_toa, (R,), "<f4"), avgpwr=pkg._to_host(ctx, res.d_avgpwr, (R,), "<f4"),
-                threshold=pkg._to_host(ctx, res.d_threshold, (R,), "<f8"), soft=pkg._to_host(ctx, res.d_soft, (R, res.soft_stride), "<f4"))
-
-
-def to_dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.float32).reshape(-1)).to("cuda:0")
-
-
-def aux(R):
-    import torch
-    return dict(sel=torch.full((R,), 9, dtype=torch.uint8, device="cuda:0"), chan=torch.full((R, 2, 5, 2), -7.0, dtype=torch.float32, device="cuda:0"),
-                win=torch.full((R,), -99, dtype=torch.int32, device="cuda:0"))
-
-
-def aux_host(a, R):
-    return dict(sel=a["sel"].cpu().numpy(), chan=a["chan"].cpu().numpy().reshape(R, 2, 10).view(np.complex64), win=a["win"].cpu().numpy())
+    """(x [2 antennas][T][S][CELL] complex64, ctype [T][S]): independent multipath per antenna and an interferer on most cells."""
+    def received(rng, o, s, t, a, n):
+        si = o.modulate(synth.normal_bits(rng, 1, ITSC)[0].astype(np.int8), 9)
+        out = []
+        for ant in (0, 1):
+            own = mlse_family.channel(rng, s, SPS, PROFILES[(t + a + ant) % 3], 22.0)[:n]
+            other = mlse_family.channel(rng, si, SPS, PROFILES[(t + ant) % 2 * 2], None)[:n]
+            ci_db = (6.0, 3.0, 10.0)[(t + a) % 3]
+            out.append(own + (0.0 if (t + a) % 5 == 0 else 10.0 ** (-ci_db / 20.0)) * other)
+        return out
+    return make_cells(53, received, SILENT0 + SILENT_BOTH, SILENT1 + SILENT_BOTH)
 
 
 @pytest.fixture(scope="module")
@@ -130,7 +62,7 @@ def run(pkg, cells):
     for name in ("div_before", "irc", "div_after"):
         a = aux(R)
         if name == "irc":
-            cov = torch.full((R + 1, 4), -5.0, dtype=torch.float32, device="cuda:0")
+            cov = canaries(R, (2, 5), cov=True)["cov"]         # [R + 1, 4]: a guard row behind
             rc = g0.combine_irc(dx[0], g1, dx[1], cov=cov, **a)
         else:
             rc = g0.combine_div(dx[0], g1, dx[1], **a)

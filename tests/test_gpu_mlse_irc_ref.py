@@ -6,28 +6,15 @@ bound through the four divisions (a set from sums within their bound lies within
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_family
 import mlse_irc_family as ifam
 import mlse_irc_model as im
 import mlse_irc_ref as iref
 import mlse_ref
+from mlse_run import dev, pkg  # noqa: F401  (the fixtures)
 from util import GpuBatch
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.float32).copy() if a.dtype == np.complex64 else a.copy()).cuda()
 
 
 @pytest.mark.parametrize("sps", [1, 4])

@@ -7,45 +7,15 @@ CPU and shows, with six mutants, that the comparison can fail."""
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_family
 import mlse_model
 import mlse_ref as ref
 import mlse_ref_family as fam
 import oraclebind
 import transceiver_model as tm
-from util import GpuBatch
+from mlse_run import ctx, pkg, run_mlse  # noqa: F401  (the fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    c = {s: pkg.TrxSig(s, 0) for s in (1, 2, 4)}
-    for v in c.values():
-        v.use_torch_stream()
-    return c
-
-
-def run_mlse(t, f):
-    """trxsig_mlse_batch on batch f: dict(soft [B, 160], hard, chan [B, 5], win [B])."""
-    import torch
-    B = len(f["off"])
-    gb = GpuBatch(f["x"], f["off"], f["length"], nsoft=148, stride=160)
-    d_amp = torch.from_numpy(np.ascontiguousarray(f["amp"]).view(np.float32).copy()).cuda()
-    d_toa = torch.from_numpy(np.ascontiguousarray(f["toa"])).cuda()
-    chan = torch.full((B, 5, 2), -7.0, dtype=torch.float32, device="cuda:0")
-    win = torch.full((B,), -99, dtype=torch.int32, device="cuda:0")
-    t.mlse(gb.x, gb.off, gb.len, f["tsc"], d_amp, d_toa, gb.soft, chan=chan, win=win, hard=gb.hard, nsoft=148, soft_stride=160)
-    r = gb.results()
-    return dict(soft=r["soft"], hard=r["hard"], chan=chan.cpu().numpy().reshape(B, 10).view(np.complex64), win=win.cpu().numpy())
 
 
 @pytest.fixture(scope="module")

@@ -7,58 +7,14 @@ workgroups and a ragged fifth.  Every output array carries canaries behind its l
 import numpy as np
 import pytest
 
-import _pkg
 import mlse_sch_family as family
 import sch_fit_model as model
 import sch_fit_ref as ref
+from mlse_run import ctx, pkg, run_fit  # noqa: F401  (the fixtures)
 from util import GpuBatch, assert_veq
 
 pytestmark = pytest.mark.gpu
 B_ALL = 37
-PAD = 5                                                        # canary entries behind each output
-
-
-@pytest.fixture(scope="module")
-def pkg():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return _pkg.load()
-
-
-@pytest.fixture(scope="module")
-def ctx(pkg):
-    c = {s: pkg.TrxSig(s, 0) for s in (1, 2, 4)}
-    for v in c.values():
-        v.use_torch_stream()
-    return c
-
-
-def run_fit(t, f, sel=None, enable=None, only=None):
-    """trxsig_sch_fit_batch on bursts `sel` of family f: dict(chan9 [B, 9], win, E, R, q [B]) and the canaries checked.  only: the
-    one output to pass (the others NULL)."""
-    import torch
-    sel = np.arange(len(f["off"])) if sel is None else np.asarray(sel)
-    B = len(sel)
-    gb = GpuBatch(f["x"], f["off"][sel], f["length"][sel], nsoft=148, stride=148)
-    d_amp = torch.from_numpy(np.ascontiguousarray(f["amp"][sel]).view(np.float32).copy()).cuda()
-    d_toa = torch.from_numpy(np.ascontiguousarray(f["toa"][sel])).cuda()
-    d_en = None if enable is None else torch.from_numpy(np.ascontiguousarray(enable[sel])).cuda()
-    buf = dict(chan9=torch.full((B + PAD, 9, 2), -7.0, dtype=torch.float32, device="cuda:0"),
-               win=torch.full((B + PAD,), -99, dtype=torch.int32, device="cuda:0"))
-    for k in ("E", "R", "q"):
-        buf[k] = torch.full((B + PAD,), -7.0, dtype=torch.float32, device="cuda:0")
-    args = {k: (v if only is None or k == only else None) for k, v in buf.items()}
-    t.sch_fit(gb.x, gb.off, gb.len, d_amp, d_toa, enable=d_en, **args)
-    t.synchronize()
-    out = {k: v.cpu().numpy() for k, v in buf.items()}
-    out["chan9"] = out["chan9"].reshape(B + PAD, 18).view(np.complex64)
-    for k, v in out.items():
-        canary = -99 if k == "win" else -7.0
-        assert np.all(v[B:].view(np.float32 if k == "chan9" else v.dtype) == canary), "written behind the last burst: " + k
-        if only is not None and k != only:
-            assert np.all(v.view(np.float32 if k == "chan9" else v.dtype) == canary), "a NULL output's neighbour was written: " + k
-        out[k] = v[:B]
-    return out
 
 
 def check(got, want, sel=None, what=""):

@@ -2,9 +2,6 @@
 one-antenna model (tests/mlse_model.py), every fallback, the selection rule, the model graded by the float64 reference
 (tests/mlse_div_ref.py) with two mutants the grading must catch, and what it is for: fewer bit errors than one antenna, no more
 than the selected antenna alone.  No GPU: the kernel is held to this model word for word in tests/test_gpu_mlse_div.py."""
-import inspect
-import types
-
 import numpy as np
 import pytest
 
@@ -15,6 +12,7 @@ import mlse_family
 import mlse_model as mm
 import mlse_ref
 import oraclebind
+from mlse_variant import variant
 
 
 def same_nan(a, b):
@@ -153,18 +151,6 @@ MUTANTS = {
 }
 
 
-def variant(name):
-    """A copy of the model, with one expression changed if `name` is a mutant's; compiled here and never stored."""
-    src = inspect.getsource(dm)
-    if name is not None:
-        old, new = MUTANTS[name]
-        assert src.count(old) == 1, "the model no longer contains %r" % old
-        src = src.replace(old, new)
-    mod = types.ModuleType("mlse_div_model_variant")
-    exec(compile(src, "<variant: %s>" % name, "exec"), mod.__dict__)
-    return mod
-
-
 def worst_ratio(model, f):
     soft, win, h = model.equalise(f["want"]["y"], f["tsc"], f["primary"])
     eq = win <= 0
@@ -178,8 +164,8 @@ def test_mutant_is_caught(name):
     """Each mutant exceeds the bound on the graded family (the unmutated copy, built the same way, stays inside)."""
     f = graded(1)
     if name == sorted(MUTANTS)[0]:
-        assert worst_ratio(variant(None), f) <= 1.0
-    worst = worst_ratio(variant(name), f)
+        assert worst_ratio(variant(dm), f) <= 1.0
+    worst = worst_ratio(variant(dm, MUTANTS[name]), f)
     print("mutant %-44s worst |soft - clamp(soft64)| / bound = %.3g" % (name, worst))
     assert worst > 1.0
 

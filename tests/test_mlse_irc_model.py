@@ -4,9 +4,6 @@ fallbacks and the given sets that must be refused, the model graded by the float
 bits and the residual sums, each within its a-priori bound) with three mutants the grading must catch, and what it is for: fewer
 payload bit errors than maximal-ratio combining under a co-channel interferer, no more without one.  No GPU: the kernel is held to
 this model word for word in tests/test_gpu_mlse_irc.py."""
-import inspect
-import types
-
 import numpy as np
 import pytest
 
@@ -17,6 +14,7 @@ import mlse_irc_family as ifam
 import mlse_irc_model as im
 import mlse_irc_ref as iref
 import mlse_ref
+from mlse_variant import variant
 
 F = np.float32
 
@@ -200,18 +198,6 @@ MUTANTS = {
 WIDE = 20.0                                                    # "a wide factor": what a mutant must exceed the bound by
 
 
-def variant(name):
-    """A copy of the model, with one expression changed if `name` is a mutant's; compiled here and never stored."""
-    src = inspect.getsource(im)
-    if name is not None:
-        old, new = MUTANTS[name]
-        assert src.count(old) == 1, "the model no longer contains %r" % old
-        src = src.replace(old, new)
-    mod = types.ModuleType("mlse_irc_model_variant")
-    exec(compile(src, "<variant: %s>" % name, "exec"), mod.__dict__)
-    return mod
-
-
 def worst_ratio(model, f):
     """The variant's soft bits against the reference on the set the TRUE model used (a mutant that changes the set is graded on
     what the set should have been)."""
@@ -228,8 +214,8 @@ def test_mutant_is_caught(name):
     inside)."""
     f = graded(1)
     if name == sorted(MUTANTS)[0]:
-        assert worst_ratio(variant(None), f) <= 1.0
-    worst = worst_ratio(variant(name), f)
+        assert worst_ratio(variant(im), f) <= 1.0
+    worst = worst_ratio(variant(im, MUTANTS[name]), f)
     print("mutant %-36s worst |soft - clamp(soft64)| / bound = %.3g" % (name, worst))
     assert worst > WIDE
 

@@ -3,9 +3,6 @@ reference's min-marginal routine against the enumeration of every assignment; th
 (tests/mlse_ref_family.py); the model's soft and hard bits within the reference's a-priori bound on every family burst and on
 mlse_family.mixed_batch; the estimator; and six one-token mutants of the model, each of which the comparison must catch.  No GPU:
 tests/test_gpu_mlse_ref.py holds the kernel to the same reference."""
-import inspect
-import types
-
 import numpy as np
 import pytest
 
@@ -14,6 +11,7 @@ import mlse_model as mm
 import mlse_ref as ref
 import mlse_ref_family as fam
 import synth
+from mlse_variant import variant
 
 MIXED_SNR = [np.nan, 12.0, 15.0, 15.0, np.nan, 8.0]           # mlse_family.mixed_batch's kinds, burst b is kind b % 6
 
@@ -204,26 +202,16 @@ def test_estimator_within_its_bounds():
 
 
 # ---- mutants: the comparison can fail ----
-MUTANTS = {
+MUTANTS = {   # name: (the token -- in the model's text, or in that of the shared pieces it calls --, its replacement)
     "right start state bit-reversed": ("bit[25] | (bit[24] << 1) | (bit[23] << 2) | (bit[22] << 3)",
                                        "bit[22] | (bit[23] << 1) | (bit[24] << 2) | (bit[25] << 3)"),
-    "tail from step 59": ("if i >= 58:", "if i >= 59:"),
+    "tail from step 59": ("i >= steps - 3:", "i >= steps - 2:"),
     "left half's taps not reversed": ("_half(yr, yi, w, hr[:, ::-1], hi[:, ::-1], start_l, True)", "_half(yr, yi, w, hr, hi, start_l, True)"),
-    "left sample index m + 3 + w": ("(60 - i + 4 + w)", "(60 - i + 3 + w)"),
+    "left sample index m + 3 + w": ("(first - i + 4 + sign_w * w)", "(first - i + 3 + sign_w * w)"),
     "window energies over four taps": ("(((p[:, k] + p[:, k + 1]) + p[:, k + 2]) + p[:, k + 3]) + p[:, k + 4]",
                                        "((p[:, k] + p[:, k + 1]) + p[:, k + 2]) + p[:, k + 3]"),
     "8 E replaced by 4 E": ("F(8.0) * E", "F(4.0) * E"),
 }
-
-
-def mutant(name):
-    """A copy of the model with one token changed, compiled here and never stored."""
-    old, new = MUTANTS[name]
-    src = inspect.getsource(mm)
-    assert src.count(old) == 1, "the model no longer contains %r" % old
-    mod = types.ModuleType("mlse_model_mutant")
-    exec(compile(src.replace(old, new), "<mutant: %s>" % name, "exec"), mod.__dict__)
-    return mod
 
 
 def worst_ratio(model, batches):
@@ -242,9 +230,7 @@ def test_mutant_is_caught(name):
     """Each mutant exceeds the bound on at least one family burst (the unmutated copy, built the same way, stays inside)."""
     batches = fam.batches(1)
     if name == sorted(MUTANTS)[0]:
-        same = types.ModuleType("mlse_model_copy")
-        exec(compile(inspect.getsource(mm), "<copy>", "exec"), same.__dict__)
-        assert worst_ratio(same, batches) <= 1.0
-    worst = worst_ratio(mutant(name), batches)
+        assert worst_ratio(variant(mm), batches) <= 1.0
+    worst = worst_ratio(variant(mm, MUTANTS[name]), batches)
     print("mutant %-32s worst |soft - clamp(soft64)| / bound = %.3g" % (name, worst))
     assert worst > 1.0

@@ -1,5 +1,5 @@
 """The synchronisation-burst sequence equaliser's float32 model (tests/mlse_sch_model.py): its least-squares table from Python
-integers, its half-burst trellis held to tests/mlse_model.py's, the model graded against the float64 reference
+integers (its trellis is every model's: tests/test_mlse_core.py), the model graded against the float64 reference
 (tests/mlse_sch_ref.py) within the bounds derived there, the one-tap channel against the demodulator's formula, five one-change
 mutants that the grading must catch, and what the equaliser buys over demodulateBurst behind acquisition's SCH detector on seeded
 multipath families.  No GPU: tests/test_gpu_mlse_sch.py holds the kernel to the model word for word,
@@ -68,19 +68,6 @@ def test_start_states():
     assert len(x) == 64
     assert model.START_RIGHT == x[63] | x[62] << 1 | x[61] << 2 | x[60] << 3 == 11
     assert model.START_LEFT == x[0] | x[1] << 1 | x[2] << 2 | x[3] << 3 == 13
-
-
-def test_half_is_the_normal_bursts_half():
-    """half() with the normal burst's numbers (61 steps, first symbols 87 and 60) equals tests/mlse_model.py's _half word for word."""
-    rng = np.random.default_rng(3)
-    B = 6
-    y = (rng.standard_normal((B, 148)) + 1j * rng.standard_normal((B, 148))).astype(np.complex64)
-    g = (rng.standard_normal((B, 5)) + 1j * rng.standard_normal((B, 5))).astype(np.complex64)
-    w = rng.integers(-4, 1, B).astype(np.int32); start = rng.integers(0, 16, B)
-    for left in (False, True):
-        a = model.half(y.real.copy(), y.imag.copy(), w, g.real.copy(), g.imag.copy(), start, left, steps=61, right0=87, left0=60)
-        b = mlse_model._half(y.real.copy(), y.imag.copy(), w, g.real.copy(), g.imag.copy(), start, left)
-        assert a.tobytes() == b.tobytes()
 
 
 # ---- the model against the float64 statement ----
