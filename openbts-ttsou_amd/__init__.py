@@ -322,46 +322,39 @@ class TrxSig:
                                                  _ptr(toa), _ptr(enable), _ptr(soft), _ptr(hard), nsoft,
                                                  soft_stride), "trxsig_demodulate_batch")
 
+    def _mlse(self, name, offset, head, tail, soft=None, nsoft=None, soft_stride=None):
+        """One sequence-equaliser call: self.L.<name>(handle, *head, B, *tail[, nsoft, soft_stride]) with B = offset's element
+        count and soft_stride = soft's row length unless given (nsoft None: the call has no soft bits); arrays go as device
+        addresses, numbers as they are."""
+        B = offset.numel() if hasattr(offset, "numel") else len(offset)
+        if nsoft is not None:
+            tail += (nsoft, soft.shape[-1] if soft_stride is None else soft_stride)
+        self._chk(getattr(self.L, name)(self.h, *[_ptr(a) if hasattr(a, "data_ptr") else a for a in head + (B,) + tail]), name)
+
     def mlse(self, samples, offset, length, tsc, amp, toa, soft, enable=None, chan=None, win=None, hard=None, nsoft=148,
              soft_stride=None):
         """The sequence equaliser with the caller's amp / TOA (trxsig_mlse_batch): chan [B, 5] complex, win [B] int32."""
-        B = offset.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, tsc, _ptr(amp), _ptr(toa),
-                                           _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride),
-                  "trxsig_mlse_batch")
+        self._mlse("trxsig_mlse_batch", offset, (samples, offset, length), (tsc, amp, toa, enable, chan, win, soft, hard), soft, nsoft,
+                   soft_stride)
 
     def mlse_normal(self, samples, offset, length, tsc, flags, amp, toa, soft, avgpwr=None, chan=None, win=None, hard=None,
                     detect_thresh=3.0, energy_thresh=0.0, nsoft=148, soft_stride=None):
         """detect_demod_normal's detector, then the sequence equaliser on the detected bursts (trxsig_mlse_normal_batch)."""
-        B = offset.numel() if hasattr(offset, "numel") else len(offset)
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_normal_batch(
-            self.h, _ptr(samples), _ptr(offset), _ptr(length), B, tsc, detect_thresh, energy_thresh, _ptr(flags), _ptr(amp),
-            _ptr(toa), _ptr(avgpwr), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_normal_batch")
+        self._mlse("trxsig_mlse_normal_batch", offset, (samples, offset, length),
+                   (tsc, detect_thresh, energy_thresh, flags, amp, toa, avgpwr, chan, win, soft, hard), soft, nsoft, soft_stride)
 
     def mlse_access(self, samples, offset, length, amp, toa, soft, enable=None, chan=None, win=None, hard=None, nsoft=148,
                     soft_stride=None):
         """The sequence equaliser for access bursts with the caller's amp / TOA (trxsig_mlse_access_batch): chan [B, 5] complex,
         win [B] int32."""
-        B = offset.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_access_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, _ptr(amp), _ptr(toa),
-                                                  _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride),
-                  "trxsig_mlse_access_batch")
+        self._mlse("trxsig_mlse_access_batch", offset, (samples, offset, length), (amp, toa, enable, chan, win, soft, hard), soft, nsoft,
+                   soft_stride)
 
     def mlse_rach(self, samples, offset, length, flags, amp, toa, soft, avgpwr=None, chan=None, win=None, hard=None,
                   detect_thresh=5.0, energy_thresh=0.0, nsoft=148, soft_stride=None):
         """detect_demod_rach's detector, then the access-burst sequence equaliser on the detected bursts (trxsig_mlse_rach_batch)."""
-        B = offset.numel() if hasattr(offset, "numel") else len(offset)
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_rach_batch(
-            self.h, _ptr(samples), _ptr(offset), _ptr(length), B, detect_thresh, energy_thresh, _ptr(flags), _ptr(amp),
-            _ptr(toa), _ptr(avgpwr), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_rach_batch")
+        self._mlse("trxsig_mlse_rach_batch", offset, (samples, offset, length),
+                   (detect_thresh, energy_thresh, flags, amp, toa, avgpwr, chan, win, soft, hard), soft, nsoft, soft_stride)
 
     def mlse_access_pinv(self):
         """The access-burst equaliser's least-squares table P32 [9, 41] float32, from the library (trxsig_mlse_access_pinv_host)."""
@@ -374,12 +367,8 @@ class TrxSig:
                  soft_stride=None):
         """The sequence equaliser for synchronisation bursts with the caller's amp / TOA (trxsig_mlse_sch_batch): chan [B, 5]
         complex, win [B] int32."""
-        B = offset.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_sch_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, _ptr(amp), _ptr(toa),
-                                               _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride),
-                  "trxsig_mlse_sch_batch")
+        self._mlse("trxsig_mlse_sch_batch", offset, (samples, offset, length), (amp, toa, enable, chan, win, soft, hard), soft, nsoft,
+                   soft_stride)
 
     def mlse_sch_pinv(self):
         """The synchronisation-burst equaliser's least-squares table P32 [9, 56] float32, from the library (trxsig_mlse_sch_pinv_host)."""
@@ -391,57 +380,37 @@ class TrxSig:
     def sch_fit(self, samples, offset, length, amp, toa, enable=None, chan9=None, win=None, E=None, R=None, q=None):
         """The fit detector's statistic for synchronisation bursts with the caller's amp / TOA (trxsig_sch_fit_batch): chan9 [B, 9]
         complex, win [B] int32, E, R, q [B] float32; each may be None."""
-        B = offset.numel()
-        self._chk(self.L.trxsig_sch_fit_batch(self.h, _ptr(samples), _ptr(offset), _ptr(length), B, _ptr(amp), _ptr(toa), _ptr(enable),
-                                              _ptr(chan9), _ptr(win), _ptr(E), _ptr(R), _ptr(q)), "trxsig_sch_fit_batch")
+        self._mlse("trxsig_sch_fit_batch", offset, (samples, offset, length), (amp, toa, enable, chan9, win, E, R, q))
 
     def mlse_div(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, chan=None,
                  win=None, hard=None, nsoft=148, soft_stride=None):
         """The sequence equaliser over two receive antennas with the caller's amp / TOA (trxsig_mlse_div_batch): one amp / TOA per
         burst, primary [B] uint8 the antenna they came from, chan [B, 2, 5] complex, win [B] int32."""
-        B = offset0.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_div_batch(
-            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, _ptr(amp), _ptr(toa),
-            _ptr(primary), _ptr(enable), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft, soft_stride), "trxsig_mlse_div_batch")
+        self._mlse("trxsig_mlse_div_batch", offset0, (samples0, offset0, samples1, offset1, length),
+                   (tsc, amp, toa, primary, enable, chan, win, soft, hard), soft, nsoft, soft_stride)
 
     def mlse_div_normal(self, samples0, offset0, samples1, offset1, length, tsc, flags, amp, toa, sel, soft, avgpwr=None, chan=None,
                         win=None, hard=None, detect_thresh=3.0, energy_thresh=0.0, nsoft=148, soft_stride=None):
         """detect_demod_normal's detector on each antenna (flags, amp, toa, avgpwr: [2, B]), the selection (sel [B] uint8) and the
         two-antenna sequence equaliser on the bursts either antenna detected (trxsig_mlse_div_normal_batch)."""
-        B = offset0.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_div_normal_batch(
-            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, detect_thresh, energy_thresh,
-            _ptr(flags), _ptr(amp), _ptr(toa), _ptr(avgpwr), _ptr(sel), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft,
-            soft_stride), "trxsig_mlse_div_normal_batch")
+        self._mlse("trxsig_mlse_div_normal_batch", offset0, (samples0, offset0, samples1, offset1, length),
+                   (tsc, detect_thresh, energy_thresh, flags, amp, toa, avgpwr, sel, chan, win, soft, hard), soft, nsoft, soft_stride)
 
     def mlse_irc(self, samples0, offset0, samples1, offset1, length, tsc, amp, toa, soft, primary=None, enable=None, loading=IRC_LOADING,
                  cov_in=None, cov=None, chan=None, win=None, hard=None, nsoft=148, soft_stride=None):
         """mlse_div with interference-rejection combining (trxsig_mlse_irc_batch): the 2 x 2 covariance of the disturbance is
         estimated per burst from the midamble residuals with `loading` on its diagonal, or given as cov_in [B, 4] float32
         (A, Bv, xr, xi); cov [B, 4] returns the set used."""
-        B = offset0.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_irc_batch(
-            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, _ptr(amp), _ptr(toa),
-            _ptr(primary), _ptr(enable), loading, _ptr(cov_in), _ptr(cov), _ptr(chan), _ptr(win), _ptr(soft), _ptr(hard), nsoft,
-            soft_stride), "trxsig_mlse_irc_batch")
+        self._mlse("trxsig_mlse_irc_batch", offset0, (samples0, offset0, samples1, offset1, length),
+                   (tsc, amp, toa, primary, enable, loading, cov_in, cov, chan, win, soft, hard), soft, nsoft, soft_stride)
 
     def mlse_irc_normal(self, samples0, offset0, samples1, offset1, length, tsc, flags, amp, toa, sel, soft, loading=IRC_LOADING,
                         avgpwr=None, cov=None, chan=None, win=None, hard=None, detect_thresh=3.0, energy_thresh=0.0, nsoft=148,
                         soft_stride=None):
         """mlse_div_normal's detector and selection, then mlse_irc with an estimated set (trxsig_mlse_irc_normal_batch)."""
-        B = offset0.numel()
-        if soft_stride is None:
-            soft_stride = soft.shape[-1]
-        self._chk(self.L.trxsig_mlse_irc_normal_batch(
-            self.h, _ptr(samples0), _ptr(offset0), _ptr(samples1), _ptr(offset1), _ptr(length), B, tsc, detect_thresh, energy_thresh,
-            loading, _ptr(flags), _ptr(amp), _ptr(toa), _ptr(avgpwr), _ptr(sel), _ptr(cov), _ptr(chan), _ptr(win), _ptr(soft),
-            _ptr(hard), nsoft, soft_stride), "trxsig_mlse_irc_normal_batch")
+        self._mlse("trxsig_mlse_irc_normal_batch", offset0, (samples0, offset0, samples1, offset1, length),
+                   (tsc, detect_thresh, energy_thresh, loading, flags, amp, toa, avgpwr, sel, cov, chan, win, soft, hard), soft, nsoft,
+                   soft_stride)
 
     def equalize_normal(self, samples, offset, length, tsc, flags, amp, toa, soft, w=None, b=None, hard=None,
                         detect_thresh=3.0, energy_thresh=0.0, variant52m=True, max_toa=4, nsoft=148,

@@ -706,84 +706,43 @@ int trx_ctx_demod_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32
                              (const trx_c32 *)d_amp, d_toa, d_enable, need_mask, d_soft, nullptr, nsoft, soft_stride, c->prof, c->soft_mode));
   return TRXSIG_OK;
 }
-int trx_ctx_mlse_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
-                        const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
-                        int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (bad_batch(d_samples, d_offset, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 || nsoft > 148 || soft_stride < nsoft ||
-      (B > 0 && (!d_amp || !d_toa || !d_soft)))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_batch: bad argument");
-  if (B == 0) return TRXSIG_OK;
+unsigned trx_tsc_bits(int tsc) {
   unsigned bits = 0;
   for (int k = 0; k < 26; k++) bits |= (unsigned)(trx_training_sequence(tsc)[k] == '1') << k;
+  return bits;
+}
+// the equaliser kinds in TrxMlseKind's order: second antenna, tsc, loading checked or not; the entry point the refusals name; the launcher
+static const struct { bool two, tsc, loading; const char *name; TrxMlseLaunch *launch; } kMlseKinds[] = {
+  { false, true, false, "trxsig_mlse_batch", trx_launch_mlse },
+  { false, false, false, "trxsig_mlse_access_batch", trx_launch_mlse_access },
+  { false, false, false, "trxsig_mlse_sch_batch", trx_launch_mlse_sch },
+  { true, true, false, "trxsig_mlse_div_batch", trx_launch_mlse_div },
+  { true, true, true, "trxsig_mlse_irc_batch", trx_launch_mlse_irc },
+};
+int trx_ctx_mlse(trxsig_ctx *c, TrxMlseKind kind, int tsc, const TrxMlseArgs &in) {
+  if (!c) return TRXSIG_EINVAL;
+  const auto &k = kMlseKinds[kind];
+  TrxMlseArgs a = in;
+  if (bad_batch(a.samples0, a.off0, a.len, a.B) || (k.two && bad_batch(a.samples1, a.off1, a.len, a.B)) || (k.tsc && (tsc < 0 || tsc > 7)) ||
+      a.nsoft < 0 || a.nsoft > 148 || a.stride < a.nsoft || (a.B > 0 && (!a.amp || !a.toa || !a.soft)))
+    return fail(c, TRXSIG_EINVAL, (std::string(k.name) + ": bad argument").c_str());
+  if (k.loading && !(a.loading >= 0.0f && a.loading <= 16.0f))   // (a NaN too; before the B == 0 return)
+    return fail(c, TRXSIG_EINVAL, (std::string(k.name) + ": loading outside 0..16").c_str());
+  if (a.B == 0) return TRXSIG_OK;
+  if (k.tsc) a.tsc_bits = trx_tsc_bits(tsc);
   TrxDeviceGuard g(c->device);
-  TRX_HIPCHK(c, trx_launch_mlse(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, bits, (const trx_c32 *)d_amp,
-                            d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+  TRX_HIPCHK(c, k.launch(c->stream, c->sps, c->d_tables, a));
   return TRXSIG_OK;
 }
-// trxsig_mlse_access_batch with the enable test spelt out (the group's TRXSIG_RACHLEG_MLSE)
-int trx_ctx_mlse_access_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
-                               const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
-                               int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (bad_batch(d_samples, d_offset, d_length, B) || nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_access_batch: bad argument");
-  if (B == 0) return TRXSIG_OK;
-  TrxDeviceGuard g(c->device);
-  TRX_HIPCHK(c, trx_launch_mlse_access(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, (const trx_c32 *)d_amp,
-                                   d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
-  return TRXSIG_OK;
-}
-// trxsig_mlse_sch_batch with the enable test spelt out (trxsig_l1acq's TRXSIG_SCHLEG_MLSE)
-int trx_ctx_mlse_sch_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
-                            const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
-                            int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (bad_batch(d_samples, d_offset, d_length, B) || nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_sch_batch: bad argument");
-  if (B == 0) return TRXSIG_OK;
-  TrxDeviceGuard g(c->device);
-  TRX_HIPCHK(c, trx_launch_mlse_sch(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, (const trx_c32 *)d_amp,
-                                d_toa, d_enable, need_mask, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
-  return TRXSIG_OK;
-}
-// trxsig_mlse_div_batch with the enable test spelt out (trxsig_trxgroup_combine_div: a launch per TSC class)
-int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
-                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
-                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan, int32_t *d_win,
-                            float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (bad_batch(d_samples0, d_offset0, d_length, B) || bad_batch(d_samples1, d_offset1, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 ||
-      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_div_batch: bad argument");
-  if (B == 0) return TRXSIG_OK;
-  unsigned bits = 0;
-  for (int k = 0; k < 26; k++) bits |= (unsigned)(trx_training_sequence(tsc)[k] == '1') << k;
-  TrxDeviceGuard g(c->device);
-  TRX_HIPCHK(c, trx_launch_mlse_div(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples0, d_offset0, (const trx_c32 *)d_samples1,
-                                d_offset1, d_length, B, bits, (const trx_c32 *)d_amp, d_toa, d_primary, d_enable, need_mask,
-                                (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
-  return TRXSIG_OK;
-}
-// trxsig_mlse_irc_batch with the enable test spelt out (trxsig_trxgroup_combine_irc: a launch per TSC class)
-int trx_ctx_mlse_irc_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
-                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
-                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, float loading, const float *d_cov_in,
-                            float *d_cov, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (bad_batch(d_samples0, d_offset0, d_length, B) || bad_batch(d_samples1, d_offset1, d_length, B) || tsc < 0 || tsc > 7 || nsoft < 0 ||
-      nsoft > 148 || soft_stride < nsoft || (B > 0 && (!d_amp || !d_toa || !d_soft)))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_irc_batch: bad argument");
-  if (!(loading >= 0.0f && loading <= 16.0f))               // (a NaN too)
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_irc_batch: loading outside 0..16");
-  if (B == 0) return TRXSIG_OK;
-  unsigned bits = 0;
-  for (int k = 0; k < 26; k++) bits |= (unsigned)(trx_training_sequence(tsc)[k] == '1') << k;
-  TrxDeviceGuard g(c->device);
-  TRX_HIPCHK(c, trx_launch_mlse_irc(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples0, d_offset0, (const trx_c32 *)d_samples1,
-                                d_offset1, d_length, B, bits, (const trx_c32 *)d_amp, d_toa, d_primary, d_enable, need_mask, loading,
-                                d_cov_in, d_cov, (trx_c32 *)d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
-  return TRXSIG_OK;
+// the record as the C ABI's entry points fill it: one antenna's worth (the second antenna, primary, loading and the sets are the caller's)
+static TrxMlseArgs mlse_args(const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, const trxsig_c32 *d_amp,
+                             const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft,
+                             uint8_t *d_hard, int nsoft, int soft_stride) {
+  TrxMlseArgs a;
+  a.samples0 = (const trx_c32 *)d_samples; a.off0 = d_offset; a.len = d_length; a.B = B; a.amp = (const trx_c32 *)d_amp; a.toa = d_toa;
+  a.flags = d_enable; a.need_mask = need_mask; a.chan = (trx_c32 *)d_chan; a.win = d_win; a.soft = d_soft; a.hard = d_hard;
+  a.nsoft = nsoft; a.stride = soft_stride;
+  return a;
 }
 extern "C" {
 
@@ -833,44 +792,48 @@ int trxsig_demodulate_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const in
 int trxsig_mlse_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
                       const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win,
                       float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  return trx_ctx_mlse_masked(c, d_samples, d_offset, d_length, B, tsc, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft,
-                             soft_stride);
+  return trx_ctx_mlse(c, TRX_MLSE_NORMAL, tsc,
+                      mlse_args(d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
+}
+
+// the body of trxsig_mlse_normal_batch (kind TRX_MLSE_NORMAL) and trxsig_mlse_rach_batch (TRX_MLSE_ACCESS: no tsc)
+static int mlse_one_detect(trxsig_ctx *c, TrxMlseKind kind, const char *bad_argument, const trxsig_c32 *d_samples, const int32_t *d_offset,
+                           const int32_t *d_length, int B, int tsc, float detect_thresh, float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp,
+                           float *d_toa, float *d_avgpwr, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft,
+                           int soft_stride) {
+  if (!c) return TRXSIG_EINVAL;
+  if (nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && !d_soft)) return fail(c, TRXSIG_EINVAL, bad_argument);
+  // the exact detector alone (nsoft = 0: no demodulator, whatever the soft mode), then the equaliser on the bursts it flagged
+  const int rc = kind == TRX_MLSE_NORMAL
+                     ? trxsig_detect_demod_normal_batch(c, d_samples, d_offset, d_length, B, tsc, detect_thresh, energy_thresh, d_flags, d_amp,
+                                                        d_toa, d_avgpwr, nullptr, nullptr, 0, 0)
+                     : trxsig_detect_demod_rach_batch(c, d_samples, d_offset, d_length, B, detect_thresh, energy_thresh, d_flags, d_amp, d_toa,
+                                                      d_avgpwr, nullptr, nullptr, 0, 0);
+  if (rc != TRXSIG_OK) return rc;
+  return trx_ctx_mlse(c, kind, tsc, mlse_args(d_samples, d_offset, d_length, B, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft,
+                                              d_hard, nsoft, soft_stride));
 }
 
 int trxsig_mlse_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
                              float detect_thresh, float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
                              trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && !d_soft))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_normal_batch: bad argument");
-  // the exact detector alone (nsoft = 0: no demodulator, whatever the soft mode), then the equaliser on the bursts it flagged
-  const int rc = trxsig_detect_demod_normal_batch(c, d_samples, d_offset, d_length, B, tsc, detect_thresh, energy_thresh, d_flags, d_amp, d_toa,
-                                                  d_avgpwr, nullptr, nullptr, 0, 0);
-  if (rc != TRXSIG_OK) return rc;
-  return trx_ctx_mlse_masked(c, d_samples, d_offset, d_length, B, tsc, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard,
-                             nsoft, soft_stride);
+  return mlse_one_detect(c, TRX_MLSE_NORMAL, "trxsig_mlse_normal_batch: bad argument", d_samples, d_offset, d_length, B, tsc, detect_thresh,
+                         energy_thresh, d_flags, d_amp, d_toa, d_avgpwr, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
 }
 
 // ---- the sequence equaliser for access bursts (trxsig_mlse_access.hip) ----
 int trxsig_mlse_access_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                              const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win,
                              float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  return trx_ctx_mlse_access_masked(c, d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft,
-                                    soft_stride);
+  return trx_ctx_mlse(c, TRX_MLSE_ACCESS, 0,
+                      mlse_args(d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
 }
 
 int trxsig_mlse_rach_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                            float detect_thresh, float energy_thresh, uint8_t *d_flags, trxsig_c32 *d_amp, float *d_toa, float *d_avgpwr,
                            trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  if (!c) return TRXSIG_EINVAL;
-  if (nsoft < 0 || nsoft > 148 || soft_stride < nsoft || (B > 0 && !d_soft))
-    return fail(c, TRXSIG_EINVAL, "trxsig_mlse_rach_batch: bad argument");
-  // the detector alone (nsoft = 0: no demodulator, whatever the soft mode), then the equaliser on the bursts it flagged
-  const int rc = trxsig_detect_demod_rach_batch(c, d_samples, d_offset, d_length, B, detect_thresh, energy_thresh, d_flags, d_amp, d_toa, d_avgpwr,
-                                                nullptr, nullptr, 0, 0);
-  if (rc != TRXSIG_OK) return rc;
-  return trx_ctx_mlse_access_masked(c, d_samples, d_offset, d_length, B, d_amp, d_toa, d_flags, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard,
-                                    nsoft, soft_stride);
+  return mlse_one_detect(c, TRX_MLSE_ACCESS, "trxsig_mlse_rach_batch: bad argument", d_samples, d_offset, d_length, B, 0, detect_thresh,
+                         energy_thresh, d_flags, d_amp, d_toa, d_avgpwr, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
 }
 
 int trxsig_mlse_access_pinv_host(float out[9 * 41]) {
@@ -883,8 +846,8 @@ int trxsig_mlse_access_pinv_host(float out[9 * 41]) {
 int trxsig_mlse_sch_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                           const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win,
                           float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  return trx_ctx_mlse_sch_masked(c, d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft,
-                                 soft_stride);
+  return trx_ctx_mlse(c, TRX_MLSE_SCH, 0,
+                      mlse_args(d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride));
 }
 
 int trxsig_mlse_sch_pinv_host(float out[9 * 56]) {
@@ -894,6 +857,7 @@ int trxsig_mlse_sch_pinv_host(float out[9 * 56]) {
 }
 
 // ---- the fit detector's statistic for synchronisation bursts (trxsig_sch_fit.hip) ----
+// (its own checks: no soft bits, so neither nsoft nor d_soft -- the table of trx_ctx_mlse has no row without them)
 int trxsig_sch_fit_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                          const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, trxsig_c32 *d_chan9, int32_t *d_win,
                          float *d_E, float *d_R, float *d_q) {
@@ -902,8 +866,9 @@ int trxsig_sch_fit_batch(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32
     return fail(c, TRXSIG_EINVAL, "trxsig_sch_fit_batch: bad argument");
   if (B == 0) return TRXSIG_OK;
   TrxDeviceGuard g(c->device);
-  TRX_HIPCHK(c, trx_launch_sch_fit(c->stream, c->sps, c->d_tables, (const trx_c32 *)d_samples, d_offset, d_length, B, (const trx_c32 *)d_amp,
-                                   d_toa, d_enable, 0, (trx_c32 *)d_chan9, d_win, d_E, d_R, d_q));
+  TrxMlseArgs a = mlse_args(d_samples, d_offset, d_length, B, d_amp, d_toa, d_enable, 0, d_chan9, d_win, nullptr, nullptr, 0, 0);
+  a.E = d_E; a.R = d_R; a.q = d_q;
+  TRX_HIPCHK(c, trx_launch_sch_fit(c->stream, c->sps, c->d_tables, a));
   return TRXSIG_OK;
 }
 
@@ -912,8 +877,9 @@ int trxsig_mlse_div_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int
                           const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
                           const uint8_t *d_primary, const uint8_t *d_enable, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft,
                           uint8_t *d_hard, int nsoft, int soft_stride) {
-  return trx_ctx_mlse_div_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, d_amp, d_toa, d_primary, d_enable, 0,
-                                 d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+  TrxMlseArgs a = mlse_args(d_samples0, d_offset0, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+  a.samples1 = (const trx_c32 *)d_samples1; a.off1 = d_offset1; a.primary = d_primary;
+  return trx_ctx_mlse(c, TRX_MLSE_DIV, tsc, a);
 }
 
 // the body of trxsig_mlse_div_normal_batch and trxsig_mlse_irc_normal_batch: irc == nullptr is the first
@@ -949,12 +915,11 @@ static int mlse_two_normal(trxsig_ctx *c, const char *bad_argument, const char *
   ds.toa0 = d_toa; ds.toa1 = d_toa + B; ds.B = B; ds.need_mask = TRXSIG_F_DETECT;
   ds.sel = d_sel; ds.amp = amp_sel; ds.toa = toa_sel; ds.valid = en;
   TRX_HIPCHK(c, trx_launch_div_select(c->stream, ds));
-  if (irc)
-    return trx_ctx_mlse_irc_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, (const trxsig_c32 *)amp_sel, toa_sel,
-                                   d_sel, en, TRXSIG_F_DETECT, irc->loading, nullptr, irc->d_cov, d_chan, d_win, d_soft, d_hard, nsoft,
-                                   soft_stride);
-  return trx_ctx_mlse_div_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, (const trxsig_c32 *)amp_sel, toa_sel, d_sel,
-                                 en, TRXSIG_F_DETECT, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+  TrxMlseArgs a = mlse_args(d_samples0, d_offset0, d_length, B, (const trxsig_c32 *)amp_sel, toa_sel, en, TRXSIG_F_DETECT, d_chan, d_win, d_soft,
+                            d_hard, nsoft, soft_stride);
+  a.samples1 = (const trx_c32 *)d_samples1; a.off1 = d_offset1; a.primary = d_sel;
+  if (irc) { a.loading = irc->loading; a.cov = irc->d_cov; }
+  return trx_ctx_mlse(c, irc ? TRX_MLSE_IRC : TRX_MLSE_DIV, tsc, a);
 }
 
 int trxsig_mlse_div_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
@@ -971,8 +936,10 @@ int trxsig_mlse_irc_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int
                           const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
                           const uint8_t *d_primary, const uint8_t *d_enable, float loading, const float *d_cov_in, float *d_cov,
                           trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride) {
-  return trx_ctx_mlse_irc_masked(c, d_samples0, d_offset0, d_samples1, d_offset1, d_length, B, tsc, d_amp, d_toa, d_primary, d_enable, 0,
-                                 loading, d_cov_in, d_cov, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+  TrxMlseArgs a = mlse_args(d_samples0, d_offset0, d_length, B, d_amp, d_toa, d_enable, 0, d_chan, d_win, d_soft, d_hard, nsoft, soft_stride);
+  a.samples1 = (const trx_c32 *)d_samples1; a.off1 = d_offset1; a.primary = d_primary;
+  a.loading = loading; a.cov_in = d_cov_in; a.cov = d_cov;
+  return trx_ctx_mlse(c, TRX_MLSE_IRC, tsc, a);
 }
 
 int trxsig_mlse_irc_normal_batch(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,

@@ -155,28 +155,13 @@ int trx_ctx_rx_demod(trxsig_ctx *c, const TrxRxGen &gen, int B, const trxsig_c32
 int trx_ctx_demod_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
                          const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, float *d_soft, int nsoft,
                          int soft_stride);
-// trxsig_mlse_batch with the enable test spelt out in the same way (the group's TRXSIG_TSCLEG_MLSE: a launch per TSC class)
-int trx_ctx_mlse_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B, int tsc,
-                        const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
-                        int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
-// trxsig_mlse_access_batch likewise (the group's TRXSIG_RACHLEG_MLSE: the access-burst rows)
-int trx_ctx_mlse_access_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
-                               const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
-                               int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
-// trxsig_mlse_sch_batch likewise (trxsig_l1acq's TRXSIG_SCHLEG_MLSE: the windows of stage 2)
-int trx_ctx_mlse_sch_masked(trxsig_ctx *c, const trxsig_c32 *d_samples, const int32_t *d_offset, const int32_t *d_length, int B,
-                            const trxsig_c32 *d_amp, const float *d_toa, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan,
-                            int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
-// trxsig_mlse_div_batch likewise (trxsig_trxgroup_combine_div)
-int trx_ctx_mlse_div_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
-                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
-                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, trxsig_c32 *d_chan, int32_t *d_win,
-                            float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
-// trxsig_mlse_irc_batch likewise (trxsig_trxgroup_combine_irc)
-int trx_ctx_mlse_irc_masked(trxsig_ctx *c, const trxsig_c32 *d_samples0, const int32_t *d_offset0, const trxsig_c32 *d_samples1,
-                            const int32_t *d_offset1, const int32_t *d_length, int B, int tsc, const trxsig_c32 *d_amp, const float *d_toa,
-                            const uint8_t *d_primary, const uint8_t *d_enable, int need_mask, float loading, const float *d_cov_in,
-                            float *d_cov, trxsig_c32 *d_chan, int32_t *d_win, float *d_soft, uint8_t *d_hard, int nsoft, int soft_stride);
+// The six equaliser kinds' one checked path from the C ABI to the launch: kind's row of the table in trxsig_api.cpp says whether
+// the second antenna, tsc (packed into a.tsc_bits here) and a.loading are checked, which entry point's name the refusal carries
+// and which launcher runs.  a.need_mask spells the enable test out as trx_ctx_demod_masked's does (the group's TRXSIG_TSCLEG_MLSE
+// and TRXSIG_RACHLEG_MLSE, trxsig_trxgroup_combine_div / _irc: a launch per TSC class)
+enum TrxMlseKind { TRX_MLSE_NORMAL, TRX_MLSE_ACCESS, TRX_MLSE_SCH, TRX_MLSE_DIV, TRX_MLSE_IRC };
+int trx_ctx_mlse(trxsig_ctx *c, TrxMlseKind kind, int tsc, const TrxMlseArgs &a);
+unsigned trx_tsc_bits(int tsc);                            // bit k = bit k of training sequence tsc (0..7)
 // the receive front end's side of a fused push (trxsig_frontend.cpp): which bursts this push completes and how the kernels
 // find their samples (begin), and the window / clock bookkeeping once the kernels are enqueued (end)
 struct trxsig_rxfe;

@@ -89,26 +89,26 @@ int stage2(trxsig_l1acq *a, const trxsig_c32 *d_samples, const long long *base64
   TRX_HIPCHK(c, trx_launch_convolve(st, a->y, a->woff, a->wlen, B, TRXSIG_L1ACQ_MAX_WINDOW * sps, a->d_seq, 64 * sps, TRXSIG_NO_DELAY, 0,
                                     1, 0, 0, a->corr, a->woff));
   TRX_HIPCHK(c, trx_launch_peak_detect(st, dT, a->corr, a->woff, a->wlen, B, a->peak, a->pidx, nullptr));
-  if (a->sch_det == TRXSIG_SCHDET_FIT) {
-    // the geometry gate, the fit on the candidates' segments (the ones step 7 takes), q > thresh
+  // the fit detector's and the equalising leg's record: the candidates' segments of the shifted windows, amplitudes, TOAs and mask
+  TrxMlseArgs ma;
+  ma.samples0 = a->y; ma.off0 = a->doff; ma.len = a->dlen; ma.B = B; ma.amp = (const trx_c32 *)amp; ma.toa = a->dtoa; ma.flags = flags;
+  ma.need_mask = TRXSIG_F_DETECT; ma.R = fit_R; ma.q = fit_q;   // (R and q: the fit's alone)
+  if (a->sch_det == TRXSIG_SCHDET_FIT) {                    // the geometry gate, the fit on the candidates' segments (the ones step 7 takes), q > thresh
     TRX_HIPCHK(c, trx_launch_l1acq_candidates(st, sps, a->wlen, a->peak, a->pidx, B, a->gain, a->seq_toa, search, flags, (trx_c32 *)amp, toa,
                                               a->doff, a->dlen, a->dtoa));
-    TRX_HIPCHK(c, trx_launch_sch_fit(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, nullptr,
-                                     nullptr, nullptr, fit_R, fit_q));
+    TRX_HIPCHK(c, trx_launch_sch_fit(st, sps, dT, ma));
     TRX_HIPCHK(c, trx_launch_l1acq_fit_verdict(st, B, fit_q, thresh, flags, ptm, state));
   } else {
     TRX_HIPCHK(c, trx_launch_l1acq_verdict(st, sps, a->corr, a->wlen, a->peak, a->pidx, B, a->gain, a->seq_toa, thresh, search, flags,
                                            (trx_c32 *)amp, toa, ptm, a->doff, a->dlen, a->dtoa, state));
   }
-  // TRXSIG_SCHLEG_MLSE: the equaliser on the same shifted windows, amplitudes, TOAs and mask, in the demodulator's place
-  if (a->sch_leg == TRXSIG_SCHLEG_MLSE) {
-    TRX_HIPCHK(c, trx_launch_mlse_sch(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, chan, win,
-                                      soft, hard, kSoft, soft_stride));
-    return TRXSIG_OK;
+  if (a->sch_leg == TRXSIG_SCHLEG_MLSE) {                   // the equaliser on the same record, in the demodulator's place
+    ma.chan = chan; ma.win = win; ma.soft = soft; ma.hard = hard; ma.nsoft = kSoft; ma.stride = soft_stride;
+    TRX_HIPCHK(c, trx_launch_mlse_sch(st, sps, dT, ma));
+  } else {                                                  // always with the exact arithmetic, whatever trxsig_set_soft_mode says
+    TRX_HIPCHK(c, trx_launch_demod(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, soft,
+                                   hard, kSoft, soft_stride, prof, TRXSIG_SOFT_EXACT));
   }
-  // acquisition always demodulates with the exact arithmetic, whatever trxsig_set_soft_mode says
-  TRX_HIPCHK(c, trx_launch_demod(st, sps, dT, a->y, a->doff, a->dlen, B, (const trx_c32 *)amp, a->dtoa, flags, TRXSIG_F_DETECT, soft,
-                                 hard, kSoft, soft_stride, prof, TRXSIG_SOFT_EXACT));
   return TRXSIG_OK;
 }
 }  // namespace

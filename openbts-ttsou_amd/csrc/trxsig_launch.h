@@ -112,40 +112,38 @@ hipError_t trx_launch_demod(hipStream_t st, int sps, const TrxTables *dT, const 
                             const float *toa, const uint8_t *flags, int need_mask, float *soft,
                             uint8_t *hard, int nsoft, int stride, TrxProfiler *prof, int soft_tolerance = 0);
 // (soft_tolerance: TRXSIG_SOFT_TOLERANCE -- the rearranged demodulator of trxsig_demod.h; hard bits exact, soft bits within 3.7e-5)
-// the sequence equaliser (trxsig_mlse.hip; trxsig_mlse_batch): flags / need_mask as trx_launch_demod; tsc_bits: bit j = bit j of the
-// training sequence; chan (B x 5) and win (B) may be NULL; nsoft <= 148.  No profiler id.
-hipError_t trx_launch_mlse(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len, int B,
-                           unsigned tsc_bits, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan,
-                           int32_t *win, float *soft, uint8_t *hard, int nsoft, int stride);
-// the sequence equaliser for access bursts (trxsig_mlse_access.hip; trxsig_mlse_access_batch): trx_launch_mlse's arguments without
-// the training sequence (the burst's 49 leading symbols are fixed).  No profiler id.
-hipError_t trx_launch_mlse_access(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
-                                  int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
-                                  float *soft, uint8_t *hard, int nsoft, int stride);
-// the sequence equaliser for synchronisation bursts (trxsig_mlse_sch.hip; trxsig_mlse_sch_batch; trxsig_l1acq's TRXSIG_SCHLEG_MLSE):
-// trx_launch_mlse_access's arguments (the burst's 64-symbol extended training sequence is fixed).  No profiler id.
-hipError_t trx_launch_mlse_sch(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
-                               int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
-                               float *soft, uint8_t *hard, int nsoft, int stride);
-// the fit detector's statistic for synchronisation bursts (trxsig_sch_fit.hip; trxsig_sch_fit_batch; trxsig_l1acq's
-// TRXSIG_SCHDET_FIT): trx_launch_mlse_sch's inputs; chan9 (B x 9), win, E, R and q (B each) may each be NULL.  No profiler id.
-hipError_t trx_launch_sch_fit(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
-                              int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan9, int32_t *win,
-                              float *E, float *R, float *q);
-// the same over two antennas (trxsig_mlse_div.hip; trxsig_mlse_div_batch): a sample pointer and an offset array per antenna, one
-// amp / TOA per burst, primary (may be NULL = 0) the antenna they came from; chan is B x 2 x 5.  No profiler id.
-hipError_t trx_launch_mlse_div(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
-                               const trx_c32 *samples1, const int32_t *off1, const int32_t *len, int B, unsigned tsc_bits, const trx_c32 *amp,
-                               const float *toa, const uint8_t *primary, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
-                               float *soft, uint8_t *hard, int nsoft, int stride);
-// the same with interference-rejection combining (trxsig_mlse_irc.hip; trxsig_mlse_irc_batch): loading (0..16) is added to the
-// diagonal of the estimated set; cov_in (B x 4, may be NULL = estimate) is the caller's set (A, Bv, xr, xi), cov (B x 4, may be
-// NULL) the set used.  No profiler id.
-hipError_t trx_launch_mlse_irc(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
-                               const trx_c32 *samples1, const int32_t *off1, const int32_t *len, int B, unsigned tsc_bits, const trx_c32 *amp,
-                               const float *toa, const uint8_t *primary, const uint8_t *flags, int need_mask, float loading,
-                               const float *cov_in, float *cov, trx_c32 *chan, int32_t *win, float *soft, uint8_t *hard, int nsoft,
-                               int stride);
+// The six sequence-equaliser kernels' arguments, one record for all (a member a kind does not read stays as it is here).  Every
+// kind reads samples0 / off0 / len / B, amp / toa, flags / need_mask (as trx_launch_demod; flags may be NULL), chan and win (may
+// each be NULL).  All but sch_fit: soft, hard, nsoft (<= 148), stride.  No profiler id.
+//   mlse        (trxsig_mlse.hip; trxsig_mlse_batch): + tsc_bits (bit j = bit j of the training sequence); chan is B x 5
+//   mlse_access (trxsig_mlse_access.hip; trxsig_mlse_access_batch): the burst's 49 leading symbols are fixed
+//   mlse_sch    (trxsig_mlse_sch.hip; trxsig_mlse_sch_batch; trxsig_l1acq's TRXSIG_SCHLEG_MLSE): the 64-symbol sequence is fixed
+//   sch_fit     (trxsig_sch_fit.hip; trxsig_sch_fit_batch; trxsig_l1acq's TRXSIG_SCHDET_FIT): chan is B x 9; + E, R, q (B each, may be NULL)
+//   mlse_div    (trxsig_mlse_div.hip; trxsig_mlse_div_batch): mlse's + samples1 / off1 (an antenna each, one amp / TOA per burst) and
+//               primary (may be NULL = 0), the antenna they came from; chan is B x 2 x 5
+//   mlse_irc    (trxsig_mlse_irc.hip; trxsig_mlse_irc_batch): mlse_div's + loading (0..16, added to the diagonal of the estimated
+//               set), cov_in (B x 4, may be NULL = estimate: the caller's set A, Bv, xr, xi) and cov (B x 4, may be NULL: the set used)
+struct TrxMlseArgs {
+  const trx_c32 *samples0 = nullptr, *samples1 = nullptr;
+  const int32_t *off0 = nullptr, *off1 = nullptr, *len = nullptr;
+  int B = 0;
+  unsigned tsc_bits = 0;
+  const trx_c32 *amp = nullptr;
+  const float *toa = nullptr;
+  const uint8_t *primary = nullptr, *flags = nullptr;
+  int need_mask = 0;
+  float loading = 0.0f;
+  const float *cov_in = nullptr;
+  float *cov = nullptr;
+  trx_c32 *chan = nullptr;
+  int32_t *win = nullptr;
+  float *soft = nullptr;
+  uint8_t *hard = nullptr;
+  int nsoft = 0, stride = 0;
+  float *E = nullptr, *R = nullptr, *q = nullptr;
+};
+typedef hipError_t TrxMlseLaunch(hipStream_t st, int sps, const TrxTables *dT, const TrxMlseArgs &a);
+TrxMlseLaunch trx_launch_mlse, trx_launch_mlse_access, trx_launch_mlse_sch, trx_launch_sch_fit, trx_launch_mlse_div, trx_launch_mlse_irc;
 // the selection rule of trxsig_mlse_div_normal_batch, v_a = (valid_a[b] & need_mask) != 0: sel (0, 1, 2 = neither); the selected
 // antenna's amp, TOA, flags byte and avgPwr (antenna 0's where neither); valid[b] = need_mask where sel < 2 else 0.  Every output,
 // and with flags / pwr their inputs, may be NULL.

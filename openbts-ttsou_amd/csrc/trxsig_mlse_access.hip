@@ -130,14 +130,9 @@ void k_mlse_access(const TrxTables *__restrict__ T, const void *__restrict__ sam
 
 }  // namespace
 
-hipError_t trx_launch_mlse_access(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
-                                  int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan, int32_t *win,
-                                  float *soft, uint8_t *hard, int nsoft, int stride) {
-  if (B <= 0) return hipSuccess;
-  if (nsoft < 0 || nsoft > 148) return hipErrorInvalidValue;
-  const int per = 4 * TRX_MLSE_WAVES;
-  const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
-#define TRX_MLSE_ACC_GO(S) k_mlse_access<S><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan, win, soft, hard, nsoft, stride)
-  TRX_MLSE_DISPATCH(sps, TRX_MLSE_ACC_GO);
-#undef TRX_MLSE_ACC_GO
+hipError_t trx_launch_mlse_access(hipStream_t st, int sps, const TrxTables *dT, const TrxMlseArgs &a) {
+  return mlse_launch<4 * TRX_MLSE_WAVES, true>(sps, a, [&](auto S, dim3 grid, dim3 block) {
+    k_mlse_access<decltype(S)::value><<<grid, block, 0, st>>>(dT, a.samples0, a.off0, a.len, a.B, a.amp, a.toa, a.flags, a.need_mask, a.chan, a.win,
+                                                              a.soft, a.hard, a.nsoft, a.stride);
+  });
 }

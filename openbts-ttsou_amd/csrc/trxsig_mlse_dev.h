@@ -7,10 +7,13 @@
 //   mlse_trellis, mlse_trellis2               a row's forward and backward pass, one antenna / two (summed or whitened metric)
 //   mlse_soft_out, mlse_put, mlse_fall_back   the soft and hard bits out
 //   bperm, sgn, mlse_expected, mlse_gamma, mlse_whiten, mlse_slice: the small pieces under them
+//   mlse_launch                               the six launchers' host side: guard, grid, sps dispatch (arguments: TrxMlseArgs, trxsig_launch.h)
 // A kernel keeps what is its own: its LDS, the loop over its bursts, which symbols its estimate reads, the start state and the map
 // from trellis step to symbol.  Numerical contract as everywhere: one float32 operation at a time, nothing fused
 // (-ffp-contract=off); every operand order and association order below is part of it.
 #pragma once
+#include <type_traits>
+
 #include "trxsig_demod.h"
 
 namespace {
@@ -19,15 +22,21 @@ namespace {
 #define TRX_MLSE_NY 152                                     /* symbols kept per burst (148, padded to a multiple of 8) */
 #define TRX_MLSE_INF __builtin_inff()
 
-// a launcher's tail: GO(S) launches the instantiation for S samples per symbol
-#define TRX_MLSE_DISPATCH(sps, GO)                                                                                          \
-  switch (sps) {                                                                                                            \
-    case 1: GO(1); break;                                                                                                   \
-    case 2: GO(2); break;                                                                                                   \
-    case 4: GO(4); break;                                                                                                   \
-    default: return hipErrorInvalidValue;                                                                                   \
-  }                                                                                                                         \
-  return hipGetLastError()
+// a launcher's body: nothing to do without bursts, nsoft inside 0..148 where the kind has soft bits (SOFT), a workgroup per PER
+// bursts; go(S, grid, block) launches the instantiation for decltype(S)::value samples per symbol
+template <int PER, bool SOFT, class Go>
+hipError_t mlse_launch(int sps, const TrxMlseArgs &a, Go go) {
+  if (a.B <= 0) return hipSuccess;
+  if (SOFT && (a.nsoft < 0 || a.nsoft > 148)) return hipErrorInvalidValue;
+  const dim3 grid((a.B + PER - 1) / PER), block(64 * TRX_MLSE_WAVES);
+  switch (sps) {
+    case 1: go(std::integral_constant<int, 1>(), grid, block); break;
+    case 2: go(std::integral_constant<int, 2>(), grid, block); break;
+    case 4: go(std::integral_constant<int, 4>(), grid, block); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
 
 __device__ __forceinline__ float bperm(int byte_addr, float v) {
   return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));

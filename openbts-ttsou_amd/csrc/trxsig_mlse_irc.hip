@@ -215,17 +215,10 @@ void k_mlse_irc(const TrxTables *__restrict__ T, const void *__restrict__ sample
 
 }  // namespace
 
-hipError_t trx_launch_mlse_irc(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples0, const int32_t *off0,
-                               const trx_c32 *samples1, const int32_t *off1, const int32_t *len, int B, unsigned tsc_bits, const trx_c32 *amp,
-                               const float *toa, const uint8_t *primary, const uint8_t *flags, int need_mask, float loading,
-                               const float *cov_in, float *cov, trx_c32 *chan, int32_t *win, float *soft, uint8_t *hard, int nsoft,
-                               int stride) {
-  if (B <= 0) return hipSuccess;
-  if (nsoft < 0 || nsoft > 148) return hipErrorInvalidValue;
-  const int per = 2 * TRX_MLSE_WAVES;
-  const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
-#define TRX_MLSE_IRC_GO(S) k_mlse_irc<S><<<grid, block, 0, st>>>(dT, samples0, off0, samples1, off1, len, B, tsc_bits, amp, toa, primary, flags, \
-                                                                 need_mask, loading, cov_in, cov, chan, win, soft, hard, nsoft, stride)
-  TRX_MLSE_DISPATCH(sps, TRX_MLSE_IRC_GO);
-#undef TRX_MLSE_IRC_GO
+hipError_t trx_launch_mlse_irc(hipStream_t st, int sps, const TrxTables *dT, const TrxMlseArgs &a) {
+  return mlse_launch<2 * TRX_MLSE_WAVES, true>(sps, a, [&](auto S, dim3 grid, dim3 block) {
+    k_mlse_irc<decltype(S)::value><<<grid, block, 0, st>>>(dT, a.samples0, a.off0, a.samples1, a.off1, a.len, a.B, a.tsc_bits, a.amp, a.toa, a.primary,
+                                                           a.flags, a.need_mask, a.loading, a.cov_in, a.cov, a.chan, a.win, a.soft, a.hard, a.nsoft,
+                                                           a.stride);
+  });
 }

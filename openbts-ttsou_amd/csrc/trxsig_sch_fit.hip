@@ -115,13 +115,9 @@ void k_sch_fit(const TrxTables *__restrict__ T, const void *__restrict__ samples
 
 }  // namespace
 
-hipError_t trx_launch_sch_fit(hipStream_t st, int sps, const TrxTables *dT, const trx_c32 *samples, const int32_t *off, const int32_t *len,
-                              int B, const trx_c32 *amp, const float *toa, const uint8_t *flags, int need_mask, trx_c32 *chan9, int32_t *win,
-                              float *E, float *R, float *q) {
-  if (B <= 0) return hipSuccess;
-  const int per = 2 * TRX_MLSE_WAVES;
-  const dim3 grid((B + per - 1) / per), block(64 * TRX_MLSE_WAVES);
-#define TRX_SCH_FIT_GO(S) k_sch_fit<S><<<grid, block, 0, st>>>(dT, samples, off, len, B, amp, toa, flags, need_mask, chan9, win, E, R, q)
-  TRX_MLSE_DISPATCH(sps, TRX_SCH_FIT_GO);
-#undef TRX_SCH_FIT_GO
+hipError_t trx_launch_sch_fit(hipStream_t st, int sps, const TrxTables *dT, const TrxMlseArgs &a) {
+  return mlse_launch<2 * TRX_MLSE_WAVES, false>(sps, a, [&](auto S, dim3 grid, dim3 block) {
+    k_sch_fit<decltype(S)::value><<<grid, block, 0, st>>>(dT, a.samples0, a.off0, a.len, a.B, a.amp, a.toa, a.flags, a.need_mask, a.chan, a.win, a.E,
+                                                          a.R, a.q);
+  });
 }

@@ -491,6 +491,13 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
   if (beside) TRX_HIPCHK(g->c, hipEventRecord(piped ? W.done : g->ev_join, g->side));
   const uint8_t *demod_gate = beside ? W.flags.p : W.gate.p;   // (gate holds TRXSIG_F_DETECT or 0: the same mask serves both)
 
+  TrxMlseArgs ma;                                           // the sequence-equalising legs': rows b0 .. b0 + n, the group's own amplitude, TOA and gate
+  ma.samples0 = (const trx_c32 *)d_samples; ma.need_mask = TRXSIG_F_DETECT; ma.nsoft = ma.stride = kSoft;
+  auto mlse_rows = [&](int b0, int n) -> const TrxMlseArgs & {
+    ma.off0 = W.off.p + b0; ma.len = W.len.p + b0; ma.B = n; ma.amp = W.amp.p + b0; ma.toa = W.toa.p + b0; ma.flags = demod_gate + b0;
+    ma.soft = W.soft.p + (size_t)b0 * kSoft;
+    return ma;
+  };
   // ---- what comes back as a SoftVector ----
   if (n_tsc > 0) {
     if (equalize) {
@@ -506,12 +513,8 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
       G_LIB(trx_ctx_group_equalize(c, d_samples, W.off.p, W.len.p, n_tsc, (const trxsig_c32 *)W.amp.p, W.toa_eq.p, W.gate.p,
                                    (const trxsig_c32 *)g->w_tab.p, (const trxsig_c32 *)g->b_tab.p, W.tap_ix.p, W.soft.p, kSoft, kSoft));
     } else if (g->leg == TRXSIG_TSCLEG_MLSE) {              // (never with src.gen: trxsig_trxgroup_pull_rxfe sends this leg through push / pop)
-      for (int k = 0; k < TRXG_CLASS_RACH; k++) {           // the sequence equaliser needs the class's training sequence: a launch per class
-        if (!count[k]) continue;
-        const int b0 = base[k];
-        G_LIB(trx_ctx_mlse_masked(c, d_samples, W.off.p + b0, W.len.p + b0, count[k], k, (const trxsig_c32 *)W.amp.p + b0, W.toa.p + b0,
-                                  demod_gate + b0, TRXSIG_F_DETECT, nullptr, nullptr, W.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
-      }
+      for (int k = 0; k < TRXG_CLASS_RACH; k++)             // the sequence equaliser needs the class's training sequence: a launch per class
+        if (count[k]) G_LIB(trx_ctx_mlse(c, TRX_MLSE_NORMAL, k, mlse_rows(base[k], count[k])));
     } else if (!src.gen) {
       G_LIB(trx_ctx_demod_masked(c, d_samples, W.off.p, W.len.p, n_tsc, (const trxsig_c32 *)W.amp.p, W.toa.p, demod_gate, TRXSIG_F_DETECT,
                                  W.soft.p, kSoft, kSoft));
@@ -522,9 +525,7 @@ int pull_core(trxsig_trxgroup *g, const PullSource &src, int fn, int tn, int n_s
     gen.sel = W.off.p;
     G_LIB(trx_ctx_rx_demod(c, gen, n_rows, (const trxsig_c32 *)W.amp.p, W.toa.p, demod_gate, TRXSIG_F_DETECT, W.soft.p, kSoft, kSoft));
   } else if (n_rows > n_tsc && g->rach_leg == TRXSIG_RACHLEG_MLSE)   // the same rows, gate and stride through the access-burst sequence equaliser
-    G_LIB(trx_ctx_mlse_access_masked(c, d_samples, W.off.p + n_tsc, W.len.p + n_tsc, n_rows - n_tsc, (const trxsig_c32 *)W.amp.p + n_tsc,
-                                     W.toa.p + n_tsc, demod_gate + n_tsc, TRXSIG_F_DETECT, nullptr, nullptr, W.soft.p + (size_t)n_tsc * kSoft,
-                                     nullptr, kSoft, kSoft));
+    G_LIB(trx_ctx_mlse(c, TRX_MLSE_ACCESS, 0, mlse_rows(n_tsc, n_rows - n_tsc)));
   else if (n_rows > n_tsc)                                  // :385-388
     G_LIB(trx_ctx_demod_masked(c, d_samples, W.off.p + n_tsc, W.len.p + n_tsc, n_rows - n_tsc, (const trxsig_c32 *)W.amp.p + n_tsc,
                                W.toa.p + n_tsc, demod_gate + n_tsc, TRXSIG_F_DETECT, W.soft.p + (size_t)n_tsc * kSoft, kSoft, kSoft));
@@ -668,18 +669,17 @@ static int combine_two(const char *name, bool irc, float loading, trxsig_trxgrou
   ds.toa0 = W0.toa.p; ds.toa1 = W1.toa.p; ds.pwr0 = W0.avgpwr.p; ds.pwr1 = W1.avgpwr.p; ds.B = n_rows; ds.need_mask = TRXSIG_F_DETECT;
   ds.sel = sel; ds.valid = D.valid.p; ds.flags = D.flags.p; ds.amp = D.amp.p; ds.toa = D.toa.p; ds.pwr = D.avgpwr.p;
   TRX_HIPCHK(c, trx_launch_div_select(st, ds));
+  TrxMlseArgs ma;
+  ma.samples0 = (const trx_c32 *)d_samples0; ma.samples1 = (const trx_c32 *)d_samples1; ma.need_mask = TRXSIG_F_DETECT; ma.loading = loading;
+  ma.nsoft = ma.stride = kSoft;
   for (int k = 0; k < TRXG_CLASS_RACH; k++) {               // the equaliser needs the class's training sequence: a launch per class in use
     const int b0 = g0->last_base[k], n = g0->last_base[k + 1] - b0;
     if (!n) continue;
-    if (irc)
-      G_LIB(trx_ctx_mlse_irc_masked(c, d_samples0, W0.off.p + b0, d_samples1, W1.off.p + b0, W0.len.p + b0, n, k, (const trxsig_c32 *)D.amp.p + b0,
-                                    D.toa.p + b0, sel + b0, D.valid.p + b0, TRXSIG_F_DETECT, loading, nullptr,
-                                    d_cov ? d_cov + (size_t)b0 * 4 : nullptr, d_chan ? d_chan + (size_t)b0 * 10 : nullptr,
-                                    d_win ? d_win + b0 : nullptr, D.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
-    else
-      G_LIB(trx_ctx_mlse_div_masked(c, d_samples0, W0.off.p + b0, d_samples1, W1.off.p + b0, W0.len.p + b0, n, k, (const trxsig_c32 *)D.amp.p + b0,
-                                    D.toa.p + b0, sel + b0, D.valid.p + b0, TRXSIG_F_DETECT, d_chan ? d_chan + (size_t)b0 * 10 : nullptr,
-                                    d_win ? d_win + b0 : nullptr, D.soft.p + (size_t)b0 * kSoft, nullptr, kSoft, kSoft));
+    ma.off0 = W0.off.p + b0; ma.off1 = W1.off.p + b0; ma.len = W0.len.p + b0; ma.B = n; ma.amp = D.amp.p + b0; ma.toa = D.toa.p + b0;
+    ma.primary = sel + b0; ma.flags = D.valid.p + b0; ma.cov = d_cov ? d_cov + (size_t)b0 * 4 : nullptr;
+    ma.chan = d_chan ? (trx_c32 *)d_chan + (size_t)b0 * 10 : nullptr; ma.win = d_win ? d_win + b0 : nullptr;
+    ma.soft = D.soft.p + (size_t)b0 * kSoft;
+    G_LIB(trx_ctx_mlse(c, irc ? TRX_MLSE_IRC : TRX_MLSE_DIV, k, ma));
   }
   if (n_rows > n_tsc)                                       // access bursts: selection only
     TRX_HIPCHK(c, trx_launch_div_copy_rows(st, n_rows - n_tsc, D.valid.p + n_tsc, sel + n_tsc, W0.soft.p + (size_t)n_tsc * kSoft,

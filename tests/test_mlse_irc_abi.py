@@ -4,23 +4,17 @@ the contract's words in the header; the kernel file in the Makefile; the binding
 need a live context -- nsoft, tsc, the loading -- are checked on one in tests/test_gpu_mlse_irc.py and
 tests/test_gpu_mlse_irc_group.py)."""
 import ctypes
-import os
-import re
 
 import pytest
 
-import _pkg
+import mlse_abi as abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = {"trxsig_mlse_irc_batch": "trxsig.h", "trxsig_mlse_irc_normal_batch": "trxsig.h", "trxsig_trxgroup_combine_irc": "trxsig_trxgroup.h"}
 
 
-@pytest.mark.parametrize("name", ["libtrxsig.so", "libtrxsig_tune.so"])
+@pytest.mark.parametrize("name", abi.LIBS)
 def test_irc_in_the_abi(name):
-    lib = ctypes.CDLL(os.path.join(ROOT, "openbts-ttsou_amd", name))
-    for s, header in SYMBOLS.items():
-        assert hasattr(lib, s), s
-        assert re.search(r"\bint\s+%s\(" % s, open(os.path.join(ROOT, "include", header)).read()), s
+    lib = abi.exported_and_declared(name, SYMBOLS)
     vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     lib.trxsig_mlse_irc_batch.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, i32]
     lib.trxsig_mlse_irc_normal_batch.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]
@@ -34,52 +28,39 @@ def test_irc_in_the_abi(name):
     assert lib.trxsig_mlse_irc_batch(None, None, None, None, None, None, 0, 0, None, None, None, None, 0.0, None, None, None, None, None, None,
                                      0, 0) == -1
     assert lib.trxsig_trxgroup_combine_irc(None, x, None, x, 1.0 / 64.0, None, None, None, None, x) == -1
-    # the new kernel has no profiler id: the table (ABI 2) stays where it was
-    assert lib.trxsig_kernel_count() == 28
-    assert lib.trxsig_abi_version() == 2
+    abi.table_stays(lib)
 
 
 def test_headers_state_the_contract():
-    h = open(os.path.join(ROOT, "include", "trxsig.h")).read()
+    h = abi.read("include", "trxsig.h")
     for word in ("S00 += r0.re*r0.re + r0.im*r0.im", "Xi += r0.im*r1.re - r0.re*r1.im", "tt = S00 + S11", "A = S00/tt + loading",
                  "det = A*Bv - (xr*xr + xi*xi)", "v < 0x1p10f", "!(det > 0)", "y1'[n].re = A*y1[n].re - (xr*y0[n].re + xi*y0[n].im)",
                  "y1'[n].im = A*y1[n].im - (xr*y0[n].im - xi*y0[n].re)", "gamma = det*(dr0*dr0 + di0*di0) + (dr1*dr1 + di1*di1)",
                  "(8.0f * E_w)", "0 <= loading <= 16", "d_cov_in", "not symmetric", "tests/mlse_irc_model.py", "tests/mlse_irc_ref.py",
                  "TRXSIG_K_COUNT = 15", "#define TRXSIG_ABI_VERSION 2"):
         assert word in h, word
-    g = open(os.path.join(ROOT, "include", "trxsig_trxgroup.h")).read()
+    g = abi.read("include", "trxsig_trxgroup.h")
     for word in ("trxsig_trxgroup_combine_irc", "k_mlse_irc", "0 <= loading <= 16", "1/64"):
         assert word in g, word
 
 
 def test_python_binding():
-    m = _pkg.load()
-    from openbts_ttsou_amd import _abi
-    for name in SYMBOLS:
-        assert name in _abi.SIGNATURES, name
+    m, _abi = abi.binding(SYMBOLS, TrxSig=("mlse_irc", "mlse_irc_normal"), TrxGroup=("combine_irc",))
     assert len(_abi.SIGNATURES["trxsig_mlse_irc_batch"][1]) == 21 and len(_abi.SIGNATURES["trxsig_mlse_irc_normal_batch"][1]) == 23
     assert len(_abi.SIGNATURES["trxsig_trxgroup_combine_irc"][1]) == 10
     assert _abi.SIGNATURES["trxsig_mlse_irc_batch"][1][12] is ctypes.c_float and _abi.SIGNATURES["trxsig_trxgroup_combine_irc"][1][4] is ctypes.c_float
-    assert callable(getattr(m.TrxSig, "mlse_irc", None)) and callable(getattr(m.TrxSig, "mlse_irc_normal", None))
-    assert callable(getattr(m.TrxGroup, "combine_irc", None))
     assert m.IRC_LOADING == 1.0 / 64.0
 
 
 def test_kernel_file_is_built():
-    mk = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^KERNELS\s*:=.*\btrxsig_mlse_irc\b", mk, re.M)
-    src = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_irc.hip")).read()
+    src = abi.kernel_file("trxsig_mlse_irc")
     assert "k_mlse_irc" in src and "amdgpu_waves_per_eu(4)" in src
     for call in ("mlse_symbols<SPS>(", "mlse_window2(", "mlse_trellis2<61, true>(", "#pragma unroll 1"):
         assert call in src, call
-    dev = open(os.path.join(ROOT, "openbts-ttsou_amd", "csrc", "trxsig_mlse_dev.h")).read()
+    dev = abi.read("openbts-ttsou_amd", "csrc", "trxsig_mlse_dev.h")
     assert "if (WEIGHTED) return det * mlse_gamma(y0, z0) + mlse_gamma(y1, z1);" in dev       # det on antenna 0's metric, and only here
 
 
 def test_documents_name_the_stage():
-    for doc in ("DESIGN.md", "README.md"):
-        text = open(os.path.join(ROOT, doc)).read()
-        for word in ("trxsig_mlse_irc_batch", "trxsig_trxgroup_combine_irc", "mlse_irc_bench"):
-            assert word in text, (doc, word)
-    readme = open(os.path.join(ROOT, "README.md")).read()
-    assert "unequal noise power per branch" not in readme
+    abi.documents_name("trxsig_mlse_irc_batch", "trxsig_trxgroup_combine_irc", "mlse_irc_bench")
+    assert "unequal noise power per branch" not in abi.read("README.md")

@@ -7,30 +7,11 @@ nothing is asserted.  Results go to profiles/mlse_bench.json (or --out) and to s
 
     hipcc --offload-arch=gfx950 -O3 tools/hbm_bench.hip -o hbm_bench
     python tools/mlse_bench.py --hbm-bench ./hbm_bench [--bursts 65536] [--reps 30] [--out profiles/mlse_bench.json]"""
-import argparse
-import json
-import os
-import sys
-
-import numpy as np
-
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import mlse_bench_lib as lib
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--bursts", type=int, default=65536)
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--tsc", type=int, default=2)
-    ap.add_argument("--hbm-bench", default=None, help="compiled tools/hbm_bench.hip, run before anything else")
-    ap.add_argument("--hbm-tbps", type=float, default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlse_bench.json"))
-    a = ap.parse_args()
-    if (a.hbm_bench is None) == (a.hbm_tbps is None):
-        raise SystemExit("give --hbm-bench or --hbm-tbps")
-    from air_bench import hbm_rate
-    tbps, line = hbm_rate(a.hbm_bench) if a.hbm_bench else (a.hbm_tbps, "given on the command line")
+    a, tbps, line = lib.parse(lib.parser("mlse_bench.json", tsc=True))
 
     import torch
     import _pkg
@@ -41,59 +22,29 @@ def main():
     ctx.use_torch_stream()
     # the library's synthetic normal bursts, plus an echo one symbol late on every burst: a channel the equaliser has work with
     x, off, length, meta = synth.normal_batch_torch(sps, B, tsc, seed=3)
-    echo = torch.zeros_like(x)
-    echo[sps:] = x[:-sps] * complex(0.45, -0.3)
-    x = (x + echo).contiguous()
-    sample_bytes = x.numel() * 8
-    n_copies = max(2, (512 << 20) // sample_bytes + 1)
-    xs = [x] + [x.clone() for _ in range(n_copies - 1)]
-    flags = torch.zeros(B, dtype=torch.uint8, device="cuda"); amp = torch.zeros(B, 2, device="cuda"); toa = torch.zeros(B, device="cuda")
-    soft = torch.zeros(B, 148, device="cuda"); soft2 = torch.zeros(B, 148, device="cuda")
-    chan = torch.zeros(B, 5, 2, device="cuda"); win = torch.zeros(B, dtype=torch.int32, device="cuda")
+    x = lib.echoed(x, sps).contiguous()
+    rot = lib.Rotation(a.reps, x)
+    xs = rot.xs[0]
+    flags, amp, toa, (soft, soft2), (chan,), (win,) = lib.one_antenna_buffers(B, 2, 1)
     ctx.detect_demod_normal(x, off, length, tsc, flags, amp, toa, soft, energy_thresh=-1.0)
     torch.cuda.synchronize()
     det = (flags & m.F_DETECT) != 0
-    turn = [0]
-
-    def window(fnc):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ts = []
-        for _ in range(a.reps):
-            turn[0] += 1
-            ev[0].record(); fnc(xs[turn[0] % n_copies]); ev[1].record(); torch.cuda.synchronize()
-            ts.append(ev[0].elapsed_time(ev[1]) * 1000.0)
-        return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
-
     en = det.to(torch.uint8)
-    demod = lambda buf: ctx.demodulate(buf, off, length, amp, toa, soft, enable=en)
-    mlse = lambda buf: ctx.mlse(buf, off, length, tsc, amp, toa, soft2, enable=en, chan=chan, win=win)
-    for _ in range(3):
-        demod(xs[0]); mlse(xs[0])
-    torch.cuda.synchronize()
-    d_us = window(demod)
-    q_us = window(mlse)
-    w = win.cpu().numpy()
-    bits = meta["bits"].cpu().numpy()
-    pay = np.r_[3:61, 87:145]
+    demod = lambda k: ctx.demodulate(xs[k], off, length, amp, toa, soft, enable=en)
+    mlse = lambda k: ctx.mlse(xs[k], off, length, tsc, amp, toa, soft2, enable=en, chan=chan, win=win)
+    d_us, q_us = rot.timed(demod, mlse)
     d = det.cpu().numpy()
-    err = lambda s: int((((s.cpu().numpy() > 0.5) != bits)[d][:, pay]).sum())
-    floor = sample_bytes / (tbps * 1e12) * 1e6
-    out = dict(bursts=B, sps=sps, tsc=tsc, detected=int(d.sum()), sample_bytes=sample_bytes, sample_buffers_in_rotation=n_copies,
-               hbm_read_tbps=tbps, hbm_bench_line=line, one_read_of_the_samples_us=round(floor, 1),
-               demodulate_us=round(d_us[0], 1), demodulate_min_max_us=[round(d_us[1], 1), round(d_us[2], 1)],
-               mlse_us=round(q_us[0], 1), mlse_min_max_us=[round(q_us[1], 1), round(q_us[2], 1)],
+    err = lib.bit_errors(meta["bits"].cpu().numpy(), d, lib.PAYLOAD)
+    out, floor = lib.one_antenna_head(B, sps, d, rot, tbps, line, tsc=tsc)
+    out.update(**lib.us("demodulate", d_us), **lib.us("mlse", q_us),
                demodulate_over_one_read=round(d_us[0] / floor, 2), mlse_over_one_read=round(q_us[0] / floor, 2),
                mlse_over_demodulate=round(q_us[0] / d_us[0], 2), mlse_ns_per_burst=round(q_us[0] * 1e3 / B, 2),
-               windows=dict((str(k), int((w == k).sum())) for k in (-4, -3, -2, -1, 0, 1, 2)),
-               payload_bit_errors=dict(demodulate=err(soft), mlse=err(soft2), of=int(d.sum()) * len(pay)),
+               windows=lib.window_counts(win),
+               payload_bit_errors=dict(demodulate=err(soft), mlse=err(soft2), of=int(d.sum()) * len(lib.PAYLOAD)),
                note="the batch: the library's synthetic normal bursts (sigma 0 / 0.1 / 0.3 in turn) plus an echo one symbol late at "
                     "0.54 of the amplitude; amplitude and TOA from trxsig_detect_demod_normal_batch, detected bursts only; medians of "
                     "--reps HIP-event windows, one call each, the samples read from a buffer not touched since the rotation came round")
-    print(json.dumps(out))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    lib.write(out, a.out)
     ctx.close()
 
 

@@ -11,16 +11,12 @@ profiles/mlse_div_bench.json (or --out) and to stdout.
 
     hipcc --offload-arch=gfx950 -O3 tools/hbm_bench.hip -o hbm_bench
     python tools/mlse_div_bench.py --hbm-bench ./hbm_bench [--bursts 65536] [--reps 30] [--arfcns 128] [--frames 104] [--out profiles/mlse_div_bench.json]"""
-import argparse
 import ctypes
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import mlse_bench_lib as lib
+
 SLOT_S = 15.0 / 26.0 * 1e-3                                   # a slot: 0.577 ms
 
 
@@ -33,56 +29,23 @@ def kernel_times(m, a, tbps, line):
     # antenna 0: the library's synthetic normal bursts plus an echo one symbol late (tools/mlse_bench.py's batch); antenna 1: the same
     # bursts through another gain and an echo two symbols late
     x, off, length, meta = synth.normal_batch_torch(sps, B, tsc, seed=3)
-    e0 = torch.zeros_like(x); e0[sps:] = x[:-sps] * complex(0.45, -0.3)
-    e1 = torch.zeros_like(x); e1[2 * sps:] = x[:-2 * sps] * complex(-0.2, 0.5)
-    x0 = (x + e0).contiguous()
-    x1 = ((x + e1) * complex(0.3, 0.8)).contiguous()
-    del e0, e1, x
-    sample_bytes = x0.numel() * 8
-    n_copies = max(2, (512 << 20) // (2 * sample_bytes) + 1)
-    xs0 = [x0] + [x0.clone() for _ in range(n_copies - 1)]
-    xs1 = [x1] + [x1.clone() for _ in range(n_copies - 1)]
-    flags = torch.zeros(2, B, dtype=torch.uint8, device="cuda"); amp = torch.zeros(2, B, 2, device="cuda"); toa = torch.zeros(2, B, device="cuda")
-    sel = torch.zeros(B, dtype=torch.uint8, device="cuda")
-    soft1 = torch.zeros(B, 148, device="cuda"); soft2 = torch.zeros(B, 148, device="cuda")
-    chan = torch.zeros(B, 2, 5, 2, device="cuda"); win = torch.zeros(B, dtype=torch.int32, device="cuda")
-    ctx.mlse_div_normal(x0, off, x1, off, length, tsc, flags, amp, toa, sel, soft2, chan=chan, win=win, energy_thresh=-1.0)
-    torch.cuda.synchronize()
-    both = sel < 2
-    pick = (sel == 1)
-    amp_s = torch.where(pick[:, None], amp[1], amp[0]).contiguous(); toa_s = torch.where(pick, toa[1], toa[0]).contiguous()
-    en = both.to(torch.uint8)
-    turn = [0]
-
-    def window(fnc):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ts = []
-        for _ in range(a.reps):
-            turn[0] += 1
-            ev[0].record(); fnc(turn[0] % n_copies); ev[1].record(); torch.cuda.synchronize()
-            ts.append(ev[0].elapsed_time(ev[1]) * 1000.0)
-        return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
-
-    one = lambda k: ctx.mlse(xs0[k], off, length, tsc, amp_s, toa_s, soft1, enable=en)
-    two = lambda k: ctx.mlse_div(xs0[k], off, xs1[k], off, length, tsc, amp_s, toa_s, soft2, primary=sel, enable=en, chan=chan, win=win)
-    for _ in range(3):
-        one(0); two(0)
-    torch.cuda.synchronize()
-    o_us = window(one)
-    t_us = window(two)
-    bits = meta["bits"].cpu().numpy()
-    pay = np.r_[3:61, 87:145]
-    d = both.cpu().numpy()
-    err = lambda s: int((((s.cpu().numpy() > 0.5) != bits)[d][:, pay]).sum())
-    floor = 2 * sample_bytes / (tbps * 1e12) * 1e6
-    out = dict(bursts=B, sps=sps, tsc=tsc, detected_by_either=int(d.sum()), selected_antenna_1=int(pick.sum().item()),
-               sample_bytes_both_antennas=2 * sample_bytes, sample_buffers_in_rotation=n_copies, hbm_read_tbps=tbps, hbm_bench_line=line,
-               one_read_of_both_sample_sets_us=round(floor, 1),
-               mlse_one_antenna_us=round(o_us[0], 1), mlse_one_antenna_min_max_us=[round(o_us[1], 1), round(o_us[2], 1)],
-               mlse_div_us=round(t_us[0], 1), mlse_div_min_max_us=[round(t_us[1], 1), round(t_us[2], 1)],
+    x0 = lib.echoed(x, sps).contiguous()
+    x1 = (lib.echoed(x, 2 * sps, complex(-0.2, 0.5)) * complex(0.3, 0.8)).contiguous()
+    del x
+    rot = lib.Rotation(a.reps, x0, x1)
+    xs0, xs1 = rot.xs
+    w = lib.TwoAntennas(B)
+    soft1, soft2 = w.soft
+    ctx.mlse_div_normal(x0, off, x1, off, length, tsc, w.flags, w.amp, w.toa, w.sel, soft2, chan=w.chan, win=w.win, energy_thresh=-1.0)
+    w.select()
+    one = lambda k: ctx.mlse(xs0[k], off, length, tsc, w.amp_s, w.toa_s, soft1, enable=w.en)
+    two = lambda k: ctx.mlse_div(xs0[k], off, xs1[k], off, length, tsc, w.amp_s, w.toa_s, soft2, primary=w.sel, enable=w.en, chan=w.chan, win=w.win)
+    o_us, t_us = rot.timed(one, two)
+    out, floor = w.head(B, sps, tsc, rot, tbps, line)
+    out.update(**lib.us("mlse_one_antenna", o_us), **lib.us("mlse_div", t_us),
                mlse_div_over_one_read=round(t_us[0] / floor, 2), mlse_div_over_mlse=round(t_us[0] / o_us[0], 2),
                mlse_div_ns_per_burst=round(t_us[0] * 1e3 / B, 2),
-               payload_bit_errors=dict(mlse_antenna_0=err(soft1), mlse_div=err(soft2), of=int(d.sum()) * len(pay)))
+               payload_bit_errors=w.errors(meta["bits"], mlse_antenna_0=soft1, mlse_div=soft2))
     ctx.close()
     return out
 
@@ -198,10 +161,7 @@ def uplink_loop(m, a):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--bursts", type=int, default=65536)
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--tsc", type=int, default=2)
+    ap = lib.parser("mlse_div_bench.json", tsc=True)
     ap.add_argument("--arfcns", type=int, default=128)
     ap.add_argument("--frames", type=int, default=104)
     ap.add_argument("--profile", default="TU6")
@@ -209,14 +169,7 @@ def main():
     ap.add_argument("--loop-taps", type=int, default=12)
     ap.add_argument("--doppler-hz", type=float, default=2.0, help="the loop's maximum Doppler shift")
     ap.add_argument("--snr-db", type=float, default=15.0, help="the loop's mean SNR, per antenna")
-    ap.add_argument("--hbm-bench", default=None, help="compiled tools/hbm_bench.hip, run before anything else")
-    ap.add_argument("--hbm-tbps", type=float, default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlse_div_bench.json"))
-    a = ap.parse_args()
-    if (a.hbm_bench is None) == (a.hbm_tbps is None):
-        raise SystemExit("give --hbm-bench or --hbm-tbps")
-    from air_bench import hbm_rate
-    tbps, line = hbm_rate(a.hbm_bench) if a.hbm_bench else (a.hbm_tbps, "given on the command line")
+    a, tbps, line = lib.parse(ap)
     import _pkg
     m = _pkg.load()
     out = kernel_times(m, a, tbps, line)
@@ -226,11 +179,7 @@ def main():
                    "trxsig_mlse_div_normal_batch; trxsig_mlse_batch runs on antenna 0 with the same amplitudes and TOAs; medians of --reps "
                    "HIP-event windows, one call each, the samples read from buffers not touched since the rotation came round.  The loop: "
                    "tools/air_fade_bench.py's without hopping, one link per (ARFCN, TN) and antenna, both groups on the MLSE leg")
-    print(json.dumps(out))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    lib.write(out, a.out)
 
 
 if __name__ == "__main__":

@@ -9,29 +9,13 @@ profiles/sch_fit_bench.json (or --out) and to stdout.
 
     hipcc --offload-arch=gfx950 -O3 tools/hbm_bench.hip -o hbm_bench
     python tools/sch_fit_bench.py --hbm-bench ./hbm_bench [--bursts 65536] [--reps 30] [--out profiles/sch_fit_bench.json]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+import mlse_bench_lib as lib
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--bursts", type=int, default=65536)
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--hbm-bench", default=None, help="compiled tools/hbm_bench.hip, run before anything else")
-    ap.add_argument("--hbm-tbps", type=float, default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sch_fit_bench.json"))
-    a = ap.parse_args()
-    if (a.hbm_bench is None) == (a.hbm_tbps is None):
-        raise SystemExit("give --hbm-bench or --hbm-tbps")
-    from air_bench import hbm_rate
-    tbps, line = hbm_rate(a.hbm_bench) if a.hbm_bench else (a.hbm_tbps, "given on the command line")
+    a, tbps, line = lib.parse(lib.parser("sch_fit_bench.json"))
 
     import torch
     import _pkg
@@ -42,9 +26,8 @@ def main():
     ctx = m.TrxSig(sps, 0)
     ctx.use_torch_stream()
     x, off, length, _ = sch_batch_torch(synth, sps, B, seed=3)
-    sample_bytes = x.numel() * 8
-    n_copies = max(2, (512 << 20) // sample_bytes + 1)
-    xs = [x] + [x.clone() for _ in range(n_copies - 1)]
+    rot = lib.Rotation(a.reps, x)
+    xs = rot.xs[0]
     f32 = lambda *shape: torch.zeros(*shape, device="cuda")
     flags = torch.zeros(B, dtype=torch.uint8, device="cuda"); amp = f32(B, 2); toa = f32(B); ptm = f32(B)
     soft = [f32(B, 148) for _ in range(3)]
@@ -66,26 +49,11 @@ def main():
     det = (flags & m.F_DETECT) != 0
     en = det.to(torch.uint8)
     amp0, toa0 = amp.clone(), toa.clone()
-    turn = [0]
-
-    def window(fnc):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ts = []
-        for _ in range(a.reps):
-            turn[0] += 1
-            ev[0].record(); fnc(xs[turn[0] % n_copies]); ev[1].record(); torch.cuda.synchronize()
-            ts.append(ev[0].elapsed_time(ev[1]) * 1000.0)
-        return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
-
-    demod = lambda buf: ctx.demodulate(buf, off, length, amp0, toa0, soft[1], enable=en)
-    sch = lambda buf: ctx.mlse_sch(buf, off, length, amp0, toa0, soft[2], enable=en, chan=chan, win=win[0])
-    fit = lambda buf: ctx.sch_fit(buf, off, length, amp0, toa0, enable=en, chan9=chan9, win=win[1], E=E, R=R, q=q)
-    for _ in range(3):
-        demod(xs[0]); sch(xs[0]); fit(xs[0])
-    torch.cuda.synchronize()
-    d_us, s_us, f_us = window(demod), window(sch), window(fit)
+    demod = lambda k: ctx.demodulate(xs[k], off, length, amp0, toa0, soft[1], enable=en)
+    sch = lambda k: ctx.mlse_sch(xs[k], off, length, amp0, toa0, soft[2], enable=en, chan=chan, win=win[0])
+    fit = lambda k: ctx.sch_fit(xs[k], off, length, amp0, toa0, enable=en, chan9=chan9, win=win[1], E=E, R=R, q=q)
+    d_us, s_us, f_us = rot.timed(demod, sch, fit)
     qv = q.cpu().numpy()[det.cpu().numpy()]
-    wv = win[1].cpu().numpy()
     acq_us, detected = {}, {}
     for dname, dcode, thresh in (("valley", m.SCHDET_VALLEY, m.ACQ_SCH_THRESH), ("fit", m.SCHDET_FIT, m.ACQ_SCH_FIT_THRESH)):
         for lname, lcode in (("demod", m.SCHLEG_DEMOD), ("mlse", m.SCHLEG_MLSE)):
@@ -93,16 +61,14 @@ def main():
             for _ in range(2):
                 detect(xs[0], thresh)
             torch.cuda.synchronize()
-            acq_us[dname + "_" + lname] = window(lambda buf: detect(buf, thresh))
+            acq_us[dname + "_" + lname] = rot.window(lambda k: detect(xs[k], thresh))
             detected[dname + "_" + lname] = int(((flags & m.F_DETECT) != 0).sum())
     acq.destroy()
-    floor = sample_bytes / (tbps * 1e12) * 1e6
+    floor = rot.sample_bytes / (tbps * 1e12) * 1e6
     r1 = lambda v: round(v, 1)
-    out = dict(bursts=B, sps=sps, detected_by_the_valley_rule=int(det.sum()), sample_bytes=sample_bytes, sample_buffers_in_rotation=n_copies,
+    out = dict(bursts=B, sps=sps, detected_by_the_valley_rule=int(det.sum()), sample_bytes=rot.sample_bytes, sample_buffers_in_rotation=rot.n,
                hbm_read_tbps=tbps, hbm_bench_line=line, one_read_of_the_samples_us=r1(floor),
-               sch_fit_us=r1(f_us[0]), sch_fit_min_max_us=[r1(f_us[1]), r1(f_us[2])],
-               mlse_sch_us=r1(s_us[0]), mlse_sch_min_max_us=[r1(s_us[1]), r1(s_us[2])],
-               demodulate_us=r1(d_us[0]), demodulate_min_max_us=[r1(d_us[1]), r1(d_us[2])],
+               **lib.us("sch_fit", f_us), **lib.us("mlse_sch", s_us), **lib.us("demodulate", d_us),
                sch_fit_over_one_read=round(f_us[0] / floor, 2), mlse_sch_over_one_read=round(s_us[0] / floor, 2),
                demodulate_over_one_read=round(d_us[0] / floor, 2), sch_fit_over_demodulate=round(f_us[0] / d_us[0], 2),
                sch_fit_over_mlse_sch=round(f_us[0] / s_us[0], 2), sch_fit_ns_per_burst=round(f_us[0] * 1e3 / B, 2),
@@ -112,16 +78,12 @@ def main():
                fit_over_valley=dict(demod=round(acq_us["fit_demod"][0] / acq_us["valley_demod"][0], 3),
                                     mlse=round(acq_us["fit_mlse"][0] / acq_us["valley_mlse"][0], 3)),
                q_on_the_detected=dict(min=float(qv.min()), median=float(np.median(qv)), max=float(qv.max())) if len(qv) else None,
-               windows=dict((str(k), int((wv == k).sum())) for k in (-4, -3, -2, -1, 0, 1, 2)),
+               windows=lib.window_counts(win[1]),
                note="the batch: tools/mlse_sch_bench.py's (synthetic SCH-shaped bursts, a delay of 0..5 symbols and a fraction, sigma 0 / 0.1 / "
                     "0.3 in turn, an echo one symbol late at 0.54 of the amplitude); the direct calls take amplitude and TOA from the valley "
                     "detector, detected bursts only; detect_sch_batch runs in four calls of 16,384 windows, each detector at its suggested "
                     "threshold; medians of --reps HIP-event windows, the samples read from a buffer not touched since the rotation came round")
-    print(json.dumps(out))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    lib.write(out, a.out)
     ctx.close()
 
 
