@@ -1,6 +1,7 @@
 // trxsig_fec_enc.h -- internal: the block coders' device routines, shared by trxsig_fec.hip (k_fec_xcch_encode,
-// k_fec_tch_encode), trxsig_l1tx.hip (k_l1tx_encode, k_l1tx_mux) and trxsig_l1ms.hip (k_l1ms_encode, k_l1ms_mux; the access
-// burst's coder rach_e36 is used there alone).  Each including file gets its own copy of the constant tables.
+// k_fec_tch_encode) and, through trxsig_l1mux_dev.h (mux_encode_block, mux_normal_bit), by the two transmit multiplexers'
+// kernels in trxsig_l1tx.hip and trxsig_l1ms.hip (the SCH coder's kGen and the access burst's coder rach_e36 are used by those
+// two files directly).  Each including file gets its own copy of the constant tables.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -4,7 +4,6 @@
 // k_l1ms_mux, k_l1ms_commit), per radiate one (k_l1ms_radiate).
 #include <hip/hip_runtime_api.h>
 
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -12,21 +11,13 @@
 #include "trxsig_l1ms.h"
 #include "trxsig_l1ms_dev.h"
 #include "trxsig_l1msrx_dev.h"
-#include "trxsig_plan.h"
+#include "trxsig_l1mux_host.h"
 
 namespace {
 const int8_t kPower[3][32] = TRX_POWER_TABLES_INIT;
 
 // the power a handset of the band radiates when ordered to `power` dBm: POWER[band][encodePower(band, power)]
-int level_power(int band, int power) {
-  int min_err = std::abs(power - kPower[band][0]), code = 0;
-  for (int i = 1; i < 32; i++) {
-    const int e = std::abs(power - kPower[band][i]);
-    if (e == 0) { code = i; break; }
-    if (e < min_err) { min_err = e; code = i; }
-  }
-  return kPower[band][code];
-}
+int level_power(int band, int power) { return kPower[band][trx_encode_power(kPower[band], power)]; }
 constexpr long long kMaxOutBytes = 1LL << 34;
 }  // namespace
 
@@ -60,71 +51,40 @@ int set_active(trxsig_l1ms *ms, int cls, int chan, int open) {
 
 // block geometry of a call
 void geometry(const trxsig_l1ms *ms, int fn, int F, TrxL1msCall &k) {
-  std::memset(&k, 0, sizeof k);
-  const TrxPlan &pl = ms->plan;
-  k.fn = fn; k.n_frames = F; k.n_arfcn = pl.A;
-  k.n_tch = pl.n[0]; k.n_xcch = pl.n[1]; k.n_all = ms->n_all;
-  k.r104 = fn % 104; k.r102 = fn % 102; k.r51 = fn % 51; k.r26 = fn % 26;
+  k = TrxL1msCall{};
+  trx_plan_tx_geometry(ms->plan, 2, fn, F, &k);
   k.cur = ms->cur; k.band = ms->band; k.bsic = ms->bsic;
-  for (int m = 0; m < TRX_N_MAPS; m++) {
-    const TrxBlockGeom bg = trx_plan_block_geometry(trx_plan_maps(TRX_PLAN_UL)[m], fn, F);
-    k.p_first[m] = bg.p_first; k.p_end[m] = bg.p_end; k.base[m] = bg.base;
-    for (int cl = 0; cl < 2; cl++)
-      if (pl.map_used[cl][m] && bg.nb_started > k.nb[cl]) k.nb[cl] = bg.nb_started;
-  }
-  if (pl.n[TRX_PLAN_RACH]) k.n_rach = (int)(k.p_end[TRX_MAP_RACH_C5] - k.p_first[TRX_MAP_RACH_C5]);
-  long long u = 0;
-  for (int cl = 0; cl < 2; cl++) { k.unit0[cl] = u; u += (long long)pl.n[cl] * k.nb[cl]; }
+  if (ms->plan.n[TRX_PLAN_RACH]) k.n_rach = (int)(k.p_end[TRX_MAP_RACH_C5] - k.p_first[TRX_MAP_RACH_C5]);
 }
 }  // namespace
 
 int trxsig_l1ms_create(trxsig_l1ms **out, trxsig_ctx *c, int n_arfcn, const uint8_t *h_comb, int bsic, int band) {
   if (!out || !c) return TRXSIG_EINVAL;
   *out = nullptr;
-  const int bidx = trx_plan_band_index(band);
-  if (n_arfcn <= 0 || n_arfcn > 0xffff || !h_comb || bsic < 0 || bsic > 63 || bidx < 0 || !trx_plan_selfcheck())
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1ms_create: bad argument", hipSuccess);
-  if (!trx_plan_validate(h_comb, n_arfcn))
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1ms_create: unsupported channel combination or placement", hipSuccess);
+  int bidx = -1;
+  const std::string err = trx_plan_create_error("trxsig_l1ms_create", n_arfcn, h_comb, bsic, band, true, &bidx);
+  if (!err.empty()) return trx_ctx_fail(c, TRXSIG_EINVAL, err.c_str(), hipSuccess);
   trxsig_l1ms *ms = new (std::nothrow) trxsig_l1ms;
   if (!ms) return TRXSIG_ENOMEM;
   ms->c = c; ms->bsic = bsic; ms->band = bidx;
   ms->plan = TrxPlan(n_arfcn, h_comb, TRX_PLAN_UL, 3);
   const TrxPlan &pl = ms->plan;
   ms->n_all = pl.first[TRX_PLAN_RACH];
-  std::vector<int8_t> writer;           // the slot owners, by mapping id
-  const bool disjoint = trx_plan_owner_table(TRX_PLAN_UL, true, false, writer);
-  const std::vector<int16_t> cnt = trx_plan_count_table(TRX_PLAN_UL);
-  const size_t N = (size_t)ms->n_all, S = 8 * (size_t)n_arfcn;
+  const size_t N = (size_t)ms->n_all;
   std::vector<TrxL1msChan> rec(2 * N);
   if (N) std::memset(rec.data(), 0, rec.size() * sizeof(TrxL1msChan));
   for (size_t i = 0; i < 2 * N; i++) {
     const int g = (int)(i % N);
     const bool sacch = g >= pl.first[TRX_PLAN_XCCH] && pl.sacch(g);
-    rec[i].active = 1;
+    rec[i].h.active = 1;
     rec[i].power = sacch ? level_power(bidx, 40) : -1;
     rec[i].ta = sacch ? 0 : -1;
   }
-  const TrxCarve cv = { 2 * N * sizeof(TrxL1msChan), (N + 1) * 4, S * 4, S * 4, (N + 1) * 4, writer.size(), cnt.size() * 2 };
   TrxDeviceGuard gd(trxsig_device(c));
-  if (!disjoint) { delete ms; return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1ms_create: device allocation", hipSuccess); }
-  const int rc = trx_device_block(c, "trxsig_l1ms_create", cv.total,
-                                  { { cv.off[0], rec.data(), 2 * N * sizeof(TrxL1msChan) }, { cv.off[1], pl.chinfo.data(), N * 4 },
-                                    { cv.off[2], pl.slot.data(), S * 4 }, { cv.off[3], pl.slot_x.data(), S * 4 },
-                                    { cv.off[4], pl.handset.data(), N * 4 }, { cv.off[5], writer.data(), writer.size() },
-                                    { cv.off[6], cnt.data(), cnt.size() * 2 } }, &ms->d_persist);
+  void *handset = nullptr;
+  const int rc = trx_mux_device_block(c, "trxsig_l1ms_create", pl, rec, N * 4, pl.handset.data(), ms->dv, &ms->d_persist, &handset);
   if (rc != TRXSIG_OK) { delete ms; return rc; }
-  void *b = ms->d_persist;
-  TrxL1msDev &d = ms->dv;
-  ms->d_st = cv.at<TrxL1msChan>(b, 0);
-  d.st = ms->d_st; d.chinfo = cv.at<int32_t>(b, 1); d.slot = cv.at<int32_t>(b, 2); d.slot_x = cv.at<int32_t>(b, 3);
-  d.handset = cv.at<int32_t>(b, 4); d.writer = cv.at<int8_t>(b, 5); d.cnt = cv.at<int16_t>(b, 6);
-  d.filler = trx_ctx_tch_filler(c);
-  if (!d.filler) {
-    (void)hipFree(ms->d_persist);
-    delete ms;
-    return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_l1ms_create: upload", hipSuccess);
-  }
+  ms->d_st = ms->dv.st; ms->dv.handset = (const int32_t *)handset;
   trx_ctx_retain(c);
   *out = ms;
   return TRXSIG_OK;
@@ -180,8 +140,7 @@ int trxsig_l1ms_follow(trxsig_l1ms *ms, const trxsig_l1msrx *rx) {
   if (rx) {
     TrxL1msrxFollow fo{};
     trx_l1msrx_follow(rx, &fo);
-    if (fo.ctx != ms->c || fo.n_arfcn != ms->plan.A || fo.bsic != ms->bsic || fo.band != ms->band || fo.n_xcch != ms->plan.n[1] ||
-        std::memcmp(fo.comb, ms->plan.comb.data(), ms->plan.comb.size()) != 0)
+    if (fo.ctx != ms->c || fo.bsic != ms->bsic || fo.band != ms->band || !trx_plan_same(ms->plan, fo.n_arfcn, fo.n_xcch, fo.comb))
       return fail(ms, "trxsig_l1ms_follow: the trxsig_l1msrx's plan (or context) is not this object's");
   }
   ms->fol = rx;
@@ -203,7 +162,7 @@ int trxsig_l1ms_encode(trxsig_l1ms *ms, int fn, int F, const trxsig_l1ms_in *in,
   TrxL1txSib sb{};
   if (sib) {
     trx_l1tx_sibling(sib, &sb);
-    if (sb.ctx != ms->c || sb.n_arfcn != pl.A || std::memcmp(sb.comb, pl.comb.data(), pl.comb.size()) != 0 || sb.n_xcch != pl.n[1])
+    if (sb.ctx != ms->c || !trx_plan_same(pl, sb.n_arfcn, sb.n_xcch, sb.comb))
       return fail(ms, "trxsig_l1ms_encode: the sibling's plan (or context) is not this object's");
   }
   // workspace: scratch c words and flags per unit, bits, what, who, the handsets after the call

@@ -1,62 +1,34 @@
 // trxsig_l1ms_dev.h -- internal: what the mobile-side uplink L1 (include/trxsig_l1ms.h) shares between its host side
-// (trxsig_l1ms.cpp) and its kernels (trxsig_l1ms.hip).  The mappings are the uplink tables of trxsig_tdma.h; positions, blocks
-// and the per-call geometry are trxsig_l1tx's (TrxL1txCall), over those tables.
+// (trxsig_l1ms.cpp) and its kernels (trxsig_l1ms.hip).  The mappings are the uplink tables of trxsig_tdma.h; the call, record and
+// device structs are that file's TrxMuxCall / TrxMuxChan / TrxMuxDev with the uplink's own fields after them.
 #pragma once
 #include "trxsig_launch.h"
 #include "trxsig_tdma.h"
 
-// what one encode needs of its call (by value); per mapping as TrxL1txCall
-struct TrxL1msCall {
-  int fn, n_frames, n_arfcn, n_tch, n_xcch, n_all;
-  int nb[2];                         // per class (TCH, XCCH): the most blocks any channel opens
+struct TrxL1msCall : TrxMuxCall {    // has_sib: 0 none, 1 a sibling trxsig_l1tx's orders, 2 a followed trxsig_l1msrx's
   int n_rach;                        // RACH frames of the call (0 without a combination-V slot)
-  long long unit0[2];                // per class: the first scratch unit ([n_chan][nb] after it)
-  int r104, r102, r51, r26;          // fn mod 104 / 102 / 51 / 26
-  int cur, has_sib, band, bsic;      // has_sib: 0 none, 1 a sibling trxsig_l1tx's orders, 2 a followed trxsig_l1msrx's
-  long long p_first[TRX_N_MAPS], p_end[TRX_N_MAPS], base[TRX_N_MAPS];
 };
 
-// a channel's record in the object (two copies: the call reads copy `cur`, the commit writes copy `cur ^ 1`)
 struct TrxL1msChan {
-  uint32_t last_c[16];               // c[456] of the last block the channel encoded, bit i = word i/32 bit i%32
-  uint32_t prev_c[16];               // ... and of the one before it (TCH: the odd half interleaves into the next block)
-  uint8_t last_f, prev_f;            // their FACCH flags
-  uint8_t pend;                      // the last block's last burst lies after the last call: its tail goes out next
-  uint8_t active;
+  TrxMuxChan h;
   int32_t power, ta;                 // the handset (SACCH channels): actual power (dBm) and TA; -1 on the others
   uint32_t pad[5];
 };
+// trxsig_l1ms_state hands these bytes to callers
 static_assert(sizeof(TrxL1msChan) == 160, "TrxL1msChan layout");
+static_assert(offsetof(TrxL1msChan, h.last_c) == 0 && offsetof(TrxL1msChan, h.prev_c) == 64 && offsetof(TrxL1msChan, h.last_f) == 128 &&
+              offsetof(TrxL1msChan, h.prev_f) == 129 && offsetof(TrxL1msChan, h.pend) == 130 && offsetof(TrxL1msChan, h.active) == 131 &&
+              offsetof(TrxL1msChan, power) == 132 && offsetof(TrxL1msChan, ta) == 136 && offsetof(TrxL1msChan, pad) == 140,
+              "TrxL1msChan layout");
 
-struct TrxL1msDev {
-  const int32_t *chinfo;             // [n_all]: arfcn | tn << 16 | map << 20
-  const int32_t *slot;               // [n_arfcn * 8]: combination | the slot's TCH channel << 4
-  const int32_t *slot_x;             // [n_arfcn * 8]: the slot's first XCCH channel (index over all classes)
+struct TrxL1msDev : TrxMuxDev<TrxL1msChan> {
   const int32_t *handset;            // [n_all]: the XCCH index of the SACCH channel whose handset sends this channel
-  const int8_t *writer;              // [3][8][104]: the mapping that owns (combination I / V / VII, TN, fn mod 104 or 102)
-  const int16_t *cnt;                // [TRX_N_MAPS][105]
-  TrxL1msChan *st;                   // [2][n_all]
-  uint32_t *c;                       // scratch [units][16]
-  uint8_t *flag;                     // scratch [units]: 1 encoded, 2 FACCH
-  const uint8_t *kind[2], *payload[2];   // TCH / XCCH grids
   const uint8_t *rach_kind, *rach_ra, *rach_bsic;
-  const uint8_t *filler;             // the context's TCH filler c[456]
   int32_t *ms_power, *ms_ta;         // [n_xcch] out: the handsets after the call
-  uint8_t *bits, *what;              // [n_arfcn][8 F][148], [n_arfcn][8 F]
   int32_t *who;                      // [n_arfcn][8 F]: the slot's channel within its class, or its RACH entry
   const TrxL1txChan *sib;            // the sibling's XCCH records (current copy), or null
   const int32_t *fol_power, *fol_ta; // the followed trxsig_l1msrx's decoded SACCH orders (XCCH-indexed), or null
 };
-
-// what trxsig_l1ms reads of a sibling trxsig_l1tx (trxsig_l1tx.cpp): its plan and its XCCH channels' current records
-struct trxsig_l1tx;
-struct TrxL1txSib {
-  trxsig_ctx *ctx;
-  int n_arfcn, n_xcch;
-  const uint8_t *comb;               // [n_arfcn * 8] (host)
-  const TrxL1txChan *xcch;           // [n_xcch] device: the records the next call of the sibling reads
-};
-void trx_l1tx_sibling(const trxsig_l1tx *l1, TrxL1txSib *out);
 
 // one radiate (by value)
 struct TrxL1msAir {

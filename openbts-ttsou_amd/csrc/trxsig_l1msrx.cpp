@@ -102,20 +102,17 @@ int set_active(trxsig_l1msrx *rx, int cls, int chan, int open) {
 int trxsig_l1msrx_create(trxsig_l1msrx **out, trxsig_ctx *c, int n_arfcn, const uint8_t *h_comb, int bsic, int band) {
   if (!out || !c) return TRXSIG_EINVAL;
   *out = nullptr;
-  const int bidx = trx_plan_band_index(band);
-  if (n_arfcn <= 0 || n_arfcn > 0xffff || !h_comb || bsic < 0 || bsic > 63 || bidx < 0 || !block_lengths_ok() || !trx_plan_selfcheck())
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1msrx_create: bad argument", hipSuccess);
-  if (!trx_plan_validate(h_comb, n_arfcn))
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1msrx_create: unsupported channel combination or placement", hipSuccess);
+  int bidx = -1;
+  const std::string err = trx_plan_create_error("trxsig_l1msrx_create", n_arfcn, h_comb, bsic, band, block_lengths_ok(), &bidx);
+  if (!err.empty()) return trx_ctx_fail(c, TRXSIG_EINVAL, err.c_str(), hipSuccess);
   trxsig_l1msrx *rx = new (std::nothrow) trxsig_l1msrx;
   if (!rx) return TRXSIG_ENOMEM;
   rx->c = c; rx->bsic = bsic; rx->band = bidx;
   rx->plan = TrxPlan(n_arfcn, h_comb, TRX_PLAN_DL, TRX_PLAN_CLASSES);
   const TrxPlan &pl = rx->plan;
   const size_t N = (size_t)pl.all(), T = (size_t)pl.n[K_TCH], X = (size_t)pl.n[K_XCCH], G = (size_t)rx->n_ctl(), NB = T + G;
-  std::vector<int32_t> power(X, -1), ta(X, -1);
-  for (size_t i = 0; i < X; i++)
-    if (pl.sacch((int)(T + i))) { power[i] = 40; ta[i] = 0; }
+  std::vector<int32_t> power, ta;
+  trx_plan_sacch_start(pl, power, ta);
   const std::vector<uint8_t> ones(NB, 1);
   TrxCarve cv = { T * TRXSIG_TCH_RX_STATE_BYTES, G * TRXSIG_XCCH_RX_STATE_BYTES, NB, N * 4, NB * 4, NB * 4, X * 4, X * 4, NB * 4 };
   if (cv.total == 0) cv.total = 256;
@@ -165,9 +162,7 @@ int trxsig_l1msrx_state(trxsig_l1msrx *rx, int cls, void **d_state) {
 
 int trxsig_l1msrx_decode(trxsig_l1msrx *rx, const trxsig_trxgroup_result *res, int fn, int wire, trxsig_l1msrx_out *out) {
   if (!rx) return TRXSIG_EINVAL;
-  if (!res || !out || fn < 0 || fn >= kTrxHyperframe || res->n_arfcn != rx->plan.A || res->n_slots <= 0 || (res->n_slots & 7) ||
-      res->n_rows < 0 || !res->d_row ||
-      (res->n_rows > 0 && (!res->d_valid || !res->d_soft || !res->d_amp || !res->d_toa || res->soft_stride < 148)))
+  if (!out || fn < 0 || fn >= kTrxHyperframe || !trx_plan_result_ok(res, rx->plan.A))
     return fail(rx, "trxsig_l1msrx_decode: bad argument (whole frames from TN 0 of the object's ARFCNs)");
   trxsig_ctx *c = rx->c;
   TrxL1msrxCall k{};

@@ -10,7 +10,8 @@
 //   Positions and frames are 32-bit here and every division is by a constant (the mappings have 4, 5 or 24 frames).  The SCH channel's
 //   wave lists its frames of the call and gathers each burst's 78 coded values for the Viterbi launcher; the FCCH channel's
 //   wave lists its frames and counts each burst's soft values above 0.5 with a ballot.
-// k_l1msrx_finish: after the decoders -- the SACCH orders folded over the call's good SACCH frames, a thread per XCCH channel;
+// k_l1msrx_finish: after the decoders -- the SACCH orders folded over the call's good SACCH frames (trx_sacch_fold,
+//   trxsig_tdma.h: the header SACCHL1Encoder::sendFrame wrote), a thread per XCCH channel;
 //   the SCH verdict (tail, parity, LSB8MSB undone, the fields, the frame number, sync), a thread per list entry; the TC of every
 //   BCCH block, a thread per block.
 #include <hip/hip_runtime.h>
@@ -127,21 +128,7 @@ __global__ __launch_bounds__(256) void k_l1msrx_finish(TrxL1msrxCall c, TrxL1msr
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < c.n_xcch) {                                         // the XCCH channels come first in the control grid
     const int m = d.chinfo[c.n_tch + i] >> 20;
-    const bool sacch = (m >= TRX_MAP_SACCH_TF && m < TRX_MAP_SDCCH8) || (m >= TRX_MAP_SACCH_C8 && m < TRX_MAP_SDCCH4) ||
-                       (m >= TRX_MAP_SACCH_C4 && m < TRX_DL_CCCH);
-    if (sacch) {
-      int pw = d.ord_power[i], ta = d.ord_ta[i];
-      for (int b = 0; b < c.nb_ctl; b++) {
-        const size_t k = (size_t)i * c.nb_ctl + b;
-        if ((d.ctl_status[k] & (TRXSIG_FEC_DECODED | TRXSIG_FEC_TCH_GOOD)) != (TRXSIG_FEC_DECODED | TRXSIG_FEC_TCH_GOOD)) continue;
-        const uint8_t *fr = d.ctl_frames + k * 23;
-        pw = c_power[c.band][fr[0] & 31];                     // the header's 5-bit level (SACCHL1Encoder::sendFrame's octet 0)
-        const int taf = fr[1] & 127;
-        if (taf < 64) ta = taf;
-      }
-      d.ord_power[i] = pw;
-      d.ord_ta[i] = ta;
-    }
+    if (trx_map_is_sacch(m)) trx_sacch_fold(d.ctl_status, d.ctl_frames, c.nb_ctl, i, c_power[c.band], d.ord_power, d.ord_ta);
   }
   if (i < c.sch_cap) {
     unsigned ok = 0, bsic = 0, sync = 0;

@@ -72,20 +72,17 @@ int set_active(trxsig_l1rx *l1, int cls, int chan, int open) {
 int trxsig_l1rx_create(trxsig_l1rx **out, trxsig_ctx *c, int n_arfcn, const uint8_t *h_comb, int bsic, int band) {
   if (!out || !c) return TRXSIG_EINVAL;
   *out = nullptr;
-  const int bidx = trx_plan_band_index(band);
-  if (n_arfcn <= 0 || n_arfcn > 0xffff || !h_comb || bsic < 0 || bsic > 63 || bidx < 0 || !trx_plan_selfcheck())
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1rx_create: bad argument", hipSuccess);
-  if (!trx_plan_validate(h_comb, n_arfcn))
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1rx_create: unsupported channel combination or placement", hipSuccess);
+  int bidx = -1;
+  const std::string err = trx_plan_create_error("trxsig_l1rx_create", n_arfcn, h_comb, bsic, band, true, &bidx);
+  if (!err.empty()) return trx_ctx_fail(c, TRXSIG_EINVAL, err.c_str(), hipSuccess);
   trxsig_l1rx *l1 = new (std::nothrow) trxsig_l1rx;
   if (!l1) return TRXSIG_ENOMEM;
   l1->c = c; l1->bsic = bsic; l1->band = bidx;
   l1->plan = TrxPlan(n_arfcn, h_comb, TRX_PLAN_UL, 3);
   const TrxPlan &pl = l1->plan;
   const size_t N = (size_t)pl.all(), T = (size_t)pl.n[TRX_PLAN_TCH], X = (size_t)pl.n[TRX_PLAN_XCCH];
-  std::vector<int32_t> power(X, -1), ta(X, -1);
-  for (size_t i = 0; i < X; i++)
-    if (pl.sacch((int)(T + i))) { power[i] = 40; ta[i] = 0; }
+  std::vector<int32_t> power, ta;
+  trx_plan_sacch_start(pl, power, ta);
   const std::vector<uint8_t> ones(N, 1);
   const TrxCarve cv = { T * TRXSIG_TCH_RX_STATE_BYTES, X * TRXSIG_XCCH_RX_STATE_BYTES, N, N * 4, N * 4, N * 4, X * 4, X * 4, N * 4 };
   TrxDeviceGuard g(trxsig_device(c));
@@ -129,9 +126,7 @@ int trxsig_l1rx_state(trxsig_l1rx *l1, int cls, void **d_state) {
 
 int trxsig_l1rx_decode(trxsig_l1rx *l1, const trxsig_trxgroup_result *res, int fn, int wire, trxsig_l1rx_out *out) {
   if (!l1) return TRXSIG_EINVAL;
-  if (!res || !out || fn < 0 || fn >= kTrxHyperframe || res->n_arfcn != l1->plan.A || res->n_slots <= 0 || (res->n_slots & 7) ||
-      res->n_rows < 0 || !res->d_row ||
-      (res->n_rows > 0 && (!res->d_valid || !res->d_soft || !res->d_amp || !res->d_toa || res->soft_stride < 148)))
+  if (!out || fn < 0 || fn >= kTrxHyperframe || !trx_plan_result_ok(res, l1->plan.A))
     return fail(l1, "trxsig_l1rx_decode: bad argument (whole frames from TN 0 of the object's ARFCNs)");
   trxsig_ctx *c = l1->c;
   TrxL1rxCall k{};

@@ -7,8 +7,9 @@
 //   same bursts.  The same pass keeps the last accepted burst's RSSI / timing (processBurst's mRSSI / mTimingError), writes the
 //   TCH phase b0 and every block's closing FN, and, on the RACH channel, lists the detected access bursts in FN order and
 //   gathers their soft rows for the RACH decoder.
-// k_l1rx_finish: after the decoders -- SACCHL1Decoder::handleGoodFrame's power / TA fold, a thread per XCCH channel, and the RACH
-//   verdict ok = tail_ok && BSIC == the cell's (RACHL1Decoder::writeLowSide), a thread per list entry.
+// k_l1rx_finish: after the decoders -- SACCHL1Decoder::handleGoodFrame's power / TA fold (trx_sacch_fold, trxsig_tdma.h), a thread
+//   per XCCH channel, and the RACH verdict ok = tail_ok && BSIC == the cell's (RACHL1Decoder::writeLowSide), a thread per list
+//   entry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "trxsig_l1_phy.h"
@@ -94,21 +95,7 @@ __global__ __launch_bounds__(256) void k_l1rx_finish(TrxL1rxCall c, TrxL1rxDev d
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < c.n_xcch) {
     const int m = d.chinfo[c.n_tch + i] >> 20;
-    const bool sacch = (m >= TRX_MAP_SACCH_TF && m < TRX_MAP_SDCCH8) || (m >= TRX_MAP_SACCH_C8 && m < TRX_MAP_SDCCH4) ||
-                       (m >= TRX_MAP_SACCH_C4 && m < TRX_MAP_RACH_C5);
-    if (sacch) {
-      int pw = d.ms_power[i], ta = d.ms_ta[i];
-      for (int b = 0; b < c.nb_xcch; b++) {
-        const size_t k = (size_t)i * c.nb_xcch + b;
-        if ((d.xcch_status[k] & (TRXSIG_FEC_DECODED | TRXSIG_FEC_TCH_GOOD)) != (TRXSIG_FEC_DECODED | TRXSIG_FEC_TCH_GOOD)) continue;
-        const uint8_t *fr = d.xcch_frames + k * 23;
-        pw = c_power[c.band][fr[0] & 31];                     // mU.peekField(3,5): the frame's bits 3..7 (mD aliases mU)
-        const int taf = fr[1] & 127;                          // mU.peekField(9,7)
-        if (taf < 64) ta = taf;
-      }
-      d.ms_power[i] = pw;
-      d.ms_ta[i] = ta;
-    }
+    if (trx_map_is_sacch(m)) trx_sacch_fold(d.xcch_status, d.xcch_frames, c.nb_xcch, i, c_power[c.band], d.ms_power, d.ms_ta);
   }
   if (i < c.rach_cap) {
     const bool ok = i < *d.rach_count && d.rach_tail[i] != 0 && d.rach_bsic[i] == d.bsic;

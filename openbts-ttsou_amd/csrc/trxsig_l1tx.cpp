@@ -8,8 +8,7 @@
 
 #include "trxsig_ctx.h"
 #include "trxsig_l1tx.h"
-#include "trxsig_l1ms_dev.h"
-#include "trxsig_plan.h"
+#include "trxsig_l1mux_host.h"
 
 namespace {
 constexpr long long kMaxOutBytes = 1LL << 34;
@@ -48,69 +47,39 @@ int set_active(trxsig_l1tx *l1, int cls, int chan, int open) {
 
 // block geometry of a call
 void geometry(const trxsig_l1tx *l1, int fn, int F, TrxL1txCall &k) {
-  std::memset(&k, 0, sizeof k);
-  const TrxPlan &pl = l1->plan;
-  k.fn = fn; k.n_frames = F; k.n_arfcn = pl.A;
-  k.n_tch = pl.n[0]; k.n_xcch = pl.n[1]; k.n_ccch = pl.n[2]; k.n_bcch = pl.n[3]; k.n_all = pl.all();
-  k.r104 = fn % 104; k.r102 = fn % 102; k.r51 = fn % 51; k.r26 = fn % 26;
+  k = TrxL1txCall{};
+  trx_plan_tx_geometry(l1->plan, 4, fn, F, &k);
+  k.n_ccch = l1->plan.n[2]; k.n_bcch = l1->plan.n[3];
   k.cur = l1->cur; k.band = l1->band; k.bsic = l1->bsic; k.rssi_target = l1->target;
-  for (int m = 0; m < TRX_N_DL_MAPS; m++) {
-    const TrxBlockGeom bg = trx_plan_block_geometry(trx_plan_maps(TRX_PLAN_DL)[m], fn, F);
-    k.p_first[m] = bg.p_first; k.p_end[m] = bg.p_end; k.base[m] = bg.base;
-    for (int cl = 0; cl < 4; cl++)
-      if (pl.map_used[cl][m] && bg.nb_started > k.nb[cl]) k.nb[cl] = bg.nb_started;
-  }
-  long long u = 0;
-  for (int cl = 0; cl < 4; cl++) { k.unit0[cl] = u; u += (long long)pl.n[cl] * k.nb[cl]; }
 }
 }  // namespace
 
 int trxsig_l1tx_create(trxsig_l1tx **out, trxsig_ctx *c, int n_arfcn, const uint8_t *h_comb, int bsic, int band, float target) {
   if (!out || !c) return TRXSIG_EINVAL;
   *out = nullptr;
-  const int bidx = trx_plan_band_index(band);
-  if (n_arfcn <= 0 || n_arfcn > 0xffff || !h_comb || bsic < 0 || bsic > 63 || bidx < 0 || !trx_plan_selfcheck() || !(target == target))
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1tx_create: bad argument", hipSuccess);
-  if (!trx_plan_validate(h_comb, n_arfcn))
-    return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1tx_create: unsupported channel combination or placement", hipSuccess);
+  int bidx = -1;
+  const std::string err = trx_plan_create_error("trxsig_l1tx_create", n_arfcn, h_comb, bsic, band, target == target, &bidx);
+  if (!err.empty()) return trx_ctx_fail(c, TRXSIG_EINVAL, err.c_str(), hipSuccess);
   trxsig_l1tx *l1 = new (std::nothrow) trxsig_l1tx;
   if (!l1) return TRXSIG_ENOMEM;
   l1->c = c; l1->bsic = bsic; l1->band = bidx; l1->target = target;
   l1->plan = TrxPlan(n_arfcn, h_comb, TRX_PLAN_DL, 4);
   const TrxPlan &pl = l1->plan;
-  std::vector<int8_t> writer;           // the slot owners, by mapping id
-  const bool disjoint = trx_plan_owner_table(TRX_PLAN_DL, true, false, writer);
-  const std::vector<int16_t> cnt = trx_plan_count_table(TRX_PLAN_DL);
-  const size_t N = (size_t)pl.all(), S = 8 * (size_t)n_arfcn;
+  const size_t N = (size_t)pl.all();
   std::vector<TrxL1txChan> rec(2 * N);
   std::memset(rec.data(), 0, rec.size() * sizeof(TrxL1txChan));
   for (size_t i = 0; i < 2 * N; i++) {
     const int g = (int)(i % N);
     const bool sacch = g >= pl.first[TRX_PLAN_XCCH] && g < pl.first[TRX_PLAN_CCCH] && pl.sacch(g);
-    rec[i].active = 1;
+    rec[i].h.active = 1;
     rec[i].ord_pow = sacch ? 40 : -1;
     rec[i].ord_ta = sacch ? 0.0F : -1.0F;
   }
-  const TrxCarve cv = { 2 * N * sizeof(TrxL1txChan), N * 4, S * 4, S * 4, writer.size(), cnt.size() * 2, 96 };
   TrxDeviceGuard gd(trxsig_device(c));
-  if (!disjoint) { delete l1; return trx_ctx_fail(c, TRXSIG_EINVAL, "trxsig_l1tx_create: device allocation", hipSuccess); }
-  const int rc = trx_device_block(c, "trxsig_l1tx_create", cv.total,
-                                  { { cv.off[0], rec.data(), 2 * N * sizeof(TrxL1txChan) }, { cv.off[1], pl.chinfo.data(), N * 4 },
-                                    { cv.off[2], pl.slot.data(), S * 4 }, { cv.off[3], pl.slot_x.data(), S * 4 },
-                                    { cv.off[4], writer.data(), writer.size() }, { cv.off[5], cnt.data(), cnt.size() * 2 } }, &l1->d_persist);
+  void *si = nullptr;                   // [4][23] + [92], zero: no SIs yet
+  const int rc = trx_mux_device_block(c, "trxsig_l1tx_create", pl, rec, 96, nullptr, l1->dv, &l1->d_persist, &si);
   if (rc != TRXSIG_OK) { delete l1; return rc; }
-  void *b = l1->d_persist;
-  TrxL1txDev &d = l1->dv;
-  l1->d_st = cv.at<TrxL1txChan>(b, 0);
-  d.st = l1->d_st; d.chinfo = cv.at<int32_t>(b, 1); d.slot = cv.at<int32_t>(b, 2); d.slot_x = cv.at<int32_t>(b, 3);
-  d.writer = cv.at<int8_t>(b, 4); d.cnt = cv.at<int16_t>(b, 5);
-  l1->d_si = cv.at<uint8_t>(b, 6); d.si = l1->d_si;
-  d.filler = trx_ctx_tch_filler(c);
-  if (!d.filler) {
-    (void)hipFree(l1->d_persist);
-    delete l1;
-    return trx_ctx_fail(c, TRXSIG_EHIP, "trxsig_l1tx_create: upload", hipSuccess);
-  }
+  l1->d_st = l1->dv.st; l1->d_si = (uint8_t *)si; l1->dv.si = l1->d_si;
   trx_ctx_retain(c);
   *out = l1;
   return TRXSIG_OK;
@@ -175,7 +144,7 @@ int trxsig_l1tx_encode(trxsig_l1tx *l1, int fn, int F, const trxsig_l1tx_in *in,
   TrxL1rxSib sb{};
   if (sib) {
     trx_l1rx_sibling(sib, &sb);
-    if (sb.n_arfcn != pl.A || std::memcmp(sb.comb, pl.comb.data(), pl.comb.size()) != 0 || sb.n_xcch != pl.n[1])
+    if (!trx_plan_same(pl, sb.n_arfcn, sb.n_xcch, sb.comb))
       return fail(l1, "trxsig_l1tx_encode: the sibling's plan is not this object's");
   }
   TrxL1txCall k;

@@ -3,6 +3,7 @@
 #define TRX_TDMA_TABLES_ONLY
 #include "trxsig_plan.h"
 
+#include <cstring>
 #include <utility>
 
 namespace {
@@ -70,9 +71,29 @@ void trx_plan_map_kind(int m, int dir, int *kind, int *sub) {
   if (k != TRXSIG_L1_SACCH_TF) *sub = m - first[k];
 }
 
-bool trx_plan_map_sacch(int m) {
-  return (m >= TRX_MAP_SACCH_TF && m < TRX_MAP_SDCCH8) || (m >= TRX_MAP_SACCH_C8 && m < TRX_MAP_SDCCH4) ||
-         (m >= TRX_MAP_SACCH_C4 && m < TRX_MAP_RACH_C5);
+std::string trx_plan_create_error(const char *who, int n_arfcn, const uint8_t *h_comb, int bsic, int band, bool more_ok, int *band_index) {
+  *band_index = trx_plan_band_index(band);
+  if (n_arfcn <= 0 || n_arfcn > 0xffff || !h_comb || bsic < 0 || bsic > 63 || *band_index < 0 || !more_ok || !trx_plan_selfcheck())
+    return std::string(who) + ": bad argument";
+  if (!trx_plan_validate(h_comb, n_arfcn)) return std::string(who) + ": unsupported channel combination or placement";
+  return std::string();
+}
+
+bool trx_plan_result_ok(const trxsig_trxgroup_result *res, int n_arfcn) {
+  return res && res->n_arfcn == n_arfcn && res->n_slots > 0 && !(res->n_slots & 7) && res->n_rows >= 0 && res->d_row &&
+         (res->n_rows == 0 || (res->d_valid && res->d_soft && res->d_amp && res->d_toa && res->soft_stride >= 148));
+}
+
+bool trx_plan_same(const TrxPlan &pl, int n_arfcn, int n_xcch, const uint8_t *comb) {
+  return n_arfcn == pl.A && n_xcch == pl.n[TRX_PLAN_XCCH] && std::memcmp(comb, pl.comb.data(), pl.comb.size()) == 0;
+}
+
+void trx_plan_sacch_start(const TrxPlan &pl, std::vector<int32_t> &power, std::vector<int32_t> &ta) {
+  const size_t X = (size_t)pl.n[TRX_PLAN_XCCH];
+  power.assign(X, -1);
+  ta.assign(X, -1);
+  for (size_t i = 0; i < X; i++)
+    if (pl.sacch(pl.first[TRX_PLAN_XCCH] + (int)i)) { power[i] = 40; ta[i] = 0; }
 }
 
 TrxPlan::TrxPlan(int n_arfcn, const uint8_t *h_comb, int dir_, int n_cls_) : A(n_arfcn), dir(dir_), n_cls(n_cls_) {
@@ -173,4 +194,19 @@ TrxBlockGeom trx_plan_block_geometry(const TrxTdmaMap &M, int fn, int F) {
   g.nb_touched = g.p_end > g.p_first ? (int)(trx_fdiv(g.p_end - 1, 4) - trx_fdiv(g.p_first, 4) + 1) : 0;
   g.nb_started = (int)(ceil4(g.p_end) - ceil4(g.p_first));
   return g;
+}
+
+void trx_plan_tx_geometry(const TrxPlan &pl, int n_cls, int fn, int F, TrxMuxCall *k) {
+  *k = TrxMuxCall{};
+  k->fn = fn; k->n_frames = F; k->n_arfcn = pl.A;
+  k->n_tch = pl.n[TRX_PLAN_TCH]; k->n_xcch = pl.n[TRX_PLAN_XCCH]; k->n_all = pl.first[n_cls];
+  k->r104 = fn % 104; k->r102 = fn % 102; k->r51 = fn % 51; k->r26 = fn % 26;
+  for (int m = 0; m < trx_plan_n_maps(pl.dir); m++) {
+    const TrxBlockGeom bg = trx_plan_block_geometry(trx_plan_maps(pl.dir)[m], fn, F);
+    k->p_first[m] = bg.p_first; k->p_end[m] = bg.p_end; k->base[m] = bg.base;
+    for (int cl = 0; cl < n_cls; cl++)
+      if (pl.map_used[cl][m] && bg.nb_started > k->nb[cl]) k->nb[cl] = bg.nb_started;
+  }
+  long long u = 0;
+  for (int cl = 0; cl < n_cls; cl++) { k->unit0[cl] = u; u += (long long)pl.n[cl] * k->nb[cl]; }
 }

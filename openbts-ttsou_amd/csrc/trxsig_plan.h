@@ -11,6 +11,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "trxsig_l1msrx.h"
@@ -31,9 +32,14 @@ bool trx_plan_selfcheck();
 bool trx_plan_slot_ok(int comb, int a, int tn);
 bool trx_plan_validate(const uint8_t *h_comb, int n_arfcn);
 int trx_plan_band_index(int band);                             // 850 / 900 -> 0, 1800 -> 1, 1900 -> 2, else -1
+// the create arguments of a plan-based object (trxsig_l1rx, _l1tx, _l1ms, _l1msrx): empty and the band's index, or the refusal
+// as `who` reports it.  more_ok: the caller's own conditions, refused as a bad argument
+std::string trx_plan_create_error(const char *who, int n_arfcn, const uint8_t *h_comb, int bsic, int band, bool more_ok, int *band_index);
+// whether res holds whole frames from TN 0 of n_arfcn ARFCNs, with every array its rows need (the two receivers' decode)
+bool trx_plan_result_ok(const trxsig_trxgroup_result *res, int n_arfcn);
 // TRXSIG_L1_* kind and sub-channel of mapping id m of a direction's table
 void trx_plan_map_kind(int m, int dir, int *kind, int *sub);
-bool trx_plan_map_sacch(int m);
+inline bool trx_plan_map_sacch(int m) { return trx_map_is_sacch(m); }
 
 struct TrxPlan {
   int A = 0, dir = 0, n_cls = 0;
@@ -57,6 +63,11 @@ struct TrxPlan {
   int describe(int index, int *arfcn, int *tn, int *kind, int *sub) const;
 };
 
+// whether a sibling's plan -- its ARFCNs, XCCH channels and combinations comb[8 n_arfcn] -- is pl's
+bool trx_plan_same(const TrxPlan &pl, int n_arfcn, int n_xcch, const uint8_t *comb);
+// the SACCH power / TA the receivers start from, per XCCH channel: 40 dBm / 0 on SACCH channels, -1 on the others
+void trx_plan_sacch_start(const TrxPlan &pl, std::vector<int32_t> &power, std::vector<int32_t> &ta);
+
 // the slot owners of a direction, appended to out: [combination I / V / VII][TN][fn mod 104 (I) or 102 (V, VII)] -> -1 or the
 // owning mapping's value.  common: combination V's common channels take part.  code: the value is 0 for the TCH and 1 + the XCCH
 // channel's place among the slot's, else the mapping id.  Returns whether no frame had two owners.
@@ -70,6 +81,10 @@ std::vector<int16_t> trx_plan_count_table(int dir);
 // encoded when its first burst goes out).  Two numbers on purpose.
 struct TrxBlockGeom { long long p_first, p_end, base; int nb_touched, nb_started; };
 TrxBlockGeom trx_plan_block_geometry(const TrxTdmaMap &M, int fn, int F);
+// a transmit multiplexer's call over frames [fn, fn + F): k zeroed, then the plan's counts (the first n_cls classes have records:
+// n_all), fn's remainders, p_first / p_end / base of every mapping of the plan's direction, nb[] = the most blocks a class's
+// channels start in the call and unit0[] = the classes' scratch units one after the other
+void trx_plan_tx_geometry(const TrxPlan &pl, int n_cls, int fn, int F, TrxMuxCall *k);
 
 // Cell layouts.  trxsig_air_cells, trxsig_l1ms_radiate, trxsig_l1trk_slice and trxsig_l1hop_cells address T slots of A columns,
 // cells of `cell` samples, by two strides.  Cells must not overlap in either nesting: the smaller stride holds a cell and the

@@ -8,6 +8,7 @@
 // construction below follows the reference's evaluation order operation by operation.  Build
 // with -ffp-contract=off.
 #include "trxsig_tablegen.h"
+#include "trxsig_bursts.h"
 
 #include <cmath>
 #include <cstring>
@@ -113,10 +114,7 @@ cx peakDetect(const Trig &tr, const cvec &x, float *peakIndex) {                
   return interpolate(tr, x, maxIndex);
 }
 
-const char *kTSC[8] = {                                                  // GSM/GSMCommon.cpp:44-53
-  "00100101110000100010010111", "00101101110111100010110111", "01000011101110100100001110",
-  "01000111101101000100011110", "00011010111001000001101011", "01001110101100000100111010",
-  "10100111110110001010011111", "11101111000100101110111100" };
+const char *kTSC[8] = TRX_TSC_BITS;                                      // trxsig_bursts.h
 const char *kRACH = "01001011011111111001100110101010001111000";       // GSM/GSMCommon.cpp:57
 const char *kXTS = "1011100101100010000001000000111100101101010001010111011000011011";   // SCH extended training sequence, GSM 05.02 5.2.5
 

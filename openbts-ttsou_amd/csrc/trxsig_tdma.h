@@ -1,7 +1,9 @@
-// trxsig_tdma.h -- internal: the uplink TDMA mappings of GSM 05.02 that the uplink L1 demultiplexer (trxsig_l1rx.cpp / .hip)
-// routes by: the numbers of GSM/GSMTDMA.cpp's uplink TDMAMapping tables (repeat length, frame list in reverse-mapping order).
-// tests/golden/tdma_uplink.npz records the same tables for the CPU model (tests/l1_demux_model.py); tests/test_gpu_l1rx.py
-// checks this routing against the model.
+// trxsig_tdma.h -- internal: the TDMA mappings of GSM 05.02 in both directions -- the numbers of GSM/GSMTDMA.cpp's TDMAMapping
+// tables (repeat length, frame list in reverse-mapping order) -- with the position arithmetic over them, the SACCH rule and the
+// power-level tables, and the by-value structs of the stages that walk them: the uplink demultiplexer (trxsig_l1rx) and the two
+// transmit multiplexers (trxsig_l1tx here, trxsig_l1ms in trxsig_l1ms_dev.h), whose common part is TrxMuxCall / TrxMuxChan /
+// TrxMuxDev below and the device code of trxsig_l1mux_dev.h.  tests/golden/tdma_uplink.npz and tdma_downlink.npz record the
+// same tables for the CPU models (tests/l1_demux_model.py, tests/l1_mux_model.py).
 //
 // Positions.  A mapping with n frames per repeat R numbers its bursts in time order: the burst of frame u (an unwrapped frame
 // count) sits at position p(u) = n * floor((u - f[0]) / R) + r, where f[r] == u mod R.  Because f[r] - f[0] (mod R) grows with r
@@ -9,6 +11,7 @@
 // n = 24, p mod 8 the TCH decoder's.  R divides 5304 and 5304 divides the hyperframe, so the numbering is the same modulo the
 // hyperframe wrap up to a multiple of n * 5304 / R positions (a whole number of blocks).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 // TRX_TDMA_TABLES_ONLY (trxsig_plan.cpp, which a plain host compiler builds too): the tables, the position arithmetic and the
@@ -77,6 +80,23 @@ __host__ __device__ inline long long trx_map_count(const TrxTdmaMap &m, long lon
     { 30, 28, 26, 24, 22, 20, 18, 16, 14, 12, 10, 8, 6, 4, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }         \
   }
 
+// whether mapping m is a SACCH: ids below 33 name the same logical channel in both directions' tables
+__host__ __device__ inline bool trx_map_is_sacch(int m) {
+  return (m >= TRX_MAP_SACCH_TF && m < TRX_MAP_SDCCH8) || (m >= TRX_MAP_SACCH_C8 && m < TRX_MAP_SDCCH4) ||
+         (m >= TRX_MAP_SACCH_C4 && m < TRX_MAP_RACH_C5);
+}
+
+// encodePower over a band's row of the tables above: nearest code, first on ties, an exact match at once
+__host__ __device__ inline int trx_encode_power(const int8_t *row, int power) {
+  unsigned minErr = (unsigned)(power < row[0] ? row[0] - power : power - row[0]), code = 0;
+  for (int i = 1; i < 32; i++) {
+    const unsigned e = (unsigned)(power < row[i] ? row[i] - power : power - row[i]);
+    if (e == 0) return i;
+    if (e < minErr) { minErr = e; code = (unsigned)i; }
+  }
+  return (int)code;
+}
+
 // what the demux kernel and the fold need of one call (by value)
 struct TrxL1rxCall {
   int fn, n_frames, n_arfcn, n_rows, soft_stride, sps;
@@ -103,6 +123,24 @@ struct TrxL1rxDev {
 };
 
 #ifndef TRX_TDMA_TABLES_ONLY
+// The receive sides' finish (k_l1rx_finish, k_l1msrx_finish), a thread per SACCH channel: channel i's power / TA folded over the
+// call's good SACCH frames (SACCHL1Decoder::handleGoodFrame): octet 0's bits 3..7 are the level (mU.peekField(3,5)), octet 1's
+// low seven the TA, kept where below 64 (mU.peekField(9,7)).  levels: the band's row of the tables above
+__device__ inline void trx_sacch_fold(const uint8_t *status, const uint8_t *frames, int nb, int i, const int8_t *levels,
+                                      int32_t *power, int32_t *ta) {
+  int pw = power[i], t = ta[i];
+  for (int b = 0; b < nb; b++) {
+    const size_t k = (size_t)i * nb + b;
+    if ((status[k] & (TRXSIG_FEC_DECODED | TRXSIG_FEC_TCH_GOOD)) != (TRXSIG_FEC_DECODED | TRXSIG_FEC_TCH_GOOD)) continue;
+    const uint8_t *fr = frames + k * 23;
+    pw = levels[fr[0] & 31];
+    const int taf = fr[1] & 127;
+    if (taf < 64) t = taf;
+  }
+  power[i] = pw;
+  ta[i] = t;
+}
+
 hipError_t trx_launch_l1rx_demux(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, const int32_t *row,
                                  const uint8_t *valid, const float *soft, const trx_c32 *amp, const float *toa, TrxProfiler *prof);
 hipError_t trx_launch_l1rx_finish(hipStream_t st, const TrxL1rxCall &call, const TrxL1rxDev &dv, TrxProfiler *prof);
@@ -144,50 +182,72 @@ enum {
     TRX_M5(51, 1, 11, 21, 31, 41), TRX_M5(51, 0, 10, 20, 30, 40)                                                           \
   }
 
-// what one encode needs of its call (by value).  Per mapping m: p_first = the first position at or after fn, p_end = the
+// ---- the transmit multiplexers: what trxsig_l1tx and trxsig_l1ms (trxsig_l1ms_dev.h) have in common ----------------------
+// What one encode needs of its call (by value).  Per mapping m: p_first = the first position at or after fn, p_end = the
 // first position at or after fn + n_frames, base = p_first minus the mapping's positions in frames [fn - fn % R, fn) -- so
 // the frame fn + k, k = q * R + rem - fn % R, is position base + n * q + cnt[m][rem] (cnt: the host's table of frames below
-// rem), no division by a variable.
-struct TrxL1txCall {
-  int fn, n_frames, n_arfcn, n_tch, n_xcch, n_ccch, n_bcch, n_all;
+// rem), no division by a variable.  trx_plan_tx_geometry (trxsig_plan.h) fills everything but cur, has_sib, band and bsic.
+// The per-class and per-mapping arrays have the downlink's lengths in both directions (the uplink uses 2 classes, 34 mappings).
+struct TrxMuxCall {
+  int fn, n_frames, n_arfcn, n_tch, n_xcch, n_all;   // n_all: the channels that have records
   int nb[4];                         // per class (TCH, XCCH, CCCH, BCCH): the most blocks any channel opens
   long long unit0[4];                // per class: the first scratch unit ([n_chan][nb] after it)
   int r104, r102, r51, r26;          // fn mod 104 / 102 / 51 / 26
   int cur, has_sib, band, bsic;
-  float rssi_target;
   long long p_first[TRX_N_DL_MAPS], p_end[TRX_N_DL_MAPS], base[TRX_N_DL_MAPS];
 };
 
-// a channel's record in the object (two copies: the call reads copy `cur`, the mux writes copy `cur ^ 1`)
-struct TrxL1txChan {
+// the head of a channel's record in the object (two copies: the call reads copy `cur`, the commit writes copy `cur ^ 1`)
+struct TrxMuxChan {
   uint32_t last_c[16];               // c[456] of the last block the channel encoded, bit i = word i/32 bit i%32
   uint32_t prev_c[16];               // ... and of the one before it (TCH: the odd half interleaves into the next block)
   uint8_t last_f, prev_f;            // their FACCH flags
   uint8_t pend;                      // the last block's last burst lies after the last call: its tail goes out next
   uint8_t active;
+};
+static_assert(sizeof(TrxMuxChan) == 132, "TrxMuxChan layout");
+
+// the device side of one object (pointers into its allocations); Chan is the direction's record, TrxMuxChan h first
+template <class Chan>
+struct TrxMuxDev {
+  const int32_t *chinfo;             // [n_all]: arfcn | tn << 16 | map << 20
+  const int32_t *slot;               // [n_arfcn * 8]: combination | the slot's TCH channel << 4
+  const int32_t *slot_x;             // [n_arfcn * 8]: the slot's first XCCH channel (index over all classes)
+  const int8_t *writer;              // [3][8][104]: the mapping that owns (combination I / V / VII, TN, fn mod 104 or 102)
+  const int16_t *cnt;                // [the direction's mappings][105]
+  Chan *st;                          // [2][n_all]
+  uint32_t *c;                       // scratch [units][16]
+  uint8_t *flag;                     // scratch [units]: 1 encoded, 2 FACCH
+  const uint8_t *kind[3], *payload[3];   // TCH / XCCH / CCCH grids
+  const uint8_t *filler;             // the context's TCH filler c[456]
+  uint8_t *bits, *what;              // [n_arfcn][8 F][148], [n_arfcn][8 F]
+};
+
+// ---- the downlink multiplexer (trxsig_l1tx) ---------------------------------------------------------------------------------
+struct TrxL1txCall : TrxMuxCall {
+  int n_ccch, n_bcch;
+  float rssi_target;
+};
+
+struct TrxL1txChan {
+  TrxMuxChan h;
   int32_t idle_left;                 // dummy bursts still to send (close)
   int32_t ord_pow;                   // SACCH orders (dBm), -1 on channels that are not SACCH
   float ord_ta;
   uint32_t seen;                     // the sibling's accepted-burst count when the orders were last decided
   uint32_t pad[3];
 };
+// trxsig_l1tx_state hands these bytes to callers
 static_assert(sizeof(TrxL1txChan) == 160, "TrxL1txChan layout");
+static_assert(offsetof(TrxL1txChan, h.last_c) == 0 && offsetof(TrxL1txChan, h.prev_c) == 64 && offsetof(TrxL1txChan, h.last_f) == 128 &&
+              offsetof(TrxL1txChan, h.prev_f) == 129 && offsetof(TrxL1txChan, h.pend) == 130 && offsetof(TrxL1txChan, h.active) == 131 &&
+              offsetof(TrxL1txChan, idle_left) == 132 && offsetof(TrxL1txChan, ord_pow) == 136 && offsetof(TrxL1txChan, ord_ta) == 140 &&
+              offsetof(TrxL1txChan, seen) == 144 && offsetof(TrxL1txChan, pad) == 148, "TrxL1txChan layout");
 
-struct TrxL1txDev {
-  const int32_t *chinfo;             // [n_all]: arfcn | tn << 16 | map << 20
-  const int32_t *slot;               // [n_arfcn * 8]: combination | the slot's TCH channel << 4
-  const int32_t *slot_x;             // [n_arfcn * 8]: the slot's first XCCH channel (index over all classes)
-  const int8_t *writer;              // [3][8][104]: the mapping that owns (combination I / V / VII, TN, fn mod 104 or 102)
-  const int16_t *cnt;                // [TRX_N_DL_MAPS][105]
-  TrxL1txChan *st;                   // [2][n_all]
-  uint32_t *c;                       // scratch [units][16]
-  uint8_t *flag;                     // scratch [units]: 1 encoded, 2 FACCH
-  const uint8_t *kind[3], *payload[3];   // TCH / XCCH / CCCH grids
+struct TrxL1txDev : TrxMuxDev<TrxL1txChan> {
   const uint8_t *si;                 // [4][23] + [92] = 1 once set
-  const uint8_t *filler;             // the context's TCH filler c[456]
   int32_t *ord_pow;                  // [n_xcch] out
   float *ord_ta;                     // [n_xcch] out
-  uint8_t *bits, *what;              // [n_arfcn][8 F][148], [n_arfcn][8 F]
   // sibling (trxsig_l1rx) device state, or null
   const int32_t *sib_rssi, *sib_timing, *sib_power, *sib_ta;   // XCCH-indexed
   const uint32_t *sib_count;         // XCCH-indexed accepted-burst counters
@@ -211,6 +271,15 @@ struct TrxL1txLast {
   const uint8_t *what, *bits;        // [n_arfcn][8 n_frames], [n_arfcn][8 n_frames][148] (device)
 };
 void trx_l1tx_last(const trxsig_l1tx *l1, TrxL1txLast *out);
+
+// what trxsig_l1ms reads of a sibling trxsig_l1tx (trxsig_l1tx.cpp): its plan and its XCCH channels' current records
+struct TrxL1txSib {
+  trxsig_ctx *ctx;
+  int n_arfcn, n_xcch;
+  const uint8_t *comb;               // [n_arfcn * 8] (host)
+  const TrxL1txChan *xcch;           // [n_xcch] device: the records the next call of the sibling reads
+};
+void trx_l1tx_sibling(const trxsig_l1tx *l1, TrxL1txSib *out);
 
 #ifndef TRX_TDMA_TABLES_ONLY
 hipError_t trx_launch_l1tx_encode(hipStream_t st, const TrxL1txCall &call, const TrxL1txDev &dv, TrxProfiler *prof);

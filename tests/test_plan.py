@@ -144,6 +144,21 @@ def test_block_geometry_against_the_mappings(ask, maps):
         assert [int(x) for x in ln.split()] == [p0, p1, base, touched, started], (d, NAMES[d][m], fn, F)
 
 
+def test_transmit_geometry_against_a_frame_by_frame_count(ask):
+    """trx_plan_tx_geometry, the one geometry function of the two transmit multiplexers, for both directions on the smallest plan
+    that uses every mapping (combinations I, V and VII on two ARFCNs): plan_check.cpp counts p_first, p_end, base, nb and unit0
+    frame by frame with trx_map_count / trx_map_frame and checks that frame fn + k lands on base + n * Q + cnt[rem]."""
+    cases = [(d, fn, F) for d in (UL, DL) for fn in (0, 25, 50, 101, 103, 5303, 2715648 - 1) for F in (1, 3, 4, 51, 104)]
+    got = ask(["txgeom %d %d %d 2 %s" % (d, fn, F, " ".join(map(str, PLAN2))) for d, fn, F in cases])
+    assert got == ["ok"] * len(cases), [(c, g) for c, g in zip(cases, got) if g != "ok"]
+
+
+def test_encode_power_on_the_host(ask):
+    """trx_encode_power (trxsig_tdma.h), the one copy the kernels and the host share: every band, power -5..45 dBm, against the
+    rule written out in plan_check.cpp -- nearest code, first on ties, an exact match at once."""
+    assert ask(["power"]) == ["ok"]
+
+
 def test_stated_once():
     """The placement rule, the channel word's packing and the cell-layout rule are each written in one file of csrc/, and the
     256-byte rounding is one function (trx_align256: no stage file keeps a copy under the old name)."""
@@ -153,6 +168,12 @@ def test_stated_once():
     assert where("tn << 16 | m << 20") == ["trxsig_plan.cpp"]
     assert where("bool strides_ok(") == ["trxsig_plan.h"]
     assert where("size_t trx_align256(") == ["trxsig_ctx.h"] and where("size_t al(") == []
+    # what the two transmit multiplexers share is written once: the SACCH rule and encodePower (host and device), the training
+    # sequences, the XCCH inverse interleaver, the position arithmetic, the last-two-blocks scan and the launch slicing
+    assert where("m >= TRX_MAP_SACCH_C8 && m < TRX_MAP_SDCCH4") == ["trxsig_tdma.h"] and where("minErr = e") == ["trxsig_tdma.h"]
+    assert where('"00100101110000100010010111"') == ["trxsig_bursts.h"]
+    for text in ("xinv[c & 3][", "c.r26 + k", "x &= x - 1) { L2 = L;", "kMaxWg = "):
+        assert where(text) == ["trxsig_l1mux_dev.h"], text
     host = lambda text: [f for f in where(text) if not f.endswith(".hip")]                  # the host's one copy of the tables
     assert host("TRX_TDMA_MAPS_INIT") == ["trxsig_plan.cpp", "trxsig_tdma.h"]
     assert host("TRX_TDMA_DL_MAPS_INIT") == ["trxsig_plan.cpp", "trxsig_tdma.h"]
