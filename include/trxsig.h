@@ -663,6 +663,72 @@ int trxsig_fec_tch_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft_s
 int trxsig_fec_viterbi_batch(trxsig_ctx *ctx, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
                              uint8_t *d_bits, int64_t out_stride);
 
+/* ---- GPRS packet data channel: the block coders CS-1..CS-4 (GSM 05.03 5.1) ------------------------------------------
+ * One radio block = four normal bursts, as XCCH: the same rate-1/2 K = 5 coder (BitVector::encode), the same 456-bit
+ * rectangular interleaver (GSM 05.03 4.1.4: c[k] in burst k mod 4 at e-bit j = 2 ((49 k) mod 57) + (k mod 8) / 4, e-bits at
+ * 3..59 and 88..144), the same SoftVector::decode and the same wire_quantise.  The reference has no packet channel.
+ * NOT CHECKED AGAINST THE STANDARD: the tables, the puncturing and the flag words below are written from memory of GSM 05.03;
+ * no copy of it was at hand.  What follows from them is pinned by tests/test_pdtch_model.py: the bit counts close (456 each
+ * way), the 6-bit and 12-bit tables are linear codes of minimum distance 3 and 5, the four flag words are at least 5 apart,
+ * and CS-1 is the XCCH coder bit for bit.  tests/pdtch_model.py is this statement in numpy.
+ *
+ * Payload.  Scheme cs = TRXSIG_CS1..TRXSIG_CS4 carries K = 184 / 271 / 315 / 431 information bits d(0..K-1) in 23 / 34 / 40 /
+ *   54 octets; a block is a row of TRXSIG_PDTCH_BLOCK_BYTES = 54 octets whatever its scheme.  d(k) is bit k mod 8 of octet
+ *   k / 8, counted from the least significant bit (what LSB8MSB makes of XCCH's 23 octets: a CS-1 block is an XCCH frame).  The
+ *   spare high bits of the last octet are ignored on encode and written 0 on decode; octets past the scheme's size are ignored
+ *   on encode and written 0 on decode.  usf = d(0) | d(1) << 1 | d(2) << 2.
+ * Block check, CS-2..4.  p(0..15) with g(D) = D^16 + D^12 + D^5 + 1: d(0) D^(K+15) + ... + d(K-1) D^16 + p(0) D^15 + ... +
+ *   p(15) leaves the all-ones remainder -- Parity(0x11021, 16, K) with the inverted parity word written most significant
+ *   bit first, as XCCH and SCH use theirs.  It is computed on d, before the pre-coding.
+ * USF pre-coding.  Row d(0) d(1) d(2) (a string: d(0) first) of
+ *     000  001  010  011  100  101  110  111
+ *   CS-2 / CS-3: 000000 001011 010110 011101 100101 101110 110011 111000
+ *   CS-4: 000000000000 000011011101 001101110110 001110101011 110100001011 110111010110 111001111101 111010100000
+ *   the first character being the first bit sent.
+ * Code word c[456].
+ *   CS-1: XCCH's, word for word: u = d(0..183), 40 inverted Fire parity bits, 0000; c = the coder's 456 bits.
+ *   CS-2: u' = precoded(6), d(3..270), p(0..15), 0000 (294 bits); the coder gives C(0..587); C(3 + 4j) is deleted for j = 3..146
+ *     except j = 9, 21, 33, ..., 141 (j = 9 mod 12): 132 deleted, 456 left, in order.
+ *   CS-3: u' = precoded(6), d(3..314), p(0..15), 0000 (338 bits); C(0..675); C(3 + 6j) and C(5 + 6j) are deleted for j = 2..111:
+ *     220 deleted, 456 left.
+ *   CS-4: c = precoded(12), d(3..430), p(0..15), uncoded.
+ * Bursts.  c[] through XCCH's interleaver; zero tails; training sequence d_tsc[k] at 61..86; the eight stealing flags carry
+ *   q(0..7) in the order XCCH's interleaver places its flags: q(2B) is bit 87 and q(2B + 1) bit 60 of burst B.
+ *     CS-1 11111111   CS-2 11001000   CS-3 00100001   CS-4 00010110
+ *   CS-1's four bursts equal trxsig_fec_xcch_encode_batch's byte for byte.
+ * Encode: d_blocks [n][54], d_cs [n], d_tsc [n] -> d_bits [n][4][148], one bit per byte.  A block whose d_cs is above 3 or
+ *   whose d_tsc is above 7 encodes as four all-zero bursts.
+ * Decode.  Burst t of block k is row d_index[k][t] of d_soft (148 values at d_soft + row * soft_stride); d_index == NULL means
+ *   rows 4k..4k+3.  A row outside [0, n_rows) means the burst is missing: all its values, flags included, are exactly 0.5.
+ *   Present values pass the UDP hop first when wire_quantise != 0.  Values the demodulator never produces behave as the
+ *   paragraph above says for XCCH; a sliced value (a flag, a CS-4 bit) is v > 0.5F, false for a NaN.
+ *   Scheme: cs_force in 0..3, or -1 to detect: hard flags q(i) = v > 0.5F, the Hamming distance to the four words, the
+ *     smallest, ties to the lower scheme.  d_cs = the scheme decoded with, d_cs_dist = the hard flags' distance to its word
+ *     (with cs_force that of the forced scheme).
+ *   CS-1: the XCCH decoder; ok = the Fire syndrome is zero; octets 0..22 equal trxsig_fec_xcch_decode_batch's frame.
+ *   CS-2 / CS-3: the 588 / 676 coder outputs with the deleted positions reading exactly 0.5F; SoftVector::decode gives u'
+ *     (294 / 338 bits).  Its first 6 bits go to the nearest row of the table (Hamming distance, ties to the first row), which
+ *     gives d(0..2); the rest of d is copied; ok = the block check on that d against the received p.  The tail bits are not
+ *     checked (XCCH does not check its own).
+ *   CS-4: v > 0.5F on all 456; the first 12 go to the nearest row; ok = the block check.
+ *   Outputs: d_blocks [n][54], d_cs [n], d_cs_dist [n], d_ok [n], d_usf [n]; any but d_blocks may be NULL.  One block's output
+ *   never depends on another block's input.
+ * Host side: a NULL context or required pointer, a negative size, n_blocks > TRXSIG_PDTCH_MAX_BLOCKS, soft_stride < 148,
+ *   cs_force outside -1..3 or a d_index not 4-byte aligned return TRXSIG_EINVAL before any launch; n_blocks == 0 is a no-op.
+ *   One launch each (k_fec_pdtch_encode, k_fec_pdtch_decode; DESIGN.md 5.4.x, GPRS packet data blocks), booked under TRXSIG_K_FEC.
+ * trxsig_pdch_map_host: frame fn of the 52-multiframe (fn mod 52) -> *block = 0..11 (B0..B11: frames 0-3, 4-7, 8-11, 13-16,
+ *   17-20, 21-24, 26-29, 30-33, 34-37, 39-42, 43-46, 47-50) and *burst = 0..3; frames 12 and 38 (PTCCH) and 25 and 51 (idle)
+ *   give -1 in both.  A negative fn or a NULL pointer returns TRXSIG_EINVAL. */
+enum { TRXSIG_CS1 = 0, TRXSIG_CS2 = 1, TRXSIG_CS3 = 2, TRXSIG_CS4 = 3 };
+#define TRXSIG_PDTCH_BLOCK_BYTES 54
+#define TRXSIG_PDTCH_MAX_BLOCKS 16777216    /* 2^24 blocks a call */
+int trxsig_fec_pdtch_encode_batch(trxsig_ctx *ctx, const uint8_t *d_blocks, const uint8_t *d_cs, const uint8_t *d_tsc,
+                                  int n_blocks, uint8_t *d_bits);
+int trxsig_fec_pdtch_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft_stride, int64_t n_rows, const int32_t *d_index,
+                                  int n_blocks, int wire_quantise, int cs_force, uint8_t *d_blocks, uint8_t *d_cs,
+                                  uint8_t *d_cs_dist, uint8_t *d_ok, uint8_t *d_usf);
+int trxsig_pdch_map_host(int32_t fn, int *block, int *burst);
+
 /* ---- uplink TCH/FACCH and XCCH decoders as multi-channel streams ---------------------------------------------------
  * The reference's per-channel decoders -- TCHFACCHL1Decoder::processBurst / deinterleave / decodeTCH up to the parity and
  * tail check (GSML1FEC.cpp:1030-1163) and XCCHL1Decoder::writeLowSide / processBurst / deinterleave / decode (:556-653) --

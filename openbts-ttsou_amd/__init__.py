@@ -23,6 +23,8 @@ TCH_FILLER, TCH_SPEECH, TCH_FACCH = 0, 1, 2      # block kinds of trxsig_fec_tch
 TCH_TX_STATE_BYTES = 32                          # TRXSIG_TCH_TX_STATE_BYTES
 FEC_DECODED, FEC_STOLEN, FEC_FACCH_OK, FEC_TCH_GOOD = 1, 2, 4, 8   # status bits of the stream decoders (TRXSIG_FEC_*)
 TCH_RX_STATE_BYTES, XCCH_RX_STATE_BYTES = 3664, 1840              # TRXSIG_TCH_RX_STATE_BYTES, TRXSIG_XCCH_RX_STATE_BYTES
+CS1, CS2, CS3, CS4 = 0, 1, 2, 3                  # TRXSIG_CS1..TRXSIG_CS4: the GPRS coding schemes of pdtch_encode / pdtch_decode
+PDTCH_BLOCK_BYTES = 54                           # TRXSIG_PDTCH_BLOCK_BYTES
 
 
 def build(verbose=False):
@@ -640,6 +642,22 @@ class TrxSig:
     def fec_viterbi(self, soft, n_soft, n_blocks, bits, in_stride=None, out_stride=None):
         self._chk(self.L.trxsig_fec_viterbi_batch(self.h, _ptr(soft), n_soft, in_stride or soft.shape[-1], n_blocks,
                                                   _ptr(bits), out_stride or bits.shape[-1]), "trxsig_fec_viterbi_batch")
+
+    def pdtch_encode(self, blocks, cs, tsc, bits):
+        """GPRS packet data blocks: blocks[n, PDTCH_BLOCK_BYTES], cs[n] (CS1..CS4), tsc[n] (uint8) -> bits[n, 4, 148] (all device)."""
+        self._chk(self.L.trxsig_fec_pdtch_encode_batch(self.h, _ptr(blocks), _ptr(cs), _ptr(tsc), cs.numel(), _ptr(bits)),
+                  "trxsig_fec_pdtch_encode_batch")
+
+    def pdtch_decode(self, soft, n_blocks, blocks, cs=None, cs_dist=None, ok=None, usf=None, index=None, wire=True, cs_force=-1,
+                     n_rows=None, soft_stride=None):
+        """The inverse: soft[n_rows, >= 148] float32 (a tensor, or a device address with n_rows / soft_stride given), index[n, 4]
+        int32 (None: rows 4k..4k+3; a row outside [0, n_rows) = a missing burst) -> blocks[n, PDTCH_BLOCK_BYTES] and, where
+        given, cs[n], cs_dist[n], ok[n], usf[n] (uint8).  cs_force: CS1..CS4, or -1 to read the scheme from the stealing flags."""
+        if n_rows is None:
+            n_rows = soft.shape[0]
+        self._chk(self.L.trxsig_fec_pdtch_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n_rows, _ptr(index),
+                                                       n_blocks, int(wire), cs_force, _ptr(blocks), _ptr(cs), _ptr(cs_dist),
+                                                       _ptr(ok), _ptr(usf)), "trxsig_fec_pdtch_decode_batch")
 
     def unpack_half(self, iq, n, out):
         self._chk(self.L.trxsig_unpack_half(self.h, _ptr(iq), n, _ptr(out)), "trxsig_unpack_half")
@@ -1446,6 +1464,16 @@ class L1Ciph(_PlanView):
         self.ctx.synchronize()
         return {name: _to_host(self.ctx, self.state(cls), (self.channels(cls), 4), "<i4").view(self.np.uint32)
                 for name, cls in (("tch", L1_TCH), ("xcch", L1_XCCH))}
+
+
+def pdch_map(fn):
+    """trxsig_pdch_map_host: frame fn of the packet channel's 52-multiframe -> (block 0..11, burst 0..3), or (-1, -1) on the
+    PTCCH (12, 38) and idle (25, 51) frames.  No device, no context."""
+    block, burst = C.c_int(), C.c_int()
+    rc = lib().trxsig_pdch_map_host(int(fn), C.byref(block), C.byref(burst))
+    if rc < 0:
+        raise TrxSigError("trxsig_pdch_map_host(%d): %d" % (fn, rc))
+    return block.value, burst.value
 
 
 L1HOP_MAX_N = 64                                         # TRXSIG_L1HOP_MAX_N

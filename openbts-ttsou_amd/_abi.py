@@ -166,6 +166,9 @@ SIGNATURES = {
     "trxsig_fec_xcch_encode_batch": (i32, [vp, vp, i32, i32, vp]),
     "trxsig_fec_tch_decode_batch": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "trxsig_fec_viterbi_batch": (i32, [vp, vp, i32, i64, i32, vp, i64]),
+    "trxsig_fec_pdtch_encode_batch": (i32, [vp, vp, vp, vp, i32, vp]),
+    "trxsig_fec_pdtch_decode_batch": (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "trxsig_pdch_map_host": (i32, [i32, P(i32), P(i32)]),
     "trxsig_fec_tch_decode_stream": (i32, [vp, i32, i32, vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
     "trxsig_fec_xcch_decode_stream": (i32, [vp, i32, i32, vp, i32, i64, vp, i32, vp, vp, vp, vp]),
     "trxsig_fec_tch_set_filler": (i32, [vp, vp]),

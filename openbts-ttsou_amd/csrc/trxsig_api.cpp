@@ -1531,6 +1531,40 @@ int trxsig_fec_xcch_decode_stream(trxsig_ctx *c, int n_chan, int n_slots, const 
   return fec_rx_stream(c, "trxsig_fec_xcch_decode_stream: bad argument", 0, n_chan, n_slots, d_soft, soft_stride, n_rows, d_index,
                        nullptr, wire, d_state, d_status, nullptr, d_frames, d_fer);
 }
+int trxsig_fec_pdtch_encode_batch(trxsig_ctx *c, const uint8_t *d_blocks, const uint8_t *d_cs, const uint8_t *d_tsc, int n_blocks,
+                                  uint8_t *d_bits) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n_blocks < 0 || n_blocks > TRXSIG_PDTCH_MAX_BLOCKS || (n_blocks > 0 && (!d_blocks || !d_cs || !d_tsc || !d_bits)))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_pdtch_encode_batch: bad argument");
+  if (n_blocks == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  const int rc = upload_tsc_bits(c);
+  if (rc != TRXSIG_OK) return rc;
+  TRX_HIPCHK(c, trx_launch_fec_pdtch_encode(c->stream, d_blocks, d_cs, d_tsc, n_blocks, c->d_tsc, d_bits, c->prof));
+  return TRXSIG_OK;
+}
+int trxsig_fec_pdtch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int64_t n_rows, const int32_t *d_index,
+                                  int n_blocks, int wire_quantise, int cs_force, uint8_t *d_blocks, uint8_t *d_cs,
+                                  uint8_t *d_cs_dist, uint8_t *d_ok, uint8_t *d_usf) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n_blocks < 0 || n_blocks > TRXSIG_PDTCH_MAX_BLOCKS || n_rows < 0 || soft_stride < 148 || cs_force < -1 || cs_force > 3 ||
+      (n_blocks > 0 && (!d_soft || !d_blocks)) || ((uintptr_t)d_index & 3))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_pdtch_decode_batch: bad argument");
+  if (n_blocks == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec_pdtch_decode(c->stream, d_soft, soft_stride, n_rows, d_index, n_blocks, wire_quantise, cs_force,
+                                            d_blocks, d_cs, d_cs_dist, d_ok, d_usf, c->prof));
+  return TRXSIG_OK;
+}
+int trxsig_pdch_map_host(int32_t fn, int *block, int *burst) {
+  if (fn < 0 || !block || !burst) return TRXSIG_EINVAL;
+  int r = fn % 52;
+  if (r % 13 == 12) { *block = -1; *burst = -1; return TRXSIG_OK; }   // PTCCH (12, 38), idle (25, 51)
+  r -= r / 13;
+  *block = r >> 2;
+  *burst = r & 3;
+  return TRXSIG_OK;
+}
 int trxsig_fec_viterbi_batch(trxsig_ctx *c, const float *d_soft, int n_soft, int64_t in_stride, int n_blocks,
                              uint8_t *d_bits, int64_t out_stride) {
   if (!c) return TRXSIG_EINVAL;

@@ -719,6 +719,285 @@ __global__ __launch_bounds__(64) void k_fec_rx_fold(RxStream a, int ch0, uint8_t
   if (lane >= 1 && lane < 4) reinterpret_cast<unsigned *>(st)[lane] = 0u;
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_fec_pdtch_encode / k_fec_pdtch_decode: the GPRS packet data block coders CS-1..CS-4 (GSM 05.03 5.1) as include/trxsig.h
+// states them.  They share the coder (kGen), the interleaver and the trellis with XCCH; theirs are the payload convention, the
+// 16-bit block check, the USF pre-coding, the puncturing and the scheme in the eight stealing flags.  The reference has no
+// packet channel: the constants are the header's, the arithmetic is tests/pdtch_model.py's.
+//
+// One bit stream per scheme, so that both kernels treat the four alike: the bits in front of d(3) (`pre` of them: d(0..2)
+// themselves for CS-1, the 6- or 12-bit USF word otherwise), d(3..K-1), the parity bits, the tail.  CS-1..3 send it through
+// the coder, CS-4 as it is.
+// ---------------------------------------------------------------------------------------------
+struct PdPar {                                             // r[m]: encoderShift response (generator 0x11021, 16 bits) to a 1 with m zeros behind it
+  uint16_t r[431];
+  constexpr PdPar() : r() {
+    unsigned st = 0x1021u;                                 // the bit just went in: fb = 1, state = coeff
+    for (int m = 0; m < 431; m++) {
+      r[m] = (uint16_t)st;
+      const unsigned fb = (st >> 15) & 1u;
+      st = (st << 1) & 0xFFFFu;
+      if (fb) st ^= 0x1021u;
+    }
+  }
+};
+__device__ __constant__ const PdPar kPdPar;
+
+constexpr unsigned long long pd_pack(const char *const *rows, int n, int width) {   // row r at bits r*width .., first character lowest
+  unsigned long long w = 0;
+  for (int r = 0; r < n; r++)
+    for (int i = 0; i < width; i++) w |= (unsigned long long)(rows[r][i] == '1') << (r * width + i);
+  return w;
+}
+constexpr const char *kPdUsf6Rows[8] = { "000000", "001011", "010110", "011101", "100101", "101110", "110011", "111000" };
+constexpr const char *kPdUsf12Rows[8] = { "000000000000", "000011011101", "001101110110", "001110101011",
+                                          "110100001011", "110111010110", "111001111101", "111010100000" };
+constexpr const char *kPdFlagRows[4] = { "11111111", "11001000", "00100001", "00010110" };
+constexpr unsigned long long kPdUsf6 = pd_pack(kPdUsf6Rows, 8, 6);
+constexpr unsigned long long kPdUsf12Lo = pd_pack(kPdUsf12Rows, 4, 12), kPdUsf12Hi = pd_pack(kPdUsf12Rows + 4, 4, 12);
+constexpr unsigned kPdFlags = (unsigned)pd_pack(kPdFlagRows, 4, 8);
+
+__device__ __forceinline__ int pd_k(unsigned cs) { return cs == 0 ? 184 : cs == 1 ? 271 : cs == 2 ? 315 : 431; }
+__device__ __forceinline__ int pd_nu(unsigned cs) { return cs == 0 ? 228 : cs == 1 ? 294 : cs == 2 ? 338 : 456; }   // the stream's length
+__device__ __forceinline__ int pd_pre(unsigned cs) { return cs == 0 ? 3 : cs == 3 ? 12 : 6; }
+// the USF word of row r = d(0) d(1) d(2) read as a number, bit i = the i-th bit sent
+__device__ __forceinline__ unsigned pd_usf_word(unsigned cs, unsigned r) {
+  if (cs == 3) return (unsigned)((r < 4 ? kPdUsf12Lo >> (12 * r) : kPdUsf12Hi >> (12 * (r - 4))) & 0xFFFu);
+  return (unsigned)(kPdUsf6 >> (6 * r)) & 0x3Fu;
+}
+__device__ __forceinline__ unsigned pd_flag_word(unsigned cs) { return (kPdFlags >> (8 * cs)) & 0xFFu; }   // bit i = q(i)
+
+// The puncturing in closed form: coder output C(P) -> its index in c[456], or -1 where C(P) is deleted.
+// CS-2 deletes C(3 + 4j), j = 3..146 but not j = 9 mod 12; CS-3 deletes C(3 + 6j) and C(5 + 6j), j = 2..111.
+__device__ __forceinline__ int pd_cindex(unsigned cs, int P) {
+  if (cs == 1) {
+    const int j = (P - 3) >> 2;
+    if ((P & 3) == 3 && j >= 3 && j <= 146 && j % 12 != 9) return -1;
+    int m = (P - 4) >> 2;                                  // the last j with 3 + 4j < P
+    if (m > 146) m = 146;
+    return m < 3 ? P : P - (m - 2 - (m + 3) / 12);
+  }
+  if (cs == 2) {
+    const int j = P / 6, r = P - 6 * j;
+    const bool in = j >= 2 && j <= 111;
+    if (in && (r == 3 || r == 5)) return -1;
+    const int full = (j < 112 ? j : 112) - 2;              // whole groups below P's own
+    return P - (full > 0 ? 2 * full : 0) - ((in && r > 3) ? 1 : 0);
+  }
+  return P;
+}
+
+// A wave per block, laid out as k_fec_xcch_encode: the payload and the stream in LDS (a byte per bit), the parity word by the
+// register's GF(2) linearity, the coder with the puncturing as a scatter into c[456], and the four bursts gathered through
+// the inverse interleaver table, 16 bytes a lane.  A cs above 3 or a tsc above 7: four all-zero bursts.
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_fec_pdtch_encode(const uint8_t *__restrict__ blocks, const uint8_t *__restrict__ css,
+                                                         const uint8_t *__restrict__ tscs, int nblk,
+                                                         const uint8_t *__restrict__ tsc_bits /* 8 x 26 */, uint8_t *__restrict__ bits) {
+  __shared__ uint8_t pls[56], u[456], c[456];
+  const int lane = threadIdx.x, blk = blockIdx.x;
+  if (blk >= nblk) return;
+  uint8_t *out = bits + (size_t)blk * 592;
+  const unsigned cs = css[blk], tsc = tscs[blk];
+  if (cs > 3 || tsc > 7) {
+    if (VEC) { if (lane < 37) reinterpret_cast<uint4 *>(out)[lane] = make_uint4(0, 0, 0, 0); }
+    else for (int i = lane; i < 592; i += 64) out[i] = 0;
+    return;
+  }
+  if (lane < 54) pls[lane] = blocks[(size_t)blk * 54 + lane];
+  wave_fence();
+  auto dq = [&](int k) { return (unsigned)(pls[k >> 3] >> (k & 7)) & 1u; };   // d(k): bit k mod 8 of octet k / 8, LSB first
+  const int K = pd_k(cs), nu = pd_nu(cs), pre = pd_pre(cs), np = cs == 0 ? 40 : 16;
+  // the parity word of d(0..K-1): XOR of the unit responses of its set bits (CS-1: XCCH's Fire code)
+  unsigned long long par = 0;
+  for (int i = lane; i < K; i += 64)
+    if (dq(i)) par ^= cs == 0 ? kXcchPar.v[i] : (unsigned long long)kPdPar.r[K - 1 - i];
+  unsigned lo = (unsigned)par, hi = (unsigned)(par >> 32);
+  for (int m = 1; m < 64; m <<= 1) { lo ^= (unsigned)__shfl_xor((int)lo, m, 64); hi ^= (unsigned)__shfl_xor((int)hi, m, 64); }
+  const unsigned long long pw = ~(((unsigned long long)hi << 32) | lo) & ((1ULL << np) - 1);   // inverted (bv:413)
+  const unsigned head = cs == 0 ? (dq(0) | (dq(1) << 1) | (dq(2) << 2)) : pd_usf_word(cs, (dq(0) << 2) | (dq(1) << 1) | dq(2));
+  for (int i = lane; i < nu; i += 64) {
+    const int k = i - pre + 3;                             // d's index from the stream's, past the head
+    unsigned v = 0;
+    if (i < pre) v = (head >> i) & 1u;
+    else if (k < K) v = dq(k);
+    else if (k < K + np) v = (unsigned)(pw >> (np - 1 - (k - K))) & 1u;   // MSB first; the tail bits stay 0
+    u[i] = (uint8_t)v;
+  }
+  wave_fence();
+  if (cs == 3) {
+    for (int i = lane; i < 456; i += 64) c[i] = u[i];
+  } else {
+    for (int k = lane; k < nu; k += 64) {
+      unsigned idx = 0;
+      for (int h = 0; h < 5; h++) idx |= (k - h >= 0 ? (unsigned)u[k - h] : 0u) << h;
+      const unsigned g = (unsigned)(kGen >> (2 * idx)) & 3u;
+      const int c0 = pd_cindex(cs, 2 * k), c1 = pd_cindex(cs, 2 * k + 1);
+      if (c0 >= 0) c[c0] = (uint8_t)(g >> 1);
+      if (c1 >= 0) c[c1] = (uint8_t)(g & 1u);
+    }
+  }
+  wave_fence();
+  const uint8_t *tb = tsc_bits + 26 * tsc;
+  const unsigned fw = pd_flag_word(cs);
+  auto obyte = [&](int p) -> unsigned {
+    const int b = p / 148, pos = p - 148 * b;
+    if (pos < 3 || pos >= 145) return 0u;
+    if (pos == 87) return (fw >> (2 * b)) & 1u;            // q(2b)
+    if (pos == 60) return (fw >> (2 * b + 1)) & 1u;        // q(2b + 1)
+    if (pos > 60 && pos < 87) return tb[pos - 61] & 1u;
+    const int j = pos < 60 ? pos - 3 : pos - 31;
+    return c[kTchInv.k[b][j]];                             // XCCH's interleaver: burst k mod 4, the same j as TCH's
+  };
+  if (VEC) {
+    if (lane < 37) {
+      unsigned w[4];
+      for (int q = 0; q < 4; q++) {
+        unsigned v = 0;
+        for (int r = 0; r < 4; r++) v |= obyte(16 * lane + 4 * q + r) << (8 * r);
+        w[q] = v;
+      }
+      reinterpret_cast<uint4 *>(out)[lane] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  } else {
+    for (int i = lane; i < 592; i += 64) out[i] = (uint8_t)obyte(i);
+  }
+}
+
+struct PdDecode {
+  const float *soft;
+  long long stride, n_rows;
+  const int32_t *index;                                    // [nblk][4] or null
+  int nblk, cs_force;
+  uint8_t *blocks, *cs, *dist, *ok, *usf;                  // all but blocks may be null
+};
+
+// 16 lanes a block, four blocks a wave, as k_fec_viterbi; the four rows may hold four schemes (fec_trellis takes the row's n
+// and the wave's step count).  Per row: the four bursts' rows (a missing burst costs no load: its values are 0.5), the flag
+// vote on the row's lanes 0..7, then CS-4 slices its 456 values while CS-1..3 wait for nothing (a CS-4 row is not live in
+// the trellis), the trellis with the depuncturing in the fetch functor, and the finish: XCCH's for CS-1; for CS-2..4 the
+// stream's words in LDS, d() as a funnel shift of two of them, the nearest USF row, the block check by unit responses.
+// WIRE: the UDP hop's quantisation of every value read (wire_quantise != 0).
+template <bool WIRE>
+__global__ __launch_bounds__(64) void k_fec_pdtch_decode(PdDecode a) {
+  __shared__ float4 ktab[4][kChunk];
+  __shared__ int srcd[4][4];
+  const int lane = threadIdx.x & 63, row = lane >> 4, s = lane & 15;
+  const int blk = blockIdx.x * 4 + row;
+  const bool live = blk < a.nblk;
+  if (s < 4) {
+    long long i = -1;
+    if (live) i = a.index ? (long long)a.index[(size_t)blk * 4 + s] : 4LL * blk + s;
+    srcd[row][s] = (i >= 0 && i < a.n_rows) ? (int)i : -1;
+  }
+  wave_fence();
+  const int *sd = srcd[row];
+  auto value = [&](int k) -> float {                       // c[k] as the decoder sees it
+    const int src = sd[k & 3];
+    if (src < 0) return 0.5F;
+    const int j = 2 * ((49 * k) % 57) + ((k % 8) / 4);     // GSM 05.03 4.1.4 (fec:622-625)
+    const float v = a.soft[(size_t)src * a.stride + rx_pos(j)];
+    return WIRE ? wire_value(v) : v;
+  };
+  // the scheme: hard flags q(i) on lane i (bit 87, then bit 60, of burst i / 2), nearest word, ties to the lower scheme
+  bool flag = false;
+  if (s < 8 && sd[s >> 1] >= 0) {
+    float v = a.soft[(size_t)sd[s >> 1] * a.stride + ((s & 1) ? 60 : 87)];
+    if (WIRE) v = wire_value(v);
+    flag = v > 0.5F;
+  }
+  const unsigned hard = (unsigned)(__builtin_amdgcn_ballot_w64(flag) >> (lane & 48)) & 0xFFu;
+  unsigned cs = 0;
+  int dist = __builtin_popcount(hard ^ pd_flag_word(0));
+  for (unsigned r = 1; r < 4; r++) {
+    const int d = __builtin_popcount(hard ^ pd_flag_word(r));
+    if (d < dist) { dist = d; cs = r; }
+  }
+  if (a.cs_force >= 0) { cs = (unsigned)a.cs_force; dist = __builtin_popcount(hard ^ pd_flag_word(cs)); }
+  // CS-4: the 456 values sliced, sixteen a row at a time; lane s keeps the stream's word s
+  const bool c4 = live && cs == 3;
+  unsigned word = 0;
+  if (__builtin_amdgcn_ballot_w64(c4)) {
+    for (int q = 0; q < 29; q++) {
+      const int k = s + 16 * q;
+      const bool b = c4 && k < 456 && value(k) > 0.5F;
+      const unsigned w16 = (unsigned)(__builtin_amdgcn_ballot_w64(b) >> (lane & 48)) & 0xFFFFu;
+      if ((q >> 1) == s) word |= w16 << (16 * (q & 1));
+    }
+  }
+  // CS-1..3: the trellis over the coder's 2 nu outputs, a deleted one reading exactly 0.5 (wire_value(0.5F) is 0.5F, so
+  // `finish` need not know which they are)
+  const bool dec = live && cs != 3;
+  const int nu = pd_nu(cs);
+  const int steps = __builtin_amdgcn_ballot_w64(dec && cs == 2) ? 338 + kDeferral
+                  : __builtin_amdgcn_ballot_w64(dec && cs == 1) ? 294 + kDeferral
+                  : __builtin_amdgcn_ballot_w64(dec) ? 228 + kDeferral : 0;
+  auto fetch = [&](int p) -> float {
+    const int k = pd_cindex(cs, p);
+    if (k < 0) return 0.5F;
+    const int src = sd[k & 3];
+    if (src < 0) return 0.5F;
+    const int j = 2 * ((49 * k) % 57) + ((k % 8) / 4);
+    return a.soft[(size_t)src * a.stride + rx_pos(j)];
+  };
+  auto finish = [&](float v, int) -> float { return WIRE ? wire_value(v) : v; };
+  const unsigned outw = fec_trellis(ktab[row], 2 * nu, steps, dec, lane, fetch, finish);
+  if (!live) return;
+
+  uint8_t *ob = a.blocks + (size_t)blk * 54;
+  bool ok;
+  unsigned usf;
+  if (cs == 0) {
+    ok = xcch_finish(outw, s, ob);                         // octets 0..22 and the Fire syndrome
+    for (int o = 23 + s; o < 54; o += 16) ob[o] = 0;
+    usf = (unsigned)__shfl((int)outw, lane & 48, 64) & 7u;
+  } else {
+    if (cs != 3) word = outw;
+    unsigned *uw = reinterpret_cast<unsigned *>(ktab[row]); // the stream, bit i = (uw[i / 32] >> i % 32) & 1
+    uw[s] = word;
+    if (s == 0) uw[16] = 0;
+    wave_fence();
+    const int K = pd_k(cs), pre = pd_pre(cs), sh = pre - 3; // d(k) = stream bit k + sh for k >= 3
+    // d(0..2): the nearest row of the USF table (Hamming, ties to the first row)
+    const unsigned head = uw[0] & ((1u << pre) - 1u);
+    unsigned best = 0;
+    int bd = __builtin_popcount(head ^ pd_usf_word(cs, 0));
+    for (unsigned r = 1; r < 8; r++) {
+      const int d = __builtin_popcount(head ^ pd_usf_word(cs, r));
+      if (d < bd) { bd = d; best = r; }
+    }
+    usf = ((best >> 2) & 1u) | (((best >> 1) & 1u) << 1) | ((best & 1u) << 2);
+    // this lane's word of d: bits 32s .. 32s+31, nothing at or past K
+    unsigned dw = (unsigned)(((((unsigned long long)uw[s + 1]) << 32) | uw[s]) >> sh);
+    if (s == 0) dw = (dw & ~7u) | usf;
+    const int nb = K - 32 * s;
+    if (nb <= 0) dw = 0;
+    else if (nb < 32) dw &= (1u << nb) - 1u;
+    for (int q = 0; q < 4; q++)
+      if (4 * s + q < 54) ob[4 * s + q] = (uint8_t)(dw >> (8 * q));
+    // the block check on d: the parity register's word against the sent one, which is its inverse
+    unsigned par = 0;
+    for (int k = 0; k < 32; k++)
+      if ((dw >> k) & 1u) par ^= kPdPar.r[K - 1 - (32 * s + k)];
+    par ^= (unsigned)dpp_i<0xB1>((int)par);
+    par ^= (unsigned)dpp_i<0x4E>((int)par);
+    par ^= (unsigned)dpp_i<0x141>((int)par);
+    par ^= (unsigned)dpp_i<0x140>((int)par);
+    unsigned sent = 0;
+    for (int k = 0; k < 16; k++) {
+      const int i = K + sh + k;
+      sent |= ((uw[i >> 5] >> (i & 31)) & 1u) << (15 - k);
+    }
+    ok = (par ^ sent) == 0xFFFFu;
+  }
+  if (s == 0) {
+    if (a.cs) a.cs[blk] = (uint8_t)cs;
+    if (a.dist) a.dist[blk] = (uint8_t)dist;
+    if (a.ok) a.ok[blk] = ok;
+    if (a.usf) a.usf[blk] = (uint8_t)usf;
+  }
+}
+
 }  // namespace
 
 hipError_t trx_launch_fec_xcch_encode(hipStream_t st, const uint8_t *frames, int nblk, const uint8_t *tsc_bits, uint8_t *bits,
@@ -804,5 +1083,32 @@ hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_s
     else k_fec_rx_fold<false><<<grid, block, 0, st>>>(a, (int)c0, state, status, reinterpret_cast<uint8_t *>(fer));
   }
   if (prof) prof->end(TRXSIG_K_FEC_RX_FOLD, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_pdtch_encode(hipStream_t st, const uint8_t *blocks, const uint8_t *cs, const uint8_t *tsc, int nblk,
+                                       const uint8_t *tsc_bits, uint8_t *bits, TrxProfiler *prof) {
+  if (nblk <= 0) return hipSuccess;
+  const dim3 grid((unsigned)nblk), block(64);
+  if (prof) prof->begin(TRXSIG_K_FEC, st);
+  if (((uintptr_t)bits & 15) == 0)
+    k_fec_pdtch_encode<true><<<grid, block, 0, st>>>(blocks, cs, tsc, nblk, tsc_bits, bits);
+  else
+    k_fec_pdtch_encode<false><<<grid, block, 0, st>>>(blocks, cs, tsc, nblk, tsc_bits, bits);
+  if (prof) prof->end(TRXSIG_K_FEC, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_pdtch_decode(hipStream_t st, const float *soft, long long stride, long long n_rows, const int32_t *index,
+                                       int nblk, int wire, int cs_force, uint8_t *blocks, uint8_t *cs, uint8_t *dist, uint8_t *ok,
+                                       uint8_t *usf, TrxProfiler *prof) {
+  if (nblk <= 0) return hipSuccess;
+  if (cs_force < -1 || cs_force > 3) return hipErrorInvalidValue;
+  const PdDecode a = { soft, stride, n_rows, index, nblk, cs_force, blocks, cs, dist, ok, usf };
+  const dim3 grid((unsigned)((nblk + 3) / 4)), block(64);
+  if (prof) prof->begin(TRXSIG_K_FEC, st);
+  if (wire) k_fec_pdtch_decode<true><<<grid, block, 0, st>>>(a);
+  else k_fec_pdtch_decode<false><<<grid, block, 0, st>>>(a);
+  if (prof) prof->end(TRXSIG_K_FEC, st);
   return hipGetLastError();
 }

@@ -316,6 +316,14 @@ hipError_t trx_launch_fec_tch_encode(hipStream_t st, int n_chan, int n_blocks, c
 // SCH encode (trxsig_fec_sch_encode_batch): n (FN, BSIC) -> n bursts of 148 bits; xts: bit t = extended training sequence bit t
 hipError_t trx_launch_fec_sch_encode(hipStream_t st, const uint32_t *fns, const uint8_t *bsics, int n, unsigned long long xts,
                                      uint8_t *bits, TrxProfiler *prof);
+// GPRS packet data blocks (trxsig_fec_pdtch_encode_batch / _decode_batch): k_fec_pdtch_encode, k_fec_pdtch_decode.  blocks: 54
+// octets per block; cs, tsc: per block; tsc_bits: the 8 x 26 training-sequence bits (device); index: [nblk][4] or NULL; every
+// decoder output but blocks may be NULL
+hipError_t trx_launch_fec_pdtch_encode(hipStream_t st, const uint8_t *blocks, const uint8_t *cs, const uint8_t *tsc, int nblk,
+                                       const uint8_t *tsc_bits, uint8_t *bits, TrxProfiler *prof);
+hipError_t trx_launch_fec_pdtch_decode(hipStream_t st, const float *soft, long long stride, long long n_rows, const int32_t *index,
+                                       int nblk, int wire, int cs_force, uint8_t *blocks, uint8_t *cs, uint8_t *dist, uint8_t *ok,
+                                       uint8_t *usf, TrxProfiler *prof);
 // uplink stream decode (trxsig_fec_tch_decode_stream / _xcch_decode_stream): k_fec_rx_stream, then k_fec_rx_fold.  tch != 0:
 // TCH/FACCH (out_tch = 33 octets, out_l2 = the FACCH frame), 0: XCCH (out_l2 = the frame; out_tch and b0 unused)
 hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_slots, const float *soft, long long stride,
