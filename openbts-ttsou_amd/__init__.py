@@ -11,6 +11,7 @@ import subprocess
 
 from ._abi import (TrxSigError, bind, C32, TrxGroupResult, L1RxOut, L1TxIn, L1TxOut, L1MsIn, L1MsOut, L1MsAir,  # noqa: F401
                    L1MsRxOut, L1AcqOut, AirCellParams, AirStreamParams, L1TrkView, L1TrkMeas)
+from ._abi_l1pdch import L1PdchIn, L1PdchOut, L1PdchDec  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRXSIG_LIB", os.path.join(_HERE, "libtrxsig.so"))   # TRXSIG_LIB: tuning builds
@@ -1541,3 +1542,91 @@ class L1Hop(_Object):
         self._call("result", int(fn), C.byref(res), C.byref(out))
         self.row = _dev_tensor(self.ctx, out.d_row, (out.n_slots, out.n_arfcn), "<i4")
         return out
+
+
+L1PDCH_DOWN, L1PDCH_UP = 0, 1                    # TRXSIG_L1PDCH_DOWN / _UP
+L1PDCH_PDTCH, L1PDCH_PTCCH = 0, 1                # the channel classes of trxsig_l1pdch.h
+L1PDCH_COMB = 13                                 # TRXSIG_L1PDCH_COMB: a packet data channel in comb
+L1TX_PDCH = 8                                    # TRXSIG_L1TX_PDCH: the d_what code of a slot L1Pdch wrote
+L1PDCH_STATE_BYTES, L1PDCH_RING = 3104, 32       # TRXSIG_L1PDCH_STATE_BYTES, TRXSIG_L1PDCH_RING
+
+
+class L1Pdch(_Object):
+    """ctypes view of include/trxsig_l1pdch.h: packet data channels through L1 -- payloads of the PDCH slots (13 in comb) to timed
+    bursts and a Transceiver group pull to payloads, on the device.  direction: L1PDCH_DOWN or L1PDCH_UP."""
+    _prefix = "trxsig_l1pdch"
+
+    def __init__(self, ctx, comb, bsic, direction):
+        super().__init__(ctx)
+        self.comb = self.np.ascontiguousarray(comb, self.np.uint8)
+        self._create(self.comb.shape[0], self.comb.ctypes.data, int(bsic), int(direction))
+        self.out = self.dec = self._keep = None
+
+    def circuit_plan(self):
+        """comb with the packet slots as 0: what L1Tx / L1Rx / L1Ms / L1MsRx and the group take."""
+        return self.np.where(self.comb == L1PDCH_COMB, 0, self.comb).astype(self.np.uint8)
+
+    def channels(self, cls):
+        return self._call("channels", cls)
+
+    def channel(self, cls, chan):
+        """(arfcn, tn) of a channel"""
+        v = [C.c_int() for _ in range(2)]
+        self._call("channel", cls, chan, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def grid(self, fn, n_frames):
+        """(nb_pdtch, nb_ptcch) of an encode call"""
+        v = [C.c_int() for _ in range(2)]
+        self._call("grid", int(fn), int(n_frames), *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def state(self, cls):
+        p = C.c_void_p()
+        self._call("state", cls, C.byref(p))
+        return p.value
+
+    def encode(self, fn, n_frames, pdtch_kind=None, pdtch_cs=None, pdtch_payload=None, ptcch_kind=None, ptcch_payload=None,
+               bits_onto=None, what_onto=None):
+        """Grids as torch uint8 tensors on the context's device (None for a class without channels); bits_onto / what_onto:
+        tensors or device addresses of a grid to overlay (L1Tx's out.d_bits / out.d_what), or None for the object's own grid."""
+        ins, out = L1PdchIn(), L1PdchOut()
+        keep = _fill(ins, None, (pdtch_kind, pdtch_cs, pdtch_payload, ptcch_kind, ptcch_payload), itemsize=1, empty_as_one=True)
+        self._call("encode", int(fn), int(n_frames), C.byref(ins), _ptr(bits_onto), _ptr(what_onto), C.byref(out))
+        self._keep = keep + (bits_onto, what_onto)
+        self.out = out
+        return out
+
+    def decode(self, res, fn, wire=True, cs_force=-1, sibling=None):
+        """res: a TrxGroupResult of whole frames from (fn, TN 0)."""
+        out = L1PdchDec()
+        self._call("decode", C.byref(res), int(fn), int(bool(wire)), int(cs_force), sibling.h if sibling is not None else None,
+                   C.byref(out))
+        self.dec = out
+        return out
+
+    def states(self):
+        """{class: the channel records, uint8 [n, L1PDCH_STATE_BYTES]} on the host (synchronises)."""
+        self.ctx.synchronize()
+        return {cls: _to_host(self.ctx, self.state(cls), (self.channels(cls), L1PDCH_STATE_BYTES), "|u1")
+                for cls in (L1PDCH_PDTCH, L1PDCH_PTCCH)}
+
+    def collect(self):
+        """The last encode's grid as host numpy arrays (synchronises the context's stream)."""
+        o = self.out
+        self.ctx.synchronize()
+        A, F = o.n_arfcn, o.n_frames
+        return dict(bits=_to_host(self.ctx, o.d_bits, (A, 8 * F, 148), "|u1"), what=_to_host(self.ctx, o.d_what, (A, 8 * F), "|u1"))
+
+    def collect_decode(self):
+        """The last decode's outputs as host numpy arrays (synchronises the context's stream)."""
+        o = self.dec
+        self.ctx.synchronize()
+        host = lambda p, shape, ts: _to_host(self.ctx, p, shape, ts)
+        r = {}
+        for name, n, nb, np_ in (("pdtch", o.n_pdtch, o.nb_pdtch, 54), ("ptcch", o.n_ptcch, o.nb_ptcch, 23)):
+            get = lambda f: getattr(o, "d_%s_%s" % (name, f))
+            r[name] = dict(payload=host(get("payload"), (n, nb, np_), "|u1"), fn=host(get("fn"), (n, nb), "<i4"),
+                           rssi=host(get("rssi"), (n,), "<i4"), timing=host(get("timing"), (n,), "<i4"),
+                           **{f: host(get(f), (n, nb), "|u1") for f in ("cs", "cs_dist", "ok", "usf", "nb", "granted")})
+        return r

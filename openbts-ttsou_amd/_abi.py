@@ -374,6 +374,15 @@ SIGNATURES = {
     "trxsig_l1hop_bits": (i32, [vp, i32, i32, i32, vp, vp]),
     "trxsig_l1hop_cells": (i32, [vp, i32, i32, i32, vp, i64, i64, vp, i64, i64]),
     "trxsig_l1hop_result": (i32, [vp, i32, P(TrxGroupResult), P(TrxGroupResult)]),
+    # ---- include/trxsig_l1pdch.h ----
+    "trxsig_l1pdch_create": (i32, [P(vp), vp, i32, vp, i32, i32]),
+    "trxsig_l1pdch_destroy": (None, [vp]),
+    "trxsig_l1pdch_channels": (i32, [vp, i32]),
+    "trxsig_l1pdch_channel": (i32, [vp, i32, i32, P(i32), P(i32)]),
+    "trxsig_l1pdch_grid": (i32, [vp, i32, i32, P(i32), P(i32)]),
+    "trxsig_l1pdch_state": (i32, [vp, i32, P(vp)]),
+    "trxsig_l1pdch_encode": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "trxsig_l1pdch_decode": (i32, [vp, P(TrxGroupResult), i32, i32, i32, vp, vp]),
 }
 
 
