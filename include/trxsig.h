@@ -729,6 +729,51 @@ int trxsig_fec_pdtch_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft
                                   uint8_t *d_cs_dist, uint8_t *d_ok, uint8_t *d_usf);
 int trxsig_pdch_map_host(int32_t fn, int *block, int *burst);
 
+/* ---- the access burst's coders, both formats (GSM 05.03 4.6 and 5.3.2) ------------------------------------------------
+ * What a handset sends before it has a channel: the 8-bit access burst of the RACH and, on a packet data channel (PRACH,
+ * PTCCH/U), either that or the 11-bit packet access burst.  One burst of 148 bits, laid out as trxsig_l1ms.h states it: bits
+ * 0..7 the extended tail, 8..48 the 41-bit synch sequence (GSM 05.02 5.2.7), 49..84 the 36 coded bits e(0..35), the rest zero.
+ * TRXSIG_ACCESS_8 (GSM 05.03 4.6, the reference's RACHL1Decoder read backwards): d(0..7) = the RA, least significant bit
+ *   first; p = ~(bsic ^ parity) in six bits, most significant first, parity = Parity(0x6f, 6, 8) over d; four zero tail bits;
+ *   u(0..17) through the rate-1/2 coder gives e(0..35).  The encoder writes the bytes trxsig_l1ms_encode writes for an access
+ *   burst, the decoder returns what trxsig_fec_rach_decode_batch returns.
+ * TRXSIG_ACCESS_11 (GSM 05.03 5.3.2): d(0..10) = the 11-bit word, least significant bit first; six parity bits by the same
+ *   generator over d(0..10), coloured with the BSIC and written the same way; four zero tail bits give u(0..20); the same coder
+ *   gives C(0..41); C(0), C(2), C(5), C(37), C(39) and C(41) are not sent, which leaves e(0..35), in order.
+ *   NOT CHECKED AGAINST THE STANDARD: these six positions and the bit order of d and p are written from memory of GSM 05.03;
+ *   no copy of it was at hand.  What follows from them is pinned by tests/test_access_model.py: 21 -> 42 -> 36 bits, the
+ *   punctured code's minimum weight over its 2^11 - 1 nonzero words is 7, every word comes back from clean bits, and after
+ *   any single flipped bit the word and the BSIC still do.  The tail bits do not always: SoftVector::decode does not end its
+ *   trellis in the zero state, so a flip in e(31..35) -- in e(34..35) of the 8-bit format, the reference's own -- comes out as
+ *   a nonzero tail bit.  tests/access_model.py is this statement in numpy on the oracle's coder and decoder.
+ * Encode: d_ra [n] (uint16), d_fmt [n], d_bsic [n] -> d_bits [n][148], one bit per byte.  A d_fmt above 1, a d_bsic above 63 or
+ *   a d_ra that does not fit its format (above 255 / 2047) encodes as an all-zero row.
+ * Decode.  Burst k is row d_index[k] of d_soft (values 49..84 of d_soft + row * soft_stride are read); d_index == NULL means
+ *   row k.  A row outside [0, n_rows) means the burst is missing: its 36 values are exactly 0.5.  Present values pass the UDP
+ *   hop first when wire_quantise != 0.  Values the demodulator never produces behave as the paragraph above says for XCCH.
+ *   fmt 0: SoftVector::decode of e(0..35) into u(0..17).  fmt 1: the 42 coder outputs with the six deleted positions reading
+ *   exactly 0.5F, decoded into u(0..20).  Either way d_ra = d as a number, d_tail_ok = the four tail bits are zero, d_bsic = the
+ *   BSIC the parity word encodes, ~p ^ parity(d) (the caller compares it with its own), d_fmt = fmt.
+ *   fmt -1 (either): both hypotheses are decoded.  A hypothesis holds if its tail bits are zero and its parity gives `bsic`
+ *   (0..63; not looked at for fmt 0 or 1).  The result is the 11-bit one only if it holds and the 8-bit one does not; otherwise
+ *   the 8-bit one -- ties to the lower scheme, as the PDTCH decoder's vote.  All four outputs are the chosen hypothesis's.
+ *   Ten bits decide whether a hypothesis holds, so about one clean 11-bit word in 2^10 also holds as an 8-bit burst of the
+ *   same cell and is returned as that (3 of the 8192 that tests/test_access_model.py tries); a cell that uses one format
+ *   passes it as fmt.
+ *   Outputs: d_ra [n] (uint16), d_fmt [n], d_tail_ok [n], d_bsic [n]; any but d_ra may be NULL.  One burst's output never
+ *   depends on another burst's input.
+ * Host side: a NULL context or required pointer, a negative size, n > TRXSIG_ACCESS_MAX_BURSTS, soft_stride < 85, fmt outside
+ *   -1..1, bsic outside 0..63 with fmt -1, a d_index not 4-byte aligned or a d_ra not 2-byte aligned return TRXSIG_EINVAL
+ *   before any launch; n == 0 is a no-op.  One launch each (k_fec_access_encode, k_fec_access_decode; a row of 16 lanes per
+ *   code word, four rows a wave, through the trellis every decoder here shares), booked under TRXSIG_K_FEC. */
+enum { TRXSIG_ACCESS_8 = 0, TRXSIG_ACCESS_11 = 1 };
+#define TRXSIG_ACCESS_MAX_BURSTS 16777216    /* 2^24 bursts a call */
+int trxsig_fec_access_encode_batch(trxsig_ctx *ctx, const uint16_t *d_ra, const uint8_t *d_fmt, const uint8_t *d_bsic, int n,
+                                   uint8_t *d_bits);
+int trxsig_fec_access_decode_batch(trxsig_ctx *ctx, const float *d_soft, int soft_stride, int64_t n_rows, const int32_t *d_index,
+                                   int n, int wire_quantise, int fmt, int bsic, uint16_t *d_ra, uint8_t *d_fmt, uint8_t *d_tail_ok,
+                                   uint8_t *d_bsic);
+
 /* ---- uplink TCH/FACCH and XCCH decoders as multi-channel streams ---------------------------------------------------
  * The reference's per-channel decoders -- TCHFACCHL1Decoder::processBurst / deinterleave / decodeTCH up to the parity and
  * tail check (GSML1FEC.cpp:1030-1163) and XCCHL1Decoder::writeLowSide / processBurst / deinterleave / decode (:556-653) --

@@ -12,6 +12,7 @@ import subprocess
 from ._abi import (TrxSigError, bind, C32, TrxGroupResult, L1RxOut, L1TxIn, L1TxOut, L1MsIn, L1MsOut, L1MsAir,  # noqa: F401
                    L1MsRxOut, L1AcqOut, AirCellParams, AirStreamParams, L1TrkView, L1TrkMeas)
 from ._abi_l1pdch import L1PdchIn, L1PdchOut, L1PdchDec  # noqa: F401
+from ._abi_l1pacc import L1PaccIn, L1PaccOut, L1PaccDet  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRXSIG_LIB", os.path.join(_HERE, "libtrxsig.so"))   # TRXSIG_LIB: tuning builds
@@ -26,6 +27,7 @@ FEC_DECODED, FEC_STOLEN, FEC_FACCH_OK, FEC_TCH_GOOD = 1, 2, 4, 8   # status bits
 TCH_RX_STATE_BYTES, XCCH_RX_STATE_BYTES = 3664, 1840              # TRXSIG_TCH_RX_STATE_BYTES, TRXSIG_XCCH_RX_STATE_BYTES
 CS1, CS2, CS3, CS4 = 0, 1, 2, 3                  # TRXSIG_CS1..TRXSIG_CS4: the GPRS coding schemes of pdtch_encode / pdtch_decode
 PDTCH_BLOCK_BYTES = 54                           # TRXSIG_PDTCH_BLOCK_BYTES
+ACCESS_8, ACCESS_11 = 0, 1                       # TRXSIG_ACCESS_8 / _11: the access burst's formats of access_encode / access_decode
 
 
 def build(verbose=False):
@@ -659,6 +661,23 @@ class TrxSig:
         self._chk(self.L.trxsig_fec_pdtch_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n_rows, _ptr(index),
                                                        n_blocks, int(wire), cs_force, _ptr(blocks), _ptr(cs), _ptr(cs_dist),
                                                        _ptr(ok), _ptr(usf)), "trxsig_fec_pdtch_decode_batch")
+
+    def access_encode(self, ra, fmt, bsic, bits):
+        """Access bursts of either format: ra[n] (int16 / uint16), fmt[n] (ACCESS_8 / ACCESS_11), bsic[n] (uint8) -> bits[n, 148]
+        (all device)."""
+        self._chk(self.L.trxsig_fec_access_encode_batch(self.h, _ptr(ra), _ptr(fmt), _ptr(bsic), fmt.numel(), _ptr(bits)),
+                  "trxsig_fec_access_encode_batch")
+
+    def access_decode(self, soft, n, ra, fmt_out=None, tail_ok=None, bsic_out=None, index=None, wire=True, fmt=-1, bsic=0,
+                      n_rows=None, soft_stride=None):
+        """The inverse: soft[n_rows, >= 85] float32 (a tensor, or a device address with n_rows / soft_stride given), index[n] int32
+        (None: row k; a row outside [0, n_rows) = a missing burst) -> ra[n] (16 bits a row) and, where given, fmt_out[n],
+        tail_ok[n], bsic_out[n] (uint8).  fmt: ACCESS_8, ACCESS_11, or -1 to try both against the cell's bsic."""
+        if n_rows is None:
+            n_rows = soft.shape[0]
+        self._chk(self.L.trxsig_fec_access_decode_batch(self.h, _ptr(soft), soft_stride or soft.shape[-1], n_rows, _ptr(index), n,
+                                                        int(wire), fmt, bsic, _ptr(ra), _ptr(fmt_out), _ptr(tail_ok),
+                                                        _ptr(bsic_out)), "trxsig_fec_access_decode_batch")
 
     def unpack_half(self, iq, n, out):
         self._chk(self.L.trxsig_unpack_half(self.h, _ptr(iq), n, _ptr(out)), "trxsig_unpack_half")
@@ -1629,4 +1648,97 @@ class L1Pdch(_Object):
             r[name] = dict(payload=host(get("payload"), (n, nb, np_), "|u1"), fn=host(get("fn"), (n, nb), "<i4"),
                            rssi=host(get("rssi"), (n,), "<i4"), timing=host(get("timing"), (n,), "<i4"),
                            **{f: host(get(f), (n, nb), "|u1") for f in ("cs", "cs_dist", "ok", "usf", "nb", "granted")})
+        return r
+
+
+L1TX_PACC = 9                                    # TRXSIG_L1TX_PACC: the d_what code of a slot L1Pacc wrote
+L1PACC_NONE, L1PACC_PTCCH, L1PACC_PRACH = 0, 1, 2   # d_kind of a frame in L1Pacc.detect's outputs
+L1PACC_STATE_BYTES = 144                         # TRXSIG_L1PACC_STATE_BYTES
+
+
+class L1Pacc(_Object):
+    """ctypes view of include/trxsig_l1pacc.h: packet access through L1 -- a handset's access bursts on the PTCCH/U frames and
+    PRACH blocks of the PDCH slots (13 in comb) to timed bursts; a base station's detector on those frames of the slot cells, the
+    timing advances per TAI and the PTCCH/D message; a handset's reading of that message."""
+    _prefix = "trxsig_l1pacc"
+
+    def __init__(self, ctx, comb, bsic):
+        super().__init__(ctx)
+        self.comb = self.np.ascontiguousarray(comb, self.np.uint8)
+        self._create(self.comb.shape[0], self.comb.ctypes.data, int(bsic))
+        self.out = self.det = self._keep = None
+
+    def channels(self):
+        return self._call("channels")
+
+    def channel(self, chan):
+        """(arfcn, tn) of a PDCH"""
+        v = [C.c_int() for _ in range(2)]
+        self._call("channel", chan, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+    def grid(self, fn, n_frames):
+        """nb: the blocks with a frame in the call"""
+        v = C.c_int()
+        self._call("grid", int(fn), int(n_frames), C.byref(v))
+        return v.value
+
+    def state(self):
+        p = C.c_void_p()
+        self._call("state", C.byref(p))
+        return p.value
+
+    def encode(self, fn, n_frames, ptcch_kind, ptcch_ra, prach_kind, prach_ra, fmt=0, bits_onto=None, what_onto=None):
+        """ptcch_kind [n, 16] uint8, ptcch_ra [n, 16] int16, prach_kind [n, nb, 4] uint8, prach_ra [n, nb, 4] int16 (the 16 bits
+        of a uint16) on the context's device; bits_onto / what_onto: a grid to overlay, or None for the object's own."""
+        ins, out = L1PaccIn(), L1PaccOut()
+        ins.fmt = int(fmt)
+        keep = _fill(ins, None, (ptcch_kind, ptcch_ra, prach_kind, prach_ra), empty_as_one=True)
+        self._call("encode", int(fn), int(n_frames), C.byref(ins), _ptr(bits_onto), _ptr(what_onto), C.byref(out))
+        self._keep = keep + (bits_onto, what_onto)
+        self.out = out
+        return out
+
+    def detect(self, samples, slot_stride, arfcn_stride, fn, n_frames, prach=None, fmt=-1, leg=RACHLEG_DEMOD, detect_thresh=5.0,
+               energy_thresh=-1.0, wire=True):
+        """samples: the slot cells (a tensor or a device address); prach: a HOST uint8 array [n, nb] (nonzero: a PRACH block) or None."""
+        out = L1PaccDet()
+        h = None if prach is None else self.np.ascontiguousarray(prach, self.np.uint8)
+        self._call("detect", _ptr(samples), int(slot_stride), int(arfcn_stride), int(fn), int(n_frames),
+                   None if h is None else h.ctypes.data, int(fmt), int(leg), float(detect_thresh), float(energy_thresh), int(bool(wire)),
+                   C.byref(out))
+        self.det = out
+        return out
+
+    def ta_message(self, kind, payload, nb_pt):
+        """kind [n, nb_pt], payload [n, nb_pt, 23] uint8 on the device: L1Pdch.encode's PTCCH inputs."""
+        self._call("ta_message", _ptr(kind), _ptr(payload), int(nb_pt))
+
+    def ta_read(self, dec, ta):
+        """dec: the L1PdchDec of a handset's decode; ta [n, 16] uint8 on the device, updated where a PTCCH/D block came with ok."""
+        self._call("ta_read", C.byref(dec), _ptr(ta))
+
+    def states(self):
+        """The PDCHs' tables as dict(ta, fn: int32 [n, 16]; valid: uint8 [n, 16]) on the host (synchronises)."""
+        self.ctx.synchronize()
+        n = self.channels()
+        raw = _to_host(self.ctx, self.state(), (n, L1PACC_STATE_BYTES), "|u1")
+        return dict(ta=raw[:, :64].copy().view("<i4"), fn=raw[:, 64:128].copy().view("<i4"), valid=raw[:, 128:].copy())
+
+    def collect(self):
+        """The last encode's grid and the last detect's outputs as host numpy arrays (synchronises the context's stream)."""
+        self.ctx.synchronize()
+        r = {}
+        if self.out is not None:
+            o = self.out
+            A, F = o.n_arfcn, o.n_frames
+            r.update(bits=_to_host(self.ctx, o.d_bits, (A, 8 * F, 148), "|u1"), what=_to_host(self.ctx, o.d_what, (A, 8 * F), "|u1"))
+        if self.det is not None:
+            d = self.det
+            shape = (d.n_pdch, d.n_frames)
+            for name, ts in (("kind", "|u1"), ("tai", "|i1"), ("det", "|u1"), ("fmt", "|u1"), ("ok", "|u1"), ("toa", "<f4"),
+                             ("avgpwr", "<f4"), ("ta", "|u1")):
+                r[name] = _to_host(self.ctx, getattr(d, "d_" + name), shape, ts)
+            r["amp"] = _to_host(self.ctx, d.d_amp, shape + (2,), "<f4")
+            r["ra"] = _to_host(self.ctx, d.d_ra, shape, "<i2").view("<u2")      # (16 bits a word: torch has no unsigned view of them)
         return r

@@ -169,6 +169,8 @@ SIGNATURES = {
     "trxsig_fec_pdtch_encode_batch": (i32, [vp, vp, vp, vp, i32, vp]),
     "trxsig_fec_pdtch_decode_batch": (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "trxsig_pdch_map_host": (i32, [i32, P(i32), P(i32)]),
+    "trxsig_fec_access_encode_batch": (i32, [vp, vp, vp, vp, i32, vp]),
+    "trxsig_fec_access_decode_batch": (i32, [vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "trxsig_fec_tch_decode_stream": (i32, [vp, i32, i32, vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
     "trxsig_fec_xcch_decode_stream": (i32, [vp, i32, i32, vp, i32, i64, vp, i32, vp, vp, vp, vp]),
     "trxsig_fec_tch_set_filler": (i32, [vp, vp]),
@@ -383,6 +385,17 @@ SIGNATURES = {
     "trxsig_l1pdch_state": (i32, [vp, i32, P(vp)]),
     "trxsig_l1pdch_encode": (i32, [vp, i32, i32, vp, vp, vp, vp]),
     "trxsig_l1pdch_decode": (i32, [vp, P(TrxGroupResult), i32, i32, i32, vp, vp]),
+    # ---- include/trxsig_l1pacc.h ----
+    "trxsig_l1pacc_create": (i32, [P(vp), vp, i32, vp, i32]),
+    "trxsig_l1pacc_destroy": (None, [vp]),
+    "trxsig_l1pacc_channels": (i32, [vp]),
+    "trxsig_l1pacc_channel": (i32, [vp, i32, P(i32), P(i32)]),
+    "trxsig_l1pacc_grid": (i32, [vp, i32, i32, P(i32)]),
+    "trxsig_l1pacc_state": (i32, [vp, P(vp)]),
+    "trxsig_l1pacc_encode": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "trxsig_l1pacc_detect": (i32, [vp, vp, i64, i64, i32, i32, vp, i32, i32, f32, f32, i32, vp]),
+    "trxsig_l1pacc_ta_message": (i32, [vp, vp, vp, i32]),
+    "trxsig_l1pacc_ta_read": (i32, [vp, vp, vp]),
 }
 
 

@@ -1556,6 +1556,29 @@ int trxsig_fec_pdtch_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_s
                                             d_blocks, d_cs, d_cs_dist, d_ok, d_usf, c->prof));
   return TRXSIG_OK;
 }
+int trxsig_fec_access_encode_batch(trxsig_ctx *c, const uint16_t *d_ra, const uint8_t *d_fmt, const uint8_t *d_bsic, int n,
+                                   uint8_t *d_bits) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n < 0 || n > TRXSIG_ACCESS_MAX_BURSTS || (n > 0 && (!d_ra || !d_fmt || !d_bsic || !d_bits)) || ((uintptr_t)d_ra & 1))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_access_encode_batch: bad argument");
+  if (n == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec_access_encode(c->stream, d_ra, d_fmt, d_bsic, n, d_bits, c->prof));
+  return TRXSIG_OK;
+}
+int trxsig_fec_access_decode_batch(trxsig_ctx *c, const float *d_soft, int soft_stride, int64_t n_rows, const int32_t *d_index,
+                                   int n, int wire_quantise, int fmt, int bsic, uint16_t *d_ra, uint8_t *d_fmt, uint8_t *d_tail_ok,
+                                   uint8_t *d_bsic) {
+  if (!c) return TRXSIG_EINVAL;
+  if (n < 0 || n > TRXSIG_ACCESS_MAX_BURSTS || n_rows < 0 || soft_stride < 85 || fmt < -1 || fmt > 1 ||
+      (fmt < 0 && (bsic < 0 || bsic > 63)) || (n > 0 && (!d_soft || !d_ra)) || ((uintptr_t)d_index & 3) || ((uintptr_t)d_ra & 1))
+    return fail(c, TRXSIG_EINVAL, "trxsig_fec_access_decode_batch: bad argument");
+  if (n == 0) return TRXSIG_OK;
+  TrxDeviceGuard g(c->device);
+  TRX_HIPCHK(c, trx_launch_fec_access_decode(c->stream, d_soft, soft_stride, n_rows, d_index, n, wire_quantise, fmt, bsic, d_ra,
+                                             d_fmt, d_tail_ok, d_bsic, c->prof));
+  return TRXSIG_OK;
+}
 int trxsig_pdch_map_host(int32_t fn, int *block, int *burst) {
   if (fn < 0 || !block || !burst) return TRXSIG_EINVAL;
   int r = fn % 52;

@@ -998,6 +998,99 @@ __global__ __launch_bounds__(64) void k_fec_pdtch_decode(PdDecode a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_fec_access_encode / k_fec_access_decode: the access burst in both formats, the 8-bit one of GSM 05.03 4.6 (rach_e36, what
+// FEC_RACH decodes) and the 11-bit packet access burst of 5.3.2 as include/trxsig.h states it.  The coder is access_e36 of
+// trxsig_fec_enc.h; the reference has no 11-bit format: its arithmetic is tests/access_model.py's.
+// ---------------------------------------------------------------------------------------------
+
+// 16 lanes a burst, each storing dwords of its 148 bytes, as k_fec_sch_encode.  A format above 1, a BSIC above 63 or a word
+// that does not fit its format: an all-zero row.
+template <bool VEC>
+__global__ __launch_bounds__(64) void k_fec_access_encode(const uint16_t *__restrict__ ras, const uint8_t *__restrict__ fmts,
+                                                          const uint8_t *__restrict__ bsics, int n, uint8_t *__restrict__ bits) {
+  const int lane = threadIdx.x & 15, i = blockIdx.x * 4 + (threadIdx.x >> 4);
+  if (i >= n) return;
+  const unsigned ra = ras[i], fmt = fmts[i], bsic = bsics[i];
+  const bool valid = fmt <= 1u && bsic < 64u && ra < (fmt ? 2048u : 256u);
+  const unsigned long long e = valid ? access_e36(ra, fmt, bsic) : 0ULL;
+  auto obyte = [&](int pos) -> unsigned {
+    if (!valid || pos >= 85) return 0u;
+    return (unsigned)((pos < 49 ? kAccessHead >> pos : e >> (pos - 49)) & 1ULL);
+  };
+  uint8_t *out = bits + (size_t)i * 148;
+  for (int w = lane; w < 37; w += 16) {
+    if (VEC) {
+      unsigned v = 0;
+      for (int r = 0; r < 4; r++) v |= obyte(4 * w + r) << (8 * r);
+      reinterpret_cast<unsigned *>(out)[w] = v;
+    } else {
+      for (int r = 0; r < 4; r++) out[4 * w + r] = (uint8_t)obyte(4 * w + r);
+    }
+  }
+}
+
+struct AccDecode {
+  const float *soft;
+  long long stride, n_rows;
+  const int32_t *index;                                    // [n] or null
+  int n, fmt, bsic;
+  uint16_t *ra;
+  uint8_t *ofmt, *tail_ok, *obsic;                         // may be null
+};
+
+// what a hypothesis reads out of its u[]: ND data bits, six parity bits MSB first, four tail bits (fec:485-507 for ND = 8)
+template <int ND>
+__device__ __forceinline__ void access_verdict(unsigned u, unsigned *ra, unsigned *tail_ok, unsigned *bsic) {
+  unsigned sent = 0, st = 0;
+  for (int k = 0; k < 6; k++) sent |= ((u >> (ND + k)) & 1u) << (5 - k);
+  for (int k = 0; k < ND; k++) {                           // encoderShift (bh:80-85), generator 0x6f
+    const unsigned fb = ((st >> 5) ^ (u >> k)) & 1u;
+    st <<= 1;
+    if (fb) st ^= 0x6fu;
+  }
+  *tail_ok = ((u >> (ND + 6)) & 0xFu) == 0;
+  *bsic = (~sent ^ st) & 0x3fu;
+  *ra = u & ((1u << ND) - 1u);
+}
+
+// 16 lanes a burst, four bursts a wave, as k_fec_viterbi<FEC_RACH>, whose fetch the 8-bit pass repeats; the 11-bit pass reads
+// the six deleted coder outputs as exactly 0.5 (wire_value(0.5F) is 0.5F).  fmt -1 runs both passes on every row.
+template <bool WIRE>
+__global__ __launch_bounds__(64) void k_fec_access_decode(AccDecode a) {
+  __shared__ float4 ktab[4][kChunk];
+  const int lane = threadIdx.x & 63, row = lane >> 4, s = lane & 15;
+  const int blk = blockIdx.x * 4 + row;
+  const bool live = blk < a.n;
+  long long src = -1;
+  if (live) src = a.index ? (long long)a.index[blk] : (long long)blk;
+  if (src >= a.n_rows) src = -1;
+  const float *e = a.soft + (src < 0 ? 0 : src) * a.stride + 49;   // the 36 coded values; read only where src >= 0
+  auto finish = [&](float v, int) -> float { return WIRE ? wire_value(v) : v; };
+  unsigned u8 = 0, u11 = 0;
+  if (a.fmt != 1) {
+    auto fetch = [&](int p) -> float { return src < 0 ? 0.5F : e[p]; };
+    u8 = fec_trellis(ktab[row], 36, 18 + kDeferral, live, lane, fetch, finish);
+  }
+  if (a.fmt != 0) {
+    auto fetch = [&](int p) -> float {
+      const int k = access_cindex(p);
+      return (k < 0 || src < 0) ? 0.5F : e[k];
+    };
+    u11 = fec_trellis(ktab[row], 42, 21 + kDeferral, live, lane, fetch, finish);
+  }
+  if (!live || s != 0) return;                             // u[0..20] is in the row's lane 0
+  unsigned ra8 = 0, t8 = 0, b8 = 0, ra11 = 0, t11 = 0, b11 = 0;
+  if (a.fmt != 1) access_verdict<8>(u8, &ra8, &t8, &b8);
+  if (a.fmt != 0) access_verdict<11>(u11, &ra11, &t11, &b11);
+  bool long_fmt = a.fmt == 1;
+  if (a.fmt < 0) long_fmt = (t11 && b11 == (unsigned)a.bsic) && !(t8 && b8 == (unsigned)a.bsic);
+  a.ra[blk] = (uint16_t)(long_fmt ? ra11 : ra8);
+  if (a.ofmt) a.ofmt[blk] = (uint8_t)long_fmt;
+  if (a.tail_ok) a.tail_ok[blk] = (uint8_t)(long_fmt ? t11 : t8);
+  if (a.obsic) a.obsic[blk] = (uint8_t)(long_fmt ? b11 : b8);
+}
+
 }  // namespace
 
 hipError_t trx_launch_fec_xcch_encode(hipStream_t st, const uint8_t *frames, int nblk, const uint8_t *tsc_bits, uint8_t *bits,
@@ -1109,6 +1202,33 @@ hipError_t trx_launch_fec_pdtch_decode(hipStream_t st, const float *soft, long l
   if (prof) prof->begin(TRXSIG_K_FEC, st);
   if (wire) k_fec_pdtch_decode<true><<<grid, block, 0, st>>>(a);
   else k_fec_pdtch_decode<false><<<grid, block, 0, st>>>(a);
+  if (prof) prof->end(TRXSIG_K_FEC, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_access_encode(hipStream_t st, const uint16_t *ra, const uint8_t *fmt, const uint8_t *bsic, int n,
+                                        uint8_t *bits, TrxProfiler *prof) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((n + 3) / 4)), block(64);
+  if (prof) prof->begin(TRXSIG_K_FEC, st);
+  if (((uintptr_t)bits & 3) == 0)
+    k_fec_access_encode<true><<<grid, block, 0, st>>>(ra, fmt, bsic, n, bits);
+  else
+    k_fec_access_encode<false><<<grid, block, 0, st>>>(ra, fmt, bsic, n, bits);
+  if (prof) prof->end(TRXSIG_K_FEC, st);
+  return hipGetLastError();
+}
+
+hipError_t trx_launch_fec_access_decode(hipStream_t st, const float *soft, long long stride, long long n_rows, const int32_t *index,
+                                        int n, int wire, int fmt, int bsic, uint16_t *ra, uint8_t *ofmt, uint8_t *tail_ok,
+                                        uint8_t *obsic, TrxProfiler *prof) {
+  if (n <= 0) return hipSuccess;
+  if (fmt < -1 || fmt > 1 || (fmt < 0 && (bsic < 0 || bsic > 63))) return hipErrorInvalidValue;
+  const AccDecode a = { soft, stride, n_rows, index, n, fmt, bsic, ra, ofmt, tail_ok, obsic };
+  const dim3 grid((unsigned)((n + 3) / 4)), block(64);
+  if (prof) prof->begin(TRXSIG_K_FEC, st);
+  if (wire) k_fec_access_decode<true><<<grid, block, 0, st>>>(a);
+  else k_fec_access_decode<false><<<grid, block, 0, st>>>(a);
   if (prof) prof->end(TRXSIG_K_FEC, st);
   return hipGetLastError();
 }

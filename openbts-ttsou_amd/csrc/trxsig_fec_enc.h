@@ -70,19 +70,22 @@ __device__ __constant__ const TchInv kTchInv;
 // The access burst's 36 coded bits (GSM 05.03 4.6; the inverse of RACHL1Decoder::writeLowSide, GSML1FEC.cpp:470-510), bit i of
 // the result = e[i]: u[0..7] = the RA, LSB first (the decoder's LSB8MSB reads it back MSB first); u[8..13] = ~(bsic ^ parity),
 // MSB first, parity = the 6-bit encoderShift register (generator 0x6f) over u[0..7]; u[14..17] = 0; the rate-1/2 coder.
-__device__ __forceinline__ unsigned long long rach_e36(unsigned ra, unsigned bsic) {
+// ND = 8 is that coder.  ND = 11 is the packet access burst's (GSM 05.03 5.3.2) before its puncturing: the same register over
+// d(0..10), the same colouring, u(0..20), C(0..41).
+template <int ND>
+__device__ __forceinline__ unsigned long long access_coder(unsigned d, unsigned bsic) {
   unsigned st = 0;
-  for (int k = 0; k < 8; k++) {
-    const unsigned fb = ((st >> 5) ^ (ra >> k)) & 1u;
+  for (int k = 0; k < ND; k++) {
+    const unsigned fb = ((st >> 5) ^ (d >> k)) & 1u;
     st <<= 1;
     if (fb) st ^= 0x6fu;
   }
   const unsigned p = ~(bsic ^ st) & 0x3fu;
-  unsigned u = ra & 0xffu;
-  for (int i = 0; i < 6; i++) u |= ((p >> (5 - i)) & 1u) << (8 + i);
+  unsigned u = d & ((1u << ND) - 1u);
+  for (int i = 0; i < 6; i++) u |= ((p >> (5 - i)) & 1u) << (ND + i);
   unsigned long long e = 0;
   unsigned acc = 0;
-  for (int q = 0; q < 18; q++) {
+  for (int q = 0; q < ND + 10; q++) {
     acc = (acc << 1) | ((u >> q) & 1u);
     const unsigned long long gg = (kGen >> (2 * (acc & 31u))) & 3ULL;
     e |= (gg >> 1) << (2 * q);
@@ -90,6 +93,30 @@ __device__ __forceinline__ unsigned long long rach_e36(unsigned ra, unsigned bsi
   }
   return e;
 }
+__device__ __forceinline__ unsigned long long rach_e36(unsigned ra, unsigned bsic) { return access_coder<8>(ra, bsic); }
+
+// The 36 coded bits of either access-burst format (TRXSIG_ACCESS_8 / TRXSIG_ACCESS_11 of include/trxsig.h).  The 11-bit format
+// does not send C(0), C(2), C(5), C(37), C(39), C(41); access_cindex is that rule the other way round, for the decoder:
+// coder output C(P) -> its index in e[36], or -1 where it is deleted.
+__device__ __forceinline__ unsigned long long access_e36(unsigned word, unsigned fmt, unsigned bsic) {
+  if (fmt == 0) return rach_e36(word, bsic);
+  const unsigned long long C = access_coder<11>(word, bsic);
+  return ((C >> 1) & 1ULL) | (((C >> 3) & 3ULL) << 1) | (((C >> 6) & 0x7fffffffULL) << 3) | (((C >> 38) & 1ULL) << 34) |
+         (((C >> 40) & 1ULL) << 35);
+}
+__device__ __forceinline__ int access_cindex(int P) {
+  if (P == 0 || P == 2 || P == 5 || P == 37 || P == 39 || P == 41) return -1;
+  return P < 2 ? 0 : P < 5 ? P - 2 : P < 37 ? P - 3 : P == 38 ? 34 : 35;
+}
+
+// bits 0..48 of an access burst (GSM 05.02 5.2.7): the extended tail, then the 41-bit synch sequence; bit i = the i-th sent
+constexpr unsigned long long access_head() {
+  const char *ab = "00111010" "01001011011111111001100110101010001111000";
+  unsigned long long w = 0;
+  for (int i = 0; i < 49; i++) w |= (unsigned long long)(ab[i] == '1') << i;
+  return w;
+}
+constexpr unsigned long long kAccessHead = access_head();
 
 enum { TCH_FILLER = 0, TCH_SPEECH = 1, TCH_FACCH = 2 };
 constexpr int kTchState = 32;                              // TRXSIG_TCH_TX_STATE_BYTES

@@ -324,6 +324,13 @@ hipError_t trx_launch_fec_pdtch_encode(hipStream_t st, const uint8_t *blocks, co
 hipError_t trx_launch_fec_pdtch_decode(hipStream_t st, const float *soft, long long stride, long long n_rows, const int32_t *index,
                                        int nblk, int wire, int cs_force, uint8_t *blocks, uint8_t *cs, uint8_t *dist, uint8_t *ok,
                                        uint8_t *usf, TrxProfiler *prof);
+// access bursts in both formats (trxsig_fec_access_encode_batch / _decode_batch): k_fec_access_encode, k_fec_access_decode.
+// index: [n] or NULL; fmt: 0, 1 or -1 (either, with the cell's bsic); every decoder output but ra may be NULL
+hipError_t trx_launch_fec_access_encode(hipStream_t st, const uint16_t *ra, const uint8_t *fmt, const uint8_t *bsic, int n,
+                                        uint8_t *bits, TrxProfiler *prof);
+hipError_t trx_launch_fec_access_decode(hipStream_t st, const float *soft, long long stride, long long n_rows, const int32_t *index,
+                                        int n, int wire, int fmt, int bsic, uint16_t *ra, uint8_t *ofmt, uint8_t *tail_ok,
+                                        uint8_t *obsic, TrxProfiler *prof);
 // uplink stream decode (trxsig_fec_tch_decode_stream / _xcch_decode_stream): k_fec_rx_stream, then k_fec_rx_fold.  tch != 0:
 // TCH/FACCH (out_tch = 33 octets, out_l2 = the FACCH frame), 0: XCCH (out_l2 = the frame; out_tch and b0 unused)
 hipError_t trx_launch_fec_rx_stream(hipStream_t st, int tch, int n_chan, int n_slots, const float *soft, long long stride,
